@@ -5,19 +5,29 @@ One step = one full optimisation step on a batch of synthetic rays already resid
 render_rays coarse (64) + resample + fine (192) on two 8x256 fields -> TransientNet -> UPNeRFLoss -> backward (data +
 weight gradients, pose gradients) -> [gradient all-reduce when --gpus > 1] -> Adam + ExponentialLR on both optimisers.
 
-    python bench.py [--gpus 1] [--steps 20] [--warmup 5]
+    python bench.py [--gpus 1] [--steps 20] [--warmup 5] [--dump-outputs DIR] [--full]
     python bench.py --gpus N           # no torchrun environment: spawns the N ranks itself (fresh processes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  `value` is whole-job rays/s (N ranks x rays per step, weak scaling: every rank renders its
-own shard; model state is replicated and gradients are averaged by one flat all-reduce over RCCL).
+own shard; model state is replicated and gradients are averaged by one flat all-reduce over RCCL).  `ms_per_step` is the
+time of one of the --steps timed steps.
+
+A plain run measures the headline only: set-up, --warmup steps, one timed region of --steps steps, the line.  --full adds
+every other measurement below (each one a leg of its own after the headline's); the --no-* switches trim a --full run.
+
+--dump-outputs DIR: after the timed region, rank 0 writes what the last timed step computed -- its loss and loss terms, the
+parameters after both optimiser updates and the gradients of the step -- as DIR/<name>.npy (float32, ~18 MB at the default
+configuration).  Weights and batches are seeded, so the same arguments give the same inputs on every run.
 
 Workloads (--config):
   brandenburg   BASELINE.json configs[1]/[2]: 4096 rays per GPU, 763 images, fp32-accurate contractions (default)
   trevi         BASELINE.json configs[3]: 8192 rays per GPU, 1689 images, fp16 MLP weights/activations on MFMA (fp32 accumulate)
 
-Extra objects on the line:
+Extra objects on the line of a --full run:
+  value_spread  min / max of `value` over the reported timed region and two more of the same length
+  kernels       HIP-event times per kernel class, from eager steps run after the timed region (--kernel-timing)
   roofline      dominant kernel of the step against the matrix peak of its arithmetic; `achieved` = algorithmic FLOPs per
                 launch (SURVEY.md 8d per-sample figure x samples per launch) / average launch duration from HIP
                 events on the launch stream.  The timed region replays captured HIP graphs (no place for event records
@@ -159,6 +169,40 @@ def launch_ranks(n):
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def record_loss_terms(sysm):
+    """The loss terms of the latest step, as the step hands them to its host bookkeeping (the eager and the replayed step
+    both end in NeRFSystem._step_host); returns the dict that holds them."""
+    last, host = {}, sysm._step_host
+
+    def step_host(loss, loss_d, done):
+        last.update(loss_d)
+        host(loss, loss_d, done)
+    sysm._step_host = step_host
+    return last
+
+
+def dump_outputs(path, sysm, loss, loss_d):
+    """--dump-outputs: what a caller of the timed training step receives from its last call -- the loss it returns, the loss
+    terms, the parameters after both optimiser updates and the step's gradients -- one float32 .npy per tensor."""
+    import numpy as np
+    out = {"loss": loss}
+    out.update({"loss." + k: v for k, v in loss_d.items()})
+    for n, p in sysm.named_parameters():
+        out["param." + n] = p
+        if p.grad is not None:
+            out["grad." + n] = p.grad
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def make_batches(dev, n, seed0, rays=4096, n_images=763):
     from upnerf_amd import synth
     return [{k: v.to(dev) for k, v in synth.batch(rays, n_images, seed=seed0 + i).items()} for i in range(n)]
@@ -234,10 +278,12 @@ class Bench:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def leg(self, progress, field, graph, timer_only=None, steps=None, warmup=None, wgrad_store=None, repeats=1, nc=None, nf=None):
+    def leg(self, progress, field, graph, timer_only=None, steps=None, warmup=None, wgrad_store=None, repeats=1, nc=None, nf=None,
+            dump=None):
         """Build a fresh system, warm up, time `steps` steps (barrier + synchronize on both sides, max over ranks).  repeats > 1:
         the same bracketed measurement is taken again (repeats - 1) times after the one that is reported; `value_spread` = min /
-        max over all of them (box-to-box and run-to-run noise of this bench is ~1 %: claims below that are inside it)."""
+        max over all of them (box-to-box and run-to-run noise of this bench is ~1 %: claims below that are inside it).  dump: a
+        directory for the outputs of the last step of the reported region (rank 0), written before any repeat."""
         import torch
         import torch.distributed as dist
         from upnerf_amd import _lib, rendering
@@ -251,6 +297,7 @@ class Bench:
         if self.world > 1:
             sysm.enable_data_parallel()
         batches = make_batches(self.dev, 4, 100 + 10 * self.rank, self.rays, self.n_images)
+        loss_d = record_loss_terms(sysm) if dump is not None else None
         step = GraphedTrainingStep(sysm) if graph else sysm.training_step
         for i in range(2 if graph else 0):  # first step of a shape signature runs eagerly, the second one is captured
             step(batches[i % 4], i)
@@ -271,7 +318,7 @@ class Bench:
             self.barrier()
             t0 = time.perf_counter()
             for i in range(steps):
-                step(batches[i % 4], i)
+                loss = step(batches[i % 4], i)
             host = time.perf_counter() - t0
             self.barrier()
             dt = time.perf_counter() - t0
@@ -289,6 +336,8 @@ class Bench:
                    "sched_mult": sysm.get_schedule_mult(progress), "graph": bool(graph)}
             if comm is not None:
                 out["comm"] = comm_object(comm, graph)
+            if dump is not None and self.rank == 0:
+                dump_outputs(dump, sysm, loss, loss_d)
             if repeats > 1 and timer_only is None:
                 vals = [out["value"]]
                 for _ in range(repeats - 1):
@@ -446,7 +495,12 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay")
     ap.add_argument("--wgrad-store", choices=["f32", "f16", "f24"], default="f32",
                     help="diagnostic: storage of the trunk weight-gradient operands in the MAIN leg (f32 = the strict default; the "
-                         "other two are the options the default line reports as wgrad_f16 / wgrad_f24); named in config.wgrad_store")
+                         "other two are the options a --full line reports as wgrad_f16 / wgrad_f24); named in config.wgrad_store")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too (value_spread, the extra legs, kernel timing and roofline, "
+                         "cpu_baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--no-extras", action="store_true", help="skip the `phases` and `strict_f32` legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs34", action="store_true", help="skip the `trevi` (configs[3]) and `tto` (configs[4]) objects")
@@ -521,9 +575,10 @@ def main():
     B = Bench(args, rank, world, dev)
     graph = not args.no_graph
 
-    main_leg, _ = B.leg(args.progress, field, graph, repeats=3, wgrad_store=args.wgrad_store)
+    main_leg, _ = B.leg(args.progress, field, graph, repeats=3 if args.full else 1, wgrad_store=args.wgrad_store,
+                        dump=args.dump_outputs)
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         phases = {}
         for p in (0.05, 0.3, 0.8):
             phases[str(p)] = main_leg if abs(p - args.progress) < 1e-9 else B.leg(p, field, graph)[0]
@@ -550,13 +605,13 @@ def main():
             f32, _ = B.leg(args.progress, "f32", graph)
             extras["strict_f32"] = {"value": f32["value"], "ms_per_step": f32["ms_per_step"], "dtype": "f32",
                                     "contraction": "fp32 MFMA (v_mfma_f32_32x32x2_f32) in every field contraction"}
-    if not args.no_extras and args.config == "brandenburg" and not args.no_configs34:
+    if args.full and not args.no_extras and args.config == "brandenburg" and not args.no_configs34:
         extras["trevi"] = trevi_object(args, rank, world, dev)  # BASELINE configs[3]
         extras["default_yaml"] = default_yaml_object(args, rank, world, dev)  # the reference's shipped sampling shape
         if world == 1:
             extras["tto"] = tto_object(args, dev)               # BASELINE configs[4]
     summ = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         only = {"field_fwd", "field_bwd"} if args.kernel_timing == "field" else set()
         _, summ = B.leg(args.progress, field, False, timer_only=only if only else set(),
                         steps=min(args.steps, 10), warmup=2, wgrad_store=args.wgrad_store)
@@ -636,7 +691,7 @@ def main():
                                     + {"f16x3": "f16 dense MFMA 2516.6 TF / 3 MFMAs per fp32-accurate product (the hardware "
                                                 "executes 3x the algorithmic FLOPs); for scale: fp32 MFMA peak is 157.3 TF",
                                        "f16": "f16 dense MFMA 2516.6 TF", "f32": "fp32 MFMA 157.3 TF"}[field]}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         nthreads = min(CPU_BASELINE_THREADS, os.cpu_count() or 1)
         prev = torch.get_num_threads()
         torch.set_num_threads(nthreads)

@@ -1,5 +1,6 @@
-"""bench.py's output contract: ONE JSON line on stdout with the driver's keys, the roofline and cpu_baseline objects, and
-values that are consistent with each other (value = rays per step / time per step)."""
+"""bench.py's output contract: ONE JSON line on stdout with the driver's keys, values that are consistent with each other
+(value = rays per step / time per step), the roofline and cpu_baseline objects of a --full run, and the outputs a plain run
+writes with --dump-outputs."""
 import json
 import os
 import subprocess
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_default_shape_bench_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -67,6 +68,45 @@ def test_default_shape_bench_line():
         assert o["rays_per_step"] == 1024 and abs(o[st]["value"] - 1024 / (o[st]["ms_per_step"] * 1e-3)) < 1e-6 * o[st]["value"]
         assert o[st]["value"] > 20_000
     assert o["render"]["no_grad"] is True and o["render"]["value"] > 100_000 and o["render"]["chunk"] == 4096
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps replayed steps and nothing else; --dump-outputs writes the loss and its
+    terms, the parameters after the update and the gradients of the last timed step, float32, within 64 MB.  The same
+    arguments give the same outputs bit for bit (seeded inputs, deterministic step); one more timed step changes them."""
+    import numpy as np
+
+    def plain(name, steps):
+        d = tmp_path / name
+        out = _run(["--gpus", "1", "--steps", str(steps), "--warmup", "2", "--dump-outputs", str(d)], timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        assert all(f.endswith(".npy") for f in os.listdir(d))
+        return json.loads(lines[0]), {f[:-len(".npy")]: np.load(d / f) for f in os.listdir(d)}
+
+    d, files = plain("a", 3)
+    assert d["metric"] == "training rays/sec" and d["unit"] == "rays/s" and d["higher_is_better"] is True
+    assert d["dtype"].startswith("f32 (f16x3") and d["steps"] == 3 and d["warmup"] == 2
+    assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    # the first call runs eagerly, the second is captured and replayed, then warm-up and timed steps replay
+    assert d["graph_stats"] == {"eager": 1, "captures": 1, "replays": 1 + 2 + 3}
+    for k in ("value_spread", "phases", "strict_f32", "wgrad_f16", "trevi", "tto", "kernels", "roofline", "cpu_baseline"):
+        assert d.get(k) is None, k
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert files["loss"].size == 1 and "param.nerf_fine.xyz_encoding_1.0.weight" in files
+    assert np.abs(files["grad.nerf_fine.xyz_encoding_1.0.weight"]).max() > 0 and np.abs(files["grad.se3_refine.weight"]).max() > 0
+    terms = [float(a.sum()) for k, a in files.items() if k.startswith("loss.")]
+    loss = float(files["loss"].reshape(()))
+    assert terms and abs(sum(terms) - loss) <= 1e-4 * max(1e-2, abs(loss))  # the terms of the same step as the loss
+    _, again = plain("b", 3)
+    assert sorted(again) == sorted(files) and all(np.array_equal(files[k], again[k]) for k in files)
+    _, later = plain("c", 4)
+    assert sorted(later) == sorted(files)
+    w = "param.nerf_fine.xyz_encoding_1.0.weight"
+    assert not np.array_equal(files[w], later[w]) and not np.array_equal(files["loss"], later["loss"])
 
 
 def _run(args, env=None, timeout=300):

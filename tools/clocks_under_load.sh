@@ -1,7 +1,8 @@
 #!/bin/bash
 # Engine clock / power while the training step runs (is the MFMA peak in MI355X_MICROARCH.md reachable at this clock?).
 #   bash tools/clocks_under_load.sh [steps]
-python bench.py --steps ${1:-400} --warmup 10 --no-cpu-baseline > gpurun_out/clk_bench.json 2>/dev/null &
+J=$(mktemp)
+python bench.py --full --steps ${1:-400} --warmup 10 --no-cpu-baseline > "$J" 2>/dev/null &
 pid=$!
 sleep 25
 for i in 1 2 3 4 5 6; do
@@ -10,4 +11,5 @@ for i in 1 2 3 4 5 6; do
   sleep 1
 done
 wait $pid
-tail -c 400 gpurun_out/clk_bench.json
+tail -c 400 "$J"
+rm -f "$J"

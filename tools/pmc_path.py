@@ -55,7 +55,7 @@ def main():
         shutil.rmtree(d, ignore_errors=True)
         cmd = ["rocprofv3", "--pmc", "GRBM_GUI_ACTIVE", *p, "--output-format", "csv", "-d", d, "-o", "p", "--",
                "python3", os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-kernel-timing",
-               "--no-extras", "--no-configs34", *extra]
+               "--no-extras", "--no-configs34", "--full", *extra]
         r = subprocess.run(cmd, capture_output=True, text=True, cwd="/tmp", env=env, timeout=900)
         log.append(f"pass {i} {p} rc={r.returncode}\n{r.stderr[-600:]}")
         for f in glob.glob(d + "/**/*counter_collection.csv", recursive=True):

@@ -5,7 +5,7 @@ out=gpurun_out/ab_libs; mkdir -p $out
 for r in $(seq 1 ${3:-1}); do
   for lib in $1; do for t in $2; do
     sfx=$lib; [ "$lib" = "-" ] && sfx=""
-    UPNERF_LIB=$PWD/upnerf_amd/libupnerf_hip$sfx.so UPNERF_FIELD_TILE=$t timeout 300 python bench.py --steps 10 --warmup 3 --no-extras --no-cpu-baseline ${EXTRA:-} 2>/dev/null | tail -1 > $out/b${sfx}_${t}_$r.json
+    UPNERF_LIB=$PWD/upnerf_amd/libupnerf_hip$sfx.so UPNERF_FIELD_TILE=$t timeout 300 python bench.py --full --steps 10 --warmup 3 --no-extras --no-cpu-baseline ${EXTRA:-} 2>/dev/null | tail -1 > $out/b${sfx}_${t}_$r.json
     python - $out/b${sfx}_${t}_$r.json "$lib" $t <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); k=d.get('kernels',{})

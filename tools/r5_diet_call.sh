@@ -13,7 +13,7 @@ for r in 1 2 3; do one old$r 0; one new$r 1; done
 EXTRA="--config trevi" ; for r in 1 2; do one told$r 0; one tnew$r 1; done
 R=$(pwd); O=$(realpath -m $out)
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o k -- python3 "$R/bench.py" --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-kernel-timing > "$O/prof.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o k -- python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-kernel-timing > "$O/prof.log" 2>&1
 cd "$R"
 python tools/step_sequence.py "$O/prof" > "$O/step_sequence.txt" 2>&1
 python tools/prof_summary.py "$O/prof" 67 60 > "$O/kernel_summary.txt" 2>&1

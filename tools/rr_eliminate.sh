@@ -19,7 +19,7 @@ OUT=${2:-gpurun_out/rr_eliminate.txt}
     n=${v%%:*}
     lib=upnerf_amd/libupnerf_hip_x$n.so; [ $n = full ] && lib=upnerf_amd/libupnerf_hip.so
     [ -f $lib ] || { echo "$n: no library"; continue; }
-    UPNERF_LIB=$PWD/$lib timeout 300 python bench.py --config trevi --no-extras --no-cpu-baseline --no-configs34 --steps 6 --warmup 2 2>/dev/null | tail -1 | python -c "
+    UPNERF_LIB=$PWD/$lib timeout 300 python bench.py --full --config trevi --no-extras --no-cpu-baseline --no-configs34 --steps 6 --warmup 2 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['kernels']
 print(f\"$n ({'${v##*:}'}): fwd {k['field_fwd']['avg_ms']:.3f} ms ({k['field_fwd']['tflops_algorithmic']:.0f} TF alg)  bwd {k['field_bwd']['avg_ms']:.3f} ms ({k['field_bwd']['tflops_algorithmic']:.0f} TF alg)\")"
