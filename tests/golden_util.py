@@ -101,6 +101,20 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-12)) if b.size else 0.0
 
 
+def ray_rel_err(a, b, floor=1e-3):
+    """Per-ray gate for arrays whose leading dimension is the ray: max over rays r of max|a_r - b_r| / max(max|b_r|, floor * max|b|).
+    Unlike rel_err, a wrong ray whose values are far below the batch maximum (behind an opaque surface, a transparent ray) is
+    seen; the floor keeps rays whose reference is (near) zero from turning rounding noise into a large ratio."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    if not b.size:
+        return 0.0
+    R = b.shape[0]
+    err = np.abs(a - b).reshape(R, -1).max(1)
+    mag = np.abs(b).reshape(R, -1).max(1)
+    return float((err / np.maximum(mag, max(floor * mag.max(), 1e-12))).max())
+
+
 def named_grads(state):
     """Flatten a state dict-of-dicts into golden grad names -> grad tensor (or None)."""
     out = {}

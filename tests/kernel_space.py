@@ -76,18 +76,28 @@ def excl_cumprod(x):
     return torch.cumprod(torch.cat([torch.ones_like(x[:, :1]), x], -1)[:, :-1], -1)
 
 
-def composite(f, z, mode, has_rgb, W):
-    """Per-ray sums in trunk-width space + per-sample weights, exactly the outputs of upnerf_composite_fwd."""
+def composite(f, z, mode, has_rgb, W, e32=None):
+    """Per-ray sums in trunk-width space + per-sample weights, exactly the outputs of upnerf_composite_fwd.
+
+    e32: optional {"s", "c", "all"} -> fp32 tensors of exp(-delta sigma) (shared, candidate, joint density) as the kernels'
+    expf gives them.  The kernels form alpha = 1 - expf(..) in fp32, so alpha carries the fp32 rounding of the exponential (up to
+    2^-25 absolute: a large relative error when alpha is small).  Given, every alpha takes that fp32 value with the exact
+    derivative (straight-through), so a reference run in fp64 composites the kernels' own alphas."""
     R, S = z.shape
-    sig_s = f["sigma_s"].view(R, S)
     delta = torch.cat([z[:, 1:] - z[:, :-1], 1e2 * torch.ones_like(z[:, :1])], -1)
-    a_s = 1 - torch.exp(-delta * sig_s)
+
+    def alpha(x, k):
+        a = 1 - torch.exp(-x)
+        return a if e32 is None else a + ((1 - e32[k]).to(a.dtype).view_as(a) - a).detach()  # (1 - e32: in fp32, as the kernels)
+
+    sig_s = f["sigma_s"].view(R, S)
+    a_s = alpha(delta * sig_s, "s")
     o = {}
     e = f["e"].view(R, S, -1)
     if mode <= 1:
         sig_c = f["sigma_c"].view(R, S)
-        a_c = 1 - torch.exp(-delta * sig_c)
-        a_all = 1 - torch.exp(-delta * (sig_s + sig_c))
+        a_c = alpha(delta * sig_c, "c")
+        a_all = alpha(delta * (sig_s + sig_c), "all")
         T = excl_cumprod(1 - a_all)
         o["w_all"], o["w_sj"], o["w_cj"] = a_all * T, a_s * T, a_c * T
         o["c_depth"] = (o["w_all"] * z).sum(1)
@@ -95,6 +105,8 @@ def composite(f, z, mode, has_rgb, W):
         o["E_s"] = (o["w_sj"][..., None] * e).sum(1)
         o["G_c"] = (o["w_cj"][..., None] * f["g2"].view(R, S, -1)).sum(1)
         o["sum_sfeat"] = o["w_sj"].sum(1)
+        if has_rgb:  # encode_feat = False: the shared half of c_rgb (upnerf_composite_fwd_args.rgb_joint_map)
+            o["rgb_joint_map"] = (o["w_sj"][..., None] * f["rgb"].view(R, S, 3)).sum(1)
     o["w_s"] = a_s * excl_cumprod(1 - a_s)
     o["s_depth"] = (o["w_s"] * z).sum(1)
     if mode == 3:

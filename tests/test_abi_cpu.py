@@ -76,6 +76,46 @@ def test_argument_errors_are_reported_not_crashed():
     assert _lib.lib.upnerf_field_fwd_f16x3(ctypes.byref(L), ctypes.byref(fa), None) == -1  # 640 rows < 768
 
 
+def _composite_args(kind, **kw):
+    """Composite argument structs with every pointer set (non-null, never dereferenced: each case below is refused on the host)."""
+    from upnerf_amd import _lib
+    cls = _lib.CompositeFwdArgs if kind == "fwd" else _lib.CompositeBwdArgs
+    one = ctypes.c_void_p(16)
+    a = cls(**{n: one for n, t in cls._fields_ if t is not ctypes.c_int32})
+    a.R, a.S, a.W, a.mode, a.has_rgb = 5, 64, 64, 0, 1
+    a.e16 = a.eexp = a.g2_16 = a.g2exp = None
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+@pytest.mark.parametrize("kind", ["fwd", "bwd"])
+@pytest.mark.parametrize("case,want", [
+    (dict(S=0), -1), (dict(S=1025), -1), (dict(R=0), -1), (dict(W=128), -2), (dict(mode=4), -1), (dict(mode=-1), -1),
+    # e as fp16 fragments needs W = 256 (the backward refuses it whether or not g_E_s is given)
+    (dict(e16=16, eexp=16, g_E_s=None), -1), (dict(e16=16, eexp=16), -1),
+    (dict(W=256, g2_16=16, g2exp=16), -1),  # g2 fragments without e16
+])
+def test_composite_argument_errors_are_refused_before_launch(kind, case, want):
+    from upnerf_amd import _lib
+    if kind == "fwd":
+        case = {k: v for k, v in case.items() if k != "g_E_s"}
+    a = _composite_args(kind, **case)
+    fn = _lib.lib.upnerf_composite_fwd if kind == "fwd" else _lib.lib.upnerf_composite_bwd
+    assert fn(ctypes.byref(a), None) == want
+
+
+def test_ray_reduction_argument_errors_are_refused_before_launch():
+    from upnerf_amd import _lib
+    one = ctypes.c_void_p(16)
+    assert _lib.lib.upnerf_ray_sum(4, 8, one, 257, one, None) == -1  # one thread per column, 256 at most
+    assert _lib.lib.upnerf_ray_sum(4, 8, one, 0, one, None) == -1
+    assert _lib.lib.upnerf_ray_sum(4, 0, one, 3, one, None) == -1
+    assert _lib.lib.upnerf_ray_sum(0, 8, one, 3, one, None) == -1
+    assert _lib.lib.upnerf_ray_geom_bwd(0, 8, one, one, one, one, None) == -1
+    assert _lib.lib.upnerf_ray_geom_bwd(4, 0, one, one, one, one, None) == -1
+
+
 def test_host_wrappers_refuse_or_fall_back_cleanly_without_a_gpu():
     """Host-side guards of the newer entry points: the sampler has no CPU path (raises), the embedding helper hands CPU
     tables to the module itself, the optimiser factory keeps torch.optim.Adam for CPU parameters."""

@@ -13,7 +13,7 @@ NAMES = ["cfg1_small", "cfg1_small_fine", "cfg2_phase1", "small_tto", "small_noc
 
 
 def build_model(c, typ, st):
-    m = NeRF(typ, c2f=c.c2f, **c.nerf_kw())
+    m = NeRF(typ, c2f=c.c2f, encode_feat=c.encode_feat, **c.nerf_kw())
     sd = {k: v.detach().clone() for k, v in st[f"nerf_{typ}"].items()}
     sd["progress"] = torch.tensor(c.progress)
     m.load_state_dict(sd)
@@ -75,6 +75,42 @@ def test_packed_kernel_space_matches_oracle(name):
             assert torch.equal(ks.mat(PT, L.t_we, W, W), ks.mat(P, L.we, W, W).t())
             assert torch.equal(ks.mat(PT, L.t_w[0], 64, W), ks.mat(P, L.w[0], W, 64).t())
             assert torch.equal(ks.mat(PT, L.t_head, W, W)[:, W2:], ks.mat(P, L.wc1, W2, W + 16)[:, :W].t())
+
+
+@pytest.mark.parametrize("name", ["nofeat_phase0", "nofeat_phase1", "nofeat_w256_phase1"])
+def test_rgb_joint_map_reproduces_the_oracle_c_rgb(name):
+    """encode_feat = False: kernel_space.composite's rgb_joint_map (sum_i w_sj rgb_i, the shared half of c_rgb) plus the candidate
+    half projected per ray (W_rc G_c + b_rc t_weight) is the oracle's c_rgb."""
+    c = Case(name)
+    assert not c.encode_feat and c.sched < 1
+    st = c.state(requires_grad=False)
+    keep = {}
+    b, hp = c.batch(), c.hparams()
+    real = orc.schedule_mult
+    orc.schedule_mult = lambda p, s: c.sched
+    try:
+        with torch.no_grad():
+            _, res = orc.training_forward(st, c.cfgs(), b, hp, c.progress, u_list=c.u_list, keep=keep)
+    finally:
+        orc.schedule_mult = real
+    idx = b["img_idx"]
+    pose = orc.compose_pair(orc.se3_exp(st["se3_refine"][idx]), b["c2w"]) if c.pose_opt else b["c2w"]
+    o, d = orc.get_rays(b["directions"], pose)
+    for typ, zkey in (("coarse", "z_coarse"), ("fine", "z_fine")):
+        if typ == "fine" and not c.fine:
+            continue
+        model = build_model(c, typ, st)
+        pk = model.packer
+        with torch.no_grad():
+            P = model.packed()
+            aux = ks.ray_aux(d, st[f"embedding_{typ}_a"][idx], band_weights(4, c.progress, c.c2f))
+            z = keep[zkey]
+            f = ks.field(P, pk, o, d, z, st[f"embedding_{typ}_c"][idx], aux, band_weights(10, c.progress, c.c2f), True, True)
+            out = ks.composite(f, z, 1, True, pk.W)
+            rc = model.rgb_candidate_layer
+            c_rgb = out["rgb_joint_map"] + out["G_c"] @ rc.weight.t() + out["t_weight"][:, None] * rc.bias
+            assert rel_err(c_rgb, res[f"c_rgb_{typ}"]) < 2e-5, typ
+            assert float(out["rgb_joint_map"].abs().max()) > 0
 
 
 def test_pack_is_differentiable_to_reference_named_parameters():

@@ -304,7 +304,10 @@ __global__ __launch_bounds__(NTHREADS) void composite_fwd_kernel(upnerf_composit
 }
 
 #define MAX_CHUNKS 16
-template <int W, bool EFRAG>
+// EROWS: g_E_s is given, so the fp32-row kernel reads rows of e (without g_E_s, e may be NULL: upnerf_composite_bwd does not
+// require it).  A template parameter, not a runtime test: a runtime test split the four-row load batch below into branches
+// (the training step 3.5 % slower).
+template <int W, bool EFRAG, bool EROWS>
 __global__ __launch_bounds__(NTHREADS) void composite_bwd_kernel(upnerf_composite_bwd_args a) {
   constexpr int W2 = W / 2;
   __shared__ double carry_s[4][2][MAX_CHUNKS];
@@ -378,13 +381,14 @@ __global__ __launch_bounds__(NTHREADS) void composite_bwd_kernel(upnerf_composit
       const int nv = (S - c0) < 64 ? (S - c0) : 64;
       constexpr int B = EFRAG ? 4 : COMPOSITE_ROWS_BWD;  // (rows in flight: see COMPOSITE_ROWS_* above)
       const bool g_rows = joint && a.g_G_c && !g_frag;
-      if (!EFRAG || g_rows)
+      constexpr bool e_rows = !EFRAG && EROWS;
+      if (e_rows || g_rows)
       for (int j0 = 0; j0 < nv; j0 += B) {
         f32x4 ev[B], gv[B];
 #pragma unroll
         for (int u = 0; u < B; ++u) {
           const size_t m = base + c0 + (j0 + u < nv ? j0 + u : nv - 1);
-          if constexpr (!EFRAG) {
+          if constexpr (e_rows) {
             if (laneE) ev[u] = NT_LOAD((const f32x4*)&a.e[m * W + 4 * lane]);
           }
           if (g_rows && laneG) gv[u] = NT_LOAD((const f32x4*)&a.g2[m * W2 + 4 * lane]);
@@ -393,7 +397,7 @@ __global__ __launch_bounds__(NTHREADS) void composite_bwd_kernel(upnerf_composit
         for (int u = 0; u < B; ++u) {
           if (j0 + u < nv) {
             float pe = 0.f, pg = 0.f;
-            if constexpr (!EFRAG) {
+            if constexpr (e_rows) {
               if (laneE) pe = gE.x * ev[u].x + gE.y * ev[u].y + gE.z * ev[u].z + gE.w * ev[u].w;
               pe = wave_sum(pe);
             }
@@ -480,7 +484,8 @@ extern "C" int upnerf_composite_fwd(const upnerf_composite_fwd_args* a, void* st
   if (!a->z || !a->sigma_s || !a->w_s || !a->s_depth) return UPNERF_EINVAL;
   if (joint && (!a->sigma_c || !a->w_all || !a->w_sj || !a->w_cj || !a->c_depth || !a->t_weight || (!a->g2 && !a->g2_16) || !a->G_c))
     return UPNERF_EINVAL;
-  if (want_feat && ((!a->e && !a->e16) || (a->e16 && (!a->eexp || a->W != 256)) || !a->E_s || !a->sum_sfeat)) return UPNERF_EINVAL;
+  if (a->e16 && (!a->eexp || a->W != 256)) return UPNERF_EINVAL;
+  if (want_feat && ((!a->e && !a->e16) || !a->E_s || !a->sum_sfeat)) return UPNERF_EINVAL;
   if (a->g2_16 && (!a->e16 || !a->g2exp)) return UPNERF_EINVAL;  // (the fragment walk lives in the e16 kernels)
   if (a->has_rgb && (!a->rgb || !a->rgb_map)) return UPNERF_EINVAL;
   const dim3 grid((a->R + 3) / 4), block(NTHREADS);
@@ -500,16 +505,23 @@ extern "C" int upnerf_composite_bwd(const upnerf_composite_bwd_args* a, void* st
   const bool joint = a->mode <= 1, want_feat = a->mode != 2;
   if (!a->z || !a->sigma_s || !a->d_sigma_s) return UPNERF_EINVAL;
   if (joint && (!a->sigma_c || !a->d_sigma_c)) return UPNERF_EINVAL;
-  if (want_feat && a->g_E_s && ((!a->e && !a->e16) || (a->e16 && (!a->eexp || a->W != 256)))) return UPNERF_EINVAL;
+  // (e16 with W = 64 would run the fp32-row kernel, which reads g2 even when only g2_16 was given)
+  if (a->e16 && (!a->eexp || a->W != 256)) return UPNERF_EINVAL;
+  if (want_feat && a->g_E_s && !a->e && !a->e16) return UPNERF_EINVAL;
   if (a->g2_16 && (!a->e16 || !a->g2exp)) return UPNERF_EINVAL;
   if (joint && a->g_G_c && !a->g2 && !a->g2_16) return UPNERF_EINVAL;
   if (a->has_rgb && (!a->rgb || !a->d_rgb)) return UPNERF_EINVAL;
   const dim3 grid((a->R + 3) / 4), block(NTHREADS);
+  const bool erows = a->g_E_s && want_feat;
   if (a->W == 256 && a->e16 && want_feat)
-    hipLaunchKernelGGL((composite_bwd_kernel<256, true>), grid, block, 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL((composite_bwd_kernel<256, true, false>), grid, block, 0, (hipStream_t)stream, *a);
+  else if (a->W == 256 && erows)
+    hipLaunchKernelGGL((composite_bwd_kernel<256, false, true>), grid, block, 0, (hipStream_t)stream, *a);
   else if (a->W == 256)
-    hipLaunchKernelGGL((composite_bwd_kernel<256, false>), grid, block, 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL((composite_bwd_kernel<256, false, false>), grid, block, 0, (hipStream_t)stream, *a);
+  else if (erows)
+    hipLaunchKernelGGL((composite_bwd_kernel<64, false, true>), grid, block, 0, (hipStream_t)stream, *a);
   else
-    hipLaunchKernelGGL((composite_bwd_kernel<64, false>), grid, block, 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL((composite_bwd_kernel<64, false, false>), grid, block, 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }
