@@ -702,6 +702,27 @@ int upnerf_set_scalars(float* dst, int n, const float* vals, void* stream);
  * host synchronisation (replaces rendering.py's five ATen launches per table). */
 int upnerf_scale_exponents(const float* maxima, int n, int32_t* out, void* stream);
 
+/* ---- SSIM of rendered images against their targets (utils/metric.py:23-30: kornia ssim_loss, 3x3 Gaussian window,
+ * sigma 1.5, reflect padding, C1 = 1e-4, C2 = 9e-4, eps 1e-12; the reference then takes 1 - 2 * dssim) --------------
+ * Pixel (n, c, y, x) of pred / gt is read at element offset n*s[0] + c*s[1] + y*s[2] + x*s[3] of its own strides, so
+ * NCHW images and the ray layout [N][H*W][3] are both read in place.  The window's moments are centred
+ * (sum w (x - mu)^2, not sum w x^2 - mu^2: fp32 keeps C2 = 9e-4 against the flat patches that way).
+ *   ssim[n] = 1 - 2 * mean over (c, y, x) of clamp((1 - s) / 2, 0, 1)      (NaN stays NaN)
+ *   map[n][c][y][x] = s, before the clamp (map may be NULL).
+ * Two launches: per-tile fp64 partial sums into `scratch`, then a fixed-order finish per image; the order depends on
+ * (C, H, W) only, so an image gets the same bits alone or in a batch.  H, W >= 2 (reflect padding).
+ * scratch: upnerf_ssim_scratch(a) doubles (a negative return is an error code). */
+typedef struct {
+  int32_t N, C, H, W;
+  const float* pred; const float* gt;
+  int64_t pred_stride[4];                /* (n, c, y, x), in elements */
+  int64_t gt_stride[4];
+  float* ssim;                           /* [N] */
+  float* map;                            /* [N][C][H][W] or NULL */
+} upnerf_ssim_args;
+int upnerf_ssim_scratch(const upnerf_ssim_args* a);
+int upnerf_ssim(const upnerf_ssim_args* a, double* scratch, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

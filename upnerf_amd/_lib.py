@@ -166,6 +166,11 @@ class AddPair(C.Structure):
 MAX_ADD_PAIRS = 8
 
 
+class SsimArgs(C.Structure):
+    _fields_ = [("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pred", _fp), ("gt", _fp),
+                ("pred_stride", C.c_int64 * 4), ("gt_stride", C.c_int64 * 4), ("ssim", _fp), ("map", _fp)]
+
+
 class Rng(C.Structure):
     """upnerf_rng: key of the uniform draws a kernel generates itself."""
     _fields_ = [("seed", C.c_uint64), ("step", C.c_int32), ("row0", C.c_int32), ("row_stride", C.c_int32), ("step_dev", _fp)]
@@ -233,6 +238,8 @@ _SIGNATURES = {
     "upnerf_adam_gather": [_p, _p, _p, _p, _i, _f, _f, _f, _f, _f, _p, _p],
     "upnerf_set_scalars": [_p, _i, C.POINTER(C.c_float), _p],
     "upnerf_scale_exponents": [_p, _i, _p, _p],
+    "upnerf_ssim_scratch": [C.POINTER(SsimArgs)],
+    "upnerf_ssim": [C.POINTER(SsimArgs), _p, _p],
 }
 MAX_SCALARS = 96
 EXPORTS = tuple(_SIGNATURES)
@@ -259,7 +266,7 @@ if lib.upnerf_abi_version() != ABI_VERSION:
     raise ImportError("libupnerf_hip.so ABI version mismatch; rebuild it")
 
 
-_PTR_DTYPES = (torch.float32, torch.int64, torch.int32, torch.float16, torch.uint8)
+_PTR_DTYPES = (torch.float32, torch.int64, torch.int32, torch.float16, torch.uint8, torch.float64)
 
 
 def ptr(t):

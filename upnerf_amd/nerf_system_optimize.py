@@ -9,8 +9,13 @@ come from the checkpoint and whose held-out cameras start from the aligned groun
 
 Differences by design: the reference leaves the NeRF weights trainable-but-unused (it computes and discards all
 weight gradients); here they are frozen, so the backward pass skips every weight-gradient
-kernel.  SSIM/LPIPS and the pickle
-bookkeeping are outside the accelerated path."""
+kernel.
+
+Metrics: validation reports PSNR and, when the batch carries `img_wh`, SSIM (metrics.py: a HIP kernel on the device-resident
+render, where the reference copies every render to the host for kornia).  LPIPS needs pretrained AlexNet weights and is not
+computed.  `best` records the epoch of the highest PSNR as the reference does; `write_nvs_results` / `read_nvs_results` are
+its psnr.pkl / ssim.pkl bookkeeping and what eval.py prints from it.  Unlike Lightning, run_stage has no sanity validation
+before the first epoch (tto.py:63, 87), so `best` never holds the starting PSNR."""
 from __future__ import annotations
 
 import torch
@@ -19,6 +24,7 @@ from torch import nn
 from . import zero_pool
 from .camera import refine_and_get_rays
 from .losses import _const
+from .metrics import ssim_rays
 from .nerf_system import NeRFSystem
 from .ops import EMBED_PREFETCH, embed_rows
 from .optim import get_optimizer
@@ -34,6 +40,8 @@ class NeRFSystemOptimize(NeRFSystem):
         # only s_rgb_fine is ever read here, so the coarse field stops at its density head (set False to get the
         # reference's full set of coarse maps back)
         self.coarse_sigma_only = True
+        # the best validation epoch (nerf_system_optmize.py:22-23): psnr, ssim, step and the stage's trainable rows
+        self.best = {"psnr": 0.0, "ssim": None, "step": None}
 
     def model_setup(self, trained_state=None, n_test_images: int = 1):
         super().model_setup()
@@ -113,31 +121,90 @@ class NeRFSystemOptimize(NeRFSystem):
 
     @torch.no_grad()
     def validation_step(self, batch, batch_nb=0):
-        """Full-image render in val.chunk_size chunks, perturb = 0; returns the PSNR on s_rgb_fine."""
+        """Full-image render in val.chunk_size chunks, perturb = 0; returns the PSNR on s_rgb_fine, and its SSIM when the
+        batch carries the image size `img_wh` (W, H) as the reference's validation batches do (lines 174-183)."""
         res = self(self.rays_from_batch(batch), batch["img_idx"], train=False)
         mse = ((res["s_rgb_fine"] - batch["rgbs"]) ** 2).mean()
-        return {"val_psnr": -10.0 * torch.log10(mse), "s_rgb_fine": res["s_rgb_fine"], "s_depth_fine": res["s_depth_fine"]}
+        out = {"val_psnr": -10.0 * torch.log10(mse), "s_rgb_fine": res["s_rgb_fine"], "s_depth_fine": res["s_depth_fine"]}
+        if batch.get("img_wh") is not None:
+            rgbs = batch["rgbs"].reshape(res["s_rgb_fine"].shape)
+            out["val_ssim"] = ssim_rays(res["s_rgb_fine"], rgbs, batch["img_wh"]).reshape(())
+        return out
 
     def validation_epoch_end(self, outputs):
-        """Mean PSNR over the validation images (nerf_system_optmize.py:190-196)."""
+        """Mean PSNR (and SSIM, over the outputs that carry it) of the validation images (nerf_system_optmize.py:190-196),
+        and the record of the best epoch in `self.best` (lines 195-198)."""
         if not outputs:
             return None
         out = {"val/psnr": torch.stack([x["val_psnr"].reshape(()) for x in outputs]).mean()}
-        self.log("val/psnr", out["val/psnr"])
+        ss = [x["val_ssim"].reshape(()) for x in outputs if "val_ssim" in x]
+        if ss:
+            out["val/ssim"] = torch.stack(ss).mean()
+        for k, v in out.items():
+            self.log(k, v)
+        self._update_best(out)
         return out
+
+    def _update_best(self, metrics):
+        """Replace `self.best` on a strictly greater val/psnr: that epoch's PSNR and SSIM, the step, and copies of the stage's
+        trainable rows (the reference saves them as best_pose_NN.npy)."""
+        psnr = metrics["val/psnr"]
+        if not float(psnr) > float(self.best["psnr"]):  # (a NaN never replaces it)
+            return
+        ssim = metrics.get("val/ssim")
+        best = {"psnr": psnr.detach().clone(), "ssim": None if ssim is None else ssim.detach().clone(),
+                "step": int(self.global_step), "embedding_fine_a": self.embedding_fine_a.weight.detach().clone()}
+        if self.pose_optimize:
+            best["se3_refine"] = self.se3_refine.weight.detach().clone()
+        self.best = best
 
 
 def run_stage(system: NeRFSystemOptimize, train_batches, n_batches_per_epoch: int, max_epochs: int, val_batches=(),
               graph: bool = True):
     """One test-time-optimisation stage the way tto.py:56-91 runs it: `max_epochs` passes over the held-out image's rays
     (50 for the pose stage, 20 for the appearance stage), a validation render after every epoch, no checkpoints.
-    Returns the Trainer (its `history` holds val/psnr per epoch)."""
+    Returns the Trainer (its `history` holds val/psnr per epoch, and val/ssim when the validation batches carry img_wh);
+    `system.best` holds the epoch with the highest PSNR."""
     from .trainer import Trainer
     opts = system.optimizers()
     n_opt = len(opts) if isinstance(opts, (list, tuple)) else 1
     budget = int(system.global_step) + max_epochs * n_batches_per_epoch * n_opt
     return Trainer(budget, val_check_interval=1.0, dirpath=None, graph=graph).fit(system, train_batches, n_batches_per_epoch,
                                                                                    val_batches)
+
+
+def write_nvs_results(dirpath: str, optimize_num: int, best: dict) -> None:
+    """nerf_system_optmize.py:208-228: merge the best PSNR and SSIM of held-out image `optimize_num` into
+    `<dirpath>/psnr.pkl` and `ssim.pkl` ({image number: 0-d CPU tensor}, the files eval.py reads).  No lpips.pkl."""
+    import os
+    import pickle
+    os.makedirs(dirpath, exist_ok=True)
+    for name in ("psnr", "ssim"):
+        if best.get(name) is None:
+            continue
+        path = os.path.join(dirpath, f"{name}.pkl")
+        table = {}
+        if os.path.isfile(path):
+            with open(path, "rb") as f:
+                table = pickle.load(f)
+        table[int(optimize_num)] = torch.as_tensor(best[name]).detach().reshape(()).cpu()
+        with open(path, "wb") as f:
+            pickle.dump(table, f)
+
+
+def read_nvs_results(dirpath: str) -> dict:
+    """eval.py:59-79: the mean PSNR and SSIM over the held-out images in `dirpath` (None where a file is absent); LPIPS is
+    not computed here, so `lpips` is None."""
+    import os
+    import pickle
+    out = {"psnr": None, "ssim": None, "lpips": None}
+    for name in ("psnr", "ssim"):
+        path = os.path.join(dirpath, f"{name}.pkl")
+        if os.path.isfile(path):
+            with open(path, "rb") as f:
+                vals = [float(v) for v in pickle.load(f).values()]
+            out[name] = sum(vals) / len(vals) if vals else None
+    return out
 
 
 def eval_train_poses(checkpoint, noised_poses, gt_poses, device="cuda") -> dict:
