@@ -723,6 +723,65 @@ typedef struct {
 int upnerf_ssim_scratch(const upnerf_ssim_args* a);
 int upnerf_ssim(const upnerf_ssim_args* a, double* scratch, void* stream);
 
+/* ---- scene loading: the per-pixel buffers of datasets/phototourism.py:242-323 (and custom.py, the optimize splits) ----
+ * upnerf_scene_rays writes, for every image descriptor, the rows of its column window [x0, x1) in row-major order
+ * (row = row0 + (j * (x1 - x0) + i - x0) for pixel (i, j) of the full W x H image):
+ *   directions = ((i - cx) / fx, -(j - cy) / fy, -1)            utils/ray.py:5-27 on the integer pixel grid
+ *   ray_infos  = (near, far, img_idx)                           (NULL: not written)
+ *   pxl        = (j / (H - 1), i / (W - 1))                     torch.linspace(0, n-1, n) / (n-1); (NULL: not written)
+ *   rgbs       = pixels[pix_off + (j * W + i) * 3 + c] / 255    ToTensor of uint8 RGB [H][W][3]; (NULL: not written)
+ * Every division is a correctly rounded fp32 division, so the values are the CPU tensors' bits.  H, W >= 2.
+ * `images` is host memory; it is validated against the capacities in `a` and copied into `table` (device memory of
+ * n_images * sizeof(upnerf_scene_image) bytes, stream-ordered) for the one launch. */
+typedef struct {
+  int32_t W, H;             /* full image size */
+  int32_t x0, x1;           /* column window, 0 <= x0 < x1 <= W */
+  float fx, fy, cx, cy;
+  float near, far, img_idx;
+  int32_t reserved_;
+  int64_t row0;             /* first output row of the window */
+  int64_t pix_off;          /* byte offset of the image's [H][W][3] uint8 pixels in `pixels` */
+} upnerf_scene_image;
+typedef struct {
+  int32_t n_images, reserved_;
+  int64_t rows;             /* capacity of every output, in rows */
+  int64_t pix_bytes;        /* size of `pixels` */
+  const uint8_t* pixels;    /* NULL only when rgbs is NULL */
+  float* directions;        /* [rows][3] */
+  float* ray_infos;         /* [rows][3] or NULL */
+  float* pxl;               /* [rows][2] or NULL */
+  float* rgbs;              /* [rows][3] or NULL */
+} upnerf_scene_rays_args;
+int upnerf_scene_rays(const upnerf_scene_rays_args* a, const upnerf_scene_image* images, void* table, void* stream);
+
+/* upnerf_resize_linear: cv2.resize(src, (W, H)) with INTER_LINEAR on fp32 [h][w][C] maps, C in [1, 512], every map of
+ * the table in one launch: half-pixel source coordinates, edge clamping, a horizontal then a vertical blend in fp32
+ * (a map whose size does not change is copied, as cv2.resize does).  Optional pre-step on every source pixel:
+ *   UPNERF_RESIZE_L2       x / ||x||_2 over C, no epsilon          (phototourism.py:287, 371)
+ *   UPNERF_RESIZE_INVDEPTH v = (x < 0 ? 0 : x); v / max_map(v) * scale + bias; max over the map, on the device
+ *                          (lines 318-320: scale = 1/near - 1/far, bias = 1/far, rounded to fp32 by the caller)
+ * src == dst (in place) is allowed when every map keeps its size and offset.  `maps` is host memory, validated against
+ * the capacities and copied into `scratch` (upnerf_resize_scratch(a) bytes of device memory, 16-byte aligned). */
+#define UPNERF_RESIZE_PLAIN 0
+#define UPNERF_RESIZE_L2 1
+#define UPNERF_RESIZE_INVDEPTH 2
+typedef struct {
+  int32_t h, w;             /* source size */
+  int32_t H, W;             /* destination size */
+  int64_t src_off;          /* float offset of the source map in src */
+  int64_t dst_off;          /* float offset of the destination map in dst */
+  float scale, bias;        /* UPNERF_RESIZE_INVDEPTH only */
+  int32_t reserved_[2];
+} upnerf_resize_map;
+typedef struct {
+  int32_t n_maps, C, pre, reserved_;
+  int64_t src_elems, dst_elems;  /* capacities, in floats */
+  const float* src;
+  float* dst;
+} upnerf_resize_args;
+int upnerf_resize_scratch(const upnerf_resize_args* a);
+int upnerf_resize_linear(const upnerf_resize_args* a, const upnerf_resize_map* maps, void* scratch, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

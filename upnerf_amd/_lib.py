@@ -171,6 +171,31 @@ class SsimArgs(C.Structure):
                 ("pred_stride", C.c_int64 * 4), ("gt_stride", C.c_int64 * 4), ("ssim", _fp), ("map", _fp)]
 
 
+class SceneImage(C.Structure):
+    _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("x0", C.c_int32), ("x1", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("near", C.c_float), ("far", C.c_float), ("img_idx", C.c_float), ("reserved_", C.c_int32),
+                ("row0", C.c_int64), ("pix_off", C.c_int64)]
+
+
+class SceneRaysArgs(C.Structure):
+    _fields_ = [("n_images", C.c_int32), ("reserved_", C.c_int32), ("rows", C.c_int64), ("pix_bytes", C.c_int64),
+                ("pixels", _fp), ("directions", _fp), ("ray_infos", _fp), ("pxl", _fp), ("rgbs", _fp)]
+
+
+class ResizeMap(C.Structure):
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("src_off", C.c_int64),
+                ("dst_off", C.c_int64), ("scale", C.c_float), ("bias", C.c_float), ("reserved_", C.c_int32 * 2)]
+
+
+class ResizeArgs(C.Structure):
+    _fields_ = [("n_maps", C.c_int32), ("C", C.c_int32), ("pre", C.c_int32), ("reserved_", C.c_int32),
+                ("src_elems", C.c_int64), ("dst_elems", C.c_int64), ("src", _fp), ("dst", _fp)]
+
+
+RESIZE_PLAIN, RESIZE_L2, RESIZE_INVDEPTH = 0, 1, 2  # UPNERF_RESIZE_*
+
+
 class Rng(C.Structure):
     """upnerf_rng: key of the uniform draws a kernel generates itself."""
     _fields_ = [("seed", C.c_uint64), ("step", C.c_int32), ("row0", C.c_int32), ("row_stride", C.c_int32), ("step_dev", _fp)]
@@ -240,6 +265,9 @@ _SIGNATURES = {
     "upnerf_scale_exponents": [_p, _i, _p, _p],
     "upnerf_ssim_scratch": [C.POINTER(SsimArgs)],
     "upnerf_ssim": [C.POINTER(SsimArgs), _p, _p],
+    "upnerf_scene_rays": [C.POINTER(SceneRaysArgs), C.POINTER(SceneImage), _p, _p],
+    "upnerf_resize_scratch": [C.POINTER(ResizeArgs)],
+    "upnerf_resize_linear": [C.POINTER(ResizeArgs), C.POINTER(ResizeMap), _p, _p],
 }
 MAX_SCALARS = 96
 EXPORTS = tuple(_SIGNATURES)

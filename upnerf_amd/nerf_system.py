@@ -167,10 +167,22 @@ class NeRFSystem(_Base):
             self.dataset_setup()
         self.model_setup()
 
+    dataset_device = "cuda"  # where dataset_setup builds the scene's buffers (trainer.fit_from_config sets its device)
+
     def dataset_setup(self):
-        raise NotImplementedError(
-            "dataset construction (datasets/phototourism.py) is outside the accelerated path; pass train_dataset / "
-            "val_dataset objects (anything with N_images_train and white_back) to NeRFSystem(...)")
+        """models/nerf_system.py:321-340: the train and val splits of hparams["dataset_name"] (datasets.dataset_dict)."""
+        from .datasets import dataset_dict
+        hp = self.hparams
+        dataset = dataset_dict.get(hp.get("dataset_name"))
+        if dataset is None:
+            raise NotImplementedError(
+                "dataset construction (datasets/phototourism.py) is outside the accelerated path; pass train_dataset / "
+                "val_dataset objects (anything with N_images_train and white_back) to NeRFSystem(...)")
+        kw = dict(root_dir=hp["root_dir"], scene_name=hp["scene_name"], img_downscale=hp["phototourism.img_downscale"],
+                  use_cache=hp.get("phototourism.use_cache", False), feat_dir=hp.get("feat_dir"),
+                  depth_dir=hp.get("depth_dir"), near=hp["nerf.near"], far=hp["nerf.far"], device=self.dataset_device)
+        self.train_dataset = dataset(split="train", camera_noise=hp["pose.noise"], **kw)
+        self.val_dataset = dataset(split="val", camera_noise=hp["pose.noise"], val_img_idx=hp.get("val.img_idx", (0,)), **kw)
 
     def configure_optimizers(self):
         hp = self.hparams

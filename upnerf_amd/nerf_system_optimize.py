@@ -43,7 +43,24 @@ class NeRFSystemOptimize(NeRFSystem):
         # the best validation epoch (nerf_system_optmize.py:22-23): psnr, ssim, step and the stage's trainable rows
         self.best = {"psnr": 0.0, "ssim": None, "step": None}
 
-    def model_setup(self, trained_state=None, n_test_images: int = 1):
+    def dataset_setup(self):
+        """models/nerf_system_optmize.py:233-252: the held-out image `optimize_num` of hparams["dataset_name"]'s
+        `_optimize` dataset, the whole image (pose stage) or its left / right half (appearance stage)."""
+        from .datasets import dataset_dict
+        hp = self.hparams
+        dataset = dataset_dict.get(f"{hp.get('dataset_name')}_optimize")
+        if dataset is None:
+            return super().dataset_setup()  # raises NotImplementedError
+        kw = dict(root_dir=hp["root_dir"], scene_name=hp["scene_name"], img_downscale=hp["phototourism.img_downscale"],
+                  use_cache=hp.get("phototourism.use_cache", False), near=hp["nerf.near"], far=hp["nerf.far"],
+                  pose_optimize=hp.get("pose_optimize", self.pose_optimize), optimize_num=hp["optimize_num"],
+                  device=self.dataset_device)
+        self.train_dataset = dataset(split="train", camera_noise=hp["pose.noise"], **kw)
+        self.val_dataset = dataset(split="val", camera_noise=hp["pose.noise"], **kw)
+
+    def model_setup(self, trained_state=None, n_test_images: int = None):
+        if n_test_images is None:  # the reference sizes the test tables by N_images_test (line 257); 1 without a scene
+            n_test_images = getattr(self.train_dataset, "N_images_test", None) or 1
         super().model_setup()
         if trained_state is not None:
             self.load_state_dict(trained_state, strict=False)

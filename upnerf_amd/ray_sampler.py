@@ -60,10 +60,13 @@ class GpuRaySampler:
     def from_dataset(cls, ds, device="cuda") -> "GpuRaySampler":
         """From a train-split dataset object with the reference's buffer attributes (datasets/phototourism.py:213-323:
         all_ray_infos, all_directions, all_rgbs, all_pxl_coords, all_inv_depths, feat_maps; the per-image poses are
-        `poses_dict[img_ids_train[i]]`, or a ready `poses` array of N_images_train rows)."""
+        `poses_dict[img_ids_train[i]]`, or a ready `poses` array of N_images_train rows).  A dataset whose ray image
+        index counts other ids (the optimize splits: the test images) names them in `ray_img_ids`."""
         import numpy as np
         if hasattr(ds, "poses_dict") and hasattr(ds, "img_ids_train"):
-            poses = np.stack([np.asarray(ds.poses_dict[i], dtype=np.float32) for i in ds.img_ids_train])
+            ids = getattr(ds, "ray_img_ids", None)
+            ids = ds.img_ids_train if ids is None else ids
+            poses = np.stack([np.asarray(ds.poses_dict[i], dtype=np.float32) for i in ids])
         else:
             poses = ds.poses
         g = lambda name: getattr(ds, name, None)

@@ -210,7 +210,8 @@ def fit_from_config(hparams: dict, train_dataset, val_dataset=None, device="cuda
     doubled under pose optimisation, validation every `val.log_interval` of an epoch over the validation split.
 
     `train_dataset` carries the reference's ray buffers (GpuRaySampler.from_dataset), `N_images_train` and `white_back`;
-    `val_dataset[i]` is one validation image as the reference's val `__getitem__` returns it (a dict of tensors).
+    `val_dataset[i]` is one validation image as the reference's val `__getitem__` returns it (a dict of tensors).  With
+    train_dataset None both splits are built from hparams (dataset_name, root_dir, ...: datasets.py).
     With world_size > 1 call it once per rank after torch.distributed is initialised (parallel.py)."""
     from .config import save_yaml
     from .nerf_system import NeRFSystem
@@ -223,7 +224,9 @@ def fit_from_config(hparams: dict, train_dataset, val_dataset=None, device="cuda
     if rank == 0:
         os.makedirs(save_dir, exist_ok=True)
     system = NeRFSystem(hparams, train_dataset, val_dataset)
-    system.setup()
+    system.dataset_device = device
+    system.setup()  # without datasets: NeRFSystem.dataset_setup builds them from hparams
+    train_dataset, val_dataset = system.train_dataset, system.val_dataset
     system.to(device)
     if world_size > 1:
         system.enable_data_parallel()
