@@ -782,6 +782,76 @@ typedef struct {
 int upnerf_resize_scratch(const upnerf_resize_args* a);
 int upnerf_resize_linear(const upnerf_resize_args* a, const upnerf_resize_map* maps, void* scratch, void* stream);
 
+/* ---- validation images (utils/visualization.py; models/nerf_system.py:276-307): uint8 [H][W][3] pictures of the maps of a
+ * full-image render, built where the maps are.  Every entry point: nothing allocated, no host read-back, no atomics,
+ * fixed-order reductions, all launches on `stream` (capturable).  Pixel p = y * W + x of a map is read at element offset
+ * p * stride, so a column of the ray layout [H*W][C] is read in place.  Scratch sizes are in floats (a negative return is
+ * an error code); scratch holds only what a call writes before it reads it.
+ *
+ * upnerf_viz_minmax: out[0] = min, out[1] = max over n values of nan_to_num(x) (NaN -> 0, +inf -> FLT_MAX,
+ * -inf -> -FLT_MAX, as np.nan_to_num); two launches (partials per workgroup, one finishing workgroup). */
+int upnerf_viz_minmax_scratch(long long n);
+int upnerf_viz_minmax(const float* x, long long n, long long stride, float* out, float* scratch, void* stream);
+
+/* upnerf_viz_depth: visualize_depth (visualization.py:7-23), every step in the precision numpy gives it:
+ *   x = nan_to_num(value);  (mi, ma) by `range`;  den = (float)((double)ma - (double)mi + 1e-8);
+ *   t = (x - mi) / den in fp32, the division correctly rounded;  t = clip(t, 0, 1) by comparisons;
+ *   q = (uint8)(255.0f * t), truncating (a NaN t, from an infinite range, gives 0);  rgb[p][c] = lut[q][c].
+ * The table is device memory, 256 x 3 bytes, and is copied column for column: a table in cv2's BGR order gives a picture
+ * whose first channel is cv2's blue, which is what the reference logs (it hands applyColorMap's BGR output to PIL as is).
+ * pre = UPNERF_VIZ_PRED_DEPTH: `x` holds inverse depths and value = the reference's pred_depths (nerf_system.py:249-256),
+ *   es = (float)exp((double)depth_scale[0]);  v = inv * es, then + depth_scale[1] (two roundings, no fma);
+ *   v < inv_far ? inv_far : v;  d = 1 / v, correctly rounded;  d < near ? near : d   (a NaN stays NaN until nan_to_num)
+ * range: UPNERF_VIZ_RANGE_OWN (min / max of x itself, reduced on the device), _HOST (the fields mi, ma), _DEVICE
+ * (range_dev[0], range_dev[1], e.g. what upnerf_viz_minmax wrote for another map earlier on the stream). */
+#define UPNERF_VIZ_RANGE_OWN 0
+#define UPNERF_VIZ_RANGE_HOST 1
+#define UPNERF_VIZ_RANGE_DEVICE 2
+#define UPNERF_VIZ_PLAIN 0
+#define UPNERF_VIZ_PRED_DEPTH 1
+typedef struct {
+  int32_t H, W, pre, range;
+  const float* x; int64_t x_stride;
+  const float* depth_scale;  /* [2] (scale, shift) of the image, device memory; UPNERF_VIZ_PRED_DEPTH only */
+  float inv_far, near;       /* UPNERF_VIZ_PRED_DEPTH only; inv_far = 1 / far rounded to fp32 by the caller */
+  float mi, ma;              /* UPNERF_VIZ_RANGE_HOST */
+  const float* range_dev;    /* UPNERF_VIZ_RANGE_DEVICE */
+  const uint8_t* lut;        /* [256][3] */
+  uint8_t* rgb;              /* [H][W][3] */
+  uint8_t* index;            /* [H][W], q itself, or NULL */
+  float* value;              /* [H*W], the value before nan_to_num (pred_depths under the pre-step), or NULL */
+} upnerf_viz_depth_args;
+int upnerf_viz_depth_scratch(const upnerf_viz_depth_args* a);
+int upnerf_viz_depth(const upnerf_viz_depth_args* a, float* scratch, void* stream);
+
+/* upnerf_viz_pca: get_pca_img (visualization.py:26-30) of [H*W][F] rows (row r at feat + r * feat_ld, channels contiguous),
+ * 1 <= F <= 512:  pc[r][j] = sum_k (feat[r][k] - m[k]) * c[j][k], fp32 accumulation in a fixed order (16-byte loads when
+ * F % 4 == 0 and the rows are 16-byte aligned, a scalar path otherwise);  mn / mx = ONE min and ONE max over all rows and
+ * the three components;  img[r][j] = (pc - mn) / (mx - mn);  rgb[r][j] = (uint8)min(max(255.0f * img, 0), 255), truncating.
+ * Deviation from the reference: a NaN component is left out of mn / mx and written as 0 in both outputs (the reference's
+ * whole image turns NaN); so is every component of a map with mx == mn (0 / 0).
+ * Three launches: projection + per-workgroup min / max, a one-workgroup finish, normalise + quantise. */
+typedef struct {
+  int32_t H, W, F, reserved_;
+  const float* feat; int64_t feat_ld;
+  const float* m;            /* [F] */
+  const float* c;            /* [3][F] */
+  float* img;                /* [H][W][3], the float image the reference returns */
+  uint8_t* rgb;              /* [H][W][3] */
+} upnerf_viz_pca_args;
+int upnerf_viz_pca_scratch(const upnerf_viz_pca_args* a);
+int upnerf_viz_pca(const upnerf_viz_pca_args* a, float* scratch, void* stream);
+
+/* upnerf_viz_rgb: a float map with C = 3 or C = 1 channels to uint8, pixel p channel k read at x[p * stride + k * cstride];
+ * q = (uint8)min(max(255.0f * v, 0), 255), truncating (what .mul(255).clamp(0, 255).byte() gives; NaN -> 0); a
+ * single-channel map is replicated to three channels. */
+typedef struct {
+  int32_t H, W, C, reserved_;
+  const float* x; int64_t stride, cstride;
+  uint8_t* rgb;              /* [H][W][3] */
+} upnerf_viz_rgb_args;
+int upnerf_viz_rgb(const upnerf_viz_rgb_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

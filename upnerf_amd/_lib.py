@@ -196,6 +196,26 @@ class ResizeArgs(C.Structure):
 RESIZE_PLAIN, RESIZE_L2, RESIZE_INVDEPTH = 0, 1, 2  # UPNERF_RESIZE_*
 
 
+class VizDepthArgs(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("pre", C.c_int32), ("range", C.c_int32), ("x", _fp), ("x_stride", C.c_int64),
+                ("depth_scale", _fp), ("inv_far", C.c_float), ("near", C.c_float), ("mi", C.c_float), ("ma", C.c_float),
+                ("range_dev", _fp), ("lut", _fp), ("rgb", _fp), ("index", _fp), ("value", _fp)]
+
+
+class VizPcaArgs(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("F", C.c_int32), ("reserved_", C.c_int32), ("feat", _fp),
+                ("feat_ld", C.c_int64), ("m", _fp), ("c", _fp), ("img", _fp), ("rgb", _fp)]
+
+
+class VizRgbArgs(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("reserved_", C.c_int32), ("x", _fp),
+                ("stride", C.c_int64), ("cstride", C.c_int64), ("rgb", _fp)]
+
+
+VIZ_RANGE_OWN, VIZ_RANGE_HOST, VIZ_RANGE_DEVICE = 0, 1, 2  # UPNERF_VIZ_RANGE_*
+VIZ_PLAIN, VIZ_PRED_DEPTH = 0, 1  # UPNERF_VIZ_PLAIN / UPNERF_VIZ_PRED_DEPTH
+
+
 class Rng(C.Structure):
     """upnerf_rng: key of the uniform draws a kernel generates itself."""
     _fields_ = [("seed", C.c_uint64), ("step", C.c_int32), ("row0", C.c_int32), ("row_stride", C.c_int32), ("step_dev", _fp)]
@@ -268,6 +288,13 @@ _SIGNATURES = {
     "upnerf_scene_rays": [C.POINTER(SceneRaysArgs), C.POINTER(SceneImage), _p, _p],
     "upnerf_resize_scratch": [C.POINTER(ResizeArgs)],
     "upnerf_resize_linear": [C.POINTER(ResizeArgs), C.POINTER(ResizeMap), _p, _p],
+    "upnerf_viz_minmax_scratch": [C.c_longlong],
+    "upnerf_viz_minmax": [_p, C.c_longlong, C.c_longlong, _p, _p, _p],
+    "upnerf_viz_depth_scratch": [C.POINTER(VizDepthArgs)],
+    "upnerf_viz_depth": [C.POINTER(VizDepthArgs), _p, _p],
+    "upnerf_viz_pca_scratch": [C.POINTER(VizPcaArgs)],
+    "upnerf_viz_pca": [C.POINTER(VizPcaArgs), _p, _p],
+    "upnerf_viz_rgb": [C.POINTER(VizRgbArgs), _p],
 }
 MAX_SCALARS = 96
 EXPORTS = tuple(_SIGNATURES)

@@ -398,7 +398,7 @@ class NeRFSystem(_Base):
         self._step_host(loss, loss_d, self._step_update())
         return loss
 
-    # ---- validation (nerf_system.py:231-269 without the image logging; 318-324) -------------------------------------
+    # ---- validation (nerf_system.py:231-269, 318-324; the pictures of 276-307 are visualization.validation_images on `results`) ----
     @torch.no_grad()
     def validation_step(self, batch, batch_nb=0):
         """One full validation image (DataLoader batch_size 1: every tensor has a leading 1): chunked render with

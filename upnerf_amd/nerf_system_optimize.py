@@ -177,17 +177,21 @@ class NeRFSystemOptimize(NeRFSystem):
 
 
 def run_stage(system: NeRFSystemOptimize, train_batches, n_batches_per_epoch: int, max_epochs: int, val_batches=(),
-              graph: bool = True):
+              graph: bool = True, image_sink=None):
     """One test-time-optimisation stage the way tto.py:56-91 runs it: `max_epochs` passes over the held-out image's rays
     (50 for the pose stage, 20 for the appearance stage), a validation render after every epoch, no checkpoints.
     Returns the Trainer (its `history` holds val/psnr per epoch, and val/ssim when the validation batches carry img_wh);
-    `system.best` holds the epoch with the highest PSNR."""
+    `system.best` holds the epoch with the highest PSNR.  image_sink (e.g. visualization.ImageWriter): receives `GT` and
+    `rgb_fine` of every validation render under the tag `val_<optimize_num>` (nerf_system_optmize.py:190-193); without one,
+    the sink `tto_from_checkpoint` was given, if any."""
     from .trainer import Trainer
+    if image_sink is None:
+        image_sink = getattr(system, "image_sink", None)
     opts = system.optimizers()
     n_opt = len(opts) if isinstance(opts, (list, tuple)) else 1
     budget = int(system.global_step) + max_epochs * n_batches_per_epoch * n_opt
-    return Trainer(budget, val_check_interval=1.0, dirpath=None, graph=graph).fit(system, train_batches, n_batches_per_epoch,
-                                                                                   val_batches)
+    return Trainer(budget, val_check_interval=1.0, dirpath=None, graph=graph, image_sink=image_sink).fit(
+        system, train_batches, n_batches_per_epoch, val_batches)
 
 
 def write_nvs_results(dirpath: str, optimize_num: int, best: dict) -> None:
@@ -240,10 +244,11 @@ def eval_train_poses(checkpoint, noised_poses, gt_poses, device="cuda") -> dict:
 
 
 def tto_from_checkpoint(checkpoint, pose_optimize: bool, n_test_images: int = 1, gt_train_poses=None, gt_test_poses=None,
-                        device="cuda", **overrides):
+                        device="cuda", image_sink=None, **overrides):
     """NeRFSystemOptimize for the held-out images of a trained run (nerf_system_optmize.py:254-317): hyper-parameters and
     fields from the checkpoint, a fresh appearance row per test image and, when ground-truth poses are given, their
-    initial cameras in the frame the model was trained in.  Returns (system, initial test poses or None)."""
+    initial cameras in the frame the model was trained in.  Returns (system, initial test poses or None).
+    image_sink: kept on the system (`system.image_sink`) for the stages `run_stage` runs on it."""
     from .checkpoint import read_checkpoint
     from .pose_align import init_test_poses, refined_poses
     ck = read_checkpoint(checkpoint)
@@ -256,6 +261,7 @@ def tto_from_checkpoint(checkpoint, pose_optimize: bool, n_test_images: int = 1,
     keep = {k: v for k, v in sd.items() if not k.startswith(("embedding_fine_a.", "se3_refine."))}
     system.model_setup(trained_state=keep, n_test_images=n_test_images)
     system.to(device)
+    system.image_sink = image_sink
     init = None
     if gt_train_poses is not None and gt_test_poses is not None:
         ident = torch.eye(3, 4).repeat(n_train, 1, 1)  # line 286: the trained refinements over identity poses

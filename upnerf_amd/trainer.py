@@ -81,7 +81,12 @@ def _save(system, path: str, extra: dict) -> None:
 class Trainer:
     def __init__(self, max_steps: int, val_check_interval=0.25, dirpath: Optional[str] = None, save_top_k: int = 2,
                  monitor: str = "val/psnr", mode: str = "max", seed: int = 0, log: Optional[Callable[[dict], None]] = None,
-                 write_checkpoints: bool = True, graph: bool = True):
+                 write_checkpoints: bool = True, graph: bool = True,
+                 image_sink: Optional[Callable[[str, int, dict], object]] = None):
+        # image_sink(tag, step, {name: uint8 [H, W, 3] device tensor}): called once per validation image with the pictures the
+        # reference logs (visualization.validation_images), e.g. a visualization.ImageWriter; give it to rank 0 only.  None
+        # (the default): no picture is built and validate() does what it did before there were any
+        self.image_sink = image_sink
         self.graph = graph  # replay the step from HIP graphs (graph_step.py; bitwise the eager step); False = eager launches
         self.max_steps, self.val_check_interval = int(max_steps), val_check_interval
         self.dirpath, self.monitor, self.seed = dirpath, monitor, seed
@@ -102,7 +107,15 @@ class Trainer:
         return max(1, int(v))
 
     def validate(self, system, val_batches: Sequence[dict]) -> dict:
-        outs = [system.validation_step(b, i) for i, b in enumerate(val_batches)]
+        outs = []
+        for i, b in enumerate(val_batches):
+            o = system.validation_step(b, i)
+            if self.image_sink is not None and self.write_checkpoints:
+                from .visualization import image_tag, validation_images
+                images = validation_images(system, b, o.get("results", o))  # (the TTO step returns its maps directly)
+                if images:
+                    self.image_sink(image_tag(system, b), int(system.global_step), images)
+            outs.append(o)
         for o in outs:
             o.pop("results", None)  # full-image maps: not needed for the epoch summary
         res = system.validation_epoch_end(outs) or {}
@@ -240,9 +253,13 @@ def fit_from_config(hparams: dict, train_dataset, val_dataset=None, device="cuda
         item = val_dataset[i]
         val.append({k: (v.to(device)[None] if torch.is_tensor(v) else v) for k, v in item.items()})
     max_steps = int(hparams["max_steps"]) * (2 if hparams["pose.optimize"] else 1)  # train.py:64-67
+    sink = None
+    if rank == 0 and hparams.get("val.save_images", False):  # the reference's wandb pictures, as PNG files under <save_dir>/viz
+        from .visualization import ImageWriter
+        sink = ImageWriter(os.path.join(save_dir, "viz"))
     trainer = Trainer(max_steps, hparams.get("val.log_interval", 0.25), dirpath=os.path.join(save_dir, "ckpts"),
                       seed=int(hparams["seed"]), log=log, write_checkpoints=rank == 0,
-                      graph=bool(hparams.get("hip.graph", True)))
+                      graph=bool(hparams.get("hip.graph", True)), image_sink=sink)
     if rank == 0:
         save_yaml(hparams, os.path.join(save_dir, "config.yaml"))
     trainer.fit(system, batches, n_batches, val, ckpt_path=hparams.get("resume_ckpt"))
