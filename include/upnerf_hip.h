@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define UPNERF_ABI_VERSION 10
+#define UPNERF_ABI_VERSION 11
 #define UPNERF_EINVAL (-1)   /* bad size / null pointer */
 #define UPNERF_EUNSUP (-2)   /* unsupported width/depth combination */
 
@@ -159,7 +159,7 @@ typedef struct {
                                     pair: [D + 1][tiles][threads per workgroup] words.  (D + 1) * ceil(M/128) * 512 words cover
                                     either tiling */
   float* amax;                   /* [16] or NULL: running max|.| (atomicMax; zero it first) of h_0..h_{D-1} (slots 0..D-1),
-                                    e (D), g1 (D+1), r1 (D+3), x0 (D+4) -- scale exponents of upnerf_wgrad_f16x3 */
+                                    e (D), g1 (D+1), r1 (D+3), x0 (D+4) -- scale exponents of upnerf_wgrad16 */
   float* e;                      /* [M][W]   xyz_encoding_final output */
   float* g1;                     /* [M][W/2] (use_cand) */
   float* g2;                     /* [M][W/2] (use_cand) */
@@ -190,7 +190,7 @@ typedef struct {
                                     register-resident kernels (tile_rows = 256), must be NULL otherwise */
   /* fp16 STORAGE of the trunk activations (always in the f16 mode; an option in the f16x3 mode, where it rounds only the
    * operands of the weight gradients): halves what the pass writes and what the weight-gradient kernels read back
-   * (upnerf_wgrad_f16p).  h16[l][m][k] = fp16(h_l[m][k] * 2^hexp[l][m / 64]): the content of the
+   * (UPNERF_WG_F16_TILE).  h16[l][m][k] = fp16(h_l[m][k] * 2^hexp[l][m / 64]): the content of the
    * LDS plane of the 64-sample tile, copied out as it stands, with the tile's power-of-two exponent beside it. */
   uint16_t* h16;                 /* [D][M][W] fp16 bits, or NULL (fp32 `h` as above) */
   int32_t* hexp;                 /* [D][ceil(M/64)] */
@@ -198,17 +198,17 @@ typedef struct {
                                     final-layer weight gradients read it) */
   void* x0f;                     /* reserved (was the 128-sample tiling's encoding scratch): ignored */
   uint16_t* e16;                 /* tile_rows = 256 only, or NULL: e as fp16 operand fragments [ceil(M/256) * 8][16][64][8] like one
-                                    layer of h16 (then `e` may be NULL); upnerf_composite_fwd / _bwd and upnerf_wgrad_f16p read it */
+                                    layer of h16 (then `e` may be NULL); upnerf_composite_fwd / _bwd and upnerf_wgrad16 read it */
   int32_t* eexp;                 /* [ceil(M/256) * 8] */
   uint16_t* g2_16;               /* the same for g2 (128 wide: [..][8][64][8]; then `g2` may be NULL) and for r1: compositing / */
   int32_t* g2exp;                /* upnerf_vec_wgrad_frag16 read them; the backward kernel works from the sign bits in hmask */
   uint16_t* r1_16;
   int32_t* r1exp;
-  uint16_t* g1_16;               /* and for g1 (candidate_encoding.2's weight gradient reads it: upnerf_wgrad_f16p, 128-wide fragments) */
+  uint16_t* g1_16;               /* and for g1 (candidate_encoding.2's weight gradient reads it: upnerf_wgrad16, 128-wide fragments) */
   int32_t* g1exp;
   uint8_t* h_lo8;                /* f16x3 mode with h16, or NULL: [D][M][W] bytes, the rounding residual of every h16 element in 1/32 of
                                     its tile's scaled unit (byte = round(32 lo) + 128): h16 + h_lo8 = the trunk activation to 2^-20
-                                    of its tile's maximum in 3 bytes ("24-bit" weight-gradient operands, upnerf_wgrad_f24p_chain) */
+                                    of its tile's maximum in 3 bytes ("24-bit" weight-gradient operands, UPNERF_WG_F24) */
   int64_t rows_capacity;         /* (ABI 9) tile_rows = 256: the number of rows every per-sample tensor passed here was allocated with.
                                     The register-resident kernels write whole 256-sample tiles: tensors need ceil(M / 256) * 256 rows.
                                     A caller that says so here gets UPNERF_EINVAL instead of a write past the end when it is less;
@@ -333,7 +333,7 @@ typedef struct {
                                     32 samples, finished by upnerf_ray_part_finish */
   int32_t gz_rg_ld;              /* f16x3 variant: row stride (floats) of gz_r1 and gz_g1; 0 = W/2 (two dense tensors).  With
                                     gz_g1 = gz_r1 + W/2 and a stride of W the two form ONE [M][W] tensor [gz_r1 | gz_g1], whose
-                                    weight gradient against e is one launch (upnerf_wgrad_f16x3_chain2); its running maximum is
+                                    weight gradient against e is one launch (upnerf_wgrad_desc.n2); its running maximum is
                                     tracked in gmax slot D+4 */
   int32_t reserved_;
   const float* wnorm;            /* as in upnerf_field_fwd_args (tile_rows = 256: required; else NULL) */
@@ -388,14 +388,6 @@ typedef struct {
 int upnerf_wgrad_grouped_scratch(const upnerf_wgrad_group* groups, int ngroups, int nsplit);
 int upnerf_wgrad_grouped(const upnerf_wgrad_group* groups, int ngroups, float* scratch, int nsplit, void* stream);
 
-/* Same contract, contraction on the f16 matrix cores: A and B are scaled by 2^*expo_a, 2^*expo_b (DEVICE ints, chosen so
- * that the scaled maxima are ~2^14).  planes 0 / 2 (f16x3): split into fp16 hi + lo parts, Ah Bh + Ah Bl + Al Bh
- * accumulated in fp32 -- fp32-level accuracy at 5.3x fewer matrix cycles than the fp32 MFMA (HBM-bound).  planes 1 (f16):
- * operands rounded to fp16, one MFMA per block, fp32 accumulate (the "f16" field mode). */
-int upnerf_wgrad_f16x3(int M, const float* A, int lda, int N, const float* B, int ldb, int K,
-                       float* dW, int ldo, float* db, float* slabs, int nsplit, const int* expo_a,
-                       const int* expo_b, int planes, void* stream);
-
 /* ---- TransientNet (models/transient_net.py:5-38) as one forward and one backward launch: feat_dim 384, hidden width 256,
  * transient embedding width 128 (the reference's defaults), one row per ray.  Weights in the nn.Linear layout ([out][in],
  * row-major); fp32 MFMA, fp32 accumulate.  The forward pass stores what the backward pass and the weight gradients read. */
@@ -431,12 +423,52 @@ int upnerf_transient_fwd(const upnerf_transient_args* a, void* stream);
 /* data gradients only; the weight gradients are upnerf_wgrad_grouped over (gz_*, stored inputs) */
 int upnerf_transient_bwd(const upnerf_transient_args* a, const upnerf_transient_grads* g, void* stream);
 
-/* Chained form of upnerf_wgrad_f16x3: the slabs of one weight gradient are summed by the first workgroups of the NEXT
- * weight-gradient launch (a prologue that costs it a few microseconds) instead of a reduction launch of their own (20+ us
- * each, 40 per step).  `pending` describes the problem whose slabs are written but not summed (nsplit == 0: none): the call
- * sums it -- in its kernel's prologue when the grid is large enough, by a reduction launch otherwise -- and replaces it by
- * the description of ITS problem.  upnerf_wgrad_finish sums what is pending and clears it.  The caller alternates between two
- * slab buffers: `slabs` must differ from pending->slabs.  Same arithmetic and summation order as upnerf_wgrad_f16x3. */
+/* ---- weight gradients on the f16 matrix cores: ONE entry point, the problem in a descriptor ------------------------------
+ * Same contract as upnerf_wgrad (dW[n][k] = sum_m A[m][n] B[m][k], db[n] = sum_m A[m][n], nsplit slabs summed in a fixed
+ * order: bitwise reproducible).  Both operands are brought to tensor-wide power-of-two scales 2^*expo_a / 2^*expo_b (DEVICE
+ * ints, chosen so that the scaled maxima are ~2^14; upnerf_scale_exponents) and contracted in fp16 with fp32 accumulation.
+ * How an operand is STORED is its `kind`; A and B are of the same kind, or B is fp32 rows beside a fp16-stored A (the
+ * encoding x0). */
+enum {
+  /* fp32 rows [M][ld]; ld, N, K multiples of 4.  desc.planes picks the arithmetic: 0 / 2 (f16x3) = split on load into fp16
+   * hi + lo parts, Ah Bh + Ah Bl + Al Bh accumulated in fp32 -- fp32-level accuracy at 5.3x fewer matrix cycles than the fp32
+   * MFMA (HBM-bound); 1 (f16) = rounded to fp16, one MFMA per block (the "f16" field mode).  Any N and K. */
+  UPNERF_WG_F32 = 0,
+  /* fp16 bits [M][ld], value * 2^exp[m / 64]: the f16 field mode's fp16-STORED operands (upnerf_field_bwd_f16x3's gz16 /
+   * gzexp, h16 / hexp).  Brought to the tensor-wide exponent on load (exact power-of-two scaling in fp16), one MFMA per block,
+   * fp32 accumulate.  Reads 1 KB per sample and layer instead of 2.  ld, N, K multiples of 8; 256 x 256 blocks (B stored the
+   * same way) and 256 x 64 (fp32 B). */
+  UPNERF_WG_F16_TILE,
+  /* the operand FRAGMENTS of the register-resident field kernels (upnerf_field_fwd_args.tile_rows = 256: [32-row tile]
+   * [k-block][lane][8], one exponent per 32 rows); ld is ignored.  N = 256 or 128 with a B of the same kind and K = N, or
+   * N = 256 with fp32 B (K = 64). */
+  UPNERF_WG_F16_FRAG,
+  /* "24-bit" operands (f16x3 mode): p = fp16 hi, lo = uint8 residual, both [M][ld], exponents per 64 rows, as the f16x3 field
+   * kernels write them (h16 + h_lo8, gz16 + gz_lo8); a fp32 B beside them is split into hi + lo on load.  Three MFMAs per
+   * block as for UPNERF_WG_F32 rows: the operands are exact to 2^-20 of their tile's maximum in 3 bytes per element instead
+   * of 4.  Row-major only (no fragment order); 256 x 256 and 256 x 64 blocks. */
+  UPNERF_WG_F24,
+  /* PRODUCER-SPLIT operands (round 6): p / lo are the (hi, lo) fp16 planes of the f16x3 field kernels' tiles, row-major
+   * [M][256], value = (hi + lo) * 2^-exp[m / 64] (upnerf_field_fwd_args.h16 / h_lo16 / hexp, upnerf_field_bwd_args.gz16 /
+   * gz_lo16 / gzexp) -- the 4 bytes per element of the fp32 rows, which ARE hi + lo, already split.  The kernel stages them by
+   * LDS-DMA (no conversion pass, no staging registers, three 16-row chunks in flight) and contracts as for UPNERF_WG_F32 rows
+   * (three MFMAs per block).  N = K = ld = 256 and M % 64 == 0 (UPNERF_EUNSUP otherwise: the caller keeps the fp32 rows for
+   * such shapes).  Measured, not wired into the training step. */
+  UPNERF_WG_PLANES
+};
+typedef struct {
+  const void* p;                 /* fp32 rows, fp16 bits or fragments, as `kind` says */
+  const void* lo;                /* UPNERF_WG_F24: uint8 residuals; UPNERF_WG_PLANES: fp16 lo plane; else unused */
+  const int32_t* exp;            /* per-tile exponents of the fp16-stored kinds; unused for UPNERF_WG_F32 */
+  int32_t ld, kind;
+} upnerf_wgrad_operand;
+
+/* A problem whose slabs are written but not summed (nsplit == 0: none).  Handed to upnerf_wgrad16, the slabs of one weight
+ * gradient are summed by the first workgroups of the NEXT weight-gradient launch (a prologue that costs it a few microseconds)
+ * instead of a reduction launch of their own (20+ us each, 40 per step): the call sums what is pending -- in its kernel's
+ * prologue when the grid is large enough, by a reduction launch otherwise -- and replaces it by the description of ITS
+ * problem.  upnerf_wgrad_finish sums what is pending and clears it.  The caller alternates between two slab buffers: desc.slabs
+ * must differ from pending->slabs.  One run may mix every kind of operand; same arithmetic and summation order as without. */
 typedef struct {
   const float* slabs; const float* bslabs;
   float* dW; float* db;
@@ -444,64 +476,38 @@ typedef struct {
   int32_t n2;                    /* > 0: rows n >= n2 of the result go to dW2[(n - n2) * ldo2 + k], db2[n - n2] */
   float* dW2; float* db2;
   int32_t ldo2, pad;
-  /* a vector head that shares B with the problem (upnerf_wgrad_f16x3_chain_v): per-split partial sums [nsplit][K + 4]
+  /* a vector head that shares B with the problem (upnerf_wgrad_desc.v): per-split partial sums [nsplit][K + 4]
    * (vslabs: K sums of v[m] B[m][k], then the sum of v) -> dv [K], dbv [1]; NULL: none */
   const float* vslabs; float* dv; float* dbv;
 } upnerf_wgrad_pending;
-int upnerf_wgrad_f16x3_chain(int M, const float* A, int lda, int N, const float* B, int ldb, int K, float* dW, int ldo,
-                             float* db, float* slabs, int nsplit, const int* expo_a, const int* expo_b, int planes,
-                             upnerf_wgrad_pending* pending, void* stream);
-/* the same with a result split by rows between two destinations (two layers that share B and whose A operands sit side by
- * side in one tensor: the colour and candidate heads' first layers, both fed by e) */
-int upnerf_wgrad_f16x3_chain2(int M, const float* A, int lda, int N, const float* B, int ldb, int K, float* dW, int ldo,
-                              float* db, int n2, float* dW2, int ldo2, float* db2, float* slabs, int nsplit, const int* expo_a,
-                              const int* expo_b, int planes, upnerf_wgrad_pending* pending, void* stream);
-/* upnerf_wgrad_f16x3_chain for a 256 x 256 problem, plus the gradient of a 1-wide head fed by the same B rows, in the same pass
- * over B:  dv[k] = sum_m v[m] B[m][k],  dbv[0] = sum_m v[m]  (the shared density head: share_sigma reads the last trunk
- * activation, which is also the B operand of xyz_encoding_final's weight gradient -- models/nerf.py:89, 93 -- so the separate
- * upnerf_vec_wgrad launch and its second read of that tensor, 1 KB per sample, go away).  fp32 arithmetic for the vector (as
- * upnerf_vec_wgrad), fixed summation order.  slabs: nsplit * (256 * 256 + 256 + 260) floats.  N = K = 256, planes = 2 only. */
-int upnerf_wgrad_f16x3_chain_v(int M, const float* A, int lda, int N, const float* B, int ldb, int K, float* dW, int ldo,
-                               float* db, const float* v, float* dv, float* dbv, float* slabs, int nsplit, const int* expo_a,
-                               const int* expo_b, int planes, upnerf_wgrad_pending* pending, void* stream);
-/* the same on the fragment-ordered fp16 operands of the register-resident field kernels (upnerf_wgrad_f16p_chain with
- * b_is_f16 = 3, N = K = 256): replaces upnerf_vec_wgrad_frag16 for the shared density head of the f16 mode */
-int upnerf_wgrad_f16p_chain_v(int M, const uint16_t* A16, const int32_t* aexp, const uint16_t* B16, const int32_t* bexp, float* dW,
-                              int ldo, float* db, const float* v, float* dv, float* dbv, float* slabs, int nsplit, const int* expo_a,
-                              const int* expo_b, upnerf_wgrad_pending* pending, void* stream);
+
+typedef struct {
+  int32_t M, N, K;
+  int32_t planes;                /* arithmetic for UPNERF_WG_F32 operands: 0 / 2 = 3-term split, 1 = one MFMA; else ignored */
+  upnerf_wgrad_operand A, B;     /* A [M] x N columns, B [M] x K columns */
+  const int32_t* expo_a; const int32_t* expo_b;   /* DEVICE: the tensor-wide exponents */
+  float* dW; float* db;          /* [N][ldo], [N] or NULL; ldo a multiple of 4 */
+  int32_t ldo;
+  /* n2 > 0: a result split by rows between two destinations, rows [n2, N) -> dW2 [N - n2][ldo2] / db2 (two layers that share
+   * B and whose A operands sit side by side in one tensor: the colour and candidate heads' first layers, both fed by e) */
+  int32_t n2;
+  float* dW2; float* db2;
+  int32_t ldo2, nsplit;
+  /* a 1-wide head fed by the same B rows rides on the launch, in the same pass over B:  dv[k] = sum_m v[m] B[m][k],
+   * dbv[0] = sum_m v[m]  (the shared density head: share_sigma reads the last trunk activation, which is also the B operand of
+   * xyz_encoding_final's weight gradient -- models/nerf.py:89, 93 -- so the separate upnerf_vec_wgrad / upnerf_vec_wgrad_frag16
+   * launch and its second read of that tensor, 1 KB per sample, go away).  fp32 arithmetic for the vector (as upnerf_vec_wgrad),
+   * fixed summation order.  N = K = 256 only, on UPNERF_WG_F32 rows with planes = 2 or on UPNERF_WG_F16_FRAG operands on both
+   * sides (UPNERF_EUNSUP otherwise); NULL: none. */
+  const float* v; float* dv; float* dbv;
+  float* slabs;                  /* scratch: upnerf_wgrad16_scratch(desc) floats */
+} upnerf_wgrad_desc;
+/* floats `slabs` must hold: nsplit * (slabs + bias slabs [+ the riding head's K + 4]) at the block shape the call picks for
+ * (N, K); reads N, K, nsplit and v only.  A negative return is an error code. */
+long long upnerf_wgrad16_scratch(const upnerf_wgrad_desc* d);
+/* pending == NULL: the slabs are summed at once by a reduction launch; else a link of a chained run (upnerf_wgrad_pending) */
+int upnerf_wgrad16(const upnerf_wgrad_desc* d, upnerf_wgrad_pending* pending, void* stream);
 int upnerf_wgrad_finish(upnerf_wgrad_pending* pending, void* stream);
-
-/* Same contraction for the f16 field mode with fp16-STORED operands: A16 [M][lda] fp16 bits scaled per 64-row tile by
- * 2^aexp[m / 64] (upnerf_field_bwd_f16x3's gz16 / gzexp); B either fp16 the same way (b_is_f16 = 1: B16 / bexp, from h16 /
- * hexp) or fp32 row-major (b_is_f16 = 0: x0).  b_is_f16 | 2: the fp16 operands (A16, and B16 when bit 0 is set) are the operand
- * FRAGMENTS of the register-resident field kernels (upnerf_field_fwd_args.tile_rows = 256: [32-row tile][k-block][lane][8], one
- * exponent per 32 rows, N = 256 and, for a fp16 B, K = 256; lda / ldb are ignored for them).  Operands are brought to the tensor-wide exponents *expo_a / *expo_b on load
- * (exact power-of-two scaling in fp16), one MFMA per block, fp32 accumulate.  Reads 1 KB per sample and layer instead of 2. */
-int upnerf_wgrad_f16p(int M, const uint16_t* A16, int lda, const int32_t* aexp, int N, const void* B, int ldb,
-                      const int32_t* bexp, int b_is_f16, int K, float* dW, int ldo, float* db, float* slabs, int nsplit,
-                      const int* expo_a, const int* expo_b, void* stream);
-/* chained like upnerf_wgrad_f16x3_chain, on the same pending record (a run may mix the two kinds of launches) */
-int upnerf_wgrad_f16p_chain(int M, const uint16_t* A16, int lda, const int32_t* aexp, int N, const void* B, int ldb,
-                            const int32_t* bexp, int b_is_f16, int K, float* dW, int ldo, float* db, int n2, float* dW2, int ldo2,
-                            float* db2, float* slabs, int nsplit, const int* expo_a, const int* expo_b,
-                            upnerf_wgrad_pending* pending, void* stream);  /* n2 > 0: rows [n2, N) -> dW2 / db2 (as chain2) */
-
-/* A 256 x 256 weight gradient from PRODUCER-SPLIT operands (round 6): A16 / Alo16 and B16 / Blo16 are the (hi, lo) fp16 planes of the
- * f16x3 field kernels' tiles, row-major [M][256], value = (hi + lo) * 2^-exp[m / 64] (upnerf_field_fwd_args.h16 / h_lo16 / hexp,
- * upnerf_field_bwd_args.gz16 / gz_lo16 / gzexp) -- the 4 bytes per element of the fp32 rows, which ARE hi + lo, already split.  The
- * kernel stages them by LDS-DMA (no conversion pass, no staging registers, three 16-row chunks in flight) and contracts as
- * upnerf_wgrad_f16x3 does (three MFMAs per block); dW / db / slabs / pending as upnerf_wgrad_f16x3_chain.  M % 64 == 0
- * (UPNERF_EUNSUP otherwise: the caller keeps the fp32 rows for such shapes). */
-int upnerf_wgrad_planes_chain(int M, const uint16_t* A16, const uint16_t* Alo16, const int32_t* aexp, const uint16_t* B16,
-                              const uint16_t* Blo16, const int32_t* bexp, float* dW, int ldo, float* db, float* slabs, int nsplit,
-                              const int* expo_a, const int* expo_b, upnerf_wgrad_pending* pending, void* stream);
-/* "24-bit" operands (f16x3 mode): A16 / Alo8 [M][lda] and, with b_is_f16 = 1, B16 / Blo8 [M][ldb] hold hi + lo8 as the f16x3 field
- * kernels write them (h16 + h_lo8, gz16 + gz_lo8; exponents per 64 rows); with b_is_f16 = 0 B is fp32 rows, split into hi + lo
- * on load.  Three MFMAs per block as upnerf_wgrad_f16x3: the operands are exact to 2^-20 of their tile's maximum.  256 x 256
- * and 256 x 64 blocks; chained on the same pending record as the other two kinds. */
-int upnerf_wgrad_f24p_chain(int M, const uint16_t* A16, const uint8_t* Alo8, int lda, const int32_t* aexp, int N, const void* B,
-                            const uint8_t* Blo8, int ldb, const int32_t* bexp, int b_is_f16, int K, float* dW, int ldo, float* db,
-                            float* slabs, int nsplit, const int* expo_a, const int* expo_b, upnerf_wgrad_pending* pending, void* stream);
 
 /* dw[c][k] = sum_m v[m*ldv + c] * X[m][k], c < nvec <= 3; dbv[c] = sum_m v[m*ldv + c]   (N=1/3 heads);
  * K in {32, 64, 128, 256}; scratch: nsplit * 4 * (K+1) floats */
@@ -697,8 +703,8 @@ int upnerf_adam_gather(float* p, float* m, float* v, const upnerf_adam_desc* des
 #define UPNERF_MAX_SCALARS 96
 int upnerf_set_scalars(float* dst, int n, const float* vals, void* stream);
 
-/* out[i] = 14 - ceil(log2(max(maxima[i], 1e-30))), i < n <= 64: the power-of-two exponents that upnerf_wgrad_f16x3 /
- * upnerf_wgrad_f16p take (expo_a / expo_b) from the maxima the field kernels track in `amax` / `gmax`; device to device, no
+/* out[i] = 14 - ceil(log2(max(maxima[i], 1e-30))), i < n <= 64: the power-of-two exponents that upnerf_wgrad16
+ * takes (expo_a / expo_b) from the maxima the field kernels track in `amax` / `gmax`; device to device, no
  * host synchronisation (replaces rendering.py's five ATen launches per table). */
 int upnerf_scale_exponents(const float* maxima, int n, int32_t* out, void* stream);
 

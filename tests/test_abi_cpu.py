@@ -14,7 +14,7 @@ def declared():
     src = open(os.path.join(ROOT, "include", "upnerf_hip.h")).read()
     # entry points of the diagnostic build (-DUPNERF_STAMPS, libupnerf_hip_stamps.so) are not part of the shipped library
     src = re.sub(r"#ifdef UPNERF_STAMPS.*?#endif", "", src, flags=re.S)
-    return sorted(set(re.findall(r"^int\s+(upnerf_\w+)\s*\(", src, flags=re.M)))
+    return sorted(set(re.findall(r"^(?:int|long long)\s+(upnerf_\w+)\s*\(", src, flags=re.M)))
 
 
 def test_header_symbols_are_exported_and_bound():
@@ -25,7 +25,7 @@ def test_header_symbols_are_exported_and_bound():
     for n in names:
         assert hasattr(dll, n), f"{n} declared in include/upnerf_hip.h but not exported"
     assert sorted(_lib.EXPORTS) == names, "ctypes binding and header disagree"
-    assert _lib.lib.upnerf_abi_version() == _lib.ABI_VERSION == 10
+    assert _lib.lib.upnerf_abi_version() == _lib.ABI_VERSION == 11
 
 
 def test_struct_sizes_match_the_c_layout():
@@ -36,11 +36,12 @@ def test_struct_sizes_match_the_c_layout():
     prog = r'''
     #include <stdio.h>
     #include "upnerf_hip.h"
-    int main(){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(upnerf_layout), sizeof(upnerf_field_fwd_args),
+    int main(){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(upnerf_layout), sizeof(upnerf_field_fwd_args),
       sizeof(upnerf_composite_fwd_args), sizeof(upnerf_composite_bwd_args), sizeof(upnerf_field_bwd_args),
       sizeof(upnerf_loss_args), sizeof(upnerf_loss_grads), sizeof(upnerf_frag_desc), sizeof(upnerf_frag16_desc),
       sizeof(upnerf_gather_rays_args), sizeof(upnerf_pack_desc), sizeof(upnerf_wgrad_group), sizeof(upnerf_embed_group),
-      sizeof(upnerf_embed_rows_group), sizeof(upnerf_rng), sizeof(upnerf_add_pair)); return 0; }'''
+      sizeof(upnerf_embed_rows_group), sizeof(upnerf_rng), sizeof(upnerf_add_pair), sizeof(upnerf_wgrad_pending),
+      sizeof(upnerf_wgrad_desc), sizeof(upnerf_wgrad_operand)); return 0; }'''
     with tempfile.TemporaryDirectory() as d:
         src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
         open(src, "w").write(prog)
@@ -49,7 +50,8 @@ def test_struct_sizes_match_the_c_layout():
     mine = [ctypes.sizeof(t) for t in (_lib.Layout, _lib.FieldFwdArgs, _lib.CompositeFwdArgs, _lib.CompositeBwdArgs,
                                        _lib.FieldBwdArgs, _lib.LossArgs, _lib.LossGrads, _lib.FragDesc, _lib.Frag16Desc,
                                        _lib.GatherRaysArgs, _lib.PackDesc, _lib.WgradGroup, _lib.EmbedGroup,
-                                       _lib.EmbedRowsGroup, _lib.Rng, _lib.AddPair)]
+                                       _lib.EmbedRowsGroup, _lib.Rng, _lib.AddPair, _lib.WgradPending, _lib.WgradDesc,
+                                       _lib.WgradOperand)]
     assert sizes == mine
 
 
@@ -74,6 +76,102 @@ def test_argument_errors_are_reported_not_crashed():
     fa = _lib.FieldFwdArgs(R=10, S=64, planes=1, tile_rows=256, rays_o=one, rays_d=one, z=one, P=one, P16=one, wexp=one, x0=one,
                            sigma_s=one, wnorm=one, rows_capacity=640)
     assert _lib.lib.upnerf_field_fwd_f16x3(ctypes.byref(L), ctypes.byref(fa), None) == -1  # 640 rows < 768
+
+
+def _wgrad_desc(a=None, b=None, **kw):
+    """A upnerf_wgrad_desc that upnerf_wgrad16 would launch: 256 x 256 from fp32 rows, every pointer set (non-null, never
+    dereferenced: each case below is refused on the host).  a / b: fields of the two operands, kw: fields of the descriptor."""
+    from upnerf_amd import _lib
+    one = ctypes.c_void_p(16)
+    op = lambda f: _lib.WgradOperand(**{**dict(p=one, lo=one, exp=one, ld=256, kind=_lib.WG_F32), **(f or {})})
+    d = _lib.WgradDesc(M=512, N=256, K=256, planes=2, A=op(a), B=op(b), expo_a=one, expo_b=one, dW=one, db=one, ldo=256, nsplit=2,
+                       slabs=one)
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+def _wg_kinds():
+    from upnerf_amd import _lib
+    return _lib.WG_F32, _lib.WG_F16_TILE, _lib.WG_F16_FRAG, _lib.WG_F24, _lib.WG_PLANES
+
+
+F32, TILE, FRAG, F24, PLANES = range(5)  # UPNERF_WG_* (checked against _lib below)
+EINVAL, EUNSUP = -1, -2
+# one row per refusal of upnerf_wgrad16, each reachable through one of the nine entry points it replaced (named on the right)
+WGRAD_REFUSALS = [
+    # null pointers and empty sizes
+    (None, None, dict(M=0), EINVAL), (None, None, dict(nsplit=0), EINVAL), (dict(p=None), None, {}, EINVAL), (None, dict(p=None), {}, EINVAL),
+    (None, None, dict(dW=None), EINVAL), (None, None, dict(slabs=None), EINVAL), (None, None, dict(expo_a=None), EINVAL),
+    (None, None, dict(expo_b=None), EINVAL),
+    (dict(kind=TILE, exp=None), dict(kind=TILE), {}, EINVAL),                 # f16p: A16 without its exponents
+    (None, None, dict(v=16, dv=None), EINVAL),                                # f16x3_chain_v: a riding head without its destination
+    (dict(kind=F24, lo=None), dict(kind=F24), {}, EINVAL),                    # f24p_chain: no residual bytes for A
+    (dict(kind=PLANES, lo=None), dict(kind=PLANES), {}, EINVAL),              # planes_chain: a missing lo plane
+    (dict(kind=PLANES), dict(kind=PLANES, lo=None), {}, EINVAL),
+    # alignment: & 3 for fp32 operands, & 7 for fp16 operands, ldo & 3
+    (dict(ld=258), None, {}, EINVAL), (None, dict(ld=258), {}, EINVAL), (None, None, dict(N=254), EINVAL), (None, None, dict(K=62), EINVAL),
+    (None, None, dict(ldo=258), EINVAL),
+    (dict(kind=TILE, ld=260), dict(kind=TILE), {}, EINVAL), (dict(kind=TILE), dict(kind=TILE, ld=260), {}, EINVAL),
+    (dict(kind=TILE), dict(ld=68), dict(K=64), EINVAL),                       # (a fp32 B beside fp16 A is held to 8 as well)
+    (dict(kind=TILE), dict(kind=TILE), dict(ldo=258), EINVAL), (dict(kind=PLANES), dict(kind=PLANES), dict(ldo=258), EINVAL),
+    # planes outside {0, 1, 2}
+    (None, None, dict(planes=3), EINVAL), (None, None, dict(planes=-1), EINVAL),
+    # bad n2 / dW2 / ldo2
+    (None, None, dict(n2=-1), EINVAL), (None, None, dict(n2=256), EINVAL), (None, None, dict(n2=128, dW2=None, ldo2=256), EINVAL),
+    (None, None, dict(n2=128, dW2=16, ldo2=258), EINVAL), (dict(kind=FRAG), dict(kind=FRAG), dict(n2=128, dW2=None, ldo2=256), EINVAL),
+    # a fp16 B without exp
+    (dict(kind=TILE), dict(kind=TILE, exp=None), {}, EINVAL), (dict(kind=FRAG), dict(kind=FRAG, exp=None), {}, EINVAL),
+    # F24 A with fragment order, or a fp16 F24 B without lo
+    (dict(kind=F24), dict(kind=FRAG), {}, EINVAL), (dict(kind=F24), dict(kind=F24, lo=None), {}, EINVAL),
+    # a riding head on anything but N = K = 256 with planes == 2 rows or fragment operands
+    (None, None, dict(v=16, dv=16, planes=1), EUNSUP), (None, None, dict(v=16, dv=16, planes=0), EUNSUP),
+    (None, None, dict(v=16, dv=16, N=128), EUNSUP), (None, None, dict(v=16, dv=16, K=64), EUNSUP),
+    # PLANES with M & 63
+    (dict(kind=PLANES), dict(kind=PLANES), dict(M=528), EUNSUP),
+    # fragment shapes other than 256 / 128 with K = N, or fp32 B with N = 256
+    (dict(kind=FRAG), dict(kind=FRAG), dict(N=64, K=64), EUNSUP), (dict(kind=FRAG), dict(kind=FRAG), dict(N=256, K=128), EUNSUP),
+    (dict(kind=FRAG), dict(ld=64), dict(N=128, K=64), EUNSUP),
+    # any block shape a packed kind has no instantiation for
+    (dict(kind=TILE), dict(kind=TILE), dict(N=128, K=128), EUNSUP), (dict(kind=TILE), dict(kind=TILE), dict(K=64), EUNSUP),
+    (dict(kind=TILE), None, {}, EUNSUP),                                      # (fp32 B: 256 x 64 only)
+    (dict(kind=FRAG), dict(ld=128), dict(K=128), EUNSUP),
+    (dict(kind=F24), dict(kind=F24), dict(N=128, K=128), EUNSUP), (dict(kind=F24), None, dict(K=128), EUNSUP),
+]
+
+
+@pytest.mark.parametrize("a,b,kw,want", WGRAD_REFUSALS)
+def test_wgrad16_refuses_before_launch(a, b, kw, want):
+    from upnerf_amd import _lib
+    assert _wg_kinds() == (F32, TILE, FRAG, F24, PLANES)
+    d = _wgrad_desc(a, b, **kw)
+    assert _lib.lib.upnerf_wgrad16(ctypes.byref(d), None, None) == want
+    assert _lib.lib.upnerf_wgrad16(ctypes.byref(d), ctypes.byref(_lib.WgradPending()), None) == want  # as a link of a run too
+
+
+def test_wgrad16_refuses_the_slabs_that_are_still_pending():
+    from upnerf_amd import _lib
+    d = _wgrad_desc()
+    pend = _lib.WgradPending(nsplit=2, slabs=d.slabs, rblocks=1)
+    assert _lib.lib.upnerf_wgrad16(ctypes.byref(d), ctypes.byref(pend), None) == EINVAL
+    assert _lib.lib.upnerf_wgrad16(None, None, None) == EINVAL
+
+
+@pytest.mark.parametrize("N,K,tile", [(256, 256, (256, 256)), (256, 64, (256, 64)), (128, 128, (128, 128)), (128, 256, (128, 256))])
+@pytest.mark.parametrize("nsplit", [1, 3])
+@pytest.mark.parametrize("v", [False, True])
+def test_wgrad16_scratch_is_the_closed_form_of_the_carve_up(N, K, tile, nsplit, v):
+    """nsplit * (gy gz TN TK + gy TN) floats of slabs and bias slabs, plus nsplit * (K + 4) for a riding head; not less than the
+    constants the Python side used to allocate for a 256 x 256 problem (with a riding head: + 260 per split)."""
+    from upnerf_amd import _lib
+    TN, TK = tile
+    gy, gz = -(-N // TN), -(-K // TK)
+    d = _wgrad_desc(N=N, K=K, nsplit=nsplit, v=16 if v else None)
+    got = _lib.lib.upnerf_wgrad16_scratch(ctypes.byref(d))
+    assert got == nsplit * (gy * gz * TN * TK + gy * TN) + (nsplit * (K + 4) if v else 0)
+    if (N, K) == (256, 256):
+        assert got >= nsplit * (256 * 256 + 256 + 260 if v else 256 * 256 + 256)
+    assert _lib.lib.upnerf_wgrad16_scratch(ctypes.byref(_wgrad_desc(nsplit=0))) == EINVAL
 
 
 def _composite_args(kind, **kw):

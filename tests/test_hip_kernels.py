@@ -36,6 +36,15 @@ def gen(shape, seed, lo=-1.0, hi=1.0):
     return torch.rand(*shape, generator=g) * (hi - lo) + lo
 
 
+def wg_desc(hip, M, A, N, B, K, ea, eb, dW, ldo, db, ws, ns, **kw):
+    """upnerf_wgrad_desc of dW [N][ldo] = A^T B; A / B: the fields of ops.WgOp (tensor, ld[, kind, exp, lo]); ea / eb: addresses;
+    kw: n2 / dW2 / ldo2 / db2, v / dv / dbv, planes (tensors where the descriptor holds a pointer)."""
+    L, ops = hip["lib"], hip["ops"]
+    kw = {k: (t.data_ptr() if isinstance(t, torch.Tensor) else t) for k, t in kw.items()}
+    return L.WgradDesc(M=M, N=N, K=K, planes=kw.pop("planes", 2), A=ops.WgOp(*A).c(), B=ops.WgOp(*B).c(), expo_a=ea, expo_b=eb,
+                       dW=dW.data_ptr(), ldo=ldo, db=db.data_ptr(), slabs=L.ptr(ws), nsplit=ns, **kw)
+
+
 # ------------------------------------------------------------------------------------------ a2-a4
 @pytest.mark.parametrize("identity", [True, False])
 def test_pose_rays_fwd_bwd(hip, identity):
@@ -225,9 +234,9 @@ def test_coarse_depths_with_the_jitter_generated_in_the_kernel(hip, disp):
 
 @pytest.mark.parametrize("M", [64 * 37, 64 * 512])
 def test_weight_gradient_from_producer_split_planes_staged_by_lds_dma(hip, M):
-    """upnerf_wgrad_planes_chain (round 6; measured, not wired into the step: DESIGN.md 4.9): both operands as the (hi, lo) fp16 planes
+    """upnerf_wgrad16 on UPNERF_WG_PLANES operands (round 6; measured, not wired into the step: DESIGN.md 4.9): both operands as the (hi, lo) fp16 planes
     + per-64-row exponents the f16x3 field kernels hold in LDS, staged by LDS-DMA.  Against fp64 on the values the planes decode to,
-    and against upnerf_wgrad_f16x3_chain on the fp32 rows (= hi + lo exactly): the same products, so 1e-6 of the maximum."""
+    and against the UPNERF_WG_F32 kind on the fp32 rows (= hi + lo exactly): the same products, so 1e-6 of the maximum."""
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     from bench_wgrad_planes import split_planes, tensor_exp
@@ -248,13 +257,9 @@ def test_weight_gradient_from_producer_split_planes_staged_by_lds_dma(hip, M):
         dW, db = torch.full((256, 260), 7.0, device=dev), torch.full((256,), 7.0, device=dev)
         ws = torch.empty(ns * (256 * 256 + 256 + 260), device=dev)
         pend = L.WgradPending()
-        if planes:
-            rc = lib.upnerf_wgrad_planes_chain(M, ptr(Ah), ptr(Al), ptr(aexp), ptr(Bh), ptr(Bl), ptr(bexp), ptr(dW), 260, ptr(db), ptr(ws), ns, ptr(ea),
-                                               ptr(eb), C.byref(pend), st())
-        else:
-            rc = lib.upnerf_wgrad_f16x3_chain(M, ptr(Ad), 256, 256, ptr(Bd), 256, 256, ptr(dW), 260, ptr(db), ptr(ws), ns, ptr(ea), ptr(eb), 2,
-                                              C.byref(pend), st())
-        L.check(rc, "wgrad")
+        a_op, b_op = ((Ah, 256, L.WG_PLANES, aexp, Al), (Bh, 256, L.WG_PLANES, bexp, Bl)) if planes else ((Ad, 256), (Bd, 256))
+        desc = wg_desc(hip, M, a_op, 256, b_op, 256, ptr(ea), ptr(eb), dW, 260, db, ws, ns)
+        L.check(lib.upnerf_wgrad16(C.byref(desc), C.byref(pend), st()), "wgrad")
         L.check(lib.upnerf_wgrad_finish(C.byref(pend), st()), "finish")
         torch.cuda.synchronize()
         assert float(dW[:, 256:].min()) == 7.0 and float(dW[:, 256:].max()) == 7.0  # the padding columns of the destination stay untouched
@@ -265,8 +270,9 @@ def test_weight_gradient_from_producer_split_planes_staged_by_lds_dma(hip, M):
         assert float((db.double() - refb).abs().max() / refb.abs().max()) < 2e-6
     assert float((res[0][0] - res[1][0]).abs().max() / res[1][0].abs().max()) < 1e-6
     # not a multiple of 64 rows: refused, the caller keeps the fp32 rows
-    assert lib.upnerf_wgrad_planes_chain(M + 16, ptr(Ah), ptr(Al), ptr(aexp), ptr(Bh), ptr(Bl), ptr(bexp), ptr(dW), 260, ptr(db), ptr(ws), ns, ptr(ea),
-                                         ptr(eb), C.byref(L.WgradPending()), st()) == -2  # UPNERF_EUNSUP
+    a_op, b_op = (Ah, 256, L.WG_PLANES, aexp, Al), (Bh, 256, L.WG_PLANES, bexp, Bl)
+    bad = wg_desc(hip, M + 16, a_op, 256, b_op, 256, ptr(ea), ptr(eb), dW, 260, db, ws, ns)
+    assert lib.upnerf_wgrad16(C.byref(bad), C.byref(L.WgradPending()), st()) == -2  # UPNERF_EUNSUP
 
 
 def test_fanout_sums_the_gradients_of_all_pairs_in_one_launch(hip):
@@ -841,7 +847,7 @@ def test_ray_part_finish_sums_the_per_32_sample_partials(hip, R, S):
 
 
 def test_wgrad_f16p_on_128_wide_fragments(hip):
-    """upnerf_wgrad_f16p with 128-wide fragment operands on both sides (candidate_encoding.2: gz_g2 x g1) against fp64."""
+    """upnerf_wgrad16 with 128-wide fragment operands (UPNERF_WG_F16_FRAG) on both sides (candidate_encoding.2: gz_g2 x g1) against fp64."""
     lib, rd, ops = hip["lib"], hip["rendering"], hip["ops"]
     dev, M = "cuda", 2999
     Mp = (M + 255) // 256 * 256
@@ -854,16 +860,16 @@ def test_wgrad_f16p_on_128_wide_fragments(hip):
     dW, db = torch.full((128, 128), 7.0, device=dev), torch.full((128,), 7.0, device=dev)
     ns = ops.nsplit_for(M)
     ws = torch.empty(ns * (256 * 256 + 256), device=dev)
-    rc = lib.lib.upnerf_wgrad_f16p(M, A16.data_ptr(), 128, ea.data_ptr(), 128, B16.data_ptr(), 128, eb.data_ptr(), 3, 128, dW.data_ptr(), 128,
-                                   db.data_ptr(), ws.data_ptr(), ns, expo.data_ptr(), expo.data_ptr() + 4, None)
-    assert rc == 0
+    desc = wg_desc(hip, M, (A16, 128, lib.WG_F16_FRAG, ea), 128, (B16, 128, lib.WG_F16_FRAG, eb), 128, expo.data_ptr(), expo.data_ptr() + 4,
+                   dW, 128, db, ws, ns)
+    assert lib.lib.upnerf_wgrad16(C.byref(desc), None, None) == 0
     torch.cuda.synchronize()
     assert rel_err(cpu(dW), cpu(A.t() @ B)) < 1e-5 and rel_err(cpu(db), cpu(A.sum(0))) < 1e-5
 
 
 @pytest.mark.parametrize("M,n2", [(3000, 0), (3000, 128), (100, 128)])
 def test_wgrad_f16p_chain_on_fragments_with_a_split_result(hip, M, n2):
-    """upnerf_wgrad_f16p_chain with both operands as fp16 fragments (b_is_f16 = 3) and the result split by rows between two
+    """A chained upnerf_wgrad16 with both operands as fp16 fragments (UPNERF_WG_F16_FRAG) and the result split by rows between two
     destinations, finished by upnerf_wgrad_finish, against fp64 on the decoded values."""
     lib, rd, ops = hip["lib"], hip["rendering"], hip["ops"]
     from upnerf_amd._lib import WgradPending
@@ -881,11 +887,9 @@ def test_wgrad_f16p_chain_on_fragments_with_a_split_result(hip, M, n2):
     ns = ops.nsplit_for(M)
     ws = torch.empty(ns * (256 * 256 + 256), device=dev)
     pend = WgradPending()
-    rc = lib.lib.upnerf_wgrad_f16p_chain(M, A16.data_ptr(), 256, ea.data_ptr(), 256, B16.data_ptr(), 256, eb.data_ptr(), 3, 256,
-                                         dW.data_ptr(), 256, db.data_ptr(), n2, dW2.data_ptr() if n2 else None, 300,
-                                         db2.data_ptr() if n2 else None, ws.data_ptr(), ns, expo.data_ptr(), expo.data_ptr() + 4,
-                                         C.byref(pend), None)
-    assert rc == 0
+    desc = wg_desc(hip, M, (A16, 256, lib.WG_F16_FRAG, ea), 256, (B16, 256, lib.WG_F16_FRAG, eb), 256, expo.data_ptr(), expo.data_ptr() + 4,
+                   dW, 256, db, ws, ns, n2=n2, dW2=dW2 if n2 else None, ldo2=300, db2=db2 if n2 else None)
+    assert lib.lib.upnerf_wgrad16(C.byref(desc), C.byref(pend), None) == 0
     assert lib.lib.upnerf_wgrad_finish(C.byref(pend), None) == 0
     torch.cuda.synchronize()
     ref, refb = A.t() @ B, A.sum(0)
@@ -1197,7 +1201,7 @@ def test_fused_transient_net_matches_torch(hip, R):
 @pytest.mark.parametrize("field_mode", ["f16x3", "f16"], indirect=True)
 @pytest.mark.parametrize("R,S", [(7, 40), (3, 256)])
 def test_joined_head_gradients_match_the_separate_launches(hip, R, S, field_mode):
-    """[gz_r1 | gz_g1] stored as one tensor and contracted against e in ONE launch (upnerf_wgrad_f16x3_chain2, rows split
+    """[gz_r1 | gz_g1] stored as one tensor and contracted against e in ONE launch (upnerf_wgrad_desc.n2: rows split
     between the colour and the candidate head) against one launch per head: the same sums under one joint power-of-two scale
     instead of two (differences at the 2^-22 level of the f16x3 split, 1e-2 in the f16 mode), everything else bitwise."""
     from upnerf_amd import synth
@@ -1252,7 +1256,7 @@ def test_joined_head_gradients_match_the_separate_launches(hip, R, S, field_mode
 
 @pytest.mark.parametrize("field_mode", ["f16x3", "f16"], indirect=True)
 def test_chained_slab_reductions_are_bitwise_the_separate_ones(hip, field_mode):
-    """upnerf_wgrad_f16x3_chain (the slabs of one weight gradient summed by the first workgroups of the next launch) against
+    """upnerf_wgrad16 on a pending record (the slabs of one weight gradient summed by the first workgroups of the next launch) against
     one reduction launch per weight gradient: same slabs, same summation order -- every parameter gradient bit for bit."""
     from upnerf_amd import synth
     from upnerf_amd.nerf import NeRF
@@ -1287,7 +1291,7 @@ def test_chained_slab_reductions_are_bitwise_the_separate_ones(hip, field_mode):
 
 @pytest.mark.parametrize("field_mode", ["f16x3", "f16"], indirect=True)
 def test_density_head_gradient_riding_on_the_final_layer_launch_matches_the_separate_one(hip, field_mode):
-    """upnerf_wgrad_f16x3_chain_v (round 5): the shared density head reads the B operand of the final layer's weight gradient
+    """upnerf_wgrad_desc.v (round 5): the shared density head reads the B operand of the final layer's weight gradient
     (models/nerf.py:89, 93), so its gradient dw_sigma = sum_m dpre_s[m] h[m][:] is summed inside that launch from the rows as
     they pass instead of by upnerf_vec_wgrad on a second read of h.  Same fp32 products in another summation order: 2e-6 of
     the vector's maximum; everything else of the pass bit for bit; and against fp64 on a stand-alone problem with a ragged
@@ -1329,17 +1333,18 @@ def test_density_head_gradient_riding_on_the_final_layer_launch_matches_the_sepa
     rest[sig] = False
     rest[L.bsig] = False
     assert torch.equal(dP0[rest], dP1[rest])
-    if field_mode != "f16x3":  # (f16: upnerf_wgrad_f16p_chain_v on the register-resident kernels' fragments; the pass above is its test)
+    if field_mode != "f16x3":  # (f16: the head rides on the register-resident kernels' fragments; the pass above is its test)
         return
     # stand-alone, ragged M, against fp64
     M = 64 * 37 + 5
     A, B, v = gen((M, 256), 90).cuda() * 1e-3, torch.relu(gen((M, 256), 91)).cuda(), gen((M,), 92).cuda()
     dW, db, dv, dbv = (torch.empty(n, device="cuda") for n in (256 * 256, 256, 256, 1))
-    chain = ops.WgradChain(A.device)
+    run = ops.WgradRun(A.device, chained=True)
     expo = ops.scale_exponents(A, B)
     ea, eb = (expo.data_ptr(), expo.data_ptr() + 4) if isinstance(expo, torch.Tensor) else expo
-    chain.wgrad(M, A, 256, 256, B, 256, 256, dW.data_ptr(), 256, db.data_ptr(), ea, eb, v=v, dv_ptr=dv.data_ptr(), dbv_ptr=dbv.data_ptr())
-    chain.finish()
+    run.wgrad(M, ops.WgOp(A, 256), 256, ops.WgOp(B, 256), 256, ea, eb, dW=dW.data_ptr(), ldo=256, db=db.data_ptr(), v=v, dv=dv.data_ptr(),
+              dbv=dbv.data_ptr())
+    run.finish()
     torch.cuda.synchronize()
     ref_v = (v.double()[:, None] * B.double()).sum(0)
     ref_W = A.double().t() @ B.double()
@@ -1347,6 +1352,79 @@ def test_density_head_gradient_riding_on_the_final_layer_launch_matches_the_sepa
     assert abs(float(dbv[0]) - float(v.double().sum())) <= 2e-6 * float(v.double().abs().sum())
     assert float((dW.double().view(256, 256) - ref_W).abs().max() / ref_W.abs().max()) < 2e-6
     assert float((db.double() - A.double().sum(0)).abs().max() / A.double().sum(0).abs().max()) < 2e-6
+
+
+@pytest.mark.parametrize("M,Mf,ns", [(200, 256, 1), (200, 256, 3), (16360, 16384, 256)])
+def test_a_mixed_run_on_one_pending_record_is_bitwise_the_unchained_one(hip, M, Mf, ns):
+    """Five upnerf_wgrad16 links of different operand kinds and shapes on ONE pending record against the same five descriptors with
+    pending = NULL (each summed at once by its own reduction launch): same slabs, same summation order -- every result bit for
+    bit -- and each within the fp64 tolerance of its kind (2e-6 of the maximum for fp32 rows and the riding head, 1e-5 for the
+    fp16-stored kinds on the values they decode to).
+      1. fp32 rows 256 x 64    2. fp32 rows 256 x 256 + riding head    3. fp16 tiles 256 x 256
+      4. fp16 fragments 256 x 256, rows [128, 256) to a second destination    5. fp32 rows 128 x 128
+    M rows for the row-major links (200: ragged against the 64-row tiles and the 32-row chunks), Mf for the fragments.  Every
+    shape is one block, so a launch has `ns` workgroups, and a pending 256 x 64 / 128 x 128 problem wants 64 of them for its
+    reduction, a 256 x 256 one 256.  ns = 1, 3: every link after the first finds more pending reduction blocks than it has
+    workgroups and takes the FLUSH path (a reduction launch before its own).  ns = 256 (64 rows per split): links 2 to 5 all CARRY
+    the previous reduction in their prologue.  Link 1 finds nothing pending; upnerf_wgrad_finish sums link 5."""
+    L, ops, rd = hip["lib"], hip["ops"], hip["rendering"]
+    lib, dev = L.lib, "cuda"
+    f32 = lambda shape, seed, relu=False: (torch.relu(gen(shape, seed)) if relu else gen(shape, seed) * 1e-3).to(dev)
+    A1, B1, A2, B2, A5, B5 = (f32((M, 256), 100), f32((M, 64), 101, True), f32((M, 256), 102), f32((M, 256), 103, True),
+                              f32((M, 128), 104), f32((M, 128), 105, True))
+    v = gen((M,), 106).to(dev)
+    e1, e2, e5 = ops.scale_exponents(A1, B1), ops.scale_exponents(A2, B2), ops.scale_exponents(A5, B5)
+    e16 = torch.tensor([3, 3], device=dev, dtype=torch.int32)  # tensor-wide exponents of the fp16-stored links: |x| < 1 -> |x * 2^3| < 8
+    texp = lambda n, seed: torch.randint(-2, 3, (n,), generator=torch.Generator().manual_seed(seed)).to(torch.int32).to(dev)
+    ta, tb, fa, fb = texp((M + 63) // 64, 1), texp((M + 63) // 64, 2), texp(Mf // 32, 3), texp(Mf // 32, 4)
+    tile16 = lambda x, t: (x * torch.ldexp(torch.ones((), device=dev), t.float()).repeat_interleave(64)[:M, None]).to(torch.float16)
+    A3, B3 = tile16(gen((M, 256), 107).to(dev), ta), tile16(gen((M, 256), 108).to(dev), tb)
+    A4, B4 = rd.quant16_frag(gen((Mf, 256), 109).to(dev), fa), rd.quant16_frag(gen((Mf, 256), 110).to(dev), fb)
+    at = lambda e, i: e.data_ptr() + 4 * i
+
+    def run(chained):
+        o = {k: torch.full(shape, 7.0, device=dev) for k, shape in dict(
+            W1=(256, 64), b1=(256,), W2=(256, 256), b2=(256,), dv=(256,), dbv=(1,), W3=(256, 256), b3=(256,), W4=(128, 256), b4=(128,),
+            W4b=(128, 256), b4b=(128,), W5=(128, 128), b5=(128,)).items()}
+        links = [
+            wg_desc(hip, M, (A1, 256), 256, (B1, 64), 64, at(e1, 0), at(e1, 1), o["W1"], 64, o["b1"], None, ns),
+            wg_desc(hip, M, (A2, 256), 256, (B2, 256), 256, at(e2, 0), at(e2, 1), o["W2"], 256, o["b2"], None, ns, v=v, dv=o["dv"], dbv=o["dbv"]),
+            wg_desc(hip, M, (A3, 256, L.WG_F16_TILE, ta), 256, (B3, 256, L.WG_F16_TILE, tb), 256, at(e16, 0), at(e16, 1), o["W3"], 256,
+                    o["b3"], None, ns),
+            wg_desc(hip, Mf, (A4, 256, L.WG_F16_FRAG, fa), 256, (B4, 256, L.WG_F16_FRAG, fb), 256, at(e16, 0), at(e16, 1), o["W4"], 256,
+                    o["b4"], None, ns, n2=128, dW2=o["W4b"], ldo2=256, db2=o["b4b"]),
+            wg_desc(hip, M, (A5, 128), 128, (B5, 128), 128, at(e5, 0), at(e5, 1), o["W5"], 128, o["b5"], None, ns),
+        ]  # (slabs: set below, from upnerf_wgrad16_scratch)
+        need = max(lib.upnerf_wgrad16_scratch(C.byref(d)) for d in links)
+        assert need == ns * (256 * 256 + 256 + 260)  # the 256 x 256 link with its riding head
+        ws = [torch.empty(need, device=dev) for _ in range(2)]
+        pend = L.WgradPending() if chained else None
+        carried = []
+        for i, d in enumerate(links):
+            d.slabs = ws[i & 1].data_ptr()
+            carried.append(chained and pend.nsplit > 0 and pend.rblocks <= ns)
+            assert lib.upnerf_wgrad16(C.byref(d), C.byref(pend) if chained else None, None) == 0
+        if chained:
+            assert carried == [False] + [ns == 256] * 4  # flush path for ns = 1, 3; prologue for ns = 256
+            assert lib.upnerf_wgrad_finish(C.byref(pend), None) == 0 and pend.nsplit == 0
+        torch.cuda.synchronize()
+        return o
+
+    got, alone = run(True), run(False)
+    for k in got:
+        assert torch.equal(got[k], alone[k]), k
+    near = lambda x, ref: float((x.double() - ref).abs().max() / ref.abs().max())
+    for W, b, A, B in ((got["W1"], got["b1"], A1, B1), (got["W2"], got["b2"], A2, B2), (got["W5"], got["b5"], A5, B5)):
+        assert near(W, A.double().t() @ B.double()) < 2e-6 and near(b, A.double().sum(0)) < 2e-6
+    assert near(got["dv"], (v.double()[:, None] * B2.double()).sum(0)) < 2e-6
+    assert abs(float(got["dbv"][0]) - float(v.double().sum())) <= 2e-6 * float(v.double().abs().sum())
+    A3d, B3d = rd.dequant16(A3[None], ta[None])[0].double(), rd.dequant16(B3[None], tb[None])[0].double()
+    assert rel_err(cpu(got["W3"]), cpu(A3d.t() @ B3d)) < 1e-5 and rel_err(cpu(got["b3"]), cpu(A3d.sum(0))) < 1e-5
+    A4d = rd.dequant16(A4[None], fa[None], frag=True)[0].double()
+    B4d = rd.dequant16(B4[None], fb[None], frag=True)[0].double()
+    ref, refb = A4d.t() @ B4d, A4d.sum(0)
+    assert rel_err(cpu(got["W4"]), cpu(ref[:128])) < 1e-5 and rel_err(cpu(got["b4"]), cpu(refb[:128])) < 1e-5
+    assert rel_err(cpu(got["W4b"]), cpu(ref[128:])) < 1e-5 and rel_err(cpu(got["b4b"]), cpu(refb[128:])) < 1e-5
 
 
 def test_adam_update_with_gradients_in_place_is_bitwise_the_flat_one(hip):

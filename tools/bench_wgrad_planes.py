@@ -1,4 +1,4 @@
-"""The DMA-staged weight-gradient kernel on producer-split operands (upnerf_wgrad_planes_chain, round 6) against the shipped
+"""The DMA-staged weight-gradient kernel on producer-split operands (upnerf_wgrad16 on UPNERF_WG_PLANES operands, round 6) against the shipped
 f16x3 kernel on the fp32 rows those planes decode to: accuracy of both against fp64, bitwise / relative difference between the
 two, launch time (HIP events, kernel + the chained reduction of the previous problem, as inside a training step).
 
@@ -14,7 +14,7 @@ import torch
 
 from upnerf_amd import _lib
 from upnerf_amd._lib import check, lib, ptr, stream
-from upnerf_amd.ops import nsplit_for, workspace
+from upnerf_amd.ops import WgOp, nsplit_for, workspace
 
 
 def split_planes(x, relu):
@@ -51,18 +51,19 @@ def main():
     ea = torch.tensor([tensor_exp(Ad)], dtype=torch.int32, device=dev)
     eb = torch.tensor([tensor_exp(Bd)], dtype=torch.int32, device=dev)
     ns = nsplit_for(M)
-    ws = [workspace(f"bwp{i}", ns * (256 * 256 + 256 + 260), dev) for i in range(2)]
+    ws = [workspace(f"bwp{i}", ns * (256 * 256 + 256), dev) for i in range(2)]  # upnerf_wgrad16_scratch for 256 x 256
     out = {}
     for name in ("f16x3 on fp32 rows", "planes + LDS-DMA"):
         dW, db = torch.zeros(256, 256, device=dev), torch.zeros(256, device=dev)
         pend = _lib.WgradPending()
 
-        def launch(i, dW=dW, db=db, pend=pend, name=name):
-            if name.startswith("f16x3"):
-                return lib.upnerf_wgrad_f16x3_chain(M, ptr(Ad), 256, 256, ptr(Bd), 256, 256, ptr(dW), 256, ptr(db), ptr(ws[i & 1]), ns, ptr(ea), ptr(eb),
-                                                   2, C.byref(pend), stream())
-            return lib.upnerf_wgrad_planes_chain(M, ptr(Ah), ptr(Al), ptr(aexp), ptr(Bh), ptr(Bl), ptr(bexp), ptr(dW), 256, ptr(db), ptr(ws[i & 1]), ns,
-                                                 ptr(ea), ptr(eb), C.byref(pend), stream())
+        a_op, b_op = ((WgOp(Ad, 256), WgOp(Bd, 256)) if name.startswith("f16x3") else
+                      (WgOp(Ah, 256, _lib.WG_PLANES, aexp, Al), WgOp(Bh, 256, _lib.WG_PLANES, bexp, Bl)))
+        desc = [_lib.WgradDesc(M=M, N=256, K=256, planes=2, A=a_op.c(), B=b_op.c(), expo_a=ptr(ea), expo_b=ptr(eb), dW=ptr(dW), db=ptr(db),
+                               ldo=256, nsplit=ns, slabs=ptr(w)) for w in ws]
+
+        def launch(i, desc=desc, pend=pend):
+            return lib.upnerf_wgrad16(C.byref(desc[i & 1]), C.byref(pend), stream())
 
         check(launch(0), name)
         check(lib.upnerf_wgrad_finish(C.byref(pend), stream()), "finish")

@@ -126,6 +126,19 @@ class WgradPending(C.Structure):
                 ("dW2", _fp), ("db2", _fp), ("ldo2", C.c_int32), ("pad", C.c_int32), ("vslabs", _fp), ("dv", _fp), ("dbv", _fp)]
 
 
+WG_F32, WG_F16_TILE, WG_F16_FRAG, WG_F24, WG_PLANES = range(5)  # UPNERF_WG_*: how a weight-gradient operand is stored
+
+
+class WgradOperand(C.Structure):
+    _fields_ = [("p", _fp), ("lo", _fp), ("exp", _fp), ("ld", C.c_int32), ("kind", C.c_int32)]
+
+
+class WgradDesc(C.Structure):
+    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("planes", C.c_int32), ("A", WgradOperand), ("B", WgradOperand),
+                ("expo_a", _fp), ("expo_b", _fp), ("dW", _fp), ("db", _fp), ("ldo", C.c_int32), ("n2", C.c_int32), ("dW2", _fp),
+                ("db2", _fp), ("ldo2", C.c_int32), ("nsplit", C.c_int32), ("v", _fp), ("dv", _fp), ("dbv", _fp), ("slabs", _fp)]
+
+
 class WgradGroup(C.Structure):
     _fields_ = [("A", _fp), ("B", _fp), ("dW", _fp), ("db", _fp), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
                 ("lda", C.c_int32), ("ldb", C.c_int32), ("ldo", C.c_int32)]
@@ -242,22 +255,11 @@ _SIGNATURES = {
     "upnerf_field_bwd_f16x3": [C.POINTER(Layout), C.POINTER(FieldBwdArgs), _p],
     "upnerf_frag16": [_p, _p, _p, C.POINTER(Frag16Desc), _i, C.POINTER(Frag16Desc), _i, _p, _p, _i, _i, _p, _p],
     "upnerf_wgrad": [_i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _i, _p],
-    "upnerf_wgrad_f16x3": [_i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _i, _p, _p, _i, _p],
-    "upnerf_wgrad_f16x3_chain": [_i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _i, _p, _p, _i, _p, _p],
-    "upnerf_wgrad_f16x3_chain2": [_i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _p, _p],
-    # (M, A, lda, N, B, ldb, K, dW, ldo, db, v, dv, dbv, slabs, nsplit, expo_a, expo_b, planes, pending, stream)
-    "upnerf_wgrad_f16x3_chain_v": [_i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p],
-    # (M, A16, aexp, B16, bexp, dW, ldo, db, v, dv, dbv, slabs, nsplit, expo_a, expo_b, pending, stream)
-    "upnerf_wgrad_f16p_chain_v": [_i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p],
+    "upnerf_wgrad16_scratch": [C.POINTER(WgradDesc)],
+    "upnerf_wgrad16": [C.POINTER(WgradDesc), C.POINTER(WgradPending), _p],
     "upnerf_wgrad_finish": [_p, _p],
     "upnerf_transient_fwd": [_p, _p],
     "upnerf_transient_bwd": [_p, _p, _p],
-    "upnerf_wgrad_f16p": [_i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p],
-    "upnerf_wgrad_f16p_chain": [_i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p,
-                                C.POINTER(WgradPending), _p],
-    "upnerf_wgrad_f24p_chain": [_i, _p, _p, _i, _p, _i, _p, _p, _i, _p, _i, _i, _p, _i, _p, _p, _i, _p, _p, C.POINTER(WgradPending), _p],
-    # (M, A16, Alo16, aexp, B16, Blo16, bexp, dW, ldo, db, slabs, nsplit, expo_a, expo_b, pending, stream)
-    "upnerf_wgrad_planes_chain": [_i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, C.POINTER(WgradPending), _p],
     "upnerf_wgrad_grouped_scratch": [C.POINTER(WgradGroup), _i, _i],
     "upnerf_wgrad_grouped": [C.POINTER(WgradGroup), _i, _p, _i, _p],
     "upnerf_vec_wgrad": [_i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _i, _p],
@@ -311,12 +313,12 @@ def _load():
         if fn is None:
             raise ImportError(f"{LIB_PATH} does not export {name}; rebuild it")
         fn.argtypes = argtypes
-        fn.restype = C.c_int
+        fn.restype = C.c_longlong if name == "upnerf_wgrad16_scratch" else C.c_int
     return lib
 
 
 lib = _load()
-ABI_VERSION = 10
+ABI_VERSION = 11
 if lib.upnerf_abi_version() != ABI_VERSION:
     raise ImportError("libupnerf_hip.so ABI version mismatch; rebuild it")
 

@@ -406,7 +406,7 @@ __device__ __forceinline__ void store_policy(T* p, const T& v) {
 #endif
 
 // ---- fixed-order reduction of weight-gradient slabs (upnerf_wgrad*): the work of ONE 512-thread block `bid` of the reduce
-// grid, callable from the reduce kernel and from the prologue of the NEXT weight-gradient kernel (upnerf_wgrad_f16x3_chain).
+// grid, callable from the reduce kernel and from the prologue of the NEXT weight-gradient kernel (upnerf_wgrad16 with a pending record).
 // dW[n][k] = sum_split slab[split][by][bz][n%TN][k%TK]; one thread per 4 consecutive k (16-byte loads); the splits are dealt
 // round-robin to 8 thread groups whose partial sums meet in LDS (`part`, 8 KiB); each group keeps 8 loads in flight.
 #define RED_RG 8

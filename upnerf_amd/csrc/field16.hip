@@ -326,7 +326,7 @@ __device__ __forceinline__ void tile_copy16(const char* Ph, int e, int e2, uint1
 }
 // The lo plane of the tile -> row-major byte tensor: the rounding residual of every element in 1/32 of the tile's scaled unit,
 // byte = round(32 lo) + 128 (|lo| <= half an ulp of a value below 2^14: |32 lo| <= 128, clamped to 127).  With the hi plane
-// (tile_copy16) that is the "24-bit" storage of the weight-gradient operands (upnerf_wgrad_f24p): hi + lo to 2^-20 of the
+// (tile_copy16) that is the "24-bit" storage of the weight-gradient operands (UPNERF_WG_F24): hi + lo to 2^-20 of the
 // tile's maximum in 3 bytes.  The fp16 magic-number add rounds to nearest and leaves the byte in the low mantissa bits.
 template <int W, int TILE, int THREADS>
 __device__ __forceinline__ void tile_copy8(const char* Pl, uint8_t* __restrict__ dst, int m0, int M, int tid) {

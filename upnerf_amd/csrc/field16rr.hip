@@ -34,7 +34,7 @@
 // What leaves the kernel (all written in whole 1 KiB pieces):
 //   h16 / gz16   trunk activations / pre-activation gradients as the operand fragments themselves -- [layer][32-row tile]
 //                [k-block 0..15][lane][8 fp16], the tile's exponent beside them (hexp / gzexp [layer][tile]) -- what
-//                upnerf_wgrad_f16p(frag = 1) contracts;
+//                upnerf_wgrad16 (UPNERF_WG_F16_FRAG) contracts;
 //   fp32 rows    (x0, e, g1, g2, r1, h_{D-1}; gz_e, gz_g1, gz_g2, gz_r1) through a 4 KiB per-wave LDS transposer, 8 rows x
 //                128 B per store instruction;
 //   hmask        ReLU sign bits, 128 per lane and layer (two 64-bit words), in this kernel pair's own layout.

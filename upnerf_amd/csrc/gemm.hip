@@ -10,10 +10,11 @@
 //   MFMA orientation: lane (i, h) feeds A-operand A[m+h][n0+i] and B-operand B[m+h][k0+i]; both are plain
 //   ds_read_b32 of 32 consecutive floats per half-wave (bank-conflict free without padding).
 #include "common.cuh"
+#include "wgrad_host.h"
+
+using namespace upnerf_host;
 
 namespace {
-
-#define WG_CHUNK 32
 
 // One [64 MTW x 64 NTW] block of  sum_{m in [mbeg, mend)} A[m][nblk + n] B[m][kblk + k]  -> slab (row-major [TN][TK]);
 // column sums of A -> bslab [TN] when given.  The whole workgroup works on the block.
@@ -202,16 +203,6 @@ __global__ __launch_bounds__(NTHREADS) void wgrad_grouped_reduce_kernel(WgradGro
 __global__ __launch_bounds__(RED_THREADS) void wgrad_reduce_kernel(upnerf_wgrad_pending P) {
   __shared__ f32x4 part[RED_RG][64];
   wgrad_reduce_body(blockIdx.x, threadIdx.x, P, part);
-}
-static upnerf_wgrad_pending reduce_desc(int N, int K, int TN, int TK, int nsplit, const float* slabs, const float* bslabs, float* dW,
-                                        int ldo, float* db) {
-  const int quads = N * (K / 4);
-  int rblocks = (quads + 63) / 64;
-  if (rblocks * NTHREADS < N) rblocks = (N + NTHREADS - 1) / NTHREADS;
-  return upnerf_wgrad_pending{slabs, bslabs, dW, db, N, K, TN, TK, nsplit, ldo, rblocks, 0, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr};
-}
-static void launch_reduce(hipStream_t st, const upnerf_wgrad_pending& P) {
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(P.rblocks), dim3(RED_THREADS), 0, st, P);
 }
 
 // ---- N = 1 / 3 heads: dw[c][k] = sum_m v[m][c] X[m][k].  HBM-bound stream of X: every lane owns 4 columns
@@ -759,9 +750,19 @@ int launch_wgrad(int M, const float* A, int lda, int N, const float* B, int ldb,
 
 // Scratch needed by upnerf_wgrad for (N, K, nsplit): nsplit * (roundup(N) * roundup(K) + roundup(N)) floats,
 // where roundup() is to the block shape chosen below (<= 256).
-static void wgrad_shape(int N, int K, int* TN, int* TK) {
+void upnerf_host::wgrad_shape(int N, int K, int* TN, int* TK) {
   *TN = N >= 256 ? 256 : (N > 64 ? 128 : 64);
   *TK = K >= 256 ? 256 : (K > 64 ? 128 : 64);
+}
+upnerf_wgrad_pending upnerf_host::reduce_desc(int N, int K, int TN, int TK, int nsplit, const float* slabs, const float* bslabs, float* dW,
+                                              int ldo, float* db) {
+  const int quads = N * (K / 4);
+  int rblocks = (quads + 63) / 64;
+  if (rblocks * NTHREADS < N) rblocks = (N + NTHREADS - 1) / NTHREADS;
+  return upnerf_wgrad_pending{slabs, bslabs, dW, db, N, K, TN, TK, nsplit, ldo, rblocks, 0, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr};
+}
+void upnerf_host::launch_reduce(hipStream_t st, const upnerf_wgrad_pending& P) {
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(P.rblocks), dim3(RED_THREADS), 0, st, P);
 }
 
 extern "C" int upnerf_wgrad(int M, const float* A, int lda, int N, const float* B, int ldb, int K, float* dW, int ldo,
@@ -790,225 +791,12 @@ extern "C" int upnerf_wgrad(int M, const float* A, int lda, int N, const float* 
   return (int)hipGetLastError();
 }
 
-extern "C" int upnerf_wgrad_f16x3_partial(int M, const float* A, int lda, int N, const float* B, int ldb, int K,
-                                          const int* expo_a, const int* expo_b, float* slabs, float* bslabs,
-                                          int nsplit, int rows, int TN, int TK, int planes, const upnerf_wgrad_pending* prev,
-                                          void* stream);
-
-// Same contract as upnerf_wgrad, contraction on the f16 matrix cores (wgrad_f16x3.hip): planes 0 / 2 = 3-term hi/lo
-// split (fp32-level accuracy), planes 1 = operands rounded to fp16, one MFMA per block.
-// expo_a, expo_b: DEVICE ints: A is scaled by 2^*expo_a and B by 2^*expo_b before the conversion to fp16.
-extern "C" int upnerf_wgrad_f16x3(int M, const float* A, int lda, int N, const float* B, int ldb, int K, float* dW,
-                                  int ldo, float* db, float* slabs, int nsplit, const int* expo_a, const int* expo_b,
-                                  int planes, void* stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !dW || !slabs || nsplit <= 0 || !expo_a || !expo_b)
-    return UPNERF_EINVAL;
-  if (planes != 0 && planes != 1 && planes != 2) return UPNERF_EINVAL;
-  if ((N & 3) || (K & 3) || (lda & 3) || (ldb & 3) || (ldo & 3)) return UPNERF_EINVAL;
-  int TN, TK;
-  wgrad_shape(N, K, &TN, &TK);
-  hipStream_t st = (hipStream_t)stream;
-  const int rows = (((M + nsplit - 1) / nsplit) + WG_CHUNK - 1) / WG_CHUNK * WG_CHUNK;
-  const int gy = (N + TN - 1) / TN, gz = (K + TK - 1) / TK;
-  float* bslabs = slabs + (size_t)nsplit * gy * gz * TN * TK;
-  int rc = upnerf_wgrad_f16x3_partial(M, A, lda, N, B, ldb, K, expo_a, expo_b, slabs, bslabs, nsplit, rows, TN, TK,
-                                      planes, nullptr, stream);
-  if (rc) return rc;
-  launch_reduce(st, reduce_desc(N, K, TN, TK, nsplit, slabs, bslabs, dW, ldo, db));
-  return (int)hipGetLastError();
-}
-
 extern "C" int upnerf_wgrad_finish(upnerf_wgrad_pending* p, void* stream) {
   if (!p) return UPNERF_EINVAL;
   if (p->nsplit <= 0) return 0;
   launch_reduce((hipStream_t)stream, *p);
   p->nsplit = 0;
   return (int)hipGetLastError();
-}
-
-// Chained upnerf_wgrad_f16x3 (include/upnerf_hip.h): the previous problem's slabs are summed by this launch's first workgroups.
-extern "C" int upnerf_wgrad_f16x3_chain2(int M, const float* A, int lda, int N, const float* B, int ldb, int K, float* dW, int ldo,
-                                         float* db, int n2, float* dW2, int ldo2, float* db2, float* slabs, int nsplit,
-                                         const int* expo_a, const int* expo_b, int planes, upnerf_wgrad_pending* pending,
-                                         void* stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !dW || !slabs || nsplit <= 0 || !expo_a || !expo_b || !pending)
-    return UPNERF_EINVAL;
-  if (planes != 0 && planes != 1 && planes != 2) return UPNERF_EINVAL;
-  if ((N & 3) || (K & 3) || (lda & 3) || (ldb & 3) || (ldo & 3)) return UPNERF_EINVAL;
-  if (n2 < 0 || n2 >= N || (n2 > 0 && (!dW2 || (ldo2 & 3)))) return UPNERF_EINVAL;
-  if (pending->nsplit > 0 && pending->slabs == slabs) return UPNERF_EINVAL;  // the pending slabs would be overwritten
-  int TN, TK;
-  wgrad_shape(N, K, &TN, &TK);
-  const int rows = (((M + nsplit - 1) / nsplit) + WG_CHUNK - 1) / WG_CHUNK * WG_CHUNK;
-  const int gy = (N + TN - 1) / TN, gz = (K + TK - 1) / TK;
-  float* bslabs = slabs + (size_t)nsplit * gy * gz * TN * TK;
-  if (pending->nsplit > 0 && pending->rblocks > nsplit * gy * gz) {  // grid too small to carry the previous reduction
-    int rc = upnerf_wgrad_finish(pending, stream);
-    if (rc) return rc;
-  }
-  int rc = upnerf_wgrad_f16x3_partial(M, A, lda, N, B, ldb, K, expo_a, expo_b, slabs, bslabs, nsplit, rows, TN, TK, planes,
-                                      pending->nsplit > 0 ? pending : nullptr, stream);
-  if (rc) return rc;
-  upnerf_wgrad_pending P = reduce_desc(N, K, TN, TK, nsplit, slabs, bslabs, dW, ldo, db);
-  P.n2 = n2;
-  P.dW2 = dW2;
-  P.db2 = db2;
-  P.ldo2 = ldo2;
-  *pending = P;
-  return 0;
-}
-
-extern "C" int upnerf_wgrad_f16x3_partial_v(int M, const float* A, int lda, const float* B, int ldb, const float* v, const int* expo_a,
-                                            const int* expo_b, float* slabs, float* bslabs, float* vslabs, int nsplit, int rows,
-                                            const upnerf_wgrad_pending* prev, void* stream);  // csrc/wgrad_f16x3.hip
-
-// upnerf_wgrad_f16x3_chain + the 1-wide head that shares B (include/upnerf_hip.h)
-extern "C" int upnerf_wgrad_f16x3_chain_v(int M, const float* A, int lda, int N, const float* B, int ldb, int K, float* dW, int ldo,
-                                          float* db, const float* v, float* dv, float* dbv, float* slabs, int nsplit,
-                                          const int* expo_a, const int* expo_b, int planes, upnerf_wgrad_pending* pending,
-                                          void* stream) {
-  if (M <= 0 || !A || !B || !dW || !v || !dv || !slabs || nsplit <= 0 || !expo_a || !expo_b || !pending) return UPNERF_EINVAL;
-  if (N != 256 || K != 256 || planes != 2) return UPNERF_EUNSUP;
-  if ((lda & 3) || (ldb & 3) || (ldo & 3)) return UPNERF_EINVAL;
-  if (pending->nsplit > 0 && pending->slabs == slabs) return UPNERF_EINVAL;
-  const int TN = 256, TK = 256;
-  const int rows = (((M + nsplit - 1) / nsplit) + WG_CHUNK - 1) / WG_CHUNK * WG_CHUNK;
-  float* bslabs = slabs + (size_t)nsplit * TN * TK;
-  float* vslabs = bslabs + (size_t)nsplit * TN;
-  if (pending->nsplit > 0 && pending->rblocks > nsplit) {  // grid too small to carry the previous reduction
-    int rc = upnerf_wgrad_finish(pending, stream);
-    if (rc) return rc;
-  }
-  int rc = upnerf_wgrad_f16x3_partial_v(M, A, lda, B, ldb, v, expo_a, expo_b, slabs, bslabs, vslabs, nsplit, rows,
-                                        pending->nsplit > 0 ? pending : nullptr, stream);
-  if (rc) return rc;
-  upnerf_wgrad_pending P = reduce_desc(N, K, TN, TK, nsplit, slabs, bslabs, dW, ldo, db);
-  P.vslabs = vslabs;
-  P.dv = dv;
-  P.dbv = dbv;
-  *pending = P;
-  return 0;
-}
-
-extern "C" int upnerf_wgrad_f16x3_chain(int M, const float* A, int lda, int N, const float* B, int ldb, int K, float* dW, int ldo,
-                                        float* db, float* slabs, int nsplit, const int* expo_a, const int* expo_b, int planes,
-                                        upnerf_wgrad_pending* pending, void* stream) {
-  return upnerf_wgrad_f16x3_chain2(M, A, lda, N, B, ldb, K, dW, ldo, db, 0, nullptr, 0, nullptr, slabs, nsplit, expo_a, expo_b, planes,
-                                   pending, stream);
-}
-
-extern "C" int upnerf_wgrad_f16p_partial(int M, const uint16_t* A16, int lda, const int* aexp, int N, const void* B, int ldb,
-                                         const int* bexp, int b_is_f16, int K, const int* expo_a, const int* expo_b, float* slabs,
-                                         float* bslabs, int nsplit, int rows, int TN, int TK, const upnerf_wgrad_pending* prev,
-                                         const uint8_t* Alo, const uint8_t* Blo, void* stream);
-
-// upnerf_wgrad with fp16-stored, tile-scaled operands (the f16 field mode): same slabs + fixed-order reduction.
-extern "C" int upnerf_wgrad_f16p(int M, const uint16_t* A16, int lda, const int32_t* aexp, int N, const void* B, int ldb,
-                                 const int32_t* bexp, int b_is_f16, int K, float* dW, int ldo, float* db, float* slabs, int nsplit,
-                                 const int* expo_a, const int* expo_b, void* stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || !A16 || !aexp || !B || !dW || !slabs || nsplit <= 0 || !expo_a || !expo_b)
-    return UPNERF_EINVAL;
-  if ((b_is_f16 & 1) && !bexp) return UPNERF_EINVAL;
-  if ((N & 7) || (K & 7) || (lda & 7) || (ldb & 7) || (ldo & 3)) return UPNERF_EINVAL;
-  int TN, TK;
-  wgrad_shape(N, K, &TN, &TK);
-  hipStream_t st = (hipStream_t)stream;
-  const int rows = (((M + nsplit - 1) / nsplit) + WG_CHUNK - 1) / WG_CHUNK * WG_CHUNK;
-  const int gy = (N + TN - 1) / TN, gz = (K + TK - 1) / TK;
-  float* bslabs = slabs + (size_t)nsplit * gy * gz * TN * TK;
-  int rc = upnerf_wgrad_f16p_partial(M, A16, lda, aexp, N, B, ldb, bexp, b_is_f16, K, expo_a, expo_b, slabs, bslabs, nsplit, rows,
-                                     TN, TK, nullptr, nullptr, nullptr, stream);
-  if (rc) return rc;
-  launch_reduce(st, reduce_desc(N, K, TN, TK, nsplit, slabs, bslabs, dW, ldo, db));
-  return (int)hipGetLastError();
-}
-
-// Chained upnerf_wgrad_f16p: same pending record as upnerf_wgrad_f16x3_chain (one run may mix both kinds of launches).
-static int wgrad_f16p_chain_impl(int M, const uint16_t* A16, const uint8_t* Alo, int lda, const int32_t* aexp, int N, const void* B,
-                                 const uint8_t* Blo, int ldb, const int32_t* bexp, int b_is_f16, int K, float* dW, int ldo, float* db,
-                                 int n2, float* dW2, int ldo2, float* db2, float* slabs, int nsplit, const int* expo_a,
-                                 const int* expo_b, upnerf_wgrad_pending* pending, void* stream) {
-  if (n2 < 0 || n2 >= N || (n2 > 0 && (!dW2 || (ldo2 & 3)))) return UPNERF_EINVAL;
-  if (M <= 0 || N <= 0 || K <= 0 || !A16 || !aexp || !B || !dW || !slabs || nsplit <= 0 || !expo_a || !expo_b || !pending)
-    return UPNERF_EINVAL;
-  if ((b_is_f16 & 1) && !bexp) return UPNERF_EINVAL;
-  if ((N & 7) || (K & 7) || (lda & 7) || (ldb & 7) || (ldo & 3)) return UPNERF_EINVAL;
-  if (pending->nsplit > 0 && pending->slabs == slabs) return UPNERF_EINVAL;  // the pending slabs would be overwritten
-  int TN, TK;
-  wgrad_shape(N, K, &TN, &TK);
-  const int rows = (((M + nsplit - 1) / nsplit) + WG_CHUNK - 1) / WG_CHUNK * WG_CHUNK;
-  const int gy = (N + TN - 1) / TN, gz = (K + TK - 1) / TK;
-  float* bslabs = slabs + (size_t)nsplit * gy * gz * TN * TK;
-  if (pending->nsplit > 0 && pending->rblocks > nsplit * gy * gz) {  // grid too small to carry the previous reduction
-    int rc = upnerf_wgrad_finish(pending, stream);
-    if (rc) return rc;
-  }
-  int rc = upnerf_wgrad_f16p_partial(M, A16, lda, aexp, N, B, ldb, bexp, b_is_f16, K, expo_a, expo_b, slabs, bslabs, nsplit, rows,
-                                     TN, TK, pending->nsplit > 0 ? pending : nullptr, Alo, Blo, stream);
-  if (rc) return rc;
-  upnerf_wgrad_pending P = reduce_desc(N, K, TN, TK, nsplit, slabs, bslabs, dW, ldo, db);
-  P.n2 = n2;
-  P.dW2 = dW2;
-  P.db2 = db2;
-  P.ldo2 = ldo2;
-  *pending = P;
-  return 0;
-}
-
-extern "C" int upnerf_wgrad_f16p_partial_v(int M, const uint16_t* A16, const int* aexp, const uint16_t* B16, const int* bexp, const float* v,
-                                           const int* expo_a, const int* expo_b, float* slabs, float* bslabs, float* vslabs, int nsplit,
-                                           int rows, const upnerf_wgrad_pending* prev, void* stream);  // csrc/wgrad_f16x3.hip
-
-// upnerf_wgrad_f16p_chain on fragment-ordered 256 x 256 operands + the 1-wide head that shares B (include/upnerf_hip.h)
-extern "C" int upnerf_wgrad_f16p_chain_v(int M, const uint16_t* A16, const int32_t* aexp, const uint16_t* B16, const int32_t* bexp,
-                                         float* dW, int ldo, float* db, const float* v, float* dv, float* dbv, float* slabs, int nsplit,
-                                         const int* expo_a, const int* expo_b, upnerf_wgrad_pending* pending, void* stream) {
-  if (M <= 0 || !A16 || !aexp || !B16 || !bexp || !dW || !v || !dv || !slabs || nsplit <= 0 || !expo_a || !expo_b || !pending || (ldo & 3))
-    return UPNERF_EINVAL;
-  if (pending->nsplit > 0 && pending->slabs == slabs) return UPNERF_EINVAL;
-  const int TN = 256, TK = 256;
-  const int rows = (((M + nsplit - 1) / nsplit) + WG_CHUNK - 1) / WG_CHUNK * WG_CHUNK;
-  float* bslabs = slabs + (size_t)nsplit * TN * TK;
-  float* vslabs = bslabs + (size_t)nsplit * TN;
-  if (pending->nsplit > 0 && pending->rblocks > nsplit) {
-    int rc = upnerf_wgrad_finish(pending, stream);
-    if (rc) return rc;
-  }
-  int rc = upnerf_wgrad_f16p_partial_v(M, A16, aexp, B16, bexp, v, expo_a, expo_b, slabs, bslabs, vslabs, nsplit, rows,
-                                       pending->nsplit > 0 ? pending : nullptr, stream);
-  if (rc) return rc;
-  upnerf_wgrad_pending P = reduce_desc(256, 256, TN, TK, nsplit, slabs, bslabs, dW, ldo, db);
-  P.vslabs = vslabs;
-  P.dv = dv;
-  P.dbv = dbv;
-  *pending = P;
-  return 0;
-}
-
-extern "C" int upnerf_wgrad_planes_partial(int M, const uint16_t* Ah, const uint16_t* Al, const int* aexp, const uint16_t* Bh,
-                                           const uint16_t* Bl, const int* bexp, const int* expo_a, const int* expo_b, float* slabs,
-                                           float* bslabs, int nsplit, int rows, const upnerf_wgrad_pending* prev, void* stream);  // csrc/wgrad_f16x3.hip
-
-// dW[256][ldo] = sum_m A[m][:]^T B[m][:] from producer-split operands (include/upnerf_hip.h): a link of a chained run
-extern "C" int upnerf_wgrad_planes_chain(int M, const uint16_t* A16, const uint16_t* Alo16, const int32_t* aexp, const uint16_t* B16,
-                                         const uint16_t* Blo16, const int32_t* bexp, float* dW, int ldo, float* db, float* slabs, int nsplit,
-                                         const int* expo_a, const int* expo_b, upnerf_wgrad_pending* pending, void* stream) {
-  if (M <= 0 || !A16 || !Alo16 || !aexp || !B16 || !Blo16 || !bexp || !dW || !slabs || nsplit <= 0 || !expo_a || !expo_b || !pending || (ldo & 3))
-    return UPNERF_EINVAL;
-  if (M & 63) return UPNERF_EUNSUP;  // whole 64-row tiles (one exponent each) only
-  if (pending->nsplit > 0 && pending->slabs == slabs) return UPNERF_EINVAL;
-  const int TN = 256, TK = 256;
-  const int rows = (((M + nsplit - 1) / nsplit) + 63) / 64 * 64;
-  float* bslabs = slabs + (size_t)nsplit * TN * TK;
-  if (pending->nsplit > 0 && pending->rblocks > nsplit) {
-    int rc = upnerf_wgrad_finish(pending, stream);
-    if (rc) return rc;
-  }
-  int rc = upnerf_wgrad_planes_partial(M, A16, Alo16, aexp, B16, Blo16, bexp, expo_a, expo_b, slabs, bslabs, nsplit, rows,
-                                       pending->nsplit > 0 ? pending : nullptr, stream);
-  if (rc) return rc;
-  *pending = reduce_desc(256, 256, TN, TK, nsplit, slabs, bslabs, dW, ldo, db);
-  return 0;
 }
 
 extern "C" int upnerf_vec_wgrad_frag16(int M, const float* v, int ldv, int nvec, const uint16_t* X16, const int32_t* xexp, int K,
@@ -1029,24 +817,6 @@ extern "C" int upnerf_vec_wgrad_frag16(int M, const float* v, int ldv, int nvec,
   const int total = nvec * (K + 1);
   hipLaunchKernelGGL(vec_wgrad_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, nvec, K, nsplit, scratch, dw, dbv);
   return (int)hipGetLastError();
-}
-
-extern "C" int upnerf_wgrad_f16p_chain(int M, const uint16_t* A16, int lda, const int32_t* aexp, int N, const void* B, int ldb,
-                                       const int32_t* bexp, int b_is_f16, int K, float* dW, int ldo, float* db, int n2, float* dW2,
-                                       int ldo2, float* db2, float* slabs, int nsplit, const int* expo_a, const int* expo_b,
-                                       upnerf_wgrad_pending* pending, void* stream) {
-  return wgrad_f16p_chain_impl(M, A16, nullptr, lda, aexp, N, B, nullptr, ldb, bexp, b_is_f16, K, dW, ldo, db, n2, dW2, ldo2, db2, slabs,
-                               nsplit, expo_a, expo_b, pending, stream);
-}
-// The same with "24-bit" operands: A16 / Alo8 (and B16 / Blo8 when b_is_f16 = 1; a fp32 B is split in the kernel) hold hi + lo8 as
-// written by the f16x3 field kernels (upnerf_field_fwd_args.h_lo8, upnerf_field_bwd_args.gz_lo8); three MFMAs per block.
-extern "C" int upnerf_wgrad_f24p_chain(int M, const uint16_t* A16, const uint8_t* Alo8, int lda, const int32_t* aexp, int N,
-                                       const void* B, const uint8_t* Blo8, int ldb, const int32_t* bexp, int b_is_f16, int K, float* dW,
-                                       int ldo, float* db, float* slabs, int nsplit, const int* expo_a, const int* expo_b,
-                                       upnerf_wgrad_pending* pending, void* stream) {
-  if (!Alo8 || (b_is_f16 & 2)) return UPNERF_EINVAL;
-  return wgrad_f16p_chain_impl(M, A16, Alo8, lda, aexp, N, B, Blo8, ldb, bexp, b_is_f16, K, dW, ldo, db, 0, nullptr, 0, nullptr, slabs, nsplit,
-                               expo_a, expo_b, pending, stream);
 }
 
 // ---- small matrix-vector products of the folded colour layer (packing): y[m] = add[m] + sum_k A[m][k] x[k] (trans = 0, one wave

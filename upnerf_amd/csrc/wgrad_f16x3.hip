@@ -14,6 +14,7 @@
 // column-major).  LDS image: 256-byte rows of 128 fp16 with the 16-byte-chunk XOR that makes the transposed reads
 // conflict-free (cdna_hip_programming.md T10, image (b)).
 #include "common.cuh"
+#include "wgrad_host.h"
 
 namespace {
 
@@ -72,7 +73,7 @@ __device__ __forceinline__ h4 tr_read(const char* base, int byteoff) {
 #else
 #define HALFROW_OK(T, c4) true
 #endif
-// HASV: a 1-wide head that reads the same B rows rides along (upnerf_wgrad_f16x3_chain_v): vsum[k] += v[m] B[m][k] in fp32 on the
+// HASV: a 1-wide head that reads the same B rows rides along (upnerf_wgrad_desc.v): vsum[k] += v[m] B[m][k] in fp32 on the
 // rows as they pass through the staging registers, sum of v beside it; per-split partials to vslabs[split][K + 4].
 template <int NP, int MTW, int NTW, bool HASV = false>
 __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16x3_kernel(int M, int N, int K, const float* __restrict__ A, int lda,
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16x3_kernel(int M, int N
   const int nblk = blockIdx.y * TN, kblk = blockIdx.z * TK;
   const int mbeg = split * rows_per_split;
   const int mend = (mbeg + rows_per_split < M) ? mbeg + rows_per_split : M;
-  // Prologue: the first prev.rblocks workgroups sum the slabs the PREVIOUS weight-gradient launch left (upnerf_wgrad_f16x3_chain)
+  // Prologue: the first prev.rblocks workgroups sum the slabs the PREVIOUS weight-gradient launch left (upnerf_wgrad16, pending)
   if (prev.nsplit > 0) {
     const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     if (wg < prev.rblocks) {
@@ -482,7 +483,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void wgrad_f16x3_w4_kernel(int M, in
   }
 }
 
-// ---- fp16-STORED operands (the f16 field mode, upnerf_wgrad_f16p): A16 (and B16 when PKB) hold fp16 values scaled per
+// ---- fp16-STORED operands (the f16 field mode, UPNERF_WG_F16_TILE): A16 (and B16 when PKB) hold fp16 values scaled per
 // 64-row tile by 2^exp[m / 64] (the LDS planes of the field kernels, copied out as they stood).  A thread moves 8 columns
 // (16 bytes) at a time, brings them to the tensor-wide exponent with an exact fp16 power-of-two multiply and drops them into
 // the same LDS image the fp32 path builds; one MFMA per block.  Half the HBM bytes of the fp32-stored operands.
@@ -490,11 +491,11 @@ __global__ __launch_bounds__(W4_THREADS, 1) void wgrad_f16x3_w4_kernel(int M, in
 // [k-block 16][lane 64][8], feature 16 s + 8 (j / 4) + 4 (lane / 32) + j % 4, one exponent per 32 rows.  A thread moves the 16 bytes
 // of one lane: sixteen consecutive threads read sixteen consecutive rows of one (k-block, lane half) = 256 contiguous bytes, and
 // the two 8-byte halves of the piece land at their natural columns of the same LDS image.  256-wide operands only.
-// NP = 2 ("24-bit" storage, upnerf_wgrad_f24p): beside every fp16 tensor a byte tensor of the same shape holds the rounding
+// NP = 2 ("24-bit" storage, UPNERF_WG_F24): beside every fp16 tensor a byte tensor of the same shape holds the rounding
 // residual the field kernels' lo plane held, quantised to 1/32 of the tile's scaled unit (byte = round(32 lo) + 128): the
 // operand is hi + lo again to 2^-20 of its tile's maximum, three MFMAs per block as in the f16x3 kernel; a fp32 B operand is
 // split into hi + lo here.  3 bytes per stored element instead of 4.  Row-major operands only (no FRAG).
-// HASV (fragment-ordered 256 x 256 problems): a 1-wide head that reads the same B rows rides along (upnerf_wgrad_f16p_chain_v),
+// HASV (fragment-ordered 256 x 256 problems): a 1-wide head that reads the same B rows rides along (upnerf_wgrad_desc.v),
 // as in wgrad_f16x3_kernel: vsum[col] += v[m] * B[m][col] in fp32 from the pieces as they pass, per-split partials to vslabs.
 template <int MTW, int NTW, int PKB, int FRAG, int NP, bool HASV = false>
 __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16p_kernel(int M, int N, int K, const uint16_t* __restrict__ A, int lda,
@@ -533,7 +534,7 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16p_kernel(int M, int N,
   const int nblk = blockIdx.y * TN, kblk = blockIdx.z * TK;
   const int mbeg = split * rows_per_split;
   const int mend = (mbeg + rows_per_split < M) ? mbeg + rows_per_split : M;
-  // Prologue: the first prev.rblocks workgroups sum the slabs the PREVIOUS weight-gradient launch left (upnerf_wgrad_f16p_chain)
+  // Prologue: the first prev.rblocks workgroups sum the slabs the PREVIOUS weight-gradient launch left (upnerf_wgrad16, pending)
   if (prev.nsplit > 0) {
     const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     if (wg < prev.rblocks) {
@@ -1011,16 +1012,25 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_planes_kernel(int M, cons
   }
 }
 
-template <int MTW, int NTW, int PKB, int FRAG, int NP = 1>
-int launch_p(int M, int N, int K, const uint16_t* A, int lda, const int* aexp, const void* B, int ldb, const int* bexp,
-             const int* expo_a, const int* expo_b, float* slabs, float* bslabs, int nsplit, int rows, hipStream_t st,
-             const upnerf_wgrad_pending* prevp, const uint8_t* Alo = nullptr, const uint8_t* Blo = nullptr) {
+// ---- host side: ONE implementation behind upnerf_wgrad16 (include/upnerf_hip.h) --------------------------------------------------
+// What every kernel of the family is launched with, filled once from the descriptor.
+struct Launch {
+  const upnerf_wgrad_desc* d;
+  int rows;                      // rows per split
+  float *bslabs, *vslabs;        // carved out of d->slabs behind the slabs proper
+  upnerf_wgrad_pending prev;     // nsplit == 0: nothing rides in the prologue
+  hipStream_t st;
+};
+
+// fp16-stored operands (UPNERF_WG_F16_TILE / _F16_FRAG: NP = 1, UPNERF_WG_F24: NP = 2); PKB: B is stored the same way, else fp32 rows
+template <int MTW, int NTW, int PKB, int FRAG, int NP = 1, bool HASV = false>
+int launch_p(const Launch& L) {
   constexpr int TN = 64 * MTW, TK = 64 * NTW;
-  dim3 grid(nsplit, (N + TN - 1) / TN, (K + TK - 1) / TK);
-  upnerf_wgrad_pending prev = {};
-  if (prevp) prev = *prevp;
-  hipLaunchKernelGGL((wgrad_f16p_kernel<MTW, NTW, PKB, FRAG, NP>), grid, dim3(FX_THREADS), 0, st, M, N, K, A, lda, aexp, B, ldb, bexp,
-                     expo_a, expo_b, slabs, bslabs, rows, prev, Alo, Blo);
+  const upnerf_wgrad_desc& d = *L.d;
+  dim3 grid(d.nsplit, (d.N + TN - 1) / TN, (d.K + TK - 1) / TK);
+  hipLaunchKernelGGL((wgrad_f16p_kernel<MTW, NTW, PKB, FRAG, NP, HASV>), grid, dim3(FX_THREADS), 0, L.st, d.M, d.N, d.K,
+                     (const uint16_t*)d.A.p, d.A.ld, d.A.exp, d.B.p, d.B.ld, d.B.exp, d.expo_a, d.expo_b, d.slabs, L.bslabs, L.rows, L.prev,
+                     NP == 2 ? (const uint8_t*)d.A.lo : nullptr, NP == 2 && PKB ? (const uint8_t*)d.B.lo : nullptr, d.v, L.vslabs);
   return (int)hipGetLastError();
 }
 
@@ -1032,108 +1042,140 @@ int launch_p(int M, int N, int K, const uint16_t* A, int lda, const int* aexp, c
 // as well as two waves hide them for each other.  1 = the eight-wave kernel (shipped).
 #define WG_NO_W4 1
 #endif
-template <int MTW, int NTW>
-int launch(int planes, int M, int N, int K, const float* A, int lda, const float* B, int ldb, const int* expo_a, const int* expo_b,
-           float* slabs, float* bslabs, int nsplit, int rows, hipStream_t st, const upnerf_wgrad_pending* prevp = nullptr) {
+// fp32 rows (UPNERF_WG_F32), split (planes 0 / 2) or rounded (planes 1) on load
+template <int MTW, int NTW, bool HASV = false>
+int launch(const Launch& L) {
   constexpr int TN = 64 * MTW, TK = 64 * NTW;
-  dim3 grid(nsplit, (N + TN - 1) / TN, (K + TK - 1) / TK);
-  upnerf_wgrad_pending prev = {};
-  if (prevp) prev = *prevp;
-  if (planes == 1)
-    hipLaunchKernelGGL((wgrad_f16x3_kernel<1, MTW, NTW>), grid, dim3(FX_THREADS), 0, st, M, N, K, A, lda, B, ldb, expo_a, expo_b,
-                       slabs, bslabs, rows, prev);
+  const upnerf_wgrad_desc& d = *L.d;
+  dim3 grid(d.nsplit, (d.N + TN - 1) / TN, (d.K + TK - 1) / TK);
+  const float *A = (const float*)d.A.p, *B = (const float*)d.B.p;
+  if (d.planes == 1)
+    hipLaunchKernelGGL((wgrad_f16x3_kernel<1, MTW, NTW>), grid, dim3(FX_THREADS), 0, L.st, d.M, d.N, d.K, A, d.A.ld, B, d.B.ld, d.expo_a,
+                       d.expo_b, d.slabs, L.bslabs, L.rows, L.prev);
   else
-    hipLaunchKernelGGL((wgrad_f16x3_kernel<2, MTW, NTW>), grid, dim3(FX_THREADS), 0, st, M, N, K, A, lda, B, ldb, expo_a, expo_b,
-                       slabs, bslabs, rows, prev);
+    hipLaunchKernelGGL((wgrad_f16x3_kernel<2, MTW, NTW, HASV>), grid, dim3(FX_THREADS), 0, L.st, d.M, d.N, d.K, A, d.A.ld, B, d.B.ld,
+                       d.expo_a, d.expo_b, d.slabs, L.bslabs, L.rows, L.prev, d.v, L.vslabs);
   return (int)hipGetLastError();
+}
+
+// The kernel instantiation of a validated descriptor; UPNERF_EUNSUP where a packed kind has none for the block shape.
+int launch_kind(const Launch& L, int TN, int TK) {
+  const upnerf_wgrad_desc& d = *L.d;
+  const bool pkb = d.B.kind != UPNERF_WG_F32;
+  switch (d.A.kind) {
+    case UPNERF_WG_F32:
+      if (d.v) return launch<4, 4, true>(L);
+      if (TN == 256 && TK == 256 && d.planes == 2 && d.N <= 256 && d.K <= 256 && !WG_NO_W4) {  // one wave per SIMD (wgrad_f16x3_w4_kernel)
+        hipLaunchKernelGGL((wgrad_f16x3_w4_kernel<2>), dim3(d.nsplit), dim3(W4_THREADS), 0, L.st, d.M, d.N, d.K, (const float*)d.A.p, d.A.ld,
+                           (const float*)d.B.p, d.B.ld, d.expo_a, d.expo_b, d.slabs, L.bslabs, L.rows, L.prev);
+        return (int)hipGetLastError();
+      }
+      if (TN == 256 && TK == 256) return launch<4, 4>(L);
+      if (TN == 256 && TK == 128) return launch<4, 2>(L);
+      if (TN == 256 && TK == 64) return launch<4, 1>(L);
+      if (TN == 128 && TK == 256) return launch<2, 4>(L);
+      if (TN == 128 && TK == 128) return launch<2, 2>(L);
+      if (TN == 128 && TK == 64) return launch<2, 1>(L);
+      if (TN == 64 && TK == 256) return launch<1, 4>(L);
+      if (TN == 64 && TK == 128) return launch<1, 2>(L);
+      return launch<1, 1>(L);
+    case UPNERF_WG_F16_TILE:  // 256 x 256 (both operands fp16-stored) and 256 x 64 (fp32 B: the encoding)
+      if (TN == 256 && TK == 256 && pkb) return launch_p<4, 4, 1, 0>(L);
+      if (TN == 256 && TK == 64 && !pkb) return launch_p<4, 1, 0, 0>(L);
+      return UPNERF_EUNSUP;
+    case UPNERF_WG_F16_FRAG:
+      if ((d.N != 256 && d.N != 128) || (pkb && d.K != d.N) || (!pkb && d.N != 256)) return UPNERF_EUNSUP;
+      if (d.v) return launch_p<4, 4, 1, 1, 1, true>(L);
+      if (TN == 128 && TK == 128 && pkb) return launch_p<2, 2, 1, 1>(L);  // 128-wide fragments on both sides (candidate_encoding.2: gz_g2 x g1)
+      if (TN == 256 && TK == 256 && pkb) return launch_p<4, 4, 1, 1>(L);
+      if (TN == 256 && TK == 64 && !pkb) return launch_p<4, 1, 0, 1>(L);
+      return UPNERF_EUNSUP;
+    case UPNERF_WG_F24:
+      if (TN == 256 && TK == 256 && pkb) return launch_p<4, 4, 1, 0, 2>(L);
+      if (TN == 256 && TK == 64 && !pkb) return launch_p<4, 1, 0, 0, 2>(L);
+      return UPNERF_EUNSUP;
+    default:  // UPNERF_WG_PLANES: one 256 x 256 block, staged by LDS-DMA (wgrad_planes_kernel)
+      hipLaunchKernelGGL(wgrad_planes_kernel, dim3(d.nsplit, 1, 1), dim3(FX_THREADS), 0, L.st, d.M, (const uint16_t*)d.A.p, (const uint16_t*)d.A.lo,
+                         d.A.exp, (const uint16_t*)d.B.p, (const uint16_t*)d.B.lo, d.B.exp, d.expo_a, d.expo_b, d.slabs, L.bslabs, L.rows, L.prev);
+      return (int)hipGetLastError();
+  }
+}
+
+// Every refusal that needs no launch.  Each kind keeps the rule of the entry point it came from (alignment masks, pairing of the
+// two operands); 0 = the descriptor may be launched.
+int check_desc(const upnerf_wgrad_desc& d) {
+  const upnerf_wgrad_operand &A = d.A, &B = d.B;
+  const int ak = A.kind, bk = B.kind;
+  const bool f32 = ak == UPNERF_WG_F32, b32 = bk == UPNERF_WG_F32;
+  if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.nsplit <= 0 || !A.p || !B.p || !d.dW || !d.slabs || !d.expo_a || !d.expo_b) return UPNERF_EINVAL;
+  if (ak < UPNERF_WG_F32 || ak > UPNERF_WG_PLANES || bk < UPNERF_WG_F32 || bk > UPNERF_WG_PLANES) return UPNERF_EINVAL;
+  if ((!f32 && !A.exp) || (!b32 && !B.exp) || (d.v && !d.dv)) return UPNERF_EINVAL;
+  if ((ak == UPNERF_WG_F24 || ak == UPNERF_WG_PLANES) && !A.lo) return UPNERF_EINVAL;
+  // hi + lo8 operands are row-major only, and a fp16 B beside them needs its residual bytes too
+  if (ak == UPNERF_WG_F24 && !b32 && (bk != UPNERF_WG_F24 || !B.lo)) return UPNERF_EINVAL;
+  if (ak == UPNERF_WG_PLANES && bk == UPNERF_WG_PLANES && !B.lo) return UPNERF_EINVAL;
+  // the riding head: 256 x 256, on the 3-term split of fp32 rows or on fragments on both sides
+  if (d.v && (d.N != 256 || d.K != 256 || d.n2 > 0 || !((f32 && d.planes == 2) || (ak == UPNERF_WG_F16_FRAG && bk == ak)))) return UPNERF_EUNSUP;
+  if (f32 && d.planes != 0 && d.planes != 1 && d.planes != 2) return UPNERF_EINVAL;
+  if (ak == UPNERF_WG_PLANES) {  // whole 64-row tiles (one exponent each) of [M][256] planes only
+    if (d.ldo & 3) return UPNERF_EINVAL;
+    if ((d.M & 63) || bk != ak || d.N != 256 || d.K != 256 || A.ld != 256 || B.ld != 256) return UPNERF_EUNSUP;
+  } else {
+    const int mask = f32 ? 3 : 7;  // 16-byte pieces: 4 floats, 8 fp16 (a fp32 B beside fp16 A is held to the same 8)
+    if ((d.N & mask) || (d.K & mask) || (A.ld & mask) || (B.ld & mask) || (d.ldo & 3)) return UPNERF_EINVAL;
+    if (f32 ? !b32 : (!b32 && bk != ak)) return UPNERF_EUNSUP;  // no kernel mixes these two storages
+  }
+  if (d.n2 < 0 || d.n2 >= d.N || (d.n2 > 0 && (!d.dW2 || (d.ldo2 & 3)))) return UPNERF_EINVAL;
+  return 0;
 }
 
 }  // namespace
 
-// Same contract as upnerf_wgrad_partial in gemm.hip: writes nsplit slabs (+ bias slabs) that upnerf_wgrad's reduce
-// kernel sums.  expo_a, expo_b: DEVICE pointers to the two exponents.  Returns the block shape through TN/TK.
-extern "C" int upnerf_wgrad_f16x3_partial(int M, const float* A, int lda, int N, const float* B, int ldb, int K,
-                                          const int* expo_a, const int* expo_b, float* slabs, float* bslabs, int nsplit, int rows, int TN,
-                                          int TK, int planes, const upnerf_wgrad_pending* prev, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-#define WG_ARGS planes, M, N, K, A, lda, B, ldb, expo_a, expo_b, slabs, bslabs, nsplit, rows, st, prev
-  if (TN == 256 && TK == 256 && planes == 2 && N <= 256 && K <= 256 && !WG_NO_W4) {  // one wave per SIMD (wgrad_f16x3_w4_kernel)
-    upnerf_wgrad_pending pv = {};
-    if (prev) pv = *prev;
-    hipLaunchKernelGGL((wgrad_f16x3_w4_kernel<2>), dim3(nsplit), dim3(W4_THREADS), 0, st, M, N, K, A, lda, B, ldb, expo_a, expo_b, slabs,
-                       bslabs, rows, pv);
-    return (int)hipGetLastError();
+using namespace upnerf_host;
+
+extern "C" long long upnerf_wgrad16_scratch(const upnerf_wgrad_desc* d) {
+  if (!d || d->N <= 0 || d->K <= 0 || d->nsplit <= 0) return UPNERF_EINVAL;
+  int TN, TK;
+  wgrad_shape(d->N, d->K, &TN, &TK);
+  const long long gy = (d->N + TN - 1) / TN, gz = (d->K + TK - 1) / TK;
+  return d->nsplit * (gy * gz * TN * TK + gy * TN + (d->v ? d->K + 4 : 0));  // slabs, bias slabs, the riding head's [K + 4]
+}
+
+extern "C" int upnerf_wgrad16(const upnerf_wgrad_desc* d, upnerf_wgrad_pending* pending, void* stream) {
+  if (!d) return UPNERF_EINVAL;
+  int rc = check_desc(*d);
+  if (rc) return rc;
+  if (pending && pending->nsplit > 0 && pending->slabs == d->slabs) return UPNERF_EINVAL;  // the pending slabs would be overwritten
+  int TN, TK;
+  wgrad_shape(d->N, d->K, &TN, &TK);
+  const int nsplit = d->nsplit, gy = (d->N + TN - 1) / TN, gz = (d->K + TK - 1) / TK;
+  // bitwise parity hangs on `rows`: the planes kernel walks whole 64-row tiles, every other kernel WG_CHUNK-row chunks
+  const int chunk = d->A.kind == UPNERF_WG_PLANES ? 64 : WG_CHUNK;
+  Launch L = {d, (((d->M + nsplit - 1) / nsplit) + chunk - 1) / chunk * chunk, nullptr, nullptr, {}, (hipStream_t)stream};
+  L.bslabs = d->slabs + (size_t)nsplit * gy * gz * TN * TK;
+  if (d->v) L.vslabs = L.bslabs + (size_t)nsplit * gy * TN;
+  if (pending && pending->nsplit > 0) {
+    if (pending->rblocks > nsplit * gy * gz) {  // grid too small to carry the previous reduction
+      rc = upnerf_wgrad_finish(pending, stream);
+      if (rc) return rc;
+    } else {
+      L.prev = *pending;
+    }
   }
-  if (TN == 256 && TK == 256) return launch<4, 4>(WG_ARGS);
-  if (TN == 256 && TK == 128) return launch<4, 2>(WG_ARGS);
-  if (TN == 256 && TK == 64) return launch<4, 1>(WG_ARGS);
-  if (TN == 128 && TK == 256) return launch<2, 4>(WG_ARGS);
-  if (TN == 128 && TK == 128) return launch<2, 2>(WG_ARGS);
-  if (TN == 128 && TK == 64) return launch<2, 1>(WG_ARGS);
-  if (TN == 64 && TK == 256) return launch<1, 4>(WG_ARGS);
-  if (TN == 64 && TK == 128) return launch<1, 2>(WG_ARGS);
-  return launch<1, 1>(WG_ARGS);
-#undef WG_ARGS
-}
-
-// 256 x 256 block from (hi, lo) fp16 planes, staged by LDS-DMA (wgrad_planes_kernel; upnerf_wgrad_planes_chain, gemm.hip)
-extern "C" int upnerf_wgrad_planes_partial(int M, const uint16_t* Ah, const uint16_t* Al, const int* aexp, const uint16_t* Bh,
-                                           const uint16_t* Bl, const int* bexp, const int* expo_a, const int* expo_b, float* slabs,
-                                           float* bslabs, int nsplit, int rows, const upnerf_wgrad_pending* prevp, void* stream) {
-  upnerf_wgrad_pending prev = {};
-  if (prevp) prev = *prevp;
-  hipLaunchKernelGGL(wgrad_planes_kernel, dim3(nsplit, 1, 1), dim3(FX_THREADS), 0, (hipStream_t)stream, M, Ah, Al, aexp, Bh, Bl, bexp, expo_a,
-                     expo_b, slabs, bslabs, rows, prev);
-  return (int)hipGetLastError();
-}
-
-// the same for the fragment-ordered fp16 operands of the register-resident field kernels (upnerf_wgrad_f16p_chain_v, gemm.hip)
-extern "C" int upnerf_wgrad_f16p_partial_v(int M, const uint16_t* A16, const int* aexp, const uint16_t* B16, const int* bexp, const float* v,
-                                           const int* expo_a, const int* expo_b, float* slabs, float* bslabs, float* vslabs, int nsplit,
-                                           int rows, const upnerf_wgrad_pending* prevp, void* stream) {
-  upnerf_wgrad_pending prev = {};
-  if (prevp) prev = *prevp;
-  hipLaunchKernelGGL((wgrad_f16p_kernel<4, 4, 1, 1, 1, true>), dim3(nsplit, 1, 1), dim3(FX_THREADS), 0, (hipStream_t)stream, M, 256, 256, A16,
-                     256, aexp, (const void*)B16, 256, bexp, expo_a, expo_b, slabs, bslabs, rows, prev, nullptr, nullptr, v, vslabs);
-  return (int)hipGetLastError();
-}
-
-// 256 x 256 block with a 1-wide head riding along (upnerf_wgrad_f16x3_chain_v, gemm.hip)
-extern "C" int upnerf_wgrad_f16x3_partial_v(int M, const float* A, int lda, const float* B, int ldb, const float* v, const int* expo_a,
-                                            const int* expo_b, float* slabs, float* bslabs, float* vslabs, int nsplit, int rows,
-                                            const upnerf_wgrad_pending* prevp, void* stream) {
-  upnerf_wgrad_pending prev = {};
-  if (prevp) prev = *prevp;
-  hipLaunchKernelGGL((wgrad_f16x3_kernel<2, 4, 4, true>), dim3(nsplit, 1, 1), dim3(FX_THREADS), 0, (hipStream_t)stream, M, 256, 256, A, lda,
-                     B, ldb, expo_a, expo_b, slabs, bslabs, rows, prev, v, vslabs);
-  return (int)hipGetLastError();
-}
-
-// Packed-operand variant behind upnerf_wgrad_f16p (gemm.hip): blocks of 256 x 256 (both operands fp16-stored) and
-// 256 x 64 (fp32 B: the encoding).  Returns UPNERF_EUNSUP for any other block shape.
-extern "C" int upnerf_wgrad_f16p_partial(int M, const uint16_t* A16, int lda, const int* aexp, int N, const void* B, int ldb,
-                                         const int* bexp, int b_is_f16, int K, const int* expo_a, const int* expo_b, float* slabs,
-                                         float* bslabs, int nsplit, int rows, int TN, int TK, const upnerf_wgrad_pending* prev,
-                                         const uint8_t* Alo, const uint8_t* Blo, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (Alo) {  // hi + lo8 operands ("24-bit" storage): row-major only; a fp16 B needs its residual bytes too
-    if ((b_is_f16 & 2) || ((b_is_f16 & 1) && !Blo)) return UPNERF_EINVAL;
-    if (TN == 256 && TK == 256 && (b_is_f16 & 1))
-      return launch_p<4, 4, 1, 0, 2>(M, N, K, A16, lda, aexp, B, ldb, bexp, expo_a, expo_b, slabs, bslabs, nsplit, rows, st, prev, Alo, Blo);
-    if (TN == 256 && TK == 64 && !(b_is_f16 & 1))
-      return launch_p<4, 1, 0, 0, 2>(M, N, K, A16, lda, aexp, B, ldb, bexp, expo_a, expo_b, slabs, bslabs, nsplit, rows, st, prev, Alo, nullptr);
-    return UPNERF_EUNSUP;
+  rc = launch_kind(L, TN, TK);
+  if (rc) return rc;
+  upnerf_wgrad_pending P = reduce_desc(d->N, d->K, TN, TK, nsplit, d->slabs, L.bslabs, d->dW, d->ldo, d->db);
+  P.n2 = d->n2;
+  P.dW2 = d->dW2;
+  P.db2 = d->db2;
+  P.ldo2 = d->ldo2;
+  P.vslabs = L.vslabs;
+  P.dv = d->dv;
+  P.dbv = d->dbv;
+  if (pending) {
+    *pending = P;
+    return 0;
   }
-  const bool frag = (b_is_f16 & 2) != 0;  // bit 1: fp16 operands in the fragment order of the register-resident field kernels
-  b_is_f16 &= 1;
-  if (frag && ((N != 256 && N != 128) || (b_is_f16 && K != N) || (!b_is_f16 && N != 256))) return UPNERF_EUNSUP;
-  if (TN == 128 && TK == 128 && b_is_f16 && frag)  // 128-wide fragments on both sides (candidate_encoding.2: gz_g2 x g1)
-    return launch_p<2, 2, 1, 1>(M, N, K, A16, lda, aexp, B, ldb, bexp, expo_a, expo_b, slabs, bslabs, nsplit, rows, st, prev);
-  if (TN == 256 && TK == 256 && b_is_f16)
-    return frag ? launch_p<4, 4, 1, 1>(M, N, K, A16, lda, aexp, B, ldb, bexp, expo_a, expo_b, slabs, bslabs, nsplit, rows, st, prev)
-                : launch_p<4, 4, 1, 0>(M, N, K, A16, lda, aexp, B, ldb, bexp, expo_a, expo_b, slabs, bslabs, nsplit, rows, st, prev);
-  if (TN == 256 && TK == 64 && !b_is_f16)
-    return frag ? launch_p<4, 1, 0, 1>(M, N, K, A16, lda, aexp, B, ldb, bexp, expo_a, expo_b, slabs, bslabs, nsplit, rows, st, prev)
-                : launch_p<4, 1, 0, 0>(M, N, K, A16, lda, aexp, B, ldb, bexp, expo_a, expo_b, slabs, bslabs, nsplit, rows, st, prev);
-  return UPNERF_EUNSUP;
+  launch_reduce(L.st, P);  // no run to ride on: summed at once
+  return (int)hipGetLastError();
 }

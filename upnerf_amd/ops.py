@@ -7,7 +7,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -198,107 +198,71 @@ def scale_exponents(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     return (14 - torch.ceil(torch.log2(amax))).to(torch.int32)
 
 
+class WgOp(NamedTuple):
+    """One operand of a f16 weight gradient as it is stored (include/upnerf_hip.h, upnerf_wgrad_operand): `t` [M][ld] of `kind`
+    (_lib.WG_*), the per-tile exponents `exp` and the second plane `lo` of the fp16-stored kinds, `off`: first column (fp32 rows)."""
+    t: torch.Tensor
+    ld: int
+    kind: int = _lib.WG_F32
+    exp: Optional[torch.Tensor] = None
+    lo: Optional[torch.Tensor] = None
+    off: int = 0
+
+    def c(self):
+        # (fp32 rows may be a column block of a wider tensor: the address only, as wgrad_into takes it)
+        p = self.t.data_ptr() + 4 * self.off if self.kind == _lib.WG_F32 else ptr(self.t)
+        return _lib.WgradOperand(p=p, lo=ptr(self.lo), exp=ptr(self.exp), ld=self.ld, kind=self.kind)
+
+
+_WG_TIMER = {_lib.WG_F32: "wgrad16", _lib.WG_F16_TILE: "wgrad16p", _lib.WG_F16_FRAG: "wgrad16p", _lib.WG_F24: "wgrad24p",
+             _lib.WG_PLANES: "wgrad16hl"}
+
+
+class WgradRun:
+    """A run of weight gradients on the f16 matrix cores (upnerf_wgrad16).  chained: the slab reduction of each rides on the NEXT
+    launch -- that kernel's first workgroups sum the previous problem's slabs before their own work, the last problem is summed by
+    `finish()`, nothing may read a gradient of the run before it, and the slabs alternate between two workspaces.  Not chained:
+    every launch is followed by its own reduction and `finish()` has nothing to do."""
+
+    def __init__(self, device, chained: bool):
+        self.device, self.pending, self.flip = device, _lib.WgradPending() if chained else None, 0
+
+    def wgrad(self, M: int, A: WgOp, N: int, B: WgOp, K: int, expo_a: int, expo_b: int, *, dW: int, ldo: int, db: Optional[int] = None,
+              n2: int = 0, dW2: Optional[int] = None, ldo2: int = 0, db2: Optional[int] = None, v: Optional[torch.Tensor] = None,
+              dv: Optional[int] = None, dbv: Optional[int] = None, planes: int = 2):
+        """dW[N][ldo] = sum_m A[m][n] B[m][k], db[n] = sum_m A[m][n]; destinations and exponents are device addresses.  n2 > 0: rows
+        [n2, N) of the result go to dW2 / db2 (two layers fed by the same B, A side by side).  v / dv / dbv: a 1-wide head fed by
+        the same B rows rides on the launch (dv[k] = sum_m v[m] B[m][k], dbv = sum_m v[m]).  planes: arithmetic for fp32 rows."""
+        d = _lib.WgradDesc(M=M, N=N, K=K, planes=planes, A=A.c(), B=B.c(), expo_a=expo_a, expo_b=expo_b, dW=dW, db=db, ldo=ldo, n2=n2,
+                           dW2=dW2, db2=db2, ldo2=ldo2, nsplit=nsplit_for(M), v=ptr(v), dv=dv, dbv=dbv)
+        n = lib.upnerf_wgrad16_scratch(C.byref(d))
+        if n < 0:
+            check(n, "upnerf_wgrad16_scratch")
+        if self.pending is None:
+            tag = "wgrad"
+        else:
+            self.flip ^= 1
+            tag = f"wgrad_chain{self.flip}"
+        d.slabs = ptr(workspace(tag, n, self.device))
+        pending = None if self.pending is None else C.byref(self.pending)
+        check(TIMER.run(f"{_WG_TIMER[A.kind]}_{N}x{K}", lambda: lib.upnerf_wgrad16(C.byref(d), pending, stream()), units=M), "upnerf_wgrad16")
+
+    def finish(self):
+        if self.pending is not None:
+            check(lib.upnerf_wgrad_finish(C.byref(self.pending), stream()), "upnerf_wgrad_finish")
+
+
 def wgrad_f16x3_into(M: int, A: torch.Tensor, lda: int, N: int, B: torch.Tensor, ldb: int, K: int, dW_ptr: int, ldo: int,
                      db_ptr: Optional[int], device, expo: Optional[torch.Tensor] = None, expo_a: Optional[int] = None,
                      expo_b: Optional[int] = None, a_off: int = 0, b_off: int = 0, planes: int = 2):
     """upnerf_wgrad with the contraction on the f16 matrix cores (3-term hi/lo split, fp32-level accuracy).
     Scale exponents: `expo` (device int32 [2]) or raw device pointers expo_a / expo_b; computed from A, B if absent."""
-    ns = nsplit_for(M)
-    ws = workspace("wgrad", ns * (256 * 256 + 256), device)
     if expo_a is None:
         if expo is None:
             expo = scale_exponents(A, B)
         expo_a, expo_b = expo.data_ptr(), expo.data_ptr() + 4
-    rc = TIMER.run(f"wgrad16_{N}x{K}", lambda: lib.upnerf_wgrad_f16x3(M, A.data_ptr() + 4 * a_off, lda, N,
-                                                                      B.data_ptr() + 4 * b_off, ldb, K, dW_ptr, ldo,
-                                                                      db_ptr, ptr(ws), ns, expo_a, expo_b, planes,
-                                                                      stream()),
-                   units=M)
-    check(rc, "upnerf_wgrad_f16x3")
-
-
-class WgradChain:
-    """A run of f16x3 weight gradients whose slab reductions ride on the NEXT launch (upnerf_wgrad_f16x3_chain): each kernel's
-    first workgroups sum the previous problem's slabs before their own work, the last problem is summed by `finish()`.
-    Nothing may read a gradient of the run before `finish()`; the slabs alternate between two workspaces."""
-
-    def __init__(self, device):
-        self.device, self.pending, self.flip = device, _lib.WgradPending(), 0
-
-    def _slabs(self, ns):
-        self.flip ^= 1
-        return workspace(f"wgrad_chain{self.flip}", ns * (256 * 256 + 256 + 260), self.device)  # slabs + bias slabs + a riding vector head's
-
-    def wgrad(self, M, A, lda, N, B, ldb, K, dW_ptr, ldo, db_ptr, expo_a, expo_b, a_off=0, b_off=0, planes=2, v=None, dv_ptr=None,
-              dbv_ptr=None):
-        """v / dv_ptr / dbv_ptr: a 1-wide head fed by the same B rows rides on the launch (upnerf_wgrad_f16x3_chain_v: dv[k] =
-        sum_m v[m] B[m][k], dbv = sum_m v[m]) -- 256 x 256 problems of the f16x3 arithmetic only."""
-        ns = nsplit_for(M)
-        ws = self._slabs(ns)
-        if v is not None:
-            rc = TIMER.run(f"wgrad16_{N}x{K}", lambda: lib.upnerf_wgrad_f16x3_chain_v(
-                M, A.data_ptr() + 4 * a_off, lda, N, B.data_ptr() + 4 * b_off, ldb, K, dW_ptr, ldo, db_ptr, ptr(v), dv_ptr, dbv_ptr,
-                ptr(ws), ns, expo_a, expo_b, planes, C.byref(self.pending), stream()), units=M)
-            check(rc, "upnerf_wgrad_f16x3_chain_v")
-            return
-        rc = TIMER.run(f"wgrad16_{N}x{K}", lambda: lib.upnerf_wgrad_f16x3_chain(
-            M, A.data_ptr() + 4 * a_off, lda, N, B.data_ptr() + 4 * b_off, ldb, K, dW_ptr, ldo, db_ptr, ptr(ws), ns, expo_a, expo_b,
-            planes, C.byref(self.pending), stream()), units=M)
-        check(rc, "upnerf_wgrad_f16x3_chain")
-
-    def wgrad2(self, M, A, lda, N, B, ldb, K, dW_ptr, ldo, db_ptr, n2, dW2_ptr, ldo2, db2_ptr, expo_a, expo_b, planes=2):
-        """Rows [0, n2) of the result go to dW / db, rows [n2, N) to dW2 / db2 (two layers fed by the same B, A side by side)."""
-        ns = nsplit_for(M)
-        ws = self._slabs(ns)
-        rc = TIMER.run(f"wgrad16_{N}x{K}", lambda: lib.upnerf_wgrad_f16x3_chain2(
-            M, ptr(A), lda, N, ptr(B), ldb, K, dW_ptr, ldo, db_ptr, n2, dW2_ptr, ldo2, db2_ptr, ptr(ws), ns, expo_a, expo_b, planes,
-            C.byref(self.pending), stream()), units=M)
-        check(rc, "upnerf_wgrad_f16x3_chain2")
-
-    def wgrad_p(self, M, A16, lda, aexp, N, B, ldb, bexp, K, dW_ptr, ldo, db_ptr, expo_a, expo_b, frag=False, n2=0, dW2_ptr=None,
-                ldo2=0, db2_ptr=None, v=None, dv_ptr=None, dbv_ptr=None):
-        """wgrad_f16p_into (fp16-stored operands of the f16 field mode) as a link of the run; n2 > 0: rows [n2, N) of the
-        result go to dW2 / db2 (as wgrad2).  v / dv_ptr / dbv_ptr (fragment-ordered 256 x 256 problems): a 1-wide head fed by the
-        same B rows rides on the launch (upnerf_wgrad_f16p_chain_v)."""
-        ns = nsplit_for(M)
-        ws = self._slabs(ns)
-        if v is not None:
-            assert frag and N == 256 and K == 256 and bexp is not None and n2 == 0
-            rc = TIMER.run(f"wgrad16p_{N}x{K}", lambda: lib.upnerf_wgrad_f16p_chain_v(
-                M, ptr(A16), ptr(aexp), ptr(B), ptr(bexp), dW_ptr, ldo, db_ptr, ptr(v), dv_ptr, dbv_ptr, ptr(ws), ns, expo_a, expo_b,
-                C.byref(self.pending), stream()), units=M)
-            check(rc, "upnerf_wgrad_f16p_chain_v")
-            return
-        rc = TIMER.run(f"wgrad16p_{N}x{K}", lambda: lib.upnerf_wgrad_f16p_chain(
-            M, ptr(A16), lda, ptr(aexp), N, ptr(B), ldb, ptr(bexp), int(bexp is not None) | (2 if frag else 0), K, dW_ptr, ldo, db_ptr,
-            n2, dW2_ptr, ldo2, db2_ptr, ptr(ws), ns, expo_a, expo_b, C.byref(self.pending), stream()), units=M)
-        check(rc, "upnerf_wgrad_f16p_chain")
-
-    def wgrad_p24(self, M, A16, Alo8, lda, aexp, N, B, Blo8, ldb, bexp, K, dW_ptr, ldo, db_ptr, expo_a, expo_b):
-        """The "24-bit" operands of the f16x3 mode (hi fp16 + residual byte, upnerf_wgrad_f24p_chain) as a link of the run."""
-        ns = nsplit_for(M)
-        ws = self._slabs(ns)
-        rc = TIMER.run(f"wgrad24p_{N}x{K}", lambda: lib.upnerf_wgrad_f24p_chain(
-            M, ptr(A16), ptr(Alo8), lda, ptr(aexp), N, ptr(B), ptr(Blo8), ldb, ptr(bexp), int(bexp is not None), K, dW_ptr, ldo, db_ptr,
-            ptr(ws), ns, expo_a, expo_b, C.byref(self.pending), stream()), units=M)
-        check(rc, "upnerf_wgrad_f24p_chain")
-
-    def finish(self):
-        check(lib.upnerf_wgrad_finish(C.byref(self.pending), stream()), "upnerf_wgrad_finish")
-
-
-def wgrad_f16p_into(M: int, A16: torch.Tensor, lda: int, aexp: torch.Tensor, N: int, B: torch.Tensor, ldb: int,
-                    bexp: Optional[torch.Tensor], K: int, dW_ptr: int, ldo: int, db_ptr: Optional[int], device, expo_a: int,
-                    expo_b: int, frag: bool = False):
-    """upnerf_wgrad for the f16 field mode's fp16-STORED operands: A16 [M][lda] fp16 scaled per 64-row tile by 2^aexp[tile]
-    (gz16 / gzexp), B the same (fp16, bexp) or fp32 rows (bexp None: the encoding x0).  frag: the fp16 operands are the
-    operand fragments of the register-resident field kernels (one exponent per 32 rows; include/upnerf_hip.h, tile_rows = 256)."""
-    ns = nsplit_for(M)
-    ws = workspace("wgrad", ns * (256 * 256 + 256), device)
-    rc = TIMER.run(f"wgrad16p_{N}x{K}", lambda: lib.upnerf_wgrad_f16p(M, ptr(A16), lda, ptr(aexp), N, ptr(B), ldb, ptr(bexp),
-                                                                     int(bexp is not None) | (2 if frag else 0), K, dW_ptr, ldo, db_ptr, ptr(ws), ns,
-                                                                     expo_a, expo_b, stream()), units=M)
-    check(rc, "upnerf_wgrad_f16p")
+    WgradRun(device, chained=False).wgrad(M, WgOp(A, lda, off=a_off), N, WgOp(B, ldb, off=b_off), K, expo_a, expo_b, dW=dW_ptr, ldo=ldo,
+                                          db=db_ptr, planes=planes)
 
 
 def vec_wgrad_into(M: int, v: torch.Tensor, ldv: int, nvec: int, X: torch.Tensor, ldx: int, K: int, dw_ptr: int,
