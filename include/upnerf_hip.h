@@ -858,6 +858,66 @@ typedef struct {
 } upnerf_viz_rgb_args;
 int upnerf_viz_rgb(const upnerf_viz_rgb_args* a, void* stream);
 
+/* ---- novel views along a camera path (csrc/path.hip): poses between keyframes, and the rays and blended
+ * embedding rows of whole frames without a per-pixel directions buffer.  Added under ABI 11: new symbols only.  Every entry
+ * point: arguments refused on the host (-1) before anything is launched, nothing allocated, no host read-back, no atomics,
+ * one launch on `stream`.
+ *
+ * upnerf_path_poses: frame f sits at path parameter u[f] in [0, K-1] (clamped in the kernel; NaN -> 0); k = floor(u) held to
+ * k + 1 <= K - 1, s = u - k.  Everything is evaluated in fp64 from the fp32 keys and rounded to fp32 once.
+ *   s == 0 (or s == 1 at the last key): the keyframe's twelve floats and its (near, far) are COPIED, bit for bit.
+ *   rotation: unit quaternions of keys k, k + 1 (Shepperd's branch on the largest of trace and diagonal, normalised);
+ *     q1 negated when q0 . q1 < 0 (shorter arc); slerp with sin((1-s) th) / sin th and sin(s th) / sin th, th = acos(q0 . q1);
+ *     normalised lerp when q0 . q1 > 1 - 1e-9; back to a matrix.
+ *   translation: UPNERF_PATH_LINEAR (1-s) p1 + s p2; UPNERF_PATH_CATMULL the uniform Catmull-Rom spline through
+ *     p(k-1), p(k), p(k+1), p(k+2), the first / last key standing in for a neighbour that does not exist.
+ *   near, far: always (1-s) a + s b. */
+#define UPNERF_PATH_LINEAR 0
+#define UPNERF_PATH_CATMULL 1
+typedef struct {
+  int32_t K, F, mode, reserved_;
+  const float* key_c2w;      /* [K][3][4] */
+  const float* key_nf;       /* [K][2] near, far */
+  const float* u;            /* [F] */
+  float* c2w;                /* [F][3][4] */
+  float* nf;                 /* [F][2] */
+} upnerf_path_poses_args;
+int upnerf_path_poses(const upnerf_path_poses_args* a, void* stream);
+
+/* upnerf_path_rays: rows [row0, row0 + R) of the virtual pixel list [F][H][W]; global row g is frame f = g / (H W), pixel
+ * y = (g % (H W)) / W, x = g % W.  Per row:
+ *   rays[r] = o | d | near_f | far_f   (the [R][8] rows render_rays slices) with
+ *     dir = ((x - cx) / fx, -(y - cy) / fy, -1)      utils/ray.py:22-25 on the integer pixel grid, no half-pixel shift
+ *     d = R_f dir / |R_f dir|                        fp32, correctly rounded sqrt and division (as upnerf_pose_rays_fwd)
+ *     o = c2w[f][:, 3], (near_f, far_f) = nf[f]      copied
+ *   tables[i].out[r][j] = (1 - t[f]) * T[i0[f]][j] + t[f] * T[i1[f]][j], two rounded products and a rounded sum (no fma):
+ *     t = 0 and t = 1 return a finite table row bit for bit (up to the sign of a zero entry).
+ * i0, i1, t are device arrays, so the host cannot see an index: one outside [0, n_rows) is clamped into it by the kernel.
+ * A row's values depend on its global index only: any split of the rows into calls gives the same bits.
+ * One thread per 16 bytes written; 16-byte stores for the rays when `rays` is 16-byte aligned and for a table when
+ * dim % 4 == 0 and `table` and `out` are 16-byte aligned, scalar accesses otherwise. */
+#define UPNERF_PATH_MAX_TABLES 4
+#define UPNERF_PATH_MAX_DIM 64
+typedef struct {
+  const float* table;        /* [n_rows][dim] */
+  int32_t dim, n_rows;       /* 1 <= dim <= UPNERF_PATH_MAX_DIM */
+  float* out;                /* [R][dim] */
+} upnerf_path_table;
+typedef struct {
+  int32_t F, H, W, n_tables;
+  int64_t row0;
+  int32_t R, reserved_;
+  float fx, fy, cx, cy;
+  const float* c2w;          /* [F][3][4] */
+  const float* nf;           /* [F][2] */
+  const int32_t* i0;         /* [F]; NULL allowed when n_tables == 0, like i1 and t */
+  const int32_t* i1;         /* [F] */
+  const float* t;            /* [F] */
+  float* rays;               /* [R][8] */
+  upnerf_path_table tables[UPNERF_PATH_MAX_TABLES];
+} upnerf_path_rays_args;
+int upnerf_path_rays(const upnerf_path_rays_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

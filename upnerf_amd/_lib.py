@@ -229,6 +229,26 @@ VIZ_RANGE_OWN, VIZ_RANGE_HOST, VIZ_RANGE_DEVICE = 0, 1, 2  # UPNERF_VIZ_RANGE_*
 VIZ_PLAIN, VIZ_PRED_DEPTH = 0, 1  # UPNERF_VIZ_PLAIN / UPNERF_VIZ_PRED_DEPTH
 
 
+PATH_LINEAR, PATH_CATMULL = 0, 1  # UPNERF_PATH_*
+PATH_MAX_TABLES, PATH_MAX_DIM = 4, 64  # UPNERF_PATH_MAX_*
+
+
+class PathPosesArgs(C.Structure):
+    _fields_ = [("K", C.c_int32), ("F", C.c_int32), ("mode", C.c_int32), ("reserved_", C.c_int32), ("key_c2w", _fp),
+                ("key_nf", _fp), ("u", _fp), ("c2w", _fp), ("nf", _fp)]
+
+
+class PathTable(C.Structure):
+    _fields_ = [("table", _fp), ("dim", C.c_int32), ("n_rows", C.c_int32), ("out", _fp)]
+
+
+class PathRaysArgs(C.Structure):
+    _fields_ = [("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_tables", C.c_int32), ("row0", C.c_int64),
+                ("R", C.c_int32), ("reserved_", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("c2w", _fp), ("nf", _fp), ("i0", _fp), ("i1", _fp), ("t", _fp), ("rays", _fp),
+                ("tables", PathTable * PATH_MAX_TABLES)]
+
+
 class Rng(C.Structure):
     """upnerf_rng: key of the uniform draws a kernel generates itself."""
     _fields_ = [("seed", C.c_uint64), ("step", C.c_int32), ("row0", C.c_int32), ("row_stride", C.c_int32), ("step_dev", _fp)]
@@ -297,6 +317,8 @@ _SIGNATURES = {
     "upnerf_viz_pca_scratch": [C.POINTER(VizPcaArgs)],
     "upnerf_viz_pca": [C.POINTER(VizPcaArgs), _p, _p],
     "upnerf_viz_rgb": [C.POINTER(VizRgbArgs), _p],
+    "upnerf_path_poses": [C.POINTER(PathPosesArgs), _p],
+    "upnerf_path_rays": [C.POINTER(PathRaysArgs), _p],
 }
 MAX_SCALARS = 96
 EXPORTS = tuple(_SIGNATURES)

@@ -1,0 +1,331 @@
+"""Novel views along a camera path: frames from cameras that are not in the dataset, the static scene only (TransientNet is
+not evaluated), the appearance embedding moving smoothly between photographs.
+
+    path = CameraPath.through_images(system, [3, 17, 42], n_frames=120)
+    out = render_path(system, path, outputs=("rgb", "depth"), sink=ImageWriter("frames"))
+
+The front end is two HIP kernels (csrc/path.hip): `upnerf_path_poses` turns keyframe poses into one pose per
+frame (quaternion slerp, linear or Catmull-Rom translation, fp64 rounded once), `upnerf_path_rays` writes, chunk by chunk,
+the [R][8] ray rows of the virtual [F][H][W] pixel list and the per-ray embedding rows as blends of two table rows.  The
+rows go to `render_rays` through its `embed_rows` keyword; the pictures are built by the kernels of `visualization`.
+There is no CPU path.  `plan_path` (which frame sits where, which two images it blends) is plain host arithmetic."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Callable, Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, lib, ptr, stream
+from .ops import TIMER
+
+__all__ = ["CameraPath", "plan_path", "path_poses", "path_rays", "render_path", "MODES"]
+
+MODES = {"linear": _lib.PATH_LINEAR, "catmull": _lib.PATH_CATMULL}
+LAST_WORKSPACE: Dict[str, tuple] = {}  # shapes of the per-chunk buffers the last render_path allocated (tests)
+
+
+def plan_path(n_frames: int, img_ids: Optional[Sequence[int]] = None, loop: bool = False, n_keys: Optional[int] = None,
+              appearance: Optional[Tuple[int, int]] = None):
+    """(u fp32 [F], i0 int32 [F], i1 int32 [F], t fp32 [F]) of a path with F = n_frames frames.
+
+    u: the frames' path parameters, evenly spaced over [0, K - 1] with both ends (one frame: u = [0]).
+    img_ids (the keyframes are images; `loop` appends the first one at the end, K = len(img_ids) [+ 1]): the appearance
+    follows the path -- with k = floor(u), s = u - k a frame blends image id[k] into id[k + 1] by t = s; on a keyframe
+    (integer u, the last one included) t = 0 and i0 is that keyframe's image.
+    appearance = (id0, id1) (free keyframe poses, K = n_keys): one blend from id0 to id1 over the whole path, t rising
+    linearly from 0 to 1 (one frame: t = 0).  (id, id) is a fixed appearance."""
+    if n_frames < 1:
+        raise ValueError(f"a path has at least one frame, got n_frames={n_frames}")
+    if (img_ids is None) == (appearance is None):
+        raise ValueError("give either img_ids (appearance follows the keyframes) or appearance=(id0, id1)")
+    if img_ids is not None:
+        ids = [int(i) for i in img_ids]
+        if loop:
+            ids = ids + ids[:1]
+        if n_keys is not None and n_keys != len(ids):
+            raise ValueError(f"n_keys={n_keys} but img_ids gives {len(ids)} keyframes")
+        K = len(ids)
+    else:
+        if n_keys is None:
+            raise ValueError("appearance=(id0, id1) needs n_keys")
+        K = int(n_keys)
+    if K < 2:
+        raise ValueError(f"a path needs at least two keyframes, got {K}")
+    u = np.linspace(0.0, K - 1.0, n_frames, dtype=np.float64).astype(np.float32) if n_frames > 1 else np.zeros(1, np.float32)
+    u[-1] = K - 1.0 if n_frames > 1 else 0.0
+    if img_ids is not None:
+        k = np.minimum(np.floor(u).astype(np.int64), K - 1)
+        t = (u.astype(np.float64) - k).astype(np.float32)  # exact: removing the integer part of a fp32 number
+        idv = np.asarray(ids, dtype=np.int32)
+        i0, i1 = idv[k], idv[np.minimum(k + 1, K - 1)]
+    else:
+        t = np.linspace(0.0, 1.0, n_frames, dtype=np.float64).astype(np.float32) if n_frames > 1 else np.zeros(1, np.float32)
+        i0 = np.full(n_frames, int(appearance[0]), dtype=np.int32)
+        i1 = np.full(n_frames, int(appearance[1]), dtype=np.int32)
+    return (torch.from_numpy(u), torch.from_numpy(np.ascontiguousarray(i0)), torch.from_numpy(np.ascontiguousarray(i1)),
+            torch.from_numpy(t))
+
+
+def _per_image(ds, name: str, idx: int):
+    """Entry of a per-image collection of the dataset for TRAINING image `idx`: scene datasets key theirs by image id
+    (`img_ids_train[idx]`), anything else is indexed by `idx`."""
+    v = getattr(ds, name, None)
+    if v is None:
+        return None
+    ids = getattr(ds, "img_ids_train", None)
+    return v[ids[idx]] if (ids is not None and isinstance(v, dict)) else v[idx]
+
+
+@dataclass
+class CameraPath:
+    """Keyframes and the per-frame plan of a rendered sequence, all host tensors (render_path uploads them once)."""
+    key_c2w: torch.Tensor        # [K, 3, 4] fp32
+    key_near_far: torch.Tensor   # [K, 2] fp32
+    u: torch.Tensor              # [F] fp32 in [0, K - 1]
+    i0: torch.Tensor             # [F] int32, rows of the embedding tables
+    i1: torch.Tensor             # [F] int32
+    t: torch.Tensor              # [F] fp32 blend weight of i1
+    img_wh: Tuple[int, int]      # (W, H)
+    K: torch.Tensor              # [3, 3] intrinsics
+    mode: str = "catmull"        # translation between keyframes: "linear" or "catmull"
+
+    def __post_init__(self):
+        if self.mode not in MODES:
+            raise ValueError(f"mode is one of {tuple(MODES)}, got {self.mode!r}")
+        self.key_c2w = torch.as_tensor(self.key_c2w, dtype=torch.float32).cpu().reshape(-1, 3, 4).contiguous()
+        self.key_near_far = torch.as_tensor(self.key_near_far, dtype=torch.float32).cpu().reshape(-1, 2).contiguous()
+        if self.key_c2w.shape[0] < 2 or self.key_near_far.shape[0] != self.key_c2w.shape[0]:
+            raise ValueError("a path needs K >= 2 keyframe poses [K, 3, 4] and as many (near, far) pairs")
+        self.u = torch.as_tensor(self.u, dtype=torch.float32).cpu().reshape(-1).contiguous()
+        self.i0 = torch.as_tensor(self.i0).to(torch.int32).cpu().reshape(-1).contiguous()
+        self.i1 = torch.as_tensor(self.i1).to(torch.int32).cpu().reshape(-1).contiguous()
+        self.t = torch.as_tensor(self.t, dtype=torch.float32).cpu().reshape(-1).contiguous()
+        F = self.u.numel()
+        if F < 1 or not (self.i0.numel() == self.i1.numel() == self.t.numel() == F):
+            raise ValueError("u, i0, i1 and t hold one entry per frame")
+        self.img_wh = (int(self.img_wh[0]), int(self.img_wh[1]))
+        if min(self.img_wh) < 1:
+            raise ValueError(f"img_wh = (W, H) with W, H >= 1, got {self.img_wh}")
+        self.K = torch.as_tensor(np.asarray(self.K), dtype=torch.float32).cpu().reshape(3, 3)
+
+    @property
+    def n_frames(self) -> int:
+        return self.u.numel()
+
+    @classmethod
+    def through_images(cls, system, img_ids: Sequence[int], n_frames: int, mode: str = "catmull", img_wh=None, K=None,
+                       loop: bool = False) -> "CameraPath":
+        """A path through training images `img_ids` (indices of the training set: the rows of the per-image tables).
+        Keyframes are the REFINED training poses (pose_align.refined_poses of the trained se(3) rows and the dataset's
+        poses), near / far the dataset's `nears` / `fars` (hparams nerf.near / nerf.far where it has none); the appearance
+        follows the path (plan_path).  `K` and `img_wh` default to those of the first keyframe image."""
+        from .pose_align import refined_poses
+        ids = [int(i) for i in img_ids]
+        ds, hp = system.train_dataset, system.hparams
+        w = system.se3_refine.weight
+        if not ids or min(ids) < 0 or max(ids) >= w.shape[0]:
+            raise ValueError(f"img_ids must be training image indices in [0, {w.shape[0]})")
+        if getattr(ds, "poses_dict", None) is not None:
+            poses = [torch.as_tensor(np.asarray(_per_image(ds, "poses_dict", i)), dtype=torch.float32) for i in ids]
+        elif getattr(ds, "poses", None) is not None:
+            poses = [torch.as_tensor(np.asarray(ds.poses[i]), dtype=torch.float32) for i in ids]
+        else:
+            raise ValueError("the training dataset carries no poses (poses_dict / poses): use CameraPath.from_poses")
+        poses = torch.stack([p.reshape(-1, 4)[:3] for p in poses])
+        sel = torch.as_tensor(ids, device=w.device)
+        keys = refined_poses(w.detach()[sel], poses).cpu()
+        nf = []
+        for i in ids:
+            n, f = _per_image(ds, "nears", i), _per_image(ds, "fars", i)
+            nf.append((float(hp["nerf.near"]) if n is None else float(n), float(hp["nerf.far"]) if f is None else float(f)))
+        nf = torch.tensor(nf, dtype=torch.float32)
+        if loop:
+            keys, nf = torch.cat([keys, keys[:1]]), torch.cat([nf, nf[:1]])
+        if K is None:
+            K = _per_image(ds, "Ks", ids[0])
+        if img_wh is None:
+            wh = getattr(ds, "all_imgs_wh", None)
+            img_wh = None if wh is None else tuple(int(x) for x in wh[ids[0]])
+        if K is None or img_wh is None:
+            raise ValueError("the dataset carries no intrinsics / image sizes (Ks, all_imgs_wh): pass K and img_wh")
+        u, i0, i1, t = plan_path(n_frames, img_ids=ids, loop=loop)
+        return cls(keys, nf, u, i0, i1, t, img_wh, K, mode)
+
+    @classmethod
+    def from_poses(cls, c2w, near_far, n_frames: int, appearance: Tuple[int, int], img_wh, K, mode: str = "catmull") -> "CameraPath":
+        """A path through arbitrary keyframe poses `c2w` [K, 3, 4] with `near_far` [K, 2] (or one pair for all): one
+        appearance blend from image appearance[0] to appearance[1] over the whole path."""
+        c2w = torch.as_tensor(c2w, dtype=torch.float32).cpu().reshape(-1, 3, 4)
+        nf = torch.as_tensor(near_far, dtype=torch.float32).cpu().reshape(-1, 2)
+        if nf.shape[0] == 1:
+            nf = nf.expand(c2w.shape[0], 2)
+        u, i0, i1, t = plan_path(n_frames, n_keys=c2w.shape[0], appearance=appearance)
+        return cls(c2w, nf, u, i0, i1, t, img_wh, K, mode)
+
+
+def _dev32(x: torch.Tensor, device, dtype=torch.float32) -> torch.Tensor:
+    return torch.as_tensor(x).to(device=device, dtype=dtype).contiguous()
+
+
+def path_poses(key_c2w: torch.Tensor, key_nf: torch.Tensor, u: torch.Tensor, mode="catmull"):
+    """(c2w [F, 3, 4], near_far [F, 2]) at path parameters `u` [F] between the keyframes (upnerf_path_poses; device tensors)."""
+    if not key_c2w.is_cuda:
+        raise RuntimeError("libupnerf_hip operates on device memory only (path_poses got CPU tensors)")
+    dev = key_c2w.device
+    key_c2w, key_nf, u = _dev32(key_c2w, dev).reshape(-1, 3, 4), _dev32(key_nf, dev).reshape(-1, 2), _dev32(u, dev).reshape(-1)
+    K, F = key_c2w.shape[0], u.numel()
+    if key_nf.shape[0] != K:
+        raise ValueError("one (near, far) pair per keyframe")
+    c2w = torch.empty(F, 3, 4, device=dev, dtype=torch.float32)
+    nf = torch.empty(F, 2, device=dev, dtype=torch.float32)
+    a = _lib.PathPosesArgs(K=K, F=F, mode=MODES[mode] if isinstance(mode, str) else int(mode), key_c2w=ptr(key_c2w),
+                           key_nf=ptr(key_nf), u=ptr(u), c2w=ptr(c2w), nf=ptr(nf))
+    check(lib.upnerf_path_poses(C.byref(a), stream()), "upnerf_path_poses")
+    return c2w, nf
+
+
+def path_rays(c2w: torch.Tensor, nf: torch.Tensor, img_wh, K, row0: int, R: int, tables=(), i0=None, i1=None, t=None,
+              rays: Optional[torch.Tensor] = None):
+    """Rows [row0, row0 + R) of the frames' pixel list (upnerf_path_rays): returns (rays [R, 8], [rows [R, dim] per table]).
+
+    c2w [F, 3, 4], nf [F, 2] device tensors; K = 3 x 3 intrinsics or (fx, fy, cx, cy); tables: (table [N, dim], out or None)
+    pairs, blended between rows i0[f] and i1[f] (int32 [F]) with weight t[f] -- indices outside the table are clamped into
+    it by the kernel.  `rays` / `out`: preallocated buffers with at least R rows (their first R rows are written)."""
+    if not c2w.is_cuda:
+        raise RuntimeError("libupnerf_hip operates on device memory only (path_rays got CPU tensors)")
+    dev = c2w.device
+    W, H = int(img_wh[0]), int(img_wh[1])
+    if torch.is_tensor(K) or isinstance(K, np.ndarray):
+        Km = np.asarray(torch.as_tensor(K).cpu(), dtype=np.float64)
+        fx, fy, cx, cy = Km[0, 0], Km[1, 1], Km[0, 2], Km[1, 2]
+    else:
+        fx, fy, cx, cy = K
+    F = c2w.shape[0]
+    if rays is None:
+        rays = torch.empty(R, 8, device=dev, dtype=torch.float32)
+    if rays.shape[0] < R or tuple(rays.shape[1:]) != (8,):
+        raise ValueError(f"rays must be [>= {R}, 8]")
+    if len(tables) > _lib.PATH_MAX_TABLES:
+        raise ValueError(f"at most {_lib.PATH_MAX_TABLES} embedding tables per launch, got {len(tables)}")
+    a = _lib.PathRaysArgs(F=F, H=H, W=W, n_tables=len(tables), row0=int(row0), R=int(R), fx=float(fx), fy=float(fy),
+                          cx=float(cx), cy=float(cy), c2w=ptr(c2w), nf=ptr(nf), i0=ptr(i0), i1=ptr(i1), t=ptr(t), rays=ptr(rays))
+    outs = []
+    for j, (table, out) in enumerate(tables):
+        if table.dim() != 2 or (i0 is None or i1 is None or t is None):
+            raise ValueError("a table is [N, dim] and needs i0, i1 and t")
+        for x, dt in ((i0, torch.int32), (i1, torch.int32), (t, torch.float32)):
+            if x.dtype != dt or x.numel() != F:
+                raise ValueError("i0, i1 are int32 [F] and t is fp32 [F]")
+        dim = table.shape[1]
+        if out is None:
+            out = torch.empty(R, dim, device=dev, dtype=torch.float32)
+        if out.shape[0] < R or tuple(out.shape[1:]) != (dim,):
+            raise ValueError(f"the rows of table {j} must be [>= {R}, {dim}]")
+        a.tables[j] = _lib.PathTable(table=ptr(table), dim=dim, n_rows=table.shape[0], out=ptr(out))
+        outs.append(out[:R])
+    check(TIMER.run("path_rays", lambda: lib.upnerf_path_rays(C.byref(a), stream()), units=R), "upnerf_path_rays")
+    return rays[:R], outs
+
+
+def _table_keys(system, sched_mult) -> list:
+    """The embedding tables the phase reads: appearance always, candidate while the schedule has not finished."""
+    return [k for k in system.embeddings if k.endswith("_a") or (k.endswith("_c") and sched_mult < 1)]
+
+
+@torch.no_grad()
+def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: Sequence[str] = ("rgb",),
+                depth_range: Optional[Tuple[float, float]] = None, sink: Optional[Callable] = None) -> Dict[str, torch.Tensor]:
+    """Render every frame of `path` with the static fields of `system` (perturb = 0, no gradient, validation's sample counts).
+
+    outputs: any of "rgb" (uint8 [F, H, W, 3] of `s_rgb_fine`, `s_rgb_coarse` without a fine field), "depth" (uint8
+    [F, H, W, 3], `s_depth_*` through the JET table over ONE range for the whole sequence: `depth_range`, or the min / max of
+    frame 0, kept on the device), "rgb_float" (fp32 [F, H * W, 3]).
+    sink: called as sink("path", frame, {"rgb": ..., "depth": ...}) once per finished frame, in order (an `ImageWriter`).
+    The pixel list [F][H][W] is walked in chunks of `chunk` rows (default val.chunk_size) that may straddle frames; device
+    memory is the chunk's workspace, one frame of staging and the requested outputs."""
+    from .rendering import render_rays
+    from .visualization import depth_image, min_max_of, rgb_image
+    unknown = set(outputs) - {"rgb", "depth", "rgb_float"}
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)} (rgb, depth, rgb_float)")
+    hp = system.hparams
+    sched_mult = system.get_schedule_mult(system._host_progress)
+    if sched_mult == 0:
+        raise ValueError("render_path renders the static colour s_rgb_*, which does not exist while the candidate schedule has "
+                         "not started (sched_mult == 0): this checkpoint is too early in training")
+    dev = next(system.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError("render_path runs on the GPU only (no CPU fallback)")
+    typ = "fine" if system.fine else "coarse"
+    W, H = path.img_wh
+    F, n = path.n_frames, W * H
+    total = F * n
+    chunk = int(chunk or hp["val.chunk_size"])
+    if chunk < 1:
+        raise ValueError(f"chunk must be positive, got {chunk}")
+    chunk = min(chunk, total)
+    c2w, nf = path_poses(path.key_c2w.to(dev), path.key_near_far.to(dev), path.u.to(dev), path.mode)
+    i0, i1, t = path.i0.to(dev), path.i1.to(dev), path.t.to(dev)
+    Kh = path.K.double()
+    intr = (float(Kh[0, 0]), float(Kh[1, 1]), float(Kh[0, 2]), float(Kh[1, 2]))
+    keys = _table_keys(system, sched_mult)
+    weights = [system.embeddings[k].weight.detach().contiguous() for k in keys]
+    # the workspace of every chunk, allocated once: 32 B of rays and sum(dim) * 4 B of rows per ray of the chunk
+    ws = {"rays": torch.empty(chunk, 8, device=dev, dtype=torch.float32)}
+    for k, w in zip(keys, weights):
+        ws[k] = torch.empty(chunk, w.shape[1], device=dev, dtype=torch.float32)
+    LAST_WORKSPACE.clear()
+    LAST_WORKSPACE.update({k: tuple(v.shape) for k, v in ws.items()})
+    want_depth = "depth" in outputs
+    stage_rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    stage_depth = torch.empty(n, device=dev, dtype=torch.float32) if want_depth else None
+    out: Dict[str, torch.Tensor] = {}
+    if "rgb" in outputs:
+        out["rgb"] = torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
+    if want_depth:
+        out["depth"] = torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
+    if "rgb_float" in outputs:
+        out["rgb_float"] = torch.empty(F, n, 3, device=dev, dtype=torch.float32)
+    rng_dev = None  # frame 0's (min, max) depth on the device: one colour scale for the whole sequence
+
+    def finish(f):
+        nonlocal rng_dev
+        images = {}
+        if "rgb_float" in out:
+            out["rgb_float"][f].copy_(stage_rgb)
+        if "rgb" in out:
+            out["rgb"][f].copy_(rgb_image(stage_rgb, (W, H)))
+            images["rgb"] = out["rgb"][f]
+        if want_depth:
+            if depth_range is None and rng_dev is None:
+                rng_dev = min_max_of(stage_depth)
+            out["depth"][f].copy_(depth_image(stage_depth, (W, H), min_max=depth_range if depth_range is not None else rng_dev))
+            images["depth"] = out["depth"][f]
+        if sink is not None:
+            sink("path", f, images)
+
+    for g0 in range(0, total, chunk):
+        R = min(chunk, total - g0)
+        rays, rows = path_rays(c2w, nf, (W, H), intr, g0, R, tables=[(w, ws[k]) for k, w in zip(keys, weights)], i0=i0, i1=i1,
+                               t=t, rays=ws["rays"])
+        res = render_rays(models=system.models, embeddings=system.embeddings, rays=rays, img_idx=None, sched_mult=sched_mult,
+                          sched_phase=2 if sched_mult == 1 else 1, N_samples=hp["nerf.N_samples"], use_disp=hp["nerf.use_disp"],
+                          perturb=0, N_importance=hp["nerf.N_importance"],
+                          white_back=getattr(system.train_dataset, "white_back", False), encode_feat=hp["nerf.feat_dim"] > 0,
+                          validation=True, embed_rows=dict(zip(keys, rows)))
+        rgb, depth = res[f"s_rgb_{typ}"], res[f"s_depth_{typ}"]
+        g = g0
+        while g < g0 + R:  # the chunk's rows, frame by frame
+            f, p0 = divmod(g, n)
+            cnt = min(n - p0, g0 + R - g)
+            stage_rgb[p0:p0 + cnt].copy_(rgb[g - g0:g - g0 + cnt])
+            if want_depth:
+                stage_depth[p0:p0 + cnt].copy_(depth[g - g0:g - g0 + cnt])
+            g += cnt
+            if p0 + cnt == n:
+                finish(f)
+    return out
