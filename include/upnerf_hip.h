@@ -918,6 +918,70 @@ typedef struct {
 } upnerf_path_rays_args;
 int upnerf_path_rays(const upnerf_path_rays_args* a, void* stream);
 
+/* ---- geometry: the density field on a grid and its iso-surface as a triangle mesh (csrc/mesh.hip).  Added under
+ * ABI 11: new symbols only.  Every entry point: arguments refused on the host before anything is launched, nothing allocated,
+ * no host read-back, no atomics (the same bits every run), all launches on `stream`.
+ *
+ * Grid coordinate i of n along an axis = lo + i * ((hi - lo) / (n - 1)), evaluated in fp64 from the fp32 bounds with every
+ * operation rounded on its own (lo when n == 1); grid point (x, y, z) has linear index (z * Ny + y) * Nx + x.
+ *
+ * upnerf_grid_columns: rays that make the field kernels evaluate grid points.  Column c = y * Nx + x; row r of the outputs is
+ * column col0 + r:  o[r] = (coord_x, coord_y, 0), d[r] = (0, 0, 1), z[r][s] = coord_z(min(s, Nz - 1)) for s < S -- o + d z is the
+ * grid point exactly, and S >= Nz pads a short column with its last depth (the field kernels want S >= 32).  Coordinates are
+ * rounded to fp32 once.  A row depends on its column only: any split into calls gives the same bits. */
+typedef struct {
+  int32_t Nx, Ny, Nz, S;
+  float lo[3], hi[3];
+  int64_t col0;
+  int32_t count, reserved_;
+  float* o;                  /* [count][3] */
+  float* d;                  /* [count][3] */
+  float* z;                  /* [count][S] */
+} upnerf_grid_columns_args;
+int upnerf_grid_columns(const upnerf_grid_columns_args* a, void* stream);
+
+/* Marching tetrahedra on the Kuhn split of every cell: six tetrahedra round the main diagonal, the same in every cell, so
+ * neighbouring cells agree on their face diagonals and no case is ambiguous.  A sample is inside when it is finite and
+ * >= level.  Corner c of a cell is its origin + (c & 1, (c >> 1) & 1, c >> 2).  The tables come from the caller
+ * (upnerf_amd/geometry.py defines them once); a table that does not describe such a split is UPNERF_EINVAL:
+ *   tets[t][i]      corner of vertex i of tetrahedron t; every pair of a tetrahedron's corners must be nested (a & b in {a, b})
+ *   edges[s]        offset (dx, dy, dz) in {0, 1}^3 of the far end of edge slot s from the grid point that owns it
+ *   tet_edges[e]    the two tetrahedron vertices that tet edge e joins
+ *   tris[case]      case = sum of (vertex i inside) << i: number of triangles (0..2), then three tet edges per triangle
+ * Vertices are the crossed edges in (owner point, slot) order:  t = (level - v0) / (v1 - v0) in fp32 (0.5 when an end is not
+ * finite), position = p0 + t (p1 - p0) on fp64 grid coordinates rounded once, normal = -(g0 + t (g1 - g0)) normalised, g = the
+ * grid's central differences (one-sided at the border) over the spacing; a gradient that is zero or not finite gives (0, 0, 0).
+ * Triangles come in (cell origin, tetrahedron, triangle) order and index the vertices.
+ *
+ * upnerf_mtet_scratch(Nx, Ny, Nz): bytes of scratch (16-byte aligned device memory); UPNERF_EINVAL for an axis with fewer than
+ *   two points, or when 7 Nx Ny Nz or 12 x cells does not fit int32 (the counts are int32).
+ * upnerf_mtet_count: fills the scratch (edge masks, triangle counts, their exclusive scans) and writes totals[0] = vertices,
+ *   totals[1] = triangles (device memory).  Reads Nx..grid and tab of the arguments.
+ * upnerf_mtet_emit: writes the mesh from the scratch of a count of the SAME grid, level and tables.  n_vertices / n_faces are
+ *   what that count reported; a capacity below them is UPNERF_EINVAL and nothing is written; the kernels hold every store to
+ *   the capacities besides. */
+typedef struct {
+  int8_t tets[6][4];
+  int8_t edges[7][3];
+  int8_t tet_edges[6][2];
+  int8_t tris[16][7];
+  int8_t reserved_[7];
+} upnerf_mtet_tables;
+typedef struct {
+  int32_t Nx, Ny, Nz;
+  float level;
+  float lo[3], hi[3];        /* bounds: grid point (0, 0, 0) and (Nx - 1, Ny - 1, Nz - 1); hi > lo (emit only) */
+  const float* grid;         /* [Nz][Ny][Nx] */
+  upnerf_mtet_tables tab;
+  int32_t n_vertices, n_faces, cap_vertices, cap_faces;   /* emit only, like the outputs */
+  float* vertices;           /* [cap_vertices][3] */
+  float* normals;            /* [cap_vertices][3] */
+  int32_t* faces;            /* [cap_faces][3] */
+} upnerf_mtet_args;
+long long upnerf_mtet_scratch(int Nx, int Ny, int Nz);
+int upnerf_mtet_count(const upnerf_mtet_args* a, void* scratch, int32_t* totals /*[2] device*/, void* stream);
+int upnerf_mtet_emit(const upnerf_mtet_args* a, const void* scratch, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

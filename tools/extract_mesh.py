@@ -1,0 +1,85 @@
+"""Write the surface of a trained scene as a coloured triangle mesh (upnerf_amd/geometry.py).
+
+    python tools/extract_mesh.py --ckpt last.ckpt [--config scene.yaml] --level SIGMA --out scene.ply
+                                 (--bounds X0 Y0 Z0 X1 Y1 Z1 | --from-cameras MARGIN) [--resolution 256 | NX NY NZ]
+                                 [--img-id 0] [--slab S] [--field fine|coarse] [--chunk COLUMNS]
+
+--level is the density (sigma, after the softplus) of the surface and has NO default: the useful value depends on the scale of
+the scene, so look at the histogram of a coarse grid first (--level with a low --resolution is quick).  With --config the
+scene's dataset is loaded, which --from-cameras needs (the box round the refined cameras and their far points); with --ckpt
+alone the hyper-parameters come from the checkpoint and the box from --bounds.  Colours are the static colour under the
+appearance of training image --img-id, rendered over a slab of thickness 2 S round every vertex (default: one cell diagonal).
+Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def parser():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", help="the scene's YAML configuration (as given to training); loads the dataset")
+    ap.add_argument("--ckpt", help="checkpoint of the trained system")
+    ap.add_argument("--level", type=float, required=True, help="density of the surface (no default: it depends on the scene's scale)")
+    ap.add_argument("--out", required=True, help="the PLY file to write")
+    box = ap.add_mutually_exclusive_group(required=True)
+    box.add_argument("--bounds", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    box.add_argument("--from-cameras", type=float, metavar="MARGIN", help="box round the refined cameras and their far points, grown by MARGIN")
+    ap.add_argument("--resolution", type=int, nargs="+", default=[256], help="grid points per axis: one number or NX NY NZ")
+    ap.add_argument("--img-id", type=int, default=0, help="training image whose appearance colours the mesh")
+    ap.add_argument("--slab", type=float, default=None, help="half thickness of the slab rendered round a vertex (default: a cell diagonal)")
+    ap.add_argument("--field", default="fine", choices=("fine", "coarse"))
+    ap.add_argument("--chunk", type=int, default=None, help="grid columns per field launch (default: about a million samples)")
+    return ap
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
+    if not a.config and not a.ckpt:
+        raise SystemExit("give --ckpt, --config or both")
+    if len(a.resolution) not in (1, 3):
+        raise SystemExit("--resolution takes one number or three")
+    res = tuple(a.resolution * 3 if len(a.resolution) == 1 else a.resolution)
+    if not torch.cuda.is_available():
+        raise SystemExit("extract_mesh.py runs on the GPU; none is visible")
+    from upnerf_amd import checkpoint, config, geometry
+    from upnerf_amd.nerf_system import NeRFSystem, SyntheticDataset
+    ckpt = checkpoint.read_checkpoint(a.ckpt) if a.ckpt else None
+    if a.config:
+        system = NeRFSystem(config.get_from_path(a.config))
+    else:
+        if "hyper_parameters" not in ckpt:
+            raise SystemExit("the checkpoint carries no hyper-parameters: give --config")
+        if a.from_cameras is not None:
+            raise SystemExit("--from-cameras needs the dataset's poses: give --config, or --bounds")
+        sd = ckpt.get("state_dict", ckpt)
+        system = NeRFSystem(dict(ckpt["hyper_parameters"]), SyntheticDataset(sd["se3_refine.weight"].shape[0]))
+    system.setup()
+    if ckpt is not None:
+        checkpoint.load_checkpoint(system, ckpt, resume=False)
+    system.cuda()
+    t0 = time.perf_counter()
+    bounds = (geometry.bounds_from_cameras(system, a.from_cameras) if a.from_cameras is not None
+              else (tuple(a.bounds[:3]), tuple(a.bounds[3:])))
+    grid = geometry.density_grid(system, bounds, res, field=a.field, chunk=a.chunk)
+    mesh = geometry.extract_surface(grid, bounds, a.level)
+    slab = a.slab
+    if slab is None:
+        slab = sum(((h - l) / max(n - 1, 1)) ** 2 for l, h, n in zip(bounds[0], bounds[1], res)) ** 0.5
+    if mesh.vertices.shape[0]:
+        mesh.colours = geometry.colour_vertices(system, mesh, a.img_id, slab)
+    mesh.write_ply(a.out)
+    torch.cuda.synchronize()
+    print(json.dumps({"out": a.out, "vertices": int(mesh.vertices.shape[0]), "faces": int(mesh.faces.shape[0]),
+                      "resolution": list(res), "bounds": [list(bounds[0]), list(bounds[1])], "level": a.level, "slab": slab,
+                      "sigma_min": float(grid.min()), "sigma_max": float(grid.max()), "seconds": time.perf_counter() - t0}))
+
+
+if __name__ == "__main__":
+    main()

@@ -249,6 +249,23 @@ class PathRaysArgs(C.Structure):
                 ("tables", PathTable * PATH_MAX_TABLES)]
 
 
+class GridColumnsArgs(C.Structure):
+    _fields_ = [("Nx", C.c_int32), ("Ny", C.c_int32), ("Nz", C.c_int32), ("S", C.c_int32), ("lo", C.c_float * 3),
+                ("hi", C.c_float * 3), ("col0", C.c_int64), ("count", C.c_int32), ("reserved_", C.c_int32), ("o", _fp), ("d", _fp),
+                ("z", _fp)]
+
+
+class MtetTables(C.Structure):
+    _fields_ = [("tets", (C.c_int8 * 4) * 6), ("edges", (C.c_int8 * 3) * 7), ("tet_edges", (C.c_int8 * 2) * 6),
+                ("tris", (C.c_int8 * 7) * 16), ("reserved_", C.c_int8 * 7)]
+
+
+class MtetArgs(C.Structure):
+    _fields_ = [("Nx", C.c_int32), ("Ny", C.c_int32), ("Nz", C.c_int32), ("level", C.c_float), ("lo", C.c_float * 3),
+                ("hi", C.c_float * 3), ("grid", _fp), ("tab", MtetTables), ("n_vertices", C.c_int32), ("n_faces", C.c_int32),
+                ("cap_vertices", C.c_int32), ("cap_faces", C.c_int32), ("vertices", _fp), ("normals", _fp), ("faces", _fp)]
+
+
 class Rng(C.Structure):
     """upnerf_rng: key of the uniform draws a kernel generates itself."""
     _fields_ = [("seed", C.c_uint64), ("step", C.c_int32), ("row0", C.c_int32), ("row_stride", C.c_int32), ("step_dev", _fp)]
@@ -319,6 +336,10 @@ _SIGNATURES = {
     "upnerf_viz_rgb": [C.POINTER(VizRgbArgs), _p],
     "upnerf_path_poses": [C.POINTER(PathPosesArgs), _p],
     "upnerf_path_rays": [C.POINTER(PathRaysArgs), _p],
+    "upnerf_grid_columns": [C.POINTER(GridColumnsArgs), _p],
+    "upnerf_mtet_scratch": [_i, _i, _i],
+    "upnerf_mtet_count": [C.POINTER(MtetArgs), _p, _p, _p],
+    "upnerf_mtet_emit": [C.POINTER(MtetArgs), _p, _p],
 }
 MAX_SCALARS = 96
 EXPORTS = tuple(_SIGNATURES)
@@ -335,7 +356,7 @@ def _load():
         if fn is None:
             raise ImportError(f"{LIB_PATH} does not export {name}; rebuild it")
         fn.argtypes = argtypes
-        fn.restype = C.c_longlong if name == "upnerf_wgrad16_scratch" else C.c_int
+        fn.restype = C.c_longlong if name in ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch") else C.c_int
     return lib
 
 

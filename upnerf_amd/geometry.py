@@ -1,0 +1,368 @@
+"""Geometry of a trained scene: the shared density on a grid, its iso-surface as a coloured triangle mesh, a PLY file.
+
+    bounds = bounds_from_cameras(system, margin=0.5)
+    grid = density_grid(system, bounds, (256, 256, 256))
+    mesh = extract_surface(grid, bounds, level=10.0)
+    mesh.colours = colour_vertices(system, mesh, img_id=3, slab=0.02)
+    mesh.write_ply("scene.ply")
+
+The density pass runs the field kernels the training step runs (`upnerf_field_fwd*`, density head only) on rays that ARE grid
+columns (`upnerf_grid_columns`); the surface is marching tetrahedra on the Kuhn split of every cell, in HIP
+(`upnerf_mtet_count` / `upnerf_mtet_emit`, csrc/mesh.hip).  There is no CPU path for either.  The case tables
+live HERE and are handed to the kernels; PLY files and camera bounds are plain host code."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, lib, ptr, stream
+from .ops import TIMER
+
+__all__ = ["TETS", "EDGES", "TET_EDGES", "TRI_TABLE", "edge_owner", "Mesh", "read_ply", "density_grid", "grid_columns",
+           "extract_surface", "colour_vertices", "bounds_from_cameras"]
+
+# ---- the tables of the split (the only copy: the kernels receive them as an argument) ---------------------------------------
+# Corner c of a cell is its origin + (c & 1, (c >> 1) & 1, c >> 2).  The Kuhn split: one tetrahedron per order in which the
+# three axes are walked from corner 0 to corner 7, in the order of itertools.permutations((0, 1, 2)); vertices 1 and 2 of the
+# odd orders are swapped, so that det(v1 - v0, v2 - v0, v3 - v0) > 0 for all six and one triangle table serves them all.
+TETS = ((0, 1, 3, 7), (0, 5, 1, 7), (0, 3, 2, 7), (0, 2, 6, 7), (0, 4, 5, 7), (0, 6, 4, 7))
+# The seven edges a grid point owns, slot s -> offset of the far end: +x, +y, +z, the face diagonals xy, xz, yz, the body diagonal.
+EDGES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
+# The six edges of a tetrahedron as pairs of its vertices.
+TET_EDGES = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
+# case = sum of (vertex i inside) << i  ->  triangles as triples of tet edges, wound so that the geometric normal points from the
+# inside vertices to the outside ones (towards lower density) in a positively oriented tetrahedron.  One inside (or outside)
+# vertex: its three edges in ascending order, two of them swapped where the winding asks for it; two inside vertices a < b and
+# outside c < d: the quad (ac, ad, bd, bc) cut along ac-bd.
+TRI_TABLE = (
+    (),
+    ((0, 1, 2),),
+    ((0, 4, 3),),
+    ((1, 2, 4), (1, 4, 3)),
+    ((1, 3, 5),),
+    ((0, 5, 2), (0, 3, 5)),
+    ((0, 4, 5), (0, 5, 1)),
+    ((2, 4, 5),),
+    ((2, 5, 4),),
+    ((0, 1, 5), (0, 5, 4)),
+    ((0, 5, 3), (0, 2, 5)),
+    ((1, 5, 3),),
+    ((1, 3, 4), (1, 4, 2)),
+    ((0, 3, 4),),
+    ((0, 2, 1),),
+    (),
+)
+MIN_SAMPLES = 32  # the field kernels' minimum of samples per ray (UPNERF_EUNSUP below it)
+
+
+def edge_owner(c0: int, c1: int) -> Tuple[Tuple[int, int, int], int]:
+    """The cell edge between corners c0 and c1 -> (offset of the grid point that owns it from the cell origin, its slot there).
+    Only nested corners (one contains the other's axes) are joined by an edge of the split: anything else raises."""
+    lo, hi = (c0, c1) if c0 & c1 == c0 else (c1, c0)
+    if lo & hi != lo or lo == hi:
+        raise ValueError(f"corners {c0} and {c1} are not joined by an edge of the Kuhn split")
+    d = lo ^ hi
+    return (lo & 1, (lo >> 1) & 1, lo >> 2), EDGES.index((d & 1, (d >> 1) & 1, d >> 2))
+
+
+def _tables() -> "_lib.MtetTables":
+    t = _lib.MtetTables()
+    for i, tet in enumerate(TETS):
+        for k, c in enumerate(tet):
+            t.tets[i][k] = c
+    for s, off in enumerate(EDGES):
+        for k, v in enumerate(off):
+            t.edges[s][k] = v
+    for e, pair in enumerate(TET_EDGES):
+        t.tet_edges[e][0], t.tet_edges[e][1] = pair
+    for case, tris in enumerate(TRI_TABLE):
+        t.tris[case][0] = len(tris)
+        for j, tri in enumerate(tris):
+            for k, e in enumerate(tri):
+                t.tris[case][1 + 3 * j + k] = e
+    return t
+
+
+def _bounds(bounds):
+    lo, hi = (tuple(float(v) for v in b) for b in bounds)
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("bounds is ((x0, y0, z0), (x1, y1, z1))")
+    return lo, hi
+
+
+# ---- meshes and PLY files (host code) -------------------------------------------------------------------------------------------
+
+_PLY_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex {V}\nproperty float x\nproperty float y\nproperty float z\n"
+               "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\n"
+               "property uchar blue\nelement face {F}\nproperty list uchar int vertex_indices\nend_header\n")
+_PLY_VERTEX = np.dtype([("p", "<f4", 3), ("n", "<f4", 3), ("c", "u1", 3)])
+_PLY_FACE = np.dtype([("k", "u1"), ("v", "<i4", 3)])
+
+
+@dataclass
+class Mesh:
+    """An indexed triangle mesh: device tensors out of extract_surface, host or device tensors anywhere else."""
+    vertices: torch.Tensor                   # [V, 3] fp32
+    normals: torch.Tensor                    # [V, 3] fp32, unit length or (0, 0, 0)
+    faces: torch.Tensor                      # [F, 3] int32
+    colours: Optional[torch.Tensor] = None   # [V, 3] fp32 in [0, 1] (colour_vertices) or uint8; None: written as grey
+
+    def write_ply(self, path: str) -> None:
+        """Binary little-endian PLY: x y z nx ny nz red green blue per vertex, a `uchar int` index list per face."""
+        v = self.vertices.detach().cpu().numpy().astype("<f4").reshape(-1, 3)
+        n = self.normals.detach().cpu().numpy().astype("<f4").reshape(-1, 3)
+        f = self.faces.detach().cpu().numpy().astype("<i4").reshape(-1, 3)
+        if self.colours is None:
+            c = np.full((v.shape[0], 3), 128, np.uint8)
+        else:
+            c = self.colours.detach().cpu()
+            if c.dtype != torch.uint8:  # as visualization.rgb_image quantises: x 255, clamped, truncated; NaN -> 0
+                c = torch.nan_to_num(c.float() * 255.0, nan=0.0).clamp(0, 255).to(torch.uint8)
+            c = c.numpy().reshape(-1, 3)
+        if n.shape != v.shape or c.shape != v.shape:
+            raise ValueError("normals and colours hold one row per vertex")
+        vert = np.zeros(v.shape[0], _PLY_VERTEX)
+        vert["p"], vert["n"], vert["c"] = v, n, c
+        face = np.zeros(f.shape[0], _PLY_FACE)
+        face["k"], face["v"] = 3, f
+        with open(path, "wb") as fh:
+            fh.write(_PLY_HEADER.format(V=v.shape[0], F=f.shape[0]).encode("ascii"))
+            fh.write(vert.tobytes())
+            fh.write(face.tobytes())
+
+
+def read_ply(path: str) -> Mesh:
+    """A file Mesh.write_ply wrote, back as host tensors (colours uint8).  Not a general PLY reader: another header raises."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if end < 0:
+        raise ValueError(f"{path}: no PLY header")
+    head = data[:end + 11].decode("ascii")
+    try:
+        lines = head.split("\n")
+        V, F = int(lines[2].split()[2]), int(lines[12].split()[2])
+    except (IndexError, ValueError):
+        raise ValueError(f"{path}: not a header Mesh.write_ply writes") from None
+    if head != _PLY_HEADER.format(V=V, F=F):
+        raise ValueError(f"{path}: not a header Mesh.write_ply writes")
+    body = data[end + 11:]
+    if len(body) != V * _PLY_VERTEX.itemsize + F * _PLY_FACE.itemsize:
+        raise ValueError(f"{path}: {len(body)} bytes of data for {V} vertices and {F} faces")
+    vert = np.frombuffer(body, _PLY_VERTEX, V)
+    face = np.frombuffer(body, _PLY_FACE, F, offset=V * _PLY_VERTEX.itemsize)
+    if F and not (face["k"] == 3).all():
+        raise ValueError(f"{path}: a face that is not a triangle")
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).reshape(-1, 3)
+    return Mesh(t(vert["p"], np.float32), t(vert["n"], np.float32), t(face["v"], np.int32), t(vert["c"], np.uint8))
+
+
+# ---- camera bounds (host code) --------------------------------------------------------------------------------------------------
+
+def bounds_from_cameras(system, margin: float, poses=None):
+    """((x0, y0, z0), (x1, y1, z1)): the box round the refined training camera centres and the points at `far` on their optical
+    axes (a camera looks down its -z axis: centre - far * R[:, 2]), grown by `margin` on every side.
+
+    `far` per image is the dataset's `fars` where it has them, hparams["nerf.far"] otherwise.  poses: [N, 3, 4] refined
+    camera-to-world poses to use instead of refining the dataset's with the trained se(3) rows (which runs the HIP pose kernel)."""
+    from .novel_view import _per_image
+    ds, hp = system.train_dataset, system.hparams
+    if poses is None:
+        from .pose_align import refined_poses
+        w = system.se3_refine.weight.detach()
+        N = w.shape[0]
+        if getattr(ds, "poses_dict", None) is not None:
+            raw = [torch.as_tensor(np.asarray(_per_image(ds, "poses_dict", i)), dtype=torch.float32) for i in range(N)]
+        elif getattr(ds, "poses", None) is not None:
+            raw = [torch.as_tensor(np.asarray(ds.poses[i]), dtype=torch.float32) for i in range(N)]
+        else:
+            raise ValueError("the training dataset carries no poses (poses_dict / poses): pass bounds yourself")
+        poses = refined_poses(w, torch.stack([p.reshape(-1, 4)[:3] for p in raw]))
+    c2w = np.asarray(torch.as_tensor(poses).detach().cpu(), dtype=np.float64).reshape(-1, 3, 4)
+    fars = []
+    for i in range(c2w.shape[0]):
+        f = _per_image(ds, "fars", i)
+        fars.append(float(hp["nerf.far"]) if f is None else float(f))
+    centre = c2w[:, :, 3]
+    ahead = centre - np.asarray(fars)[:, None] * c2w[:, :, 2]
+    pts = np.concatenate([centre, ahead])
+    if not np.isfinite(pts).all():
+        raise ValueError("a camera pose or far plane is not finite")
+    m = float(margin)
+    return tuple(float(v) - m for v in pts.min(0)), tuple(float(v) + m for v in pts.max(0))
+
+
+# ---- density on a grid ---------------------------------------------------------------------------------------------------------
+
+def grid_columns(bounds, resolution: Sequence[int], col0: int, count: int, S: Optional[int] = None, device="cuda"):
+    """(o [count, 3], d [count, 3], z [count, S]) of grid columns [col0, col0 + count) (upnerf_grid_columns): column y * Nx + x
+    is the ray o = (x, y, 0), d = (0, 0, 1) whose depths are the z coordinates, the last one repeated up to S >= Nz."""
+    lo, hi = _bounds(bounds)
+    Nx, Ny, Nz = (int(n) for n in resolution)
+    S = max(Nz, MIN_SAMPLES) if S is None else int(S)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("libupnerf_hip operates on device memory only (grid_columns got a CPU device)")
+    o = torch.empty(count, 3, device=dev, dtype=torch.float32)
+    d = torch.empty(count, 3, device=dev, dtype=torch.float32)
+    z = torch.empty(count, S, device=dev, dtype=torch.float32)
+    a = _lib.GridColumnsArgs(Nx=Nx, Ny=Ny, Nz=Nz, S=S, lo=(C.c_float * 3)(*lo), hi=(C.c_float * 3)(*hi), col0=int(col0),
+                             count=int(count), o=ptr(o), d=ptr(d), z=ptr(z))
+    check(lib.upnerf_grid_columns(C.byref(a), stream()), "upnerf_grid_columns")
+    return o, d, z
+
+
+def _field_sigma(model, o: torch.Tensor, d: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """sigma_s [R, S] of `model` at o + d z: the density-only forward pass of rendering._FieldPass (mode 2, nothing stored for
+    a backward pass) in the kernel family of the global field mode, without the compositing that follows it there."""
+    from . import rendering as rd
+    pk, L = model.packer, model.packer.L
+    R, S = z.shape
+    M, dev, st = R * S, z.device, stream()
+    P = model.packed().detach().contiguous()
+    use16 = rd._field16_ok(pk, S)
+    rr = use16 and rd._rr_ok(S)  # register-resident fp16 kernels: the encoding rows padded to whole 256-sample tiles
+    Mp = (M + rd.RR_TILE - 1) // rd.RR_TILE * rd.RR_TILE if rr else M
+    P16 = wexp = wnorm = None
+    if use16:
+        P16, _, wexp, wnorm = pk.frag16_hip(P, perm=rr)
+        PF = P
+    else:
+        PF = pk.frag_hip(P)
+    hp = getattr(model, "host_progress", None)
+    progress = float(model.progress.data) if hp is None else float(torch.tensor(hp, dtype=torch.float32))
+    sigma = torch.empty(R, S, device=dev, dtype=torch.float32)
+    x0 = torch.empty(Mp, _lib.X0, device=dev, dtype=torch.float32)
+    fa = _lib.FieldFwdArgs(R=R, S=S, use_cand=0, use_rgb=0, rays_o=ptr(o), rays_d=ptr(d), z=ptr(z),
+                           wk_xyz=(C.c_float * 10)(*rd.band_weights(model.xyz_L, progress, model.c2f)), P=ptr(PF),
+                           sigma_s=ptr(sigma), x0=ptr(x0), P16=ptr(P16), wexp=ptr(wexp), planes=rd._planes(),
+                           tile_rows=rd.RR_TILE if rr else 64, wnorm=ptr(wnorm), rows_capacity=Mp if rr else 0)
+    fn = lib.upnerf_field_fwd_f16x3 if use16 else lib.upnerf_field_fwd
+    check(TIMER.run("density_grid", lambda: fn(C.byref(L), C.byref(fa), st), units=M), "upnerf_field_fwd")
+    return sigma
+
+
+@torch.no_grad()
+def density_grid(system, bounds, resolution: Sequence[int], field: str = "fine", chunk: Optional[int] = None) -> torch.Tensor:
+    """[Nz, Ny, Nx] fp32 device tensor: the shared density (sigma_s, after the softplus) of the `field` ("fine" or "coarse")
+    network at the Nx x Ny x Nz grid points of `bounds`, with the BARF band weights of the model's current progress.
+
+    The grid is evaluated as rays, one per (x, y) column (grid_columns), `chunk` columns at a time (default: about a million
+    samples), so device memory is the chunk's workspace and the result whatever the resolution.  The values do not depend on
+    `chunk`.  Columns shorter than the field kernels' 32 samples are padded and the padding dropped."""
+    if field not in ("fine", "coarse"):
+        raise ValueError(f"field is 'fine' or 'coarse', got {field!r}")
+    model = system.models.get(f"nerf_{field}")
+    if model is None:
+        raise ValueError(f"the system has no {field} field")
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError("density_grid runs on the GPU only (no CPU fallback)")
+    lo, hi = _bounds(bounds)
+    Nx, Ny, Nz = (int(n) for n in resolution)
+    if min(Nx, Ny, Nz) < 1:
+        raise ValueError(f"resolution is the number of grid points per axis, got {tuple(resolution)}")
+    S = max(Nz, MIN_SAMPLES)
+    cols = Nx * Ny
+    chunk = int(chunk) if chunk is not None else max(1, (1 << 20) // S)
+    if chunk < 1:
+        raise ValueError(f"chunk must be positive, got {chunk}")
+    chunk = min(chunk, cols)
+    out = torch.empty(Nz, cols, device=dev, dtype=torch.float32)
+    for c0 in range(0, cols, chunk):
+        n = min(chunk, cols - c0)
+        o, d, z = grid_columns((lo, hi), (Nx, Ny, Nz), c0, n, S, device=dev)
+        sigma = _field_sigma(model, o, d, z)
+        out[:, c0:c0 + n].copy_(sigma[:, :Nz].t())  # (a strided copy: column-major samples into the [z][y][x] grid)
+    return out.view(Nz, Ny, Nx)
+
+
+# ---- iso-surface ---------------------------------------------------------------------------------------------------------------
+
+@torch.no_grad()
+def extract_surface(grid: torch.Tensor, bounds, level: float) -> Mesh:
+    """The surface `grid == level` of a [Nz, Ny, Nx] fp32 device tensor over `bounds` as a Mesh on the device: marching
+    tetrahedra (csrc/mesh.hip), inside = finite and >= level, normals = -gradient (towards lower values), faces wound to match.
+    Vertices come in (grid point, edge slot) order and faces in (cell, tetrahedron, triangle) order: the same grid gives the
+    same mesh, bit for bit.  `level` has no default: the useful threshold depends on the scene's scale."""
+    if not (torch.is_tensor(grid) and grid.is_cuda):
+        raise RuntimeError("extract_surface runs on the GPU only: the grid must be a device tensor (no CPU fallback)")
+    if grid.dtype != torch.float32 or grid.dim() != 3:
+        raise ValueError("the grid is a fp32 tensor [Nz, Ny, Nx]")
+    lo, hi = _bounds(bounds)
+    grid = grid.detach().contiguous()
+    Nz, Ny, Nx = grid.shape
+    dev, st = grid.device, stream()
+    nbytes = lib.upnerf_mtet_scratch(Nx, Ny, Nz)
+    if nbytes < 0:
+        check(int(nbytes), f"upnerf_mtet_scratch({Nx}, {Ny}, {Nz})")
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    totals = torch.empty(2, device=dev, dtype=torch.int32)
+    a = _lib.MtetArgs(Nx=Nx, Ny=Ny, Nz=Nz, level=float(level), lo=(C.c_float * 3)(*lo), hi=(C.c_float * 3)(*hi), grid=ptr(grid),
+                      tab=_tables())
+    check(TIMER.run("mtet_count", lambda: lib.upnerf_mtet_count(C.byref(a), ptr(scratch), ptr(totals), st), units=grid.numel()),
+          "upnerf_mtet_count")
+    V, F = (int(x) for x in totals.cpu())  # the one host read: the mesh is allocated exactly
+    vertices = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    normals = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    faces = torch.empty(F, 3, device=dev, dtype=torch.int32)
+    a.n_vertices = a.cap_vertices = V
+    a.n_faces = a.cap_faces = F
+    a.vertices, a.normals, a.faces = ptr(vertices), ptr(normals), ptr(faces)
+    check(TIMER.run("mtet_emit", lambda: lib.upnerf_mtet_emit(C.byref(a), ptr(scratch), st), units=grid.numel()), "upnerf_mtet_emit")
+    return Mesh(vertices, normals, faces)
+
+
+# ---- vertex colours ------------------------------------------------------------------------------------------------------------
+
+def vertex_rays(mesh: Mesh, slab: float) -> torch.Tensor:
+    """[V, 8] ray rows (o | d | near | far) through the surface at every vertex: o = p + slab * n, d = -n, near = 0,
+    far = 2 * slab; a vertex without a normal looks along d = (0, 0, 1)."""
+    p, n = mesh.vertices, mesh.normals
+    slab = float(slab)
+    if not slab > 0:
+        raise ValueError(f"slab must be positive, got {slab}")
+    flat = (n == 0).all(dim=1, keepdim=True)
+    d = torch.where(flat, torch.tensor([0.0, 0.0, 1.0], device=p.device), -n)
+    o = p + slab * n
+    nf = torch.tensor([0.0, 2.0 * slab], device=p.device).expand(p.shape[0], 2)
+    return torch.cat([o, d, nf], 1).contiguous()
+
+
+@torch.no_grad()
+def colour_vertices(system, mesh: Mesh, img_id: int, slab: float, chunk: Optional[int] = None) -> torch.Tensor:
+    """[V, 3] fp32 static colour (`s_rgb_fine`; `s_rgb_coarse` without a fine field) of every vertex, rendered by the public
+    render_rays along vertex_rays(mesh, slab) at sched_mult = 1 with the appearance row of training image `img_id` (passed as
+    `embed_rows`, as novel_view.render_path does), `chunk` rays at a time (default val.chunk_size)."""
+    from .rendering import render_rays
+    hp = system.hparams
+    dev = next(system.parameters()).device
+    if dev.type != "cuda" or not mesh.vertices.is_cuda:
+        raise RuntimeError("colour_vertices runs on the GPU only (no CPU fallback)")
+    typ = "fine" if system.fine else "coarse"
+    rays = vertex_rays(mesh, slab)
+    V = rays.shape[0]
+    out = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    chunk = int(chunk or hp["val.chunk_size"])
+    if chunk < 1:
+        raise ValueError(f"chunk must be positive, got {chunk}")
+    keys = [k for k in system.embeddings if k.endswith("_a")]
+    rows = {}
+    for k in keys:
+        w = system.embeddings[k].weight.detach()
+        if not 0 <= int(img_id) < w.shape[0]:
+            raise ValueError(f"img_id must be a training image index in [0, {w.shape[0]})")
+        rows[k] = w[int(img_id)].expand(min(chunk, max(V, 1)), -1).contiguous()
+    for r0 in range(0, V, chunk):
+        R = min(chunk, V - r0)
+        res = render_rays(models=system.models, embeddings=system.embeddings, rays=rays[r0:r0 + R], img_idx=None, sched_mult=1,
+                          sched_phase=2, N_samples=hp["nerf.N_samples"], use_disp=hp["nerf.use_disp"], perturb=0,
+                          N_importance=hp["nerf.N_importance"], white_back=getattr(system.train_dataset, "white_back", False),
+                          encode_feat=hp["nerf.feat_dim"] > 0, validation=True, embed_rows={k: v[:R] for k, v in rows.items()})
+        out[r0:r0 + R].copy_(res[f"s_rgb_{typ}"])
+    return out
