@@ -982,6 +982,91 @@ long long upnerf_mtet_scratch(int Nx, int Ny, int Nz);
 int upnerf_mtet_count(const upnerf_mtet_args* a, void* scratch, int32_t* totals /*[2] device*/, void* stream);
 int upnerf_mtet_emit(const upnerf_mtet_args* a, const void* scratch, void* stream);
 
+/* ---- empty-space skipping: a bit-packed occupancy grid and the rays of a frame walked through it (csrc/occupancy.hip;
+ * DESIGN.md 2.25).  Added under ABI 11: new symbols only.  Every entry point: arguments refused on the host before anything is
+ * launched, nothing allocated, no host read-back, no atomics (the same bits every run), all launches on `stream`.
+ *
+ * Geometry: that of the density grid.  A grid of Nx x Ny x Nz points spans `lo`..`hi` inclusively; its CELLS are the
+ * Cx x Cy x Cz = (Nx-1) x (Ny-1) x (Nz-1) boxes between the points (the cells marching tetrahedra walks), half-open [i, i+1)
+ * per axis.  Plane i of an axis = lo + i * ((hi - lo) / C), in fp64 from the fp32 bounds.
+ *
+ * The packed grid is upnerf_occ_words(Cx, Cy, Cz) uint32 words (UPNERF_EINVAL for an axis without a cell or more than 2^31 - 1
+ * cells):  first ceil(Cx Cy Cz / 32) words of FINE bits -- cell (x, y, z) is bit (z * Cy + y) * Cx + x, bit b of word b / 32
+ * at position b % 32 -- then ceil(Bx By Bz / 32) words of BRICK bits, B = ceil(C / 8): brick (bx, by, bz) is bit
+ * (bz * By + by) * Bx + bx of that part and is set iff any cell of the 8 x 8 x 8 block is.  Unused high bits are zero.
+ *
+ * upnerf_occ_build: from `grid` [Cz+1][Cy+1][Cx+1] (a cell is occupied iff any of its 8 corners is finite and >= level, the
+ *   comparison of upnerf_mtet_count: every triangle of the mesh at that level lies in an occupied cell) or from `cells`
+ *   [Cz][Cy][Cx] (non-zero = occupied); exactly one of the two is given.  Then `dilate` rounds of 26-neighbour dilation, then
+ *   the packing.  `scratch`: upnerf_occ_build_scratch(Cx, Cy, Cz) bytes. */
+typedef struct {
+  int32_t Cx, Cy, Cz, dilate;
+  float level;               /* with `grid`; a NaN is refused */
+  int32_t reserved_;
+  const float* grid;         /* [Cz+1][Cy+1][Cx+1] or NULL */
+  const uint8_t* cells;      /* [Cz][Cy][Cx] or NULL */
+  uint32_t* words;           /* [upnerf_occ_words] */
+  void* scratch;
+} upnerf_occ_build_args;
+long long upnerf_occ_words(int Cx, int Cy, int Cz);
+long long upnerf_occ_build_scratch(int Cx, int Cy, int Cz);
+int upnerf_occ_build(const upnerf_occ_build_args* a, void* stream);
+
+/* upnerf_occ_spans: one thread per ray row o | d | near | far (d need not be unit length: t is in units of d).  The ray is clipped
+ * to the box by the slab test and to [near, far], then walked cell by cell (Amanatides-Woo) -- brick by brick where the brick
+ * bit is clear.  Every t is (plane - o) / d evaluated in fp64 from the plane's index (no running sum) and rounded to fp32 once.
+ *   t0[r] = entry into the first occupied cell (>= near), t1[r] = exit from the last one (<= far), hit[r] = 1 iff t1 > t0 in
+ *   fp32; a miss has hit = 0, t0 = t1 = far.
+ * An axis with d == 0 never produces a t: the ray is a miss when o lies outside [lo, hi) of that axis, and keeps its cell
+ * otherwise.  A ray with a NaN in it is a miss. */
+typedef struct {
+  int32_t Cx, Cy, Cz, R;
+  float lo[3], hi[3];        /* hi > lo, finite */
+  const uint32_t* words;
+  const float* rays;         /* [R][8] */
+  float* t0;                 /* [R] */
+  float* t1;                 /* [R] */
+  uint8_t* hit;              /* [R] */
+} upnerf_occ_spans_args;
+int upnerf_occ_spans(const upnerf_occ_spans_args* a, void* stream);
+
+/* upnerf_occ_compact: the rows with hit != 0, in ascending order (block scan, scan of the block sums, emit):
+ *   index[k] = source row of the k-th hit, rays_c[k] = rays[index[k]] with near, far replaced by t0, t1,
+ *   tables[i].out[k] = tables[i].table[index[k]] (here `table` holds one row per RAY, [R][dim]; n_rows is ignored),
+ *   count[0] = number of hits (device memory).  Rows k >= count[0] of the outputs are not written.
+ * `scratch`: upnerf_occ_compact_scratch(R) bytes, 16-byte aligned. */
+typedef struct {
+  int32_t R, n_tables;
+  const uint8_t* hit;        /* [R], every byte 0 or 1 (what upnerf_occ_spans writes) */
+  const float* t0;           /* [R] */
+  const float* t1;           /* [R] */
+  const float* rays;         /* [R][8] */
+  float* rays_c;             /* [R][8] */
+  int32_t* index;            /* [R] */
+  int32_t* count;            /* [1] */
+  void* scratch;
+  upnerf_path_table tables[UPNERF_PATH_MAX_TABLES];
+} upnerf_occ_compact_args;
+long long upnerf_occ_compact_scratch(int R);
+int upnerf_occ_compact(const upnerf_occ_compact_args* a, void* stream);
+
+/* upnerf_occ_scatter: the results of the n_hit compacted rows back to the R full-length rows.  Row r finds itself in the
+ * ascending `index` (binary search): rgb[r] = rgb_c[k], depth[r] = depth_c[k] when index[k] == r; any other row is a miss:
+ * rgb[r] = (background, background, background), depth[r] = rays[r][7], the far of that ray.  n_hit is a host value (the
+ * caller read count[0] to size the render); n_hit == 0 makes every row a miss. */
+typedef struct {
+  int32_t R, n_hit;
+  float background;
+  int32_t reserved_;
+  const int32_t* index;      /* [n_hit] ascending; NULL allowed when n_hit == 0, like rgb_c */
+  const float* rays;         /* [R][8]; NULL allowed when depth is NULL */
+  const float* rgb_c;        /* [n_hit][3] */
+  const float* depth_c;      /* [n_hit]; NULL allowed when depth is NULL or n_hit == 0 */
+  float* rgb;                /* [R][3] */
+  float* depth;              /* [R] or NULL */
+} upnerf_occ_scatter_args;
+int upnerf_occ_scatter(const upnerf_occ_scatter_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

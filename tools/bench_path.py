@@ -2,12 +2,18 @@
 front end (`upnerf_path_rays`) takes beside the field kernels.
 
     python tools/bench_path.py [--frames 8] [--width 200] [--height 200] [--keys 4] [--chunk 16384] [--progress 0.8]
-                               [--images 763] [--reps 3]
+                               [--images 763] [--reps 3] [--occupancy NX NY NZ --level L [--dilate K] [--out FILE]]
 
 The system is bench.py's (two 8 x 256 fields, 64 + 128 samples, 763 images, seeded weights).  One warm-up render, then `--reps`
 timed renders of the whole sequence (wall clock around a device synchronisation); a further render with the KernelTimer on gives
 HIP-event times per kernel class, from which `path_rays_share` = time in upnerf_path_rays / sum of the timed kernel classes.
-A `validation_step` over the same number of rays (same chunk) is timed in the same run for comparison.  One JSON line."""
+A `validation_step` over the same number of rays (same chunk) is timed in the same run for comparison.  One JSON line.
+
+With --occupancy the run measures empty-space skipping instead (upnerf_amd/occupancy.py) and writes
+profiles/path_occupancy.json (--out): the same system and path rendered without a grid, with the grid of the field's density at
+--level, and with an ALL-FULL grid (every ray hits: the pure overhead of the three kernels), in alternating runs of one process
+(`--reps` rounds of none / grid / full, the median of each).  Every rate stands next to its hit share: a random-weight field has
+an arbitrary one, so no ratio means anything without it.  The box is [-2.5, 2.5]^2 x [-5.5, 0.5], in front of the cameras."""
 import argparse
 import json
 import os
@@ -32,6 +38,55 @@ def wall(fn, reps):
     return statistics.median(ts)
 
 
+def occupancy_run(a, sysm, path, rays):
+    from upnerf_amd import novel_view
+    from upnerf_amd.geometry import density_grid
+    from upnerf_amd.novel_view import render_path
+    from upnerf_amd.occupancy import OccupancyGrid
+    from upnerf_amd.ops import TIMER
+    bounds = ((-2.5, -2.5, -5.5), (2.5, 2.5, 0.5))
+    res = tuple(a.occupancy)
+    grid = density_grid(sysm, bounds, res)
+    OccupancyGrid.from_density(grid, bounds, a.level, dilate=a.dilate)  # warm-up of the build
+    build_s = wall(lambda: OccupancyGrid.from_density(grid, bounds, a.level, dilate=a.dilate), a.reps)
+    grid_s = wall(lambda: density_grid(sysm, bounds, res), 1)
+    occs = {"none": None, "grid": OccupancyGrid.from_density(grid, bounds, a.level, dilate=a.dilate),
+            "full": OccupancyGrid.from_cells(torch.ones(res[2] - 1, res[1] - 1, res[0] - 1, dtype=torch.bool, device=grid.device), bounds)}
+    times = {k: [] for k in occs}
+    share = {}
+    for k, o in occs.items():  # warm-up of every variant
+        render_path(sysm, path, outputs=("rgb",), occupancy=o)
+        share[k] = novel_view.LAST_STATS["hits"] / rays if o is not None else 1.0
+    for _ in range(a.reps):  # alternating: a drift of the clocks touches every variant alike
+        for k, o in occs.items():
+            times[k].append(wall(lambda: render_path(sysm, path, outputs=("rgb",), occupancy=o), 1))
+    kern = {}
+    for k in ("grid", "full"):
+        TIMER.reset()
+        TIMER.enabled, TIMER.only = True, {"occ_spans", "occ_compact", "occ_scatter"}
+        render_path(sysm, path, outputs=("rgb",), occupancy=occs[k])
+        kern[k] = {n: {"ms_per_launch": v["avg_ms"], "launches": v["launches"], "rays_per_launch": v["units_per_launch"]}
+                   for n, v in sorted(TIMER.summary().items())}
+        TIMER.enabled, TIMER.only = False, None
+        TIMER.reset()
+    F = path.n_frames
+    runs = {}
+    for k, ts in times.items():
+        dt = statistics.median(ts)
+        runs[k] = {"frames_per_s": F / dt, "rays_per_s": rays / dt, "hit_share": share[k], "seconds": sorted(ts)}
+    out = {"metric": "camera-path frames with and without an occupancy grid (render_path, rgb output, no grad; random weights)",
+           "frames": F, "img_wh": list(path.img_wh), "chunk": a.chunk, "progress": a.progress, "reps": a.reps,
+           "resolution": list(res), "level": a.level, "dilate": a.dilate, "bounds": [list(b) for b in bounds],
+           "occupied_share": occs["grid"].fraction, "sigma_min": float(grid.min()), "sigma_max": float(grid.max()),
+           "runs": runs, "overhead_full_vs_none": runs["none"]["rays_per_s"] / runs["full"]["rays_per_s"] - 1.0,
+           "kernels": kern, "build_ms": build_s * 1e3, "density_grid_s": grid_s}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=8)
@@ -42,7 +97,13 @@ def main():
     ap.add_argument("--progress", type=float, default=0.8)
     ap.add_argument("--images", type=int, default=763)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--occupancy", type=int, nargs=3, metavar=("NX", "NY", "NZ"), help="grid points of the occupancy grid")
+    ap.add_argument("--level", type=float, default=None, help="density above which a cell is kept (required with --occupancy)")
+    ap.add_argument("--dilate", type=int, default=1)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "path_occupancy.json"))
     a = ap.parse_args()
+    if a.occupancy is not None and a.level is None:
+        raise SystemExit("--occupancy needs --level")
     if not torch.cuda.is_available():
         raise SystemExit("bench_path.py measures on the GPU; none is visible")
     import bench
@@ -62,6 +123,8 @@ def main():
     K = torch.tensor([[0.8 * W, 0, W / 2], [0, 0.8 * W, H / 2], [0, 0, 1.0]])
     path = CameraPath.from_poses(c2w, (0.1, 5.0), F, appearance=(3, 17), img_wh=(W, H), K=K)
     rays = F * H * W
+    if a.occupancy is not None:
+        return occupancy_run(a, sysm, path, rays)
     render_path(sysm, path, outputs=("rgb",))  # warm-up (allocator growth, cached tables)
     dt = wall(lambda: render_path(sysm, path, outputs=("rgb",)), a.reps)
     TIMER.reset()

@@ -3,6 +3,13 @@ appearance moving from photograph to photograph (upnerf_amd/novel_view.py; DESIG
 
     python tools/render_path.py --config scene.yaml --ckpt last.ckpt --images 3 17 42 --frames 120 --out DIR
                                 [--mode linear|catmull] [--downscale N] [--depth] [--loop] [--chunk ROWS]
+                                [--occupancy NX NY NZ --level SIGMA [--dilate K] [--bounds X0 Y0 Z0 X1 Y1 Z1 | --margin M]]
+
+--occupancy skips empty space: the fine field's density is sampled on NX x NY x NZ grid points over the box (--bounds, or the
+box round the refined cameras and their far points grown by --margin), cells with a corner >= --level (grown by --dilate
+rounds) are kept, and only the rays that touch such a cell are rendered, over the part of the ray that does.  A skipped pixel
+shows the background, NOT what the full render would have composited from density below --level: --level (no default, as in
+tools/extract_mesh.py) and --dilate trade speed for that.
 
 Writes PNG files only -- DIR/path/step_<frame, 8 digits>/rgb.png (and depth.png with --depth).  No video encoder is installed
 with this package: turn the frames into a film with a tool of your own (e.g. ffmpeg -i DIR/path/step_%08d/rgb.png)."""
@@ -18,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True, help="the scene's YAML configuration (as given to training)")
     ap.add_argument("--ckpt", required=True, help="checkpoint of the trained system")
@@ -30,7 +37,24 @@ def main(argv=None):
     ap.add_argument("--depth", action="store_true", help="also write the colour-mapped depth of every frame (one range: frame 0's)")
     ap.add_argument("--loop", action="store_true", help="close the path on the first image")
     ap.add_argument("--chunk", type=int, default=None, help="rows per render chunk (default: val.chunk_size)")
-    a = ap.parse_args(argv)
+    ap.add_argument("--occupancy", type=int, nargs=3, metavar=("NX", "NY", "NZ"), help="skip empty space with an occupancy grid of this many grid points")
+    ap.add_argument("--level", type=float, default=None, help="density above which a cell is kept (required with --occupancy; no default)")
+    ap.add_argument("--dilate", type=int, default=1, help="rounds of 26-neighbour dilation of the kept cells")
+    ap.add_argument("--bounds", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="box of the occupancy grid")
+    ap.add_argument("--margin", type=float, default=0.5, help="without --bounds: the box round the cameras and their far points, grown by this")
+    return ap
+
+
+def check_args(a):
+    if a.occupancy is not None and a.level is None:
+        raise SystemExit("--occupancy needs --level: the useful density threshold depends on the scene's scale")
+    if a.occupancy is None and (a.level is not None or a.bounds is not None):
+        raise SystemExit("--level and --bounds belong to --occupancy")
+    return a
+
+
+def main(argv=None):
+    a = check_args(parser().parse_args(argv))
     if not torch.cuda.is_available():
         raise SystemExit("render_path.py renders on the GPU; none is visible")
     from upnerf_amd import checkpoint, config
@@ -50,12 +74,23 @@ def main(argv=None):
         path = CameraPath(path.key_c2w, path.key_near_far, path.u, path.i0, path.i1, path.t,
                           (max(1, path.img_wh[0] // n), max(1, path.img_wh[1] // n)), K, path.mode)
     writer = ImageWriter(a.out)
+    occ, extra = None, {}
+    if a.occupancy is not None:
+        from upnerf_amd import geometry, novel_view
+        from upnerf_amd.occupancy import OccupancyGrid
+        bounds = (tuple(a.bounds[:3]), tuple(a.bounds[3:])) if a.bounds else geometry.bounds_from_cameras(system, a.margin)
+        tb = time.perf_counter()
+        occ = OccupancyGrid.build(system, bounds, a.occupancy, a.level, dilate=a.dilate)
+        extra = {"occupied_share": occ.fraction, "bounds": [list(bounds[0]), list(bounds[1])], "level": a.level, "dilate": a.dilate,
+                 "occupancy_seconds": time.perf_counter() - tb}
     t0 = time.perf_counter()
-    render_path(system, path, chunk=a.chunk, outputs=("rgb", "depth") if a.depth else ("rgb",), sink=writer)
+    render_path(system, path, chunk=a.chunk, outputs=("rgb", "depth") if a.depth else ("rgb",), sink=writer, occupancy=occ)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if occ is not None:
+        extra["hit_share"] = novel_view.LAST_STATS["hits"] / max(novel_view.LAST_STATS["rays"], 1)
     print(json.dumps({"frames": path.n_frames, "img_wh": list(path.img_wh), "files": len(writer.written), "out": a.out,
-                      "seconds": dt, "frames_per_s": path.n_frames / dt}))
+                      "seconds": dt, "frames_per_s": path.n_frames / dt, **extra}))
 
 
 if __name__ == "__main__":

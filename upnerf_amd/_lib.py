@@ -266,6 +266,26 @@ class MtetArgs(C.Structure):
                 ("cap_vertices", C.c_int32), ("cap_faces", C.c_int32), ("vertices", _fp), ("normals", _fp), ("faces", _fp)]
 
 
+class OccBuildArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("dilate", C.c_int32), ("level", C.c_float),
+                ("reserved_", C.c_int32), ("grid", _fp), ("cells", _fp), ("words", _fp), ("scratch", _fp)]
+
+
+class OccSpansArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("R", C.c_int32), ("lo", C.c_float * 3),
+                ("hi", C.c_float * 3), ("words", _fp), ("rays", _fp), ("t0", _fp), ("t1", _fp), ("hit", _fp)]
+
+
+class OccCompactArgs(C.Structure):
+    _fields_ = [("R", C.c_int32), ("n_tables", C.c_int32), ("hit", _fp), ("t0", _fp), ("t1", _fp), ("rays", _fp), ("rays_c", _fp),
+                ("index", _fp), ("count", _fp), ("scratch", _fp), ("tables", PathTable * PATH_MAX_TABLES)]
+
+
+class OccScatterArgs(C.Structure):
+    _fields_ = [("R", C.c_int32), ("n_hit", C.c_int32), ("background", C.c_float), ("reserved_", C.c_int32), ("index", _fp),
+                ("rays", _fp), ("rgb_c", _fp), ("depth_c", _fp), ("rgb", _fp), ("depth", _fp)]
+
+
 class Rng(C.Structure):
     """upnerf_rng: key of the uniform draws a kernel generates itself."""
     _fields_ = [("seed", C.c_uint64), ("step", C.c_int32), ("row0", C.c_int32), ("row_stride", C.c_int32), ("step_dev", _fp)]
@@ -340,7 +360,16 @@ _SIGNATURES = {
     "upnerf_mtet_scratch": [_i, _i, _i],
     "upnerf_mtet_count": [C.POINTER(MtetArgs), _p, _p, _p],
     "upnerf_mtet_emit": [C.POINTER(MtetArgs), _p, _p],
+    "upnerf_occ_words": [_i, _i, _i],
+    "upnerf_occ_build_scratch": [_i, _i, _i],
+    "upnerf_occ_build": [C.POINTER(OccBuildArgs), _p],
+    "upnerf_occ_spans": [C.POINTER(OccSpansArgs), _p],
+    "upnerf_occ_compact_scratch": [_i],
+    "upnerf_occ_compact": [C.POINTER(OccCompactArgs), _p],
+    "upnerf_occ_scatter": [C.POINTER(OccScatterArgs), _p],
 }
+_LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
+             "upnerf_occ_compact_scratch")
 MAX_SCALARS = 96
 EXPORTS = tuple(_SIGNATURES)
 
@@ -356,7 +385,7 @@ def _load():
         if fn is None:
             raise ImportError(f"{LIB_PATH} does not export {name}; rebuild it")
         fn.argtypes = argtypes
-        fn.restype = C.c_longlong if name in ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch") else C.c_int
+        fn.restype = C.c_longlong if name in _LONGLONG else C.c_int
     return lib
 
 

@@ -26,6 +26,7 @@ __all__ = ["CameraPath", "plan_path", "path_poses", "path_rays", "render_path", 
 
 MODES = {"linear": _lib.PATH_LINEAR, "catmull": _lib.PATH_CATMULL}
 LAST_WORKSPACE: Dict[str, tuple] = {}  # shapes of the per-chunk buffers the last render_path allocated (tests)
+LAST_STATS: Dict[str, int] = {}  # rays and hits of the last render_path with an occupancy grid (empty without one)
 
 
 def plan_path(n_frames: int, img_ids: Optional[Sequence[int]] = None, loop: bool = False, n_keys: Optional[int] = None,
@@ -238,7 +239,8 @@ def _table_keys(system, sched_mult) -> list:
 
 @torch.no_grad()
 def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: Sequence[str] = ("rgb",),
-                depth_range: Optional[Tuple[float, float]] = None, sink: Optional[Callable] = None) -> Dict[str, torch.Tensor]:
+                depth_range: Optional[Tuple[float, float]] = None, sink: Optional[Callable] = None,
+                occupancy=None) -> Dict[str, torch.Tensor]:
     """Render every frame of `path` with the static fields of `system` (perturb = 0, no gradient, validation's sample counts).
 
     outputs: any of "rgb" (uint8 [F, H, W, 3] of `s_rgb_fine`, `s_rgb_coarse` without a fine field), "depth" (uint8
@@ -246,7 +248,13 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
     frame 0, kept on the device), "rgb_float" (fp32 [F, H * W, 3]).
     sink: called as sink("path", frame, {"rgb": ..., "depth": ...}) once per finished frame, in order (an `ImageWriter`).
     The pixel list [F][H][W] is walked in chunks of `chunk` rows (default val.chunk_size) that may straddle frames; device
-    memory is the chunk's workspace, one frame of staging and the requested outputs."""
+    memory is the chunk's workspace, one frame of staging and the requested outputs.
+    occupancy: an `occupancy.OccupancyGrid`.  Every chunk's rays are walked through it (upnerf_occ_spans), the rays that touch an
+    occupied cell are compacted with their embedding rows (upnerf_occ_compact) and rendered over [t0, t1] instead of
+    [near, far], and the results scattered back (upnerf_occ_scatter); a ray that touches nothing shows the BACKGROUND (1 with
+    white_back, else 0) at depth `far` -- not what the full render would have composited from density below the grid's level.
+    One host read per chunk (the hit count); a chunk without hits launches no field kernel.  LAST_STATS holds the sequence's
+    number of rays and hits.  None: nothing of this runs."""
     from .rendering import render_rays
     from .visualization import depth_image, min_max_of, rgb_image
     unknown = set(outputs) - {"rgb", "depth", "rgb_float"}
@@ -278,9 +286,26 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
     ws = {"rays": torch.empty(chunk, 8, device=dev, dtype=torch.float32)}
     for k, w in zip(keys, weights):
         ws[k] = torch.empty(chunk, w.shape[1], device=dev, dtype=torch.float32)
+    want_depth = "depth" in outputs
+    LAST_STATS.clear()
+    occ_ws = None
+    if occupancy is not None:
+        from . import occupancy as oc
+        if not isinstance(occupancy, oc.OccupancyGrid) or occupancy.words.device != dev:
+            raise ValueError("occupancy is an OccupancyGrid on the system's device")
+        occ_ws = oc.compact_workspace(chunk, [w.shape[1] for w in weights], dev)
+        occ_ws["rgb"] = torch.empty(chunk, 3, device=dev, dtype=torch.float32)
+        if want_depth:
+            occ_ws["depth"] = torch.empty(chunk, device=dev, dtype=torch.float32)
+        for k, v in occ_ws.items():
+            if k == "rows_c":
+                ws.update({f"occ_{kk}": r for kk, r in zip(keys, v)})
+            else:
+                ws[f"occ_{k}"] = v
+        LAST_STATS.update(rays=total, hits=0)
+    white_back = getattr(system.train_dataset, "white_back", False)
     LAST_WORKSPACE.clear()
     LAST_WORKSPACE.update({k: tuple(v.shape) for k, v in ws.items()})
-    want_depth = "depth" in outputs
     stage_rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
     stage_depth = torch.empty(n, device=dev, dtype=torch.float32) if want_depth else None
     out: Dict[str, torch.Tensor] = {}
@@ -312,12 +337,21 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
         R = min(chunk, total - g0)
         rays, rows = path_rays(c2w, nf, (W, H), intr, g0, R, tables=[(w, ws[k]) for k, w in zip(keys, weights)], i0=i0, i1=i1,
                                t=t, rays=ws["rays"])
-        res = render_rays(models=system.models, embeddings=system.embeddings, rays=rays, img_idx=None, sched_mult=sched_mult,
-                          sched_phase=2 if sched_mult == 1 else 1, N_samples=hp["nerf.N_samples"], use_disp=hp["nerf.use_disp"],
-                          perturb=0, N_importance=hp["nerf.N_importance"],
-                          white_back=getattr(system.train_dataset, "white_back", False), encode_feat=hp["nerf.feat_dim"] > 0,
-                          validation=True, embed_rows=dict(zip(keys, rows)))
-        rgb, depth = res[f"s_rgb_{typ}"], res[f"s_depth_{typ}"]
+        full = rays
+        if occ_ws is not None:  # only the rays that touch something, over the part of the ray that does
+            rays, rows, index, n_hit = oc.compact_rays(occupancy, full, rows, ws=occ_ws)
+            LAST_STATS["hits"] += n_hit
+        if occ_ws is None or n_hit > 0:
+            res = render_rays(models=system.models, embeddings=system.embeddings, rays=rays, img_idx=None, sched_mult=sched_mult,
+                              sched_phase=2 if sched_mult == 1 else 1, N_samples=hp["nerf.N_samples"],
+                              use_disp=hp["nerf.use_disp"], perturb=0, N_importance=hp["nerf.N_importance"], white_back=white_back,
+                              encode_feat=hp["nerf.feat_dim"] > 0, validation=True, embed_rows=dict(zip(keys, rows)))
+            rgb, depth = res[f"s_rgb_{typ}"], res[f"s_depth_{typ}"]
+        else:
+            rgb = depth = None
+        if occ_ws is not None:
+            rgb, depth = oc.scatter_results(index, full, rgb, depth if want_depth else None, background=1.0 if white_back else 0.0,
+                                            want_depth=want_depth, out_rgb=occ_ws["rgb"], out_depth=occ_ws.get("depth"))
         g = g0
         while g < g0 + R:  # the chunk's rows, frame by frame
             f, p0 = divmod(g, n)
