@@ -729,6 +729,65 @@ typedef struct {
 int upnerf_ssim_scratch(const upnerf_ssim_args* a);
 int upnerf_ssim(const upnerf_ssim_args* a, double* scratch, void* stream);
 
+/* ---- LPIPS (AlexNet) of rendered images against their targets (models/nerf_system_optmize.py:184: lpips_alex(gt, img),
+ * normalize=False) from weights the caller supplies.  Written from the published lpips 0.1.x definition:
+ *   x = (image - shift) / scale per channel, shift = (-.030, -.088, -.188), scale = (.458, .448, .450)
+ *   five taps, each after its ReLU: conv 3->64 k11 s4 p2 | maxpool k3 s2, conv 64->192 k5 p2 | maxpool k3 s2,
+ *   conv 192->384 k3 p1 | conv 384->256 k3 p1 | conv 256->256 k3 p1          (sizes floor((H + 2p - k) / s) + 1)
+ *   d_l = mean over pixels of sum_c w_l[c] * (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2,   LPIPS = sum_l d_l
+ * The library allocates nothing: upnerf_lpips_scratch reports the buffers, the caller (upnerf_amd/lpips.py) runs the twelve
+ * calls on its stream, so the sequence can sit inside a captured graph.  The render and its target go through the network
+ * as ONE batch of 2N images (renders first); no kernel's result for an image depends on the batch around it.
+ *
+ * upnerf_conv2d: y = [relu](conv(x, w) + bias) as an implicit GEMM on the fp32-input MFMA (exact fp32 products; the
+ * patch gather with stride and padding happens on the load into LDS).  Pixel (n, c, y, x) of the input is read at element
+ * offset n*s[0] + c*s[1] + y*s[2] + x*s[3], so NCHW images and the ray layout [N][H*W][3] are both read in place; w is
+ * [C_out][C_in][k][k], y is dense [N][C_out][H_out][W_out].  scale_in != 0 (C_in == 3 only) applies the scaling layer as a
+ * pixel is loaded; the zero padding is then padding of the SCALED image (a padded position contributes 0).
+ * Shapes: C_out % 64 == 0 and (C_in, k, stride, pad) one of (3, 11, 4, 2), (64, 5, 1, 2), (192 | 384 | 256, 3, 1, 1);
+ * anything else is UPNERF_EUNSUP. */
+typedef struct {
+  int32_t N, C_in, H, W;
+  int32_t C_out, k, stride, pad;
+  int32_t relu, scale_in;
+  const float* x;
+  int64_t x_stride[4];                   /* (n, c, y, x), in elements */
+  const float* w; const float* bias;
+  float* y;
+} upnerf_conv2d_args;
+int upnerf_conv2d(const upnerf_conv2d_args* a, void* stream);
+
+/* upnerf_maxpool2d: 3 x 3 window, stride 2, no padding, floor mode, dense NCHW in and out; a NaN in the window gives NaN.
+ * H, W >= 3. */
+typedef struct {
+  int32_t N, C, H, W;
+  const float* x;                        /* [N][C][H][W] */
+  float* y;                              /* [N][C][(H - 3) / 2 + 1][(W - 3) / 2 + 1] */
+} upnerf_maxpool2d_args;
+int upnerf_maxpool2d(const upnerf_maxpool2d_args* a, void* stream);
+
+/* upnerf_lpips_dist: d_l of one tap for N image pairs; feat holds the 2N feature maps, the N renders followed by their N
+ * targets.  out[n] = d (accumulate == 0) or out[n] + d (accumulate != 0): the caller adds the taps in order, tap 0 first.
+ * Norms and differences in fp64; per-tile fp64 partials into `scratch` (N * ceil(H * W / 256) doubles; the part_elems of
+ * upnerf_lpips_scratch covers every tap), then a fixed-order finish per pair -- no atomics.  w is not clamped. */
+typedef struct {
+  int32_t N, C, H, W;
+  int32_t accumulate, reserved_;
+  const float* feat;                     /* [2N][C][H][W] */
+  const float* w;                        /* [C] */
+  float* out;                            /* [N] */
+} upnerf_lpips_dist_args;
+int upnerf_lpips_dist(const upnerf_lpips_dist_args* a, double* scratch, void* stream);
+
+/* upnerf_lpips_scratch: for N pairs of H x W images (H, W >= 31: below that the last taps have no pixel, UPNERF_EINVAL),
+ * the element counts of the two fp32 activation buffers the layers alternate between (buffer 0: taps 0, 1, 2, 4; buffer 1:
+ * the pooled maps and tap 3; both for 2N images) and of the fp64 partials. */
+typedef struct {
+  int32_t N, H, W, reserved_;
+  int64_t act0_elems, act1_elems, part_elems;   /* out */
+} upnerf_lpips_scratch_args;
+int upnerf_lpips_scratch(upnerf_lpips_scratch_args* a);
+
 /* ---- scene loading: the per-pixel buffers of datasets/phototourism.py:242-323 (and custom.py, the optimize splits) ----
  * upnerf_scene_rays writes, for every image descriptor, the rows of its column window [x0, x1) in row-major order
  * (row = row0 + (j * (x1 - x0) + i - x0) for pixel (i, j) of the full W x H image):

@@ -184,6 +184,26 @@ class SsimArgs(C.Structure):
                 ("pred_stride", C.c_int64 * 4), ("gt_stride", C.c_int64 * 4), ("ssim", _fp), ("map", _fp)]
 
 
+class Conv2dArgs(C.Structure):
+    _fields_ = [("N", C.c_int32), ("C_in", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C_out", C.c_int32),
+                ("k", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32), ("relu", C.c_int32), ("scale_in", C.c_int32),
+                ("x", _fp), ("x_stride", C.c_int64 * 4), ("w", _fp), ("bias", _fp), ("y", _fp)]
+
+
+class Maxpool2dArgs(C.Structure):
+    _fields_ = [("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("x", _fp), ("y", _fp)]
+
+
+class LpipsDistArgs(C.Structure):
+    _fields_ = [("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("accumulate", C.c_int32),
+                ("reserved_", C.c_int32), ("feat", _fp), ("w", _fp), ("out", _fp)]
+
+
+class LpipsScratchArgs(C.Structure):
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("reserved_", C.c_int32),
+                ("act0_elems", C.c_int64), ("act1_elems", C.c_int64), ("part_elems", C.c_int64)]
+
+
 class SceneImage(C.Structure):
     _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("x0", C.c_int32), ("x1", C.c_int32),
                 ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
@@ -344,6 +364,10 @@ _SIGNATURES = {
     "upnerf_scale_exponents": [_p, _i, _p, _p],
     "upnerf_ssim_scratch": [C.POINTER(SsimArgs)],
     "upnerf_ssim": [C.POINTER(SsimArgs), _p, _p],
+    "upnerf_conv2d": [C.POINTER(Conv2dArgs), _p],
+    "upnerf_maxpool2d": [C.POINTER(Maxpool2dArgs), _p],
+    "upnerf_lpips_dist": [C.POINTER(LpipsDistArgs), _p, _p],
+    "upnerf_lpips_scratch": [C.POINTER(LpipsScratchArgs)],
     "upnerf_scene_rays": [C.POINTER(SceneRaysArgs), C.POINTER(SceneImage), _p, _p],
     "upnerf_resize_scratch": [C.POINTER(ResizeArgs)],
     "upnerf_resize_linear": [C.POINTER(ResizeArgs), C.POINTER(ResizeMap), _p, _p],

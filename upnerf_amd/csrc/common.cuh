@@ -37,6 +37,23 @@ __device__ __forceinline__ int swz4(int row, int k, int ldw) { return row * ldw 
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// fixed-order fp64 sums (the image metrics: metrics.hip, lpips.hip)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+// sum of v over the workgroup in a fixed order; the result is valid in thread 0
+__device__ __forceinline__ double block_sum_f64(double v) {
+  __shared__ double red[NTHREADS / 64];
+  const int tid = threadIdx.x;
+  v = wave_sum_f64(v);
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // How the four waves of a workgroup share a [TILE x N] output tile (32x32 MFMA tiles).  When there are fewer
 // than four wave-sized pieces (narrow layers of the 64-wide model) the surplus waves recompute a piece another
 // wave owns and store identical values -- harmless, and it keeps every wave on the same barrier sequence.

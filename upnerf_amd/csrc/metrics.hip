@@ -16,22 +16,6 @@ struct SsimWeights {
 
 __device__ __forceinline__ int reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
-// sum of v over the workgroup in a fixed order; the result is valid in thread 0
-__device__ __forceinline__ double block_sum_f64(double v) {
-  __shared__ double red[NTHREADS / 64];
-  const int tid = threadIdx.x;
-  v = wave_sum_f64(v);
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // one tile of one image: the map (optional) and the tile's sum over (c, y, x) of clamp((1 - s) / 2, 0, 1) in fp64
 __global__ __launch_bounds__(NTHREADS) void ssim_tile_kernel(upnerf_ssim_args a, SsimWeights wt, int tiles_x,
                                                             int tiles, double* __restrict__ part) {

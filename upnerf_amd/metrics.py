@@ -1,9 +1,11 @@
-"""Image metrics of the novel-view-synthesis table (utils/metric.py of the reference): PSNR and SSIM of held-out renders.
+"""Image metrics of the novel-view-synthesis table (utils/metric.py of the reference): PSNR, SSIM and LPIPS of held-out
+renders.
 
 `ssim` / `ssim_rays` run the HIP kernel `upnerf_ssim` (csrc/metrics.hip): kornia's `ssim_loss` with a 3x3 window, as the
 reference calls it, followed by the reference's `1 - 2 * dssim`, computed where the render already is -- no copy to the
-host.  There is no CPU path: CPU tensors raise.  `psnr` is the reference's formula in torch ops.  LPIPS needs pretrained
-AlexNet weights and is not provided."""
+host.  There is no CPU path: CPU tensors raise.  `psnr` is the reference's formula in torch ops.  LPIPS (AlexNet) is
+`LpipsAlex` / `lpips_rays` of lpips.py, re-exported here: HIP as well, on weights the user supplies (no pretrained file is
+part of this repository)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -92,3 +94,6 @@ def psnr(image_pred: torch.Tensor, image_gt: torch.Tensor, valid_mask=None, redu
     if reduction == "mean":
         value = torch.mean(value)
     return -10 * torch.log10(value)
+
+
+from .lpips import LpipsAlex, lpips_rays  # noqa: E402,F401  (lpips.py takes parse_img_wh from this module when called)

@@ -12,9 +12,11 @@ weight gradients); here they are frozen, so the backward p
 kernel.
 
 Metrics: validation reports PSNR and, when the batch carries `img_wh`, SSIM (metrics.py: a HIP kernel on the device-resident
-render, where the reference copies every render to the host for kornia).  LPIPS needs pretrained AlexNet weights and is not
-computed.  `best` records the epoch of the highest PSNR as the reference does; `write_nvs_results` / `read_nvs_results` are
-its psnr.pkl / ssim.pkl bookkeeping and what eval.py prints from it.  Unlike Lightning, run_stage has no sanity validation
+render, where the reference copies every render to the host for kornia).  LPIPS (AlexNet) is reported as well once a
+`metrics.LpipsAlex` built from the user's weight files is attached as `system.lpips_model` (lpips.py; None by default, and
+then every dictionary and file is what it is without it).  `best` records the epoch of the highest PSNR as the reference
+does; `write_nvs_results` / `read_nvs_results` are its psnr.pkl / ssim.pkl / lpips.pkl bookkeeping and what eval.py prints
+from it.  Unlike Lightning, run_stage has no sanity validation
 before the first epoch (tto.py:63, 87), so `best` never holds the starting PSNR."""
 from __future__ import annotations
 
@@ -24,7 +26,7 @@ from torch import nn
 from . import zero_pool
 from .camera import refine_and_get_rays
 from .losses import _const
-from .metrics import ssim_rays
+from .metrics import lpips_rays, ssim_rays
 from .nerf_system import NeRFSystem
 from .ops import EMBED_PREFETCH, embed_rows
 from .optim import get_optimizer
@@ -33,6 +35,7 @@ from .rendering import join_rays, render_rays
 
 class NeRFSystemOptimize(NeRFSystem):
     supports_graph_step = True  # the step splits like NeRFSystem's (graph_step.py): one graph replay per TTO step
+    lpips_model = None  # a metrics.LpipsAlex: validation then reports LPIPS too (a plain attribute: not in state_dict)
 
     def __init__(self, hparams, train_dataset=None, val_dataset=None, pose_optimize=True):
         super().__init__(hparams, train_dataset, val_dataset)
@@ -139,17 +142,20 @@ class NeRFSystemOptimize(NeRFSystem):
     @torch.no_grad()
     def validation_step(self, batch, batch_nb=0):
         """Full-image render in val.chunk_size chunks, perturb = 0; returns the PSNR on s_rgb_fine, and its SSIM when the
-        batch carries the image size `img_wh` (W, H) as the reference's validation batches do (lines 174-183)."""
+        batch carries the image size `img_wh` (W, H) as the reference's validation batches do (lines 174-183); with a
+        `lpips_model` attached, its LPIPS as well (line 184)."""
         res = self(self.rays_from_batch(batch), batch["img_idx"], train=False)
         mse = ((res["s_rgb_fine"] - batch["rgbs"]) ** 2).mean()
         out = {"val_psnr": -10.0 * torch.log10(mse), "s_rgb_fine": res["s_rgb_fine"], "s_depth_fine": res["s_depth_fine"]}
         if batch.get("img_wh") is not None:
             rgbs = batch["rgbs"].reshape(res["s_rgb_fine"].shape)
             out["val_ssim"] = ssim_rays(res["s_rgb_fine"], rgbs, batch["img_wh"]).reshape(())
+            if self.lpips_model is not None:
+                out["val_lpips"] = lpips_rays(self.lpips_model, res["s_rgb_fine"], rgbs, batch["img_wh"]).reshape(())
         return out
 
     def validation_epoch_end(self, outputs):
-        """Mean PSNR (and SSIM, over the outputs that carry it) of the validation images (nerf_system_optmize.py:190-196),
+        """Mean PSNR (and SSIM / LPIPS, over the outputs that carry them) of the validation images (nerf_system_optmize.py:190-196),
         and the record of the best epoch in `self.best` (lines 195-198)."""
         if not outputs:
             return None
@@ -157,14 +163,17 @@ class NeRFSystemOptimize(NeRFSystem):
         ss = [x["val_ssim"].reshape(()) for x in outputs if "val_ssim" in x]
         if ss:
             out["val/ssim"] = torch.stack(ss).mean()
+        ls = [x["val_lpips"].reshape(()) for x in outputs if "val_lpips" in x]
+        if ls:
+            out["val/lpips"] = torch.stack(ls).mean()
         for k, v in out.items():
             self.log(k, v)
         self._update_best(out)
         return out
 
     def _update_best(self, metrics):
-        """Replace `self.best` on a strictly greater val/psnr: that epoch's PSNR and SSIM, the step, and copies of the stage's
-        trainable rows (the reference saves them as best_pose_NN.npy)."""
+        """Replace `self.best` on a strictly greater val/psnr: that epoch's PSNR and SSIM (and LPIPS, when it was computed), the
+        step, and copies of the stage's trainable rows (the reference saves them as best_pose_NN.npy)."""
         psnr = metrics["val/psnr"]
         if not float(psnr) > float(self.best["psnr"]):  # (a NaN never replaces it)
             return
@@ -173,6 +182,8 @@ class NeRFSystemOptimize(NeRFSystem):
                 "step": int(self.global_step), "embedding_fine_a": self.embedding_fine_a.weight.detach().clone()}
         if self.pose_optimize:
             best["se3_refine"] = self.se3_refine.weight.detach().clone()
+        if "val/lpips" in metrics:
+            best["lpips"] = metrics["val/lpips"].detach().clone()
         self.best = best
 
 
@@ -196,11 +207,12 @@ def run_stage(system: NeRFSystemOptimize, train_batches, n_batches_per_epoch: in
 
 def write_nvs_results(dirpath: str, optimize_num: int, best: dict) -> None:
     """nerf_system_optmize.py:208-228: merge the best PSNR and SSIM of held-out image `optimize_num` into
-    `<dirpath>/psnr.pkl` and `ssim.pkl` ({image number: 0-d CPU tensor}, the files eval.py reads).  No lpips.pkl."""
+    `<dirpath>/psnr.pkl` and `ssim.pkl` ({image number: 0-d CPU tensor}, the files eval.py reads), and its LPIPS into
+    `lpips.pkl` when `best` holds one (a system with a `lpips_model`); no lpips.pkl otherwise."""
     import os
     import pickle
     os.makedirs(dirpath, exist_ok=True)
-    for name in ("psnr", "ssim"):
+    for name in ("psnr", "ssim", "lpips"):
         if best.get(name) is None:
             continue
         path = os.path.join(dirpath, f"{name}.pkl")
@@ -214,12 +226,12 @@ def write_nvs_results(dirpath: str, optimize_num: int, best: dict) -> None:
 
 
 def read_nvs_results(dirpath: str) -> dict:
-    """eval.py:59-79: the mean PSNR and SSIM over the held-out images in `dirpath` (None where a file is absent); LPIPS is
-    not computed here, so `lpips` is None."""
+    """eval.py:48-79: the mean PSNR, SSIM and LPIPS over the held-out images in `dirpath` (None where a file is absent, as
+    lpips.pkl is for a run without a `lpips_model`; a directory the reference wrote reads too)."""
     import os
     import pickle
     out = {"psnr": None, "ssim": None, "lpips": None}
-    for name in ("psnr", "ssim"):
+    for name in ("psnr", "ssim", "lpips"):
         path = os.path.join(dirpath, f"{name}.pkl")
         if os.path.isfile(path):
             with open(path, "rb") as f:
@@ -244,11 +256,12 @@ def eval_train_poses(checkpoint, noised_poses, gt_poses, device="cuda") -> dict:
 
 
 def tto_from_checkpoint(checkpoint, pose_optimize: bool, n_test_images: int = 1, gt_train_poses=None, gt_test_poses=None,
-                        device="cuda", image_sink=None, **overrides):
+                        device="cuda", image_sink=None, lpips=None, **overrides):
     """NeRFSystemOptimize for the held-out images of a trained run (nerf_system_optmize.py:254-317): hyper-parameters and
     fields from the checkpoint, a fresh appearance row per test image and, when ground-truth poses are given, their
     initial cameras in the frame the model was trained in.  Returns (system, initial test poses or None).
-    image_sink: kept on the system (`system.image_sink`) for the stages `run_stage` runs on it."""
+    image_sink: kept on the system (`system.image_sink`) for the stages `run_stage` runs on it.  lpips: a metrics.LpipsAlex
+    (moved to `device`), kept as `system.lpips_model`: validation then reports LPIPS as well."""
     from .checkpoint import read_checkpoint
     from .pose_align import init_test_poses, refined_poses
     ck = read_checkpoint(checkpoint)
@@ -262,6 +275,8 @@ def tto_from_checkpoint(checkpoint, pose_optimize: bool, n_test_images: int = 1,
     system.model_setup(trained_state=keep, n_test_images=n_test_images)
     system.to(device)
     system.image_sink = image_sink
+    if lpips is not None:
+        system.lpips_model = lpips.to(device)
     init = None
     if gt_train_poses is not None and gt_test_poses is not None:
         ident = torch.eye(3, 4).repeat(n_train, 1, 1)  # line 286: the trained refinements over identity poses
