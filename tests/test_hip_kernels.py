@@ -23,8 +23,8 @@ TOL_GRAD = 1e-4
 
 @pytest.fixture(scope="module")
 def hip():
-    from upnerf_amd import _lib, camera, ops, rendering
-    return dict(lib=_lib, camera=camera, ops=ops, rendering=rendering)
+    from upnerf_amd import _lib, camera, ops, pass_plan, rendering
+    return dict(lib=_lib, camera=camera, ops=ops, rendering=rendering, pass_plan=pass_plan)
 
 
 def cpu(t):
@@ -1806,3 +1806,59 @@ def test_two_virtual_ranks_draw_what_one_rank_draws(hip):
     s.global_step = 62  # another step: other numbers
     zc2, _ = depths(batch, 0)
     assert not torch.equal(zc, zc2)
+
+
+PLAN_CASES = ([(256, 8, R, S, fm) for R, S in ((5, 33), (3, 257)) for fm in ("f16x3", "f32", "f16")]
+              + [(64, 4, 5, 33, fm) for fm in ("f16x3", "f32")])  # (64-wide fields: the f16 mode refuses them)
+
+
+@pytest.mark.parametrize("W,D,R,S,field_mode", PLAN_CASES, indirect=["field_mode"])
+def test_field_pass_holds_exactly_what_its_plan_lists(hip, W, D, R, S, field_mode):
+    """Forward, backward and plan are one description: every buffer the plan lists is held with the planned shape and dtype on
+    storage of at least the planned rows, every form the plan omits is None.  Compared on the allocated tensors."""
+    from upnerf_amd import synth
+    from upnerf_amd.nerf import NeRF
+    rd = hip["rendering"]
+    kw = dict(D=D, W=W, feat_dim=384, xyz_L=10, dir_L=4, appearance_dim=48, candidate_dim=16)
+    model = NeRF("coarse", c2f=None, **kw)
+    model.load_state_dict(synth.nerf_state("coarse", seed=3, **kw))
+    model = model.cuda()
+    o, d = (gen((R, 3), 70) * 0.3).cuda(), torch.nn.functional.normalize(gen((R, 3), 71), dim=-1).cuda()
+    z = (torch.sort(gen((R, S), 72).abs() * 3 + 0.1, dim=-1).values).cuda()
+    c_rows, a_rows = gen((R, 16), 73).cuda(), gen((R, 48), 74).cuda()
+
+    def held(plan, got, names):
+        pp = hip["pass_plan"]
+        for k in names:
+            shape, t = plan.buffers[k], got[k]
+            if shape is None:
+                assert t is None, k
+                continue
+            assert tuple(t.shape) == shape and t.dtype == getattr(torch, pp.DTYPES.get(k, "float32")), (k, tuple(t.shape), t.dtype)
+            # the rows the plan allocates: Mp behind the visible ones of the tensors the kernels write in whole tiles
+            numel = int(np.prod((plan.Mp,) + shape[1:] if k in pp.PADDED else shape))
+            assert t.untyped_storage().nbytes() >= numel * t.element_size(), (k, shape, plan.Mp)
+
+    for mode, use_cand, use_rgb in ((1, True, True), (0, True, False), (2, False, True), (3, False, False)):
+        cfg = rd._PassCfg(model.packer, mode, use_cand, use_rgb, [1.0] * 10, [1.0] * 4)
+        leaves = [t.clone().requires_grad_(True) for t in (o, d, c_rows, a_rows, model.packed().detach())]
+        outs = rd._FieldPass.apply(leaves[0], leaves[1], z, leaves[2], leaves[3], leaves[4], cfg)
+        node = next(t.grad_fn for t in outs if t.grad_fn is not None)
+        plan, stages = node.plan, hip["pass_plan"].STAGES
+        assert plan == rd._plan(model.packer, R, S, mode, use_cand, use_rgb, False, True) and node.rr == plan.rr
+        held(plan, node.saved, stages["aux"] + stages["field"] + ("w_all", "w_sj", "w_cj", "w_s"))
+        names = ("E_s", "G_c", "sum_sfeat", "t_weight", "c_depth", "s_depth", "rgb_map", "w_all", "w_s", "rgb_joint_map")
+        held(plan, {k: (t if t.numel() else None) for k, t in zip(names, outs)}, names)
+        sink = {}
+        rd._DEBUG_SINK = sink
+        try:
+            sum((t * gen(tuple(t.shape), 80 + i).cuda()).sum() for i, t in enumerate(outs) if t.numel()).backward()
+        finally:
+            rd._DEBUG_SINK = None
+        held(plan, node.bwd_buffers, sum((stages[s] for s in ("cbwd", "fbwd", "part", "sums")), ()))
+        M = R * S
+        rows = dict(gz_h=(D, M, W), gz_e=(M, W), gz_g1=(M, W // 2) if use_cand else None, gz_g2=(M, W // 2) if use_cand else None,
+                    gz_r1=(M, W // 2) if use_rgb else None)
+        for k, shape in rows.items():  # ... and whatever the form, the sink shows fp32 rows of the visible samples
+            assert (sink[k] is None) if shape is None else (tuple(sink[k].shape) == shape and sink[k].dtype == torch.float32), k
+        assert all(t.grad is not None and torch.isfinite(t.grad).all() for t in (leaves[0], leaves[1], leaves[4]))

@@ -10,10 +10,13 @@ import os
 
 import torch
 
+from .pass_plan import (AUXK, RR_PART_STRIDE, TILE_PART_STRIDE, WG_F16_FRAG, WG_F16_TILE, WG_F24, WG_F32, WG_PLANES,  # noqa: F401
+                        X0)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UPNERF_LIB") or os.path.join(_HERE, "libupnerf_hip.so")  # UPNERF_LIB: diagnostic builds only
 MAX_D = 8
-TILE_ROWS, X0, AUXK, CK = int(os.environ.get("UPNERF_TILE_ROWS", 64)), 64, 80, 16  # env: diagnostic builds only
+TILE_ROWS, CK = int(os.environ.get("UPNERF_TILE_ROWS", 64)), 16  # env: diagnostic builds only
 
 _fp = C.c_void_p
 
@@ -126,9 +129,6 @@ class WgradPending(C.Structure):
                 ("dW2", _fp), ("db2", _fp), ("ldo2", C.c_int32), ("pad", C.c_int32), ("vslabs", _fp), ("dv", _fp), ("dbv", _fp)]
 
 
-WG_F32, WG_F16_TILE, WG_F16_FRAG, WG_F24, WG_PLANES = range(5)  # UPNERF_WG_*: how a weight-gradient operand is stored
-
-
 class WgradOperand(C.Structure):
     _fields_ = [("p", _fp), ("lo", _fp), ("exp", _fp), ("ld", C.c_int32), ("kind", C.c_int32)]
 
@@ -145,8 +145,6 @@ class WgradGroup(C.Structure):
 
 
 MAX_WGRAD_GROUPS = 32
-TILE_PART_STRIDE = 1288  # UPNERF_TILE_PART_STRIDE
-RR_PART_STRIDE = 512  # UPNERF_RR_PART_STRIDE
 
 
 class EmbedGroup(C.Structure):

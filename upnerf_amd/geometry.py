@@ -225,24 +225,17 @@ def _field_sigma(model, o: torch.Tensor, d: torch.Tensor, z: torch.Tensor) -> to
     R, S = z.shape
     M, dev, st = R * S, z.device, stream()
     P = model.packed().detach().contiguous()
-    use16 = rd._field16_ok(pk, S)
-    rr = use16 and rd._rr_ok(S)  # register-resident fp16 kernels: the encoding rows padded to whole 256-sample tiles
-    Mp = (M + rd.RR_TILE - 1) // rd.RR_TILE * rd.RR_TILE if rr else M
-    P16 = wexp = wnorm = None
-    if use16:
-        P16, _, wexp, wnorm = pk.frag16_hip(P, perm=rr)
-        PF = P
-    else:
-        PF = pk.frag_hip(P)
+    plan = rd._plan(pk, R, S)  # density only, no gradient: the tiling, and with it the rows x0 is allocated with
+    PF, P16, _, wexp, wnorm = rd._weights(pk, P, plan)
     hp = getattr(model, "host_progress", None)
     progress = float(model.progress.data) if hp is None else float(torch.tensor(hp, dtype=torch.float32))
     sigma = torch.empty(R, S, device=dev, dtype=torch.float32)
-    x0 = torch.empty(Mp, _lib.X0, device=dev, dtype=torch.float32)
+    x0 = torch.empty(plan.Mp, _lib.X0, device=dev, dtype=torch.float32)
     fa = _lib.FieldFwdArgs(R=R, S=S, use_cand=0, use_rgb=0, rays_o=ptr(o), rays_d=ptr(d), z=ptr(z),
                            wk_xyz=(C.c_float * 10)(*rd.band_weights(model.xyz_L, progress, model.c2f)), P=ptr(PF),
-                           sigma_s=ptr(sigma), x0=ptr(x0), P16=ptr(P16), wexp=ptr(wexp), planes=rd._planes(),
-                           tile_rows=rd.RR_TILE if rr else 64, wnorm=ptr(wnorm), rows_capacity=Mp if rr else 0)
-    fn = lib.upnerf_field_fwd_f16x3 if use16 else lib.upnerf_field_fwd
+                           sigma_s=ptr(sigma), x0=ptr(x0), P16=ptr(P16), wexp=ptr(wexp), planes=plan.planes,
+                           tile_rows=plan.tile_rows, wnorm=ptr(wnorm), rows_capacity=plan.rows_capacity)
+    fn = lib.upnerf_field_fwd_f16x3 if plan.use16 else lib.upnerf_field_fwd
     check(TIMER.run("density_grid", lambda: fn(C.byref(L), C.byref(fa), st), units=M), "upnerf_field_fwd")
     return sigma
 

@@ -1,0 +1,125 @@
+"""What one field pass stores and in which form, decided ONCE: rendering._FieldPass allocates its forward and backward buffers
+from this plan and takes the operand forms of its weight gradients from it; geometry's density-only pass takes its tiling from it.
+Host arithmetic only -- neither the library nor a device is touched, a plan can be built (and tested) anywhere."""
+from __future__ import annotations
+
+from collections import namedtuple
+
+# constants of include/upnerf_hip.h that size a pass (_lib re-exports them beside the structs)
+X0, AUXK = 64, 80
+WG_F32, WG_F16_TILE, WG_F16_FRAG, WG_F24, WG_PLANES = range(5)  # UPNERF_WG_*: how a weight-gradient operand is stored
+TILE_PART_STRIDE = 1288  # UPNERF_TILE_PART_STRIDE
+RR_PART_STRIDE = 512  # UPNERF_RR_PART_STRIDE
+RR_TILE = 256
+MODES = ("f16x3", "f32", "f16")
+
+# What is the same for every pass.  Buffer names in allocation order, by the launch they are allocated in front of:
+STAGES = {"aux": ("aux",),
+          "field": ("sigma_s", "sigma_c", "rgb", "x0", "h16", "hexp", "h_lo8", "h", "e", "e16", "eexp", "hmask", "mx32", "g1", "g1_16",
+                    "g1exp", "g2", "g2_16", "g2exp", "r1", "r1_16", "r1exp"),
+          "composite": ("w_all", "w_sj", "w_cj", "w_s", "E_s", "G_c", "sum_sfeat", "t_weight", "c_depth", "s_depth", "rgb_map",
+                        "rgb_joint_map"),
+          "cbwd": ("d_sigma_s", "d_sigma_c", "d_rgb"),
+          "fbwd": ("gz_e", "gz_h", "gz16", "gzexp", "gz_lo8", "gz_rg", "gz_rg16", "gzrgexp", "gz_g1", "gz_g2", "gz_g2_16", "gzg2exp",
+                   "gz_r1", "dpre_s", "dpre_c", "dpre_rgb"),
+          "part": ("tile_part", "ray_part"), "sums": ("rs_c", "rs_r")}
+F16 = frozenset(("h16", "e16", "g1_16", "g2_16", "r1_16", "gz16", "gz_rg16", "gz_g2_16"))
+I32 = frozenset(("hexp", "eexp", "g1exp", "g2exp", "r1exp", "gzexp", "gzrgexp", "gzg2exp"))
+DTYPES = {**dict.fromkeys(F16, "float16"), **dict.fromkeys(I32, "int32"), "h_lo8": "uint8", "gz_lo8": "uint8", "hmask": "int64"}
+# fp32 rows the field kernels write in whole tiles: allocated with the plan's Mp rows behind the M visible ones of their shape
+PADDED = frozenset(("x0", "e", "g1", "g2", "r1", "gz_rg", "gz_g1", "gz_g2", "gz_r1"))
+ZEROED = frozenset(("mx32",))  # must start at zero
+# How the weight gradients read one logical tensor: UPNERF_WG_* kind, leading dimension, the buffers that hold the data, the
+# per-tile exponents and the residual bytes, and the layer of those buffers it is (None: per call, or the buffer has none)
+Operand = namedtuple("Operand", "kind ld data exp lo at", defaults=(None, None, None))
+# The decisions of plan_pass (explained where they are taken; tile_rows and rows_capacity as the argument structs state them),
+# `buffers`: name -> shape as the kernels' callers see it (None: a form the pass does not use), `operands`: name -> Operand.
+PassPlan = namedtuple("PassPlan", "M Mp use16 rr tile_rows rows_capacity planes store16 store24 ntile e_frag joined rg16 g2f "
+                                  "partials ride buffers operands")
+
+
+def plan_pass(W, W2, D, R, S, mode, use_cand, use_rgb, rgb_joint, train, *, FIELD_MODE, WGRAD_STORE, FIELD_RR, TILE_PARTIALS,
+              WGRAD_CHAIN, JOIN_HEADS, VEC_RIDE, HMASK_SCALE) -> PassPlan:
+    if FIELD_MODE not in MODES:
+        raise ValueError(f"unknown FIELD_MODE {FIELD_MODE!r} (one of {MODES})")
+    use16 = FIELD_MODE != "f32" and W == 256 and S >= 32  # the f16 matrix-core kernels (csrc/field16*.hip); otherwise fp32 MFMA
+    if FIELD_MODE == "f16" and not use16:
+        raise ValueError("FIELD_MODE 'f16' needs W = 256 and at least 32 samples per ray")
+    if WGRAD_STORE == "f24" and not WGRAD_CHAIN:
+        raise RuntimeError("UPNERF_WGRAD_STORE=f24 needs UPNERF_WGRAD_CHAIN=1 "
+                           "(the hi + lo8 operands are read by the chained run only)")
+    # register-resident fp16 kernels: 256-sample tiles, per-sample tensors padded to whole tiles, stored as operand fragments
+    rr = bool(use16 and FIELD_MODE == "f16" and FIELD_RR)
+    M = R * S
+    Mp = (M + RR_TILE - 1) // RR_TILE * RR_TILE if rr else M
+    joint, want_feat, cand, col = mode <= 1, mode != 2, train and use_cand, train and use_rgb
+    # the trunk STORED as fp16 tiles + exponents: always in the f16 mode, on request in the f16x3 mode (rendering.WGRAD_STORE)
+    store16 = bool(train and use16 and (FIELD_MODE == "f16" or WGRAD_STORE in ("f16", "f24")))
+    store24 = store16 and FIELD_MODE != "f16" and WGRAD_STORE == "f24"
+    ntile = Mp // 32 if rr else (M + 63) // 64  # one exponent per 64 rows whatever the kernel's tile (rr: per 32)
+    # both heads on, chained f16 weight gradients, per-tile partial sums (upnerf_ray_sum, their fallback, wants dense tensors)
+    joined = bool(cand and col and use16 and JOIN_HEADS and WGRAD_CHAIN and TILE_PARTIALS)
+    # rr: e leaves as fragments only (compositing and the joined heads' weight gradient read those) unless a single head is on in
+    # training, whose separate weight gradient wants fp32 rows
+    e_frag = bool(rr and (joined if train else want_feat))
+    rg16 = joined and rr  # [gz_r1 | gz_g1] as fp16 fragments only, against e's fragments
+    g2f = bool(cand and e_frag)  # gz_g2 as fragments against g1's (candidate_encoding.2)
+    # per-tile sums from the backward kernel: the 128-wide vector heads and the per-ray sums (rr: the per-ray sums only)
+    partials = ("ray" if rr else "tile") if (use16 and TILE_PARTIALS and (cand or col)) else "none"
+    ride = bool(train and VEC_RIDE and WGRAD_CHAIN and (rr or (FIELD_MODE != "f16" and W == 256)))
+    ops = {}
+
+    def forms(name, n16, nexp, on, frag, w):
+        """Shapes of one logical [M][w] tensor (fp32 rows, or rr: fp16 operand fragments, their exponents per 32 rows) and the
+        operand that reads it; one form at most."""
+        if not on:
+            return None, None, None
+        ops[name] = Operand(WG_F16_FRAG, w, n16, nexp) if frag else Operand(WG_F32, w, name)
+        return (None, (Mp, w), (Mp // 32,)) if frag else ((M, w), None, None)
+
+    e, e16, eexp = forms("e", "e16", "eexp", train or want_feat, e_frag, W)
+    g1, g1_16, g1exp = forms("g1", "g1_16", "g1exp", cand, e_frag, W2)
+    g2, g2_16, g2exp = forms("g2", "g2_16", "g2exp", use_cand and (train or joint), e_frag, W2)
+    r1, r1_16, r1exp = forms("r1", "r1_16", "r1exp", col, e_frag, W2)
+    gz_rg, gz_rg16, gzrgexp = forms("gz_rg", "gz_rg16", "gzrgexp", joined, rg16, W)
+    gz_g2, gz_g2_16, gzg2exp = forms("gz_g2", "gz_g2_16", "gzg2exp", cand, g2f, W2)
+    per_ray, per_sample, trunk16 = (R, S), (M,), (D, Mp, W) if store16 else None
+    # Without `train` nothing only the backward pass reads is planned: the kernels skip those stores, 8 of the 11 KB per sample
+    buffers = {
+        "aux": (R, AUXK) if use_rgb else None, "sigma_s": per_sample, "sigma_c": per_sample if use_cand else None,
+        "rgb": (M, 3) if use_rgb else None, "x0": (M, X0), "h16": trunk16, "hexp": (D, ntile) if store16 else None,
+        "h_lo8": (D, M, W) if store24 else None,
+        # fp32 h: every layer, or beside h16 the last one only (for the density head and the final layer; rr: fragments do)
+        "h": ((1 if store16 else D, M, W) if not (store16 and rr) else None) if train else None,
+        "e": e, "e16": e16, "eexp": eexp,
+        # ReLU decisions, 64 bits per lane and tile (rr: 128 per lane)
+        "hmask": (((D + 3) * Mp * 4 if rr else (D + 1) * ((M + 127) // 128) * 512 * HMASK_SCALE,)) if train else None,
+        # running max|.| of the stored tensors (scales of the weight gradients): [0, 16) this pass, [16, 32) the backward kernel
+        "mx32": (32,) if train else None,
+        "g1": g1, "g1_16": g1_16, "g1exp": g1exp, "g2": g2, "g2_16": g2_16, "g2exp": g2exp, "r1": r1, "r1_16": r1_16, "r1exp": r1exp,
+        "w_all": per_ray if joint else None, "w_sj": per_ray if joint else None, "w_cj": per_ray if joint else None, "w_s": per_ray,
+        "E_s": (R, W) if want_feat else None, "G_c": (R, W2) if joint else None, "sum_sfeat": (R,) if want_feat else None,
+        "t_weight": (R,) if joint else None, "c_depth": (R,) if joint else None, "s_depth": (R,),
+        "rgb_map": (R, 3) if use_rgb else None, "rgb_joint_map": (R, 3) if rgb_joint else None,
+        "d_sigma_s": per_sample if train else None, "d_sigma_c": per_sample if (train and joint) else None,
+        "d_rgb": (M, 3) if col else None, "gz_e": (M, W) if (train and not rr) else None,  # (rr: layer D of gz16)
+        "gz_h": (D, M, W) if (train and not store16) else None, "gz16": (D + int(rr), Mp, W) if store16 else None,
+        "gzexp": (D + int(rr), ntile) if store16 else None, "gz_lo8": (D, M, W) if store24 else None,
+        "gz_rg": gz_rg, "gz_rg16": gz_rg16, "gzrgexp": gzrgexp,
+        "gz_g1": (M, W2) if (cand and not joined) else None,  # (joined: a column block of gz_rg)
+        "gz_g2": gz_g2, "gz_g2_16": gz_g2_16, "gzg2exp": gzg2exp, "gz_r1": (M, W2) if (col and not joined) else None,
+        "dpre_s": per_sample if train else None, "dpre_c": per_sample if cand else None, "dpre_rgb": (M, 4) if col else None,
+        "tile_part": ((M + 63) // 64, TILE_PART_STRIDE) if partials == "tile" else None,
+        "ray_part": (Mp // 32, RR_PART_STRIDE) if partials == "ray" else None,
+        "rs_c": (R, W2) if cand else None, "rs_r": (R, W2) if col else None}
+    if train:  # the trunk: fp32 rows, or fp16 tiles (rr: fragments; store24: + residual bytes); `at` None: the caller names the layer
+        kind16 = WG_F24 if store24 else WG_F16_FRAG if rr else WG_F16_TILE
+        ops["x0"] = Operand(WG_F32, X0, "x0")
+        ops["h"] = h = Operand(kind16, W, "h16", "hexp", "h_lo8" if store24 else None) if store16 else Operand(WG_F32, W, "h")
+        ops["gz"] = gz = Operand(kind16, W, "gz16", "gzexp", "gz_lo8" if store24 else None) if store16 else Operand(WG_F32, W, "gz_h")
+        ops["h_last"] = h._replace(at=D - 1) if rr or not store16 else Operand(WG_F32, W, "h", at=0)
+        ops["gz_e"] = gz._replace(at=D) if rr else Operand(WG_F32, W, "gz_e")
+        if not joined:
+            ops.update({k: Operand(WG_F32, W2, k) for k, on in (("gz_g1", cand), ("gz_r1", col)) if on})
+    return PassPlan(M, Mp, use16, rr, RR_TILE if rr else 64, Mp if rr else 0, 1 if FIELD_MODE == "f16" else 2, store16, store24, ntile,
+                    e_frag, joined, rg16, g2f, partials, ride, buffers, ops)
