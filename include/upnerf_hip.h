@@ -1126,6 +1126,52 @@ typedef struct {
 } upnerf_occ_scatter_args;
 int upnerf_occ_scatter(const upnerf_occ_scatter_args* a, void* stream);
 
+/* ---- surface normals from the analytic density gradient (csrc/normals.hip, csrc/viz.hip).  Added under
+ * ABI 11: new symbols only.  Every entry point: arguments refused on the host before anything is launched, nothing allocated,
+ * no host read-back, no atomics (the same bits every run), one launch on `stream`.
+ *
+ * upnerf_density_grad: sigma[m] = the shared density (after the softplus) of the field (L, P) at points[m], and
+ * grad[m] = d sigma / d x there, in world space.  One fused launch: encoding, trunk, share_sigma and the walk back through
+ * the transposed weights happen per 64-point tile in LDS and registers; nothing of size M x W is read or written.  fp32 MFMA
+ * whatever the field mode of the training step.  P: the parameters with the matrices in fragment order (what
+ * upnerf_field_fwd reads), PT: the transposed fragments (what upnerf_field_bwd reads).  Any M >= 1; a point's outputs do not
+ * depend on M or on its position in the batch, bit for bit.  softplus'(x) is the sigmoid, and 1 where x > 20 (the branch on
+ * which the softplus returns x). */
+typedef struct {
+  int32_t M, reserved_;
+  const float* points;       /* [M][3] */
+  const float* P;
+  const float* PT;
+  float wk_xyz[10];          /* BARF band weights of the xyz encoding */
+  float* sigma;              /* [M] */
+  float* grad;               /* [M][3] */
+} upnerf_density_grad_args;
+int upnerf_density_grad(const upnerf_layout* L, const upnerf_density_grad_args* a, void* stream);
+
+/* upnerf_normal_composite: normal[r] = normalise(sum_i w[r][i] * (-grad[r*S+i] / |grad[r*S+i]|)).  A term is zero where the
+ * fp32 length of the gradient is 0 or not finite (a NaN or infinite component, or an overflow of the squares) or the weight
+ * is not finite; the result is (0, 0, 0) where the length of the sum is 0 or not finite.  Never NaN.  One ray per wave, fixed
+ * summation order.  R * S < 2^31. */
+typedef struct {
+  int32_t R, S;
+  const float* grad;         /* [R*S][3] */
+  const float* w;            /* [R][S], upnerf_composite_fwd's w_s */
+  float* normal;             /* [R][3], unit length or (0, 0, 0) */
+} upnerf_normal_composite_args;
+int upnerf_normal_composite(const upnerf_normal_composite_args* a, void* stream);
+
+/* upnerf_viz_normals: normals [H*W][3] to packed RGB8.  n' = rot . n when `rot` is given (row-major 3 x 3 in device memory,
+ * e.g. a world-to-camera rotation; every product and sum rounded on its own, (r0 nx + r1 ny) + r2 nz), else n;
+ * channel = q((n' + 1) / 2) with q = upnerf_viz_rgb's rule ((uint8)min(max(255.0f * v, 0), 255), truncating; NaN -> 0).
+ * A normal whose three components are exactly zero is drawn as (128, 128, 128). */
+typedef struct {
+  int32_t H, W;
+  const float* n;            /* [H*W][3] */
+  const float* rot;          /* [3][3] DEVICE, or NULL */
+  uint8_t* rgb;              /* [H][W][3] */
+} upnerf_viz_normals_args;
+int upnerf_viz_normals(const upnerf_viz_normals_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

@@ -2,13 +2,15 @@
 
     python tools/extract_mesh.py --ckpt last.ckpt [--config scene.yaml] --level SIGMA --out scene.ply
                                  (--bounds X0 Y0 Z0 X1 Y1 Z1 | --from-cameras MARGIN) [--resolution 256 | NX NY NZ]
-                                 [--img-id 0] [--slab S] [--field fine|coarse] [--chunk COLUMNS]
+                                 [--img-id 0] [--slab S] [--field fine|coarse] [--chunk COLUMNS] [--analytic-normals]
 
 --level is the density (sigma, after the softplus) of the surface and has NO default: the useful value depends on the scale of
 the scene, so look at the histogram of a coarse grid first (--level with a low --resolution is quick).  With --config the
 scene's dataset is loaded, which --from-cameras needs (the box round the refined cameras and their far points); with --ckpt
 alone the hyper-parameters come from the checkpoint and the box from --bounds.  Colours are the static colour under the
 appearance of training image --img-id, rendered over a slab of thickness 2 S round every vertex (default: one cell diagonal).
+--analytic-normals replaces the grid's central-difference normals by the field's own, -grad sigma / |grad sigma| at the vertices
+(geometry.refine_normals), before the colouring aims its rays along them.
 Prints one JSON line."""
 import argparse
 import json
@@ -36,6 +38,7 @@ def parser():
     ap.add_argument("--slab", type=float, default=None, help="half thickness of the slab rendered round a vertex (default: a cell diagonal)")
     ap.add_argument("--field", default="fine", choices=("fine", "coarse"))
     ap.add_argument("--chunk", type=int, default=None, help="grid columns per field launch (default: about a million samples)")
+    ap.add_argument("--analytic-normals", action="store_true", help="vertex normals from the field's analytic gradient, not the grid's differences")
     return ap
 
 
@@ -72,12 +75,14 @@ def main(argv=None):
     slab = a.slab
     if slab is None:
         slab = sum(((h - l) / max(n - 1, 1)) ** 2 for l, h, n in zip(bounds[0], bounds[1], res)) ** 0.5
+    if a.analytic_normals and mesh.vertices.shape[0]:
+        mesh = geometry.refine_normals(system, mesh, field=a.field)
     if mesh.vertices.shape[0]:
         mesh.colours = geometry.colour_vertices(system, mesh, a.img_id, slab)
     mesh.write_ply(a.out)
     torch.cuda.synchronize()
     print(json.dumps({"out": a.out, "vertices": int(mesh.vertices.shape[0]), "faces": int(mesh.faces.shape[0]),
-                      "resolution": list(res), "bounds": [list(bounds[0]), list(bounds[1])], "level": a.level, "slab": slab,
+                      "resolution": list(res), "bounds": [list(bounds[0]), list(bounds[1])], "level": a.level, "slab": slab, "analytic_normals": bool(a.analytic_normals),
                       "sigma_min": float(grid.min()), "sigma_max": float(grid.max()), "seconds": time.perf_counter() - t0}))
 
 

@@ -2,7 +2,7 @@
 appearance moving from photograph to photograph (upnerf_amd/novel_view.py).
 
     python tools/render_path.py --config scene.yaml --ckpt last.ckpt --images 3 17 42 --frames 120 --out DIR
-                                [--mode linear|catmull] [--downscale N] [--depth] [--loop] [--chunk ROWS]
+                                [--mode linear|catmull] [--downscale N] [--depth] [--normals] [--loop] [--chunk ROWS]
                                 [--occupancy NX NY NZ --level SIGMA [--dilate K] [--bounds X0 Y0 Z0 X1 Y1 Z1 | --margin M]]
 
 --occupancy skips empty space: the fine field's density is sampled on NX x NY x NZ grid points over the box (--bounds, or the
@@ -11,7 +11,8 @@ rounds) are kept, and only the rays that touch such a cell are rendered, over th
 shows the background, NOT what the full render would have composited from density below --level: --level (no default, as in
 tools/extract_mesh.py) and --dilate trade speed for that.
 
-Writes PNG files only -- DIR/path/step_<frame, 8 digits>/rgb.png (and depth.png with --depth).  No video encoder is installed
+Writes PNG files only -- DIR/path/step_<frame, 8 digits>/rgb.png (and depth.png with --depth, normal.png with
+--normals: the world-space normal map, (n + 1) / 2, mid-grey where nothing was hit).  No video encoder is installed
 with this package: turn the frames into a film with a tool of your own (e.g. ffmpeg -i DIR/path/step_%08d/rgb.png)."""
 import argparse
 import json
@@ -35,6 +36,7 @@ def parser():
     ap.add_argument("--mode", default="catmull", choices=("linear", "catmull"), help="translation between keyframes")
     ap.add_argument("--downscale", type=int, default=1, help="render at 1/N of the first keyframe image's size")
     ap.add_argument("--depth", action="store_true", help="also write the colour-mapped depth of every frame (one range: frame 0's)")
+    ap.add_argument("--normals", action="store_true", help="also write the world-space normal map of every frame")
     ap.add_argument("--loop", action="store_true", help="close the path on the first image")
     ap.add_argument("--chunk", type=int, default=None, help="rows per render chunk (default: val.chunk_size)")
     ap.add_argument("--occupancy", type=int, nargs=3, metavar=("NX", "NY", "NZ"), help="skip empty space with an occupancy grid of this many grid points")
@@ -84,7 +86,7 @@ def main(argv=None):
         extra = {"occupied_share": occ.fraction, "bounds": [list(bounds[0]), list(bounds[1])], "level": a.level, "dilate": a.dilate,
                  "occupancy_seconds": time.perf_counter() - tb}
     t0 = time.perf_counter()
-    render_path(system, path, chunk=a.chunk, outputs=("rgb", "depth") if a.depth else ("rgb",), sink=writer, occupancy=occ)
+    render_path(system, path, chunk=a.chunk, outputs=("rgb",) + (("depth",) if a.depth else ()) + (("normal",) if a.normals else ()), sink=writer, occupancy=occ)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if occ is not None:

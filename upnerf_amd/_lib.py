@@ -304,6 +304,19 @@ class OccScatterArgs(C.Structure):
                 ("rays", _fp), ("rgb_c", _fp), ("depth_c", _fp), ("rgb", _fp), ("depth", _fp)]
 
 
+class DensityGradArgs(C.Structure):
+    _fields_ = [("M", C.c_int32), ("reserved_", C.c_int32), ("points", _fp), ("P", _fp), ("PT", _fp), ("wk_xyz", C.c_float * 10),
+                ("sigma", _fp), ("grad", _fp)]
+
+
+class NormalCompositeArgs(C.Structure):
+    _fields_ = [("R", C.c_int32), ("S", C.c_int32), ("grad", _fp), ("w", _fp), ("normal", _fp)]
+
+
+class VizNormalsArgs(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("n", _fp), ("rot", _fp), ("rgb", _fp)]
+
+
 class Rng(C.Structure):
     """upnerf_rng: key of the uniform draws a kernel generates itself."""
     _fields_ = [("seed", C.c_uint64), ("step", C.c_int32), ("row0", C.c_int32), ("row_stride", C.c_int32), ("step_dev", _fp)]
@@ -389,6 +402,9 @@ _SIGNATURES = {
     "upnerf_occ_compact_scratch": [_i],
     "upnerf_occ_compact": [C.POINTER(OccCompactArgs), _p],
     "upnerf_occ_scatter": [C.POINTER(OccScatterArgs), _p],
+    "upnerf_density_grad": [C.POINTER(Layout), C.POINTER(DensityGradArgs), _p],
+    "upnerf_normal_composite": [C.POINTER(NormalCompositeArgs), _p],
+    "upnerf_viz_normals": [C.POINTER(VizNormalsArgs), _p],
 }
 _LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
              "upnerf_occ_compact_scratch")

@@ -187,6 +187,39 @@ __global__ __launch_bounds__(NTHREADS) void rgb_kernel(upnerf_viz_rgb_args a, in
   }
 }
 
+// normal map: (n + 1) / 2 through quant(); a zero normal is mid-grey.  Four pixels per thread, as rgb_kernel.
+__global__ __launch_bounds__(NTHREADS) void normals_kernel(upnerf_viz_normals_args a, int packed) {
+  const int64_t n = (int64_t)a.H * a.W;
+  float r[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+  if (a.rot) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j) r[j] = a.rot[j];
+  }
+  for (int64_t p0 = ((int64_t)blockIdx.x * NTHREADS + threadIdx.x) * 4; p0 < n; p0 += (int64_t)gridDim.x * NTHREADS * 4) {
+    const int cnt = n - p0 < 4 ? (int)(n - p0) : 4;
+    uint32_t col[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j < cnt) {
+        const float* s = a.n + 3 * (p0 + j);
+        const float x = s[0], y = s[1], z = s[2];
+        if (x == 0.f && y == 0.f && z == 0.f) {
+          col[j] = 0x808080u;
+        } else {
+          float c[3] = {x, y, z};
+          if (a.rot) {
+#pragma clang fp contract(off)  // every product and sum rounded on its own, as numpy evaluates the restatement
+#pragma unroll
+            for (int k = 0; k < 3; ++k) c[k] = (r[3 * k] * x + r[3 * k + 1] * y) + r[3 * k + 2] * z;
+          }
+          col[j] = quant((c[0] + 1.0f) * 0.5f) | (quant((c[1] + 1.0f) * 0.5f) << 8) | (quant((c[2] + 1.0f) * 0.5f) << 16);
+        }
+      }
+    }
+    store_pixels4(a.rgb, p0, col, cnt, packed);
+  }
+}
+
 template <int VEC>
 __device__ __forceinline__ void load_chunk(const float* p, float (&o)[VEC]) {
   if constexpr (VEC == 4) {
@@ -411,5 +444,13 @@ extern "C" int upnerf_viz_rgb(const upnerf_viz_rgb_args* a, void* stream) {
   const int packed = aligned(a->rgb, 4);
   hipLaunchKernelGGL(rgb_kernel, dim3(map_blocks(ceil_div(n, 4 * NTHREADS))), dim3(NTHREADS), 0, (hipStream_t)stream, *a, fast,
                      packed);
+  return (int)hipGetLastError();
+}
+
+extern "C" int upnerf_viz_normals(const upnerf_viz_normals_args* a, void* stream) {
+  if (!a || a->H < 1 || a->W < 1 || !a->n || !a->rgb) return UPNERF_EINVAL;
+  const int64_t n = (int64_t)a->H * a->W;
+  hipLaunchKernelGGL(normals_kernel, dim3(map_blocks(ceil_div(n, 4 * NTHREADS))), dim3(NTHREADS), 0, (hipStream_t)stream, *a,
+                     (int)aligned(a->rgb, 4));
   return (int)hipGetLastError();
 }

@@ -24,7 +24,7 @@ from ._lib import check, lib, ptr, stream
 from .ops import TIMER
 
 __all__ = ["TETS", "EDGES", "TET_EDGES", "TRI_TABLE", "edge_owner", "Mesh", "read_ply", "density_grid", "grid_columns",
-           "extract_surface", "colour_vertices", "bounds_from_cameras"]
+           "extract_surface", "colour_vertices", "bounds_from_cameras", "refine_normals"]
 
 # ---- the tables of the split (the only copy: the kernels receive them as an argument) ---------------------------------------
 # Corner c of a cell is its origin + (c & 1, (c >> 1) & 1, c >> 2).  The Kuhn split: one tetrahedron per order in which the
@@ -309,6 +309,20 @@ def extract_surface(grid: torch.Tensor, bounds, level: float) -> Mesh:
     a.vertices, a.normals, a.faces = ptr(vertices), ptr(normals), ptr(faces)
     check(TIMER.run("mtet_emit", lambda: lib.upnerf_mtet_emit(C.byref(a), ptr(scratch), st), units=grid.numel()), "upnerf_mtet_emit")
     return Mesh(vertices, normals, faces)
+
+
+@torch.no_grad()
+def refine_normals(system, mesh: Mesh, field: str = "fine") -> Mesh:
+    """`mesh` with its vertex normals replaced by the field's own: -grad sigma / |grad sigma| at the vertices
+    (normals.density_gradient, upnerf_density_grad) instead of the central differences of the sampled grid, which are off by the
+    grid spacing where the surface is thin.  Vertices, faces and colours are the same tensors; a vertex whose analytic gradient
+    is zero or not finite keeps its grid normal."""
+    from . import normals as nm
+    _, g = nm.density_gradient(system, mesh.vertices, field=field)
+    length = g.norm(dim=1, keepdim=True)
+    ok = torch.isfinite(length) & (length > 0)
+    n = torch.where(ok, -g / torch.where(ok, length, torch.ones_like(length)), mesh.normals.to(g.dtype))
+    return Mesh(mesh.vertices, n.contiguous(), mesh.faces, mesh.colours)
 
 
 # ---- vertex colours ------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ rows go to `render_rays` through its `embed_rows` keyword; the pictures are buil
 There is no CPU path.  `plan_path` (which frame sits where, which two images it blends) is plain host arithmetic."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from dataclasses import dataclass
 from typing import Callable, Dict, Optional, Sequence, Tuple
@@ -245,7 +246,8 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
 
     outputs: any of "rgb" (uint8 [F, H, W, 3] of `s_rgb_fine`, `s_rgb_coarse` without a fine field), "depth" (uint8
     [F, H, W, 3], `s_depth_*` through the JET table over ONE range for the whole sequence: `depth_range`, or the min / max of
-    frame 0, kept on the device), "rgb_float" (fp32 [F, H * W, 3]).
+    frame 0, kept on the device), "rgb_float" (fp32 [F, H * W, 3]), "normal" (uint8 [F, H, W, 3]: the world-space normal map of
+    render_rays(normals=True) through visualization.normal_image) and "normal_float" (fp32 [F, H * W, 3], unit length or zero).
     sink: called as sink("path", frame, {"rgb": ..., "depth": ...}) once per finished frame, in order (an `ImageWriter`).
     The pixel list [F][H][W] is walked in chunks of `chunk` rows (default val.chunk_size) that may straddle frames; device
     memory is the chunk's workspace, one frame of staging and the requested outputs.
@@ -256,10 +258,10 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
     One host read per chunk (the hit count); a chunk without hits launches no field kernel.  LAST_STATS holds the sequence's
     number of rays and hits.  None: nothing of this runs."""
     from .rendering import render_rays
-    from .visualization import depth_image, min_max_of, rgb_image
-    unknown = set(outputs) - {"rgb", "depth", "rgb_float"}
+    from .visualization import depth_image, min_max_of, normal_image, rgb_image
+    unknown = set(outputs) - {"rgb", "depth", "rgb_float", "normal", "normal_float"}
     if unknown:
-        raise ValueError(f"unknown outputs {sorted(unknown)} (rgb, depth, rgb_float)")
+        raise ValueError(f"unknown outputs {sorted(unknown)} (rgb, depth, rgb_float, normal, normal_float)")
     hp = system.hparams
     sched_mult = system.get_schedule_mult(system._host_progress)
     if sched_mult == 0:
@@ -287,6 +289,7 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
     for k, w in zip(keys, weights):
         ws[k] = torch.empty(chunk, w.shape[1], device=dev, dtype=torch.float32)
     want_depth = "depth" in outputs
+    want_normal = "normal" in outputs or "normal_float" in outputs
     LAST_STATS.clear()
     occ_ws = None
     if occupancy is not None:
@@ -308,6 +311,7 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
     LAST_WORKSPACE.update({k: tuple(v.shape) for k, v in ws.items()})
     stage_rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
     stage_depth = torch.empty(n, device=dev, dtype=torch.float32) if want_depth else None
+    stage_normal = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_normal else None
     out: Dict[str, torch.Tensor] = {}
     if "rgb" in outputs:
         out["rgb"] = torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
@@ -315,6 +319,10 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
         out["depth"] = torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
     if "rgb_float" in outputs:
         out["rgb_float"] = torch.empty(F, n, 3, device=dev, dtype=torch.float32)
+    if "normal" in outputs:
+        out["normal"] = torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
+    if "normal_float" in outputs:
+        out["normal_float"] = torch.empty(F, n, 3, device=dev, dtype=torch.float32)
     rng_dev = None  # frame 0's (min, max) depth on the device: one colour scale for the whole sequence
 
     def finish(f):
@@ -330,36 +338,55 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
                 rng_dev = min_max_of(stage_depth)
             out["depth"][f].copy_(depth_image(stage_depth, (W, H), min_max=depth_range if depth_range is not None else rng_dev))
             images["depth"] = out["depth"][f]
+        if "normal_float" in out:
+            out["normal_float"][f].copy_(stage_normal)
+        if "normal" in out:
+            out["normal"][f].copy_(normal_image(stage_normal, (W, H)))
+            images["normal"] = out["normal"][f]
         if sink is not None:
             sink("path", f, images)
 
-    for g0 in range(0, total, chunk):
-        R = min(chunk, total - g0)
-        rays, rows = path_rays(c2w, nf, (W, H), intr, g0, R, tables=[(w, ws[k]) for k, w in zip(keys, weights)], i0=i0, i1=i1,
-                               t=t, rays=ws["rays"])
-        full = rays
-        if occ_ws is not None:  # only the rays that touch something, over the part of the ray that does
-            rays, rows, index, n_hit = oc.compact_rays(occupancy, full, rows, ws=occ_ws)
-            LAST_STATS["hits"] += n_hit
-        if occ_ws is None or n_hit > 0:
-            res = render_rays(models=system.models, embeddings=system.embeddings, rays=rays, img_idx=None, sched_mult=sched_mult,
-                              sched_phase=2 if sched_mult == 1 else 1, N_samples=hp["nerf.N_samples"],
-                              use_disp=hp["nerf.use_disp"], perturb=0, N_importance=hp["nerf.N_importance"], white_back=white_back,
-                              encode_feat=hp["nerf.feat_dim"] > 0, validation=True, embed_rows=dict(zip(keys, rows)))
-            rgb, depth = res[f"s_rgb_{typ}"], res[f"s_depth_{typ}"]
-        else:
-            rgb = depth = None
-        if occ_ws is not None:
-            rgb, depth = oc.scatter_results(index, full, rgb, depth if want_depth else None, background=1.0 if white_back else 0.0,
-                                            want_depth=want_depth, out_rgb=occ_ws["rgb"], out_depth=occ_ws.get("depth"))
-        g = g0
-        while g < g0 + R:  # the chunk's rows, frame by frame
-            f, p0 = divmod(g, n)
-            cnt = min(n - p0, g0 + R - g)
-            stage_rgb[p0:p0 + cnt].copy_(rgb[g - g0:g - g0 + cnt])
-            if want_depth:
-                stage_depth[p0:p0 + cnt].copy_(depth[g - g0:g - g0 + cnt])
-            g += cnt
-            if p0 + cnt == n:
-                finish(f)
+    reuse = contextlib.ExitStack()
+    if want_normal:  # parameters do not change between chunks: pack the field for upnerf_density_grad once, not per chunk
+        from .normals import reuse_fragments
+        reuse.enter_context(reuse_fragments())
+    with reuse:
+        for g0 in range(0, total, chunk):
+            R = min(chunk, total - g0)
+            rays, rows = path_rays(c2w, nf, (W, H), intr, g0, R, tables=[(w, ws[k]) for k, w in zip(keys, weights)], i0=i0, i1=i1,
+                                   t=t, rays=ws["rays"])
+            full = rays
+            if occ_ws is not None:  # only the rays that touch something, over the part of the ray that does
+                rays, rows, index, n_hit = oc.compact_rays(occupancy, full, rows, ws=occ_ws)
+                LAST_STATS["hits"] += n_hit
+            if occ_ws is None or n_hit > 0:
+                res = render_rays(models=system.models, embeddings=system.embeddings, rays=rays, img_idx=None, sched_mult=sched_mult,
+                                  sched_phase=2 if sched_mult == 1 else 1, N_samples=hp["nerf.N_samples"],
+                                  use_disp=hp["nerf.use_disp"], perturb=0, N_importance=hp["nerf.N_importance"], white_back=white_back,
+                                  encode_feat=hp["nerf.feat_dim"] > 0, validation=True, embed_rows=dict(zip(keys, rows)),
+                                  **({"normals": True} if want_normal else {}))
+                rgb, depth = res[f"s_rgb_{typ}"], res[f"s_depth_{typ}"]
+                normal = res[f"normal_{typ}"] if want_normal else None
+            else:
+                rgb = depth = normal = None
+            if occ_ws is not None and want_normal:  # a ray that touches nothing has no normal: (0, 0, 0)
+                full_normal = torch.zeros(R, 3, device=dev, dtype=torch.float32)
+                if n_hit > 0:
+                    full_normal[index[:n_hit].long()] = normal
+                normal = full_normal
+            if occ_ws is not None:
+                rgb, depth = oc.scatter_results(index, full, rgb, depth if want_depth else None, background=1.0 if white_back else 0.0,
+                                                want_depth=want_depth, out_rgb=occ_ws["rgb"], out_depth=occ_ws.get("depth"))
+            g = g0
+            while g < g0 + R:  # the chunk's rows, frame by frame
+                f, p0 = divmod(g, n)
+                cnt = min(n - p0, g0 + R - g)
+                stage_rgb[p0:p0 + cnt].copy_(rgb[g - g0:g - g0 + cnt])
+                if want_depth:
+                    stage_depth[p0:p0 + cnt].copy_(depth[g - g0:g - g0 + cnt])
+                if want_normal:
+                    stage_normal[p0:p0 + cnt].copy_(normal[g - g0:g - g0 + cnt])
+                g += cnt
+                if p0 + cnt == n:
+                    finish(f)
     return out

@@ -228,6 +228,28 @@ def rgb_image(x: torch.Tensor, img_wh) -> torch.Tensor:
     return rgb
 
 
+def normal_image(normals: torch.Tensor, img_wh, rot: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [H, W, 3] of a normal map [H * W, 3] (upnerf_viz_normals): `(n + 1) / 2` quantised as rgb_image quantises, a zero
+    normal (nothing hit) drawn as mid-grey (128, 128, 128).  rot: a 3 x 3 rotation applied first, e.g. the world-to-camera
+    rotation c2w[:, :3].T for a camera-space map; None: the world-space normals as they are."""
+    W, H = parse_img_wh(img_wh)
+    _need_cuda(normals, "the normal map")
+    n = H * W
+    if n < 1:
+        raise ValueError(f"an image needs H, W >= 1, got H={H}, W={W}")
+    if normals.numel() != 3 * n or normals.shape[-1] != 3:
+        raise ValueError(f"expected normals [{n}, 3], got {tuple(normals.shape)}")
+    x = normals.detach().reshape(n, 3).float().contiguous()
+    if rot is not None:
+        if tuple(rot.shape) != (3, 3):
+            raise ValueError("rot is a 3 x 3 rotation")
+        rot = torch.as_tensor(rot).detach().to(device=x.device, dtype=torch.float32).contiguous()
+    rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=x.device)
+    a = _lib.VizNormalsArgs(H=H, W=W, n=_lib.ptr(x), rot=_lib.ptr(rot), rgb=_lib.ptr(rgb))
+    _lib.check(_lib.lib.upnerf_viz_normals(C.byref(a), _lib.stream()), "upnerf_viz_normals")
+    return rgb
+
+
 # ---- which picture each name gets (nerf_system.py:281-305) ---------------------------------------------------------
 
 def plan_validation_images(log_image_list, results: Mapping, typ: str, has_pca: bool, has_inv_depths: bool) -> List[tuple]:
@@ -253,6 +275,8 @@ def plan_validation_images(log_image_list, results: Mapping, typ: str, has_pca: 
             plan.append((name, "pca", name))
         elif "rgb" in name:
             plan.append((name, "rgb", name))
+        elif "normal" in name:  # (not a reference picture: render_rays(normals=True))
+            plan.append((name, "normal", name))
         else:
             v = results[name]
             shape = tuple(getattr(v, "shape", v))
@@ -308,6 +332,8 @@ def validation_images(system, batch: Mapping, results: Mapping) -> Dict[str, tor
             out[name] = depth_image(results[src], wh)
         elif kind == "grey":
             out[name] = rgb_image(results[src], wh)
+        elif kind == "normal":
+            out[name] = normal_image(results[src], wh)
         else:  # pred_depth: the depth prior under the image's learnt scale and shift, over the range of the rendered depth
             row = system.depth_scale.weight.detach()[item("img_idx").reshape(-1)[:1].long()]  # the first ray's image (:249)
             out[name] = depth_image(item(src), wh, min_max=min_max_of(results[f"s_depth_{typ}"]), depth_scale=row,
