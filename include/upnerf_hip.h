@@ -1036,7 +1036,14 @@ typedef struct {
   float* vertices;           /* [cap_vertices][3] */
   float* normals;            /* [cap_vertices][3] */
   int32_t* faces;            /* [cap_faces][3] */
+  int32_t flags, reserved2_; /* UPNERF_MTET_* bits (count and emit must agree); 0: everything above, bit for bit */
 } upnerf_mtet_args;
+/* UPNERF_MTET_SKIP_NONFINITE: cells that touch a sample nobody observed emit nothing.  An edge is crossed only if BOTH its ends
+ * are finite (and one is inside, the other not), and a tetrahedron is triangulated only if all FOUR of its corners are finite --
+ * so every emitted triangle indexes emitted vertices, and no wall is built where finite samples meet non-finite ones (the
+ * back of a truncation shell, the edge of a frustum: csrc/tsdf.hip).  A vertex may remain that no triangle uses.  Any other
+ * bit in `flags` is UPNERF_EINVAL. */
+#define UPNERF_MTET_SKIP_NONFINITE 1
 long long upnerf_mtet_scratch(int Nx, int Ny, int Nz);
 int upnerf_mtet_count(const upnerf_mtet_args* a, void* scratch, int32_t* totals /*[2] device*/, void* stream);
 int upnerf_mtet_emit(const upnerf_mtet_args* a, const void* scratch, void* stream);
@@ -1171,6 +1178,84 @@ typedef struct {
   uint8_t* rgb;              /* [H][W][3] */
 } upnerf_viz_normals_args;
 int upnerf_viz_normals(const upnerf_viz_normals_args* a, void* stream);
+
+/* ---- depth-map fusion: a truncated signed distance volume (TSDF) from rendered depth maps (csrc/tsdf.hip).
+ * Added under ABI 11: new symbols only.  Every entry point: arguments refused on the host before anything is launched, nothing
+ * allocated, no host read-back, no atomics and no cross-thread reduction (the same bits every run), one launch on `stream`.
+ *
+ * The volume lives on the grid of the mesher: Nx x Ny x Nz points over lo..hi, point (x, y, z) at linear index
+ * (z * Ny + y) * Nx + x and at the grid coordinates defined above (fp64 from the fp32 bounds, rounded to fp32 ONCE: that fp32
+ * point p is what everything below sees).  Four fp32 volumes: `tsdf` (the running mean of the truncated distance in units of
+ * `trunc`, in [-1, 1]; the caller initialises it, 1 by convention), `weight` (the sum of the view weights, 0 = never observed),
+ * and optionally `rgb` [..][3] with `rgb_weight`, a volume of its OWN for the colour's weight (not packed into anything): colour
+ * is fused in a narrower set of views than distance (rule 7), so its mean needs its own denominator.
+ *
+ * upnerf_tsdf_integrate folds views[0 .. n_views) into the volume, one thread per voxel, views in index order, all in fp32,
+ * every operation rounded on its own (no fma).  A view is a pinhole camera looking down its -z axis with +y up
+ * (c2w = [R | c] row-major 3 x 4, utils/ray.py) and a map of EUCLIDEAN distances along unit-length rays (`s_depth_*`):
+ *   1. pc = R^T (p - c), zc = -pc.z; the view is skipped unless zc > 0.
+ *   2. u = fx * pc.x / zc + cx, v = cy - fy * pc.y / zc (pixel centres at integers: no half-pixel shift).
+ *   3. iu = floor(u + 0.5), jv = floor(v + 0.5); skipped outside [0, W) x [0, H).
+ *   4. d = depth[jv * W + iu]; skipped if d is not finite or d <= 0, or if the view has an opacity map and its pixel is not
+ *      >= min_opacity (a NaN opacity is skipped).
+ *   5. r = |p - c|, sdf = d - r; skipped if sdf < -trunc (behind the band; a NaN is skipped too).
+ *   6. val = min(1, sdf / trunc); w = 1 (weight_mode 0) or the pixel's opacity (weight_mode 1, which needs the map of every
+ *      view; skipped unless w > 0);  Wn = W + w;  tsdf += (val - tsdf) * (w / Wn);  W = Wn.
+ *   7. if the volume and the view both have colour and sdf <= trunc:  Cn = C + w;  rgb += (pixel - rgb) * (w / Cn);  C = Cn.
+ * A voxel's accumulators stay in registers over the views of a launch and each step rounds to fp32 exactly as a store would,
+ * so folding a list of views in one launch or in any split into consecutive launches gives the same bits.
+ * UPNERF_EINVAL: null `tsdf` / `weight` / `depth`, `rgb` without `rgb_weight`, n_views outside [1, UPNERF_TSDF_MAX_VIEWS],
+ * trunc not > 0 or not finite, a NaN min_opacity, weight_mode outside {0, 1} or 1 with a view that has no opacity map, an axis
+ * < 2, Nx Ny Nz beyond int32, bounds that are not finite with hi > lo, a view with W or H < 1 or W H beyond int32. */
+#define UPNERF_TSDF_MAX_VIEWS 8
+typedef struct {
+  float c2w[12];             /* row-major 3 x 4 camera-to-world */
+  float fx, fy, cx, cy;
+  int32_t W, H;
+  const float* depth;        /* [H*W] */
+  const float* opacity;      /* [H*W] or NULL */
+  const float* rgb;          /* [H*W][3] or NULL */
+} upnerf_tsdf_view;
+typedef struct {
+  int32_t Nx, Ny, Nz, n_views;
+  float lo[3], hi[3];
+  float trunc, min_opacity;
+  int32_t weight_mode, reserved_;
+  float* tsdf;               /* [Nz][Ny][Nx] */
+  float* weight;             /* [Nz][Ny][Nx] */
+  float* rgb;                /* [Nz][Ny][Nx][3] or NULL */
+  float* rgb_weight;         /* [Nz][Ny][Nx], with rgb */
+  upnerf_tsdf_view views[UPNERF_TSDF_MAX_VIEWS];
+} upnerf_tsdf_integrate_args;
+int upnerf_tsdf_integrate(const upnerf_tsdf_integrate_args* a, void* stream);
+
+/* upnerf_tsdf_surface: the grid upnerf_mtet_* meshes at level 0 with UPNERF_MTET_SKIP_NONFINITE:  out[i] = -tsdf[i] where
+ * weight[i] >= min_weight -- positive behind the surface, so the mesher's normals (towards lower values) point at the cameras --
+ * and NaN elsewhere (a NaN weight included).  n in [1, 2^31). */
+typedef struct {
+  int64_t n;
+  float min_weight;
+  int32_t reserved_;
+  const float* tsdf;         /* [n] */
+  const float* weight;       /* [n] */
+  float* out;                /* [n] */
+} upnerf_tsdf_surface_args;
+int upnerf_tsdf_surface(const upnerf_tsdf_surface_args* a, void* stream);
+
+/* upnerf_tsdf_sample: the colour volume at V points, trilinear and weight-aware.  Per axis g = (p - lo) / (hi - lo) * (N - 1)
+ * clamped to [0, N - 1], i = min(floor(g), N - 2), f = g - i (fp32); a corner counts with its trilinear weight if its
+ * rgb_weight is > 0 and with 0 otherwise, and the result is the weighted sum over the sum of the weights that count: corners
+ * without colour are left out and the rest renormalised.  (0.5, 0.5, 0.5) where that sum is not > 0; a point with a NaN in it
+ * gives that grey as well.  V >= 1, sizes as for upnerf_tsdf_integrate. */
+typedef struct {
+  int32_t Nx, Ny, Nz, V;
+  float lo[3], hi[3];
+  const float* rgb;          /* [Nz][Ny][Nx][3] */
+  const float* rgb_weight;   /* [Nz][Ny][Nx] */
+  const float* points;       /* [V][3] */
+  float* out;                /* [V][3] */
+} upnerf_tsdf_sample_args;
+int upnerf_tsdf_sample(const upnerf_tsdf_sample_args* a, void* stream);
 
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase

@@ -281,7 +281,33 @@ class MtetTables(C.Structure):
 class MtetArgs(C.Structure):
     _fields_ = [("Nx", C.c_int32), ("Ny", C.c_int32), ("Nz", C.c_int32), ("level", C.c_float), ("lo", C.c_float * 3),
                 ("hi", C.c_float * 3), ("grid", _fp), ("tab", MtetTables), ("n_vertices", C.c_int32), ("n_faces", C.c_int32),
-                ("cap_vertices", C.c_int32), ("cap_faces", C.c_int32), ("vertices", _fp), ("normals", _fp), ("faces", _fp)]
+                ("cap_vertices", C.c_int32), ("cap_faces", C.c_int32), ("vertices", _fp), ("normals", _fp), ("faces", _fp),
+                ("flags", C.c_int32), ("reserved2_", C.c_int32)]
+
+
+MTET_SKIP_NONFINITE = 1  # UPNERF_MTET_SKIP_NONFINITE
+TSDF_MAX_VIEWS = 8       # UPNERF_TSDF_MAX_VIEWS
+
+
+class TsdfView(C.Structure):
+    _fields_ = [("c2w", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("W", C.c_int32), ("H", C.c_int32), ("depth", _fp), ("opacity", _fp), ("rgb", _fp)]
+
+
+class TsdfIntegrateArgs(C.Structure):
+    _fields_ = [("Nx", C.c_int32), ("Ny", C.c_int32), ("Nz", C.c_int32), ("n_views", C.c_int32), ("lo", C.c_float * 3),
+                ("hi", C.c_float * 3), ("trunc", C.c_float), ("min_opacity", C.c_float), ("weight_mode", C.c_int32),
+                ("reserved_", C.c_int32), ("tsdf", _fp), ("weight", _fp), ("rgb", _fp), ("rgb_weight", _fp),
+                ("views", TsdfView * TSDF_MAX_VIEWS)]
+
+
+class TsdfSurfaceArgs(C.Structure):
+    _fields_ = [("n", C.c_int64), ("min_weight", C.c_float), ("reserved_", C.c_int32), ("tsdf", _fp), ("weight", _fp), ("out", _fp)]
+
+
+class TsdfSampleArgs(C.Structure):
+    _fields_ = [("Nx", C.c_int32), ("Ny", C.c_int32), ("Nz", C.c_int32), ("V", C.c_int32), ("lo", C.c_float * 3),
+                ("hi", C.c_float * 3), ("rgb", _fp), ("rgb_weight", _fp), ("points", _fp), ("out", _fp)]
 
 
 class OccBuildArgs(C.Structure):
@@ -405,6 +431,9 @@ _SIGNATURES = {
     "upnerf_density_grad": [C.POINTER(Layout), C.POINTER(DensityGradArgs), _p],
     "upnerf_normal_composite": [C.POINTER(NormalCompositeArgs), _p],
     "upnerf_viz_normals": [C.POINTER(VizNormalsArgs), _p],
+    "upnerf_tsdf_integrate": [C.POINTER(TsdfIntegrateArgs), _p],
+    "upnerf_tsdf_surface": [C.POINTER(TsdfSurfaceArgs), _p],
+    "upnerf_tsdf_sample": [C.POINTER(TsdfSampleArgs), _p],
 }
 _LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
              "upnerf_occ_compact_scratch")

@@ -10,26 +10,19 @@
 //                        sums, as many levels as the size needs, no atomics: the same bits every run).
 //   upnerf_mtet_emit     vertices (position on the edge, normal = -grad sigma interpolated the same way) in (point, edge slot)
 //                        order and triangles in (cell, tetrahedron, triangle) order, indexing the vertices through the scan.
+// With UPNERF_MTET_SKIP_NONFINITE (a grid with samples nobody observed: tsdf.hip) an edge is crossed only between two finite
+// samples and a tetrahedron is triangulated only if its four corners are finite; without it a non-finite sample is "outside".
 // The case tables are not here: the caller hands them over (upnerf_mtet_tables; upnerf_amd/geometry.py defines them once) and the
 // host derives from them what the kernels look up.  Everything is streaming and memory-bound: 1 + 7 cached reads per point in the
 // counting pass, 10 B of scratch per point, one thread per point in every kernel, no LDS beyond the scan and the tables.
 #include "common.cuh"
+#include "grid.cuh"
 #include "scan.cuh"
 
 #include <limits.h>
 #include <math.h>
 
 namespace {
-
-// coordinate i of n evenly spaced grid coordinates over [lo, hi]: fp64 from the fp32 bounds, every operation rounded on its
-// own (no fma), so that numpy's lo + i * ((hi - lo) / (n - 1)) in float64 gives the same bits
-__device__ __forceinline__ double grid_coord(float lo, float hi, int n, int i) {
-#pragma clang fp contract(off)
-  if (n < 2) return (double)lo;
-  const double step = ((double)hi - (double)lo) / (double)(n - 1);
-  const double p = (double)i * step;
-  return (double)lo + p;
-}
 
 // ---- column rays ----------------------------------------------------------------------------------------------------
 
@@ -128,32 +121,50 @@ __device__ __forceinline__ int corner_bits(const float* grid, const Dims& d, int
   return bits;
 }
 
+// bit c = corner c of the cell at (x, y, z) is a finite sample; corners beyond the grid read as not finite (and are never used)
+__device__ __forceinline__ int finite_bits(const float* grid, const Dims& d, int x, int y, int z) {
+  int bits = 0;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const int cx = x + (c & 1), cy = y + ((c >> 1) & 1), cz = z + (c >> 2);
+    if (cx < d.Nx && cy < d.Ny && cz < d.Nz && isfinite(grid[((int64_t)cz * d.Ny + cy) * d.Nx + cx])) bits |= 1 << c;
+  }
+  return bits;
+}
+
 // ---- pass 1: crossed edges per point, triangles per cell -------------------------------------------------------------------
 
+// skip: UPNERF_MTET_SKIP_NONFINITE -- an edge needs both ends finite, a tetrahedron all four corners (fin = every bit set
+// otherwise: the conditions below are then the ones without the flag)
 __global__ __launch_bounds__(NTHREADS) void mtet_flags_kernel(const float* grid, Dims d, float level, MtetLut lut, uint8_t* emask,
-                                                               uint8_t* tcount) {
+                                                               uint8_t* tcount, int skip) {
   __shared__ MtetLut sh;
   const MtetLut* L = stage_lut(lut, &sh);
   const int64_t g = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
   if (g >= d.N) return;
   const int x = (int)(g % d.Nx), y = (int)((g / d.Nx) % d.Ny), z = (int)(g / ((int64_t)d.Nx * d.Ny));
   const int bits = corner_bits(grid, d, x, y, z, level);
+  const int fin = skip ? finite_bits(grid, d, x, y, z) : 0xff;
   const int me = bits & 1;
   int mask = 0;
 #pragma unroll
   for (int s = 0; s < 7; ++s) {
     const int ox = L->off[s][0], oy = L->off[s][1], oz = L->off[s][2];
-    if (x + ox < d.Nx && y + oy < d.Ny && z + oz < d.Nz && ((bits >> (ox | (oy << 1) | (oz << 2))) & 1) != me) mask |= 1 << s;
+    const int far = ox | (oy << 1) | (oz << 2);
+    if (x + ox < d.Nx && y + oy < d.Ny && z + oz < d.Nz && ((bits >> far) & 1) != me && (fin & 1) && ((fin >> far) & 1)) mask |= 1 << s;
   }
   emask[g] = (uint8_t)mask;
   int nt = 0;
   if (x + 1 < d.Nx && y + 1 < d.Ny && z + 1 < d.Nz) {
 #pragma unroll
     for (int t = 0; t < 6; ++t) {
-      int cs = 0;
+      int cs = 0, ok = 1;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) cs |= ((bits >> L->corner[t][i]) & 1) << i;
-      nt += L->tris[cs][0];
+      for (int i = 0; i < 4; ++i) {
+        cs |= ((bits >> L->corner[t][i]) & 1) << i;
+        ok &= fin >> L->corner[t][i];
+      }
+      nt += ok ? L->tris[cs][0] : 0;
     }
   }
   tcount[g] = (uint8_t)nt;
@@ -279,12 +290,16 @@ __global__ __launch_bounds__(NTHREADS) void mtet_faces_kernel(upnerf_mtet_args a
   const int x = (int)(g % d.Nx), y = (int)((g / d.Nx) % d.Ny), z = (int)(g / ((int64_t)d.Nx * d.Ny));
   const int64_t sy = d.Nx, sz = (int64_t)d.Nx * d.Ny;
   const int bits = corner_bits(a.grid, d, x, y, z, a.level);
+  const int fin = (a.flags & UPNERF_MTET_SKIP_NONFINITE) ? finite_bits(a.grid, d, x, y, z) : 0xff;
   int64_t f = tscan[g];
   for (int t = 0; t < 6; ++t) {
-    int cs = 0;
+    int cs = 0, ok = 1;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) cs |= ((bits >> L->corner[t][i]) & 1) << i;
-    const int nt = L->tris[cs][0];
+    for (int i = 0; i < 4; ++i) {
+      cs |= ((bits >> L->corner[t][i]) & 1) << i;
+      ok &= fin >> L->corner[t][i];
+    }
+    const int nt = ok ? L->tris[cs][0] : 0;  // (the count of pass 1, tetrahedron by tetrahedron)
     for (int k = 0; k < nt; ++k, ++f) {
       if (f >= a.cap_faces) continue;
 #pragma unroll
@@ -322,11 +337,12 @@ extern "C" int upnerf_mtet_count(const upnerf_mtet_args* a, void* scratch, int32
   Dims d;
   MtetLut lut;
   if (!a || !dims_ok(a->Nx, a->Ny, a->Nz, &d) || !a->grid || !scratch || !totals || ((uintptr_t)scratch & 15)) return UPNERF_EINVAL;
-  if (a->level != a->level || !build_lut(a->tab, &lut)) return UPNERF_EINVAL;
+  if (a->level != a->level || !build_lut(a->tab, &lut) || (a->flags & ~UPNERF_MTET_SKIP_NONFINITE)) return UPNERF_EINVAL;
   const Scratch s = carve(scratch, d.N);
   hipStream_t st = (hipStream_t)stream;
   const unsigned nb = (unsigned)ceil_div64(d.N, NTHREADS);
-  hipLaunchKernelGGL(mtet_flags_kernel, dim3(nb), dim3(NTHREADS), 0, st, a->grid, d, a->level, lut, s.emask, s.tcount);
+  hipLaunchKernelGGL(mtet_flags_kernel, dim3(nb), dim3(NTHREADS), 0, st, a->grid, d, a->level, lut, s.emask, s.tcount,
+                     a->flags & UPNERF_MTET_SKIP_NONFINITE);
   scan_exclusive<uint8_t, true>(s.emask, d.N, s.vscan, s.levels, totals, st);      // (the levels are free again after each scan:
   scan_exclusive<uint8_t, false>(s.tcount, d.N, s.tscan, s.levels, totals + 1, st);  //  stream order)
   return (int)hipGetLastError();
@@ -336,7 +352,7 @@ extern "C" int upnerf_mtet_emit(const upnerf_mtet_args* a, const void* scratch, 
   Dims d;
   MtetLut lut;
   if (!a || !dims_ok(a->Nx, a->Ny, a->Nz, &d) || !a->grid || !scratch || ((uintptr_t)scratch & 15)) return UPNERF_EINVAL;
-  if (a->level != a->level || !build_lut(a->tab, &lut) || !bounds_ok(a)) return UPNERF_EINVAL;
+  if (a->level != a->level || !build_lut(a->tab, &lut) || !bounds_ok(a) || (a->flags & ~UPNERF_MTET_SKIP_NONFINITE)) return UPNERF_EINVAL;
   if (a->n_vertices < 0 || a->n_faces < 0 || a->n_vertices > 7 * d.N) return UPNERF_EINVAL;
   if (a->cap_vertices < a->n_vertices || a->cap_faces < a->n_faces) return UPNERF_EINVAL;  // nothing is written, not a part
   if (a->n_vertices > 0 && (!a->vertices || !a->normals)) return UPNERF_EINVAL;

@@ -9,7 +9,14 @@
 The density pass runs the field kernels the training step runs (`upnerf_field_fwd*`, density head only) on rays that ARE grid
 columns (`upnerf_grid_columns`); the surface is marching tetrahedra on the Kuhn split of every cell, in HIP
 (`upnerf_mtet_count` / `upnerf_mtet_emit`, csrc/mesh.hip).  There is no CPU path for either.  The case tables
-live HERE and are handed to the kernels; PLY files and camera bounds are plain host code."""
+live HERE and are handed to the kernels; PLY files and camera bounds are plain host code.
+
+A surface without a density threshold: the depth maps the model renders from its refined training poses, fused into a
+truncated signed distance volume whose zero level is meshed (csrc/tsdf.hip):
+
+    vol = fuse_views(system, bounds, (256, 256, 256))
+    mesh = vol.extract()           # vertices, normals towards the cameras, faces and the fused colours
+"""
 from __future__ import annotations
 
 import ctypes as C
@@ -24,7 +31,7 @@ from ._lib import check, lib, ptr, stream
 from .ops import TIMER
 
 __all__ = ["TETS", "EDGES", "TET_EDGES", "TRI_TABLE", "edge_owner", "Mesh", "read_ply", "density_grid", "grid_columns",
-           "extract_surface", "colour_vertices", "bounds_from_cameras", "refine_normals"]
+           "extract_surface", "colour_vertices", "bounds_from_cameras", "refine_normals", "TsdfVolume", "fuse_views"]
 
 # ---- the tables of the split (the only copy: the kernels receive them as an argument) ---------------------------------------
 # Corner c of a cell is its origin + (c & 1, (c >> 1) & 1, c >> 2).  The Kuhn split: one tetrahedron per order in which the
@@ -164,6 +171,23 @@ def read_ply(path: str) -> Mesh:
 
 # ---- camera bounds (host code) --------------------------------------------------------------------------------------------------
 
+def _refined_training_poses(system, otherwise: str) -> torch.Tensor:
+    """[N, 3, 4] refined camera-to-world poses of all training images: the dataset's poses composed with the trained se(3) rows
+    (pose_align.refined_poses, the HIP pose kernel).  otherwise: what the caller can do instead, for the error message."""
+    from .novel_view import _per_image
+    from .pose_align import refined_poses
+    ds = system.train_dataset
+    w = system.se3_refine.weight.detach()
+    N = w.shape[0]
+    if getattr(ds, "poses_dict", None) is not None:
+        raw = [torch.as_tensor(np.asarray(_per_image(ds, "poses_dict", i)), dtype=torch.float32) for i in range(N)]
+    elif getattr(ds, "poses", None) is not None:
+        raw = [torch.as_tensor(np.asarray(ds.poses[i]), dtype=torch.float32) for i in range(N)]
+    else:
+        raise ValueError(f"the training dataset carries no poses (poses_dict / poses): {otherwise}")
+    return refined_poses(w, torch.stack([p.reshape(-1, 4)[:3] for p in raw]))
+
+
 def bounds_from_cameras(system, margin: float, poses=None):
     """((x0, y0, z0), (x1, y1, z1)): the box round the refined training camera centres and the points at `far` on their optical
     axes (a camera looks down its -z axis: centre - far * R[:, 2]), grown by `margin` on every side.
@@ -173,16 +197,7 @@ def bounds_from_cameras(system, margin: float, poses=None):
     from .novel_view import _per_image
     ds, hp = system.train_dataset, system.hparams
     if poses is None:
-        from .pose_align import refined_poses
-        w = system.se3_refine.weight.detach()
-        N = w.shape[0]
-        if getattr(ds, "poses_dict", None) is not None:
-            raw = [torch.as_tensor(np.asarray(_per_image(ds, "poses_dict", i)), dtype=torch.float32) for i in range(N)]
-        elif getattr(ds, "poses", None) is not None:
-            raw = [torch.as_tensor(np.asarray(ds.poses[i]), dtype=torch.float32) for i in range(N)]
-        else:
-            raise ValueError("the training dataset carries no poses (poses_dict / poses): pass bounds yourself")
-        poses = refined_poses(w, torch.stack([p.reshape(-1, 4)[:3] for p in raw]))
+        poses = _refined_training_poses(system, "pass bounds yourself")
     c2w = np.asarray(torch.as_tensor(poses).detach().cpu(), dtype=np.float64).reshape(-1, 3, 4)
     fars = []
     for i in range(c2w.shape[0]):
@@ -278,11 +293,15 @@ def density_grid(system, bounds, resolution: Sequence[int], field: str = "fine",
 # ---- iso-surface ---------------------------------------------------------------------------------------------------------------
 
 @torch.no_grad()
-def extract_surface(grid: torch.Tensor, bounds, level: float) -> Mesh:
+def extract_surface(grid: torch.Tensor, bounds, level: float, observed_only: bool = False) -> Mesh:
     """The surface `grid == level` of a [Nz, Ny, Nx] fp32 device tensor over `bounds` as a Mesh on the device: marching
     tetrahedra (csrc/mesh.hip), inside = finite and >= level, normals = -gradient (towards lower values), faces wound to match.
     Vertices come in (grid point, edge slot) order and faces in (cell, tetrahedron, triangle) order: the same grid gives the
-    same mesh, bit for bit.  `level` has no default: the useful threshold depends on the scene's scale."""
+    same mesh, bit for bit.  `level` has no default: the useful threshold depends on the scene's scale.
+
+    observed_only: a non-finite sample means "nobody looked here", not "outside" (UPNERF_MTET_SKIP_NONFINITE): an edge is
+    crossed only between two finite samples and a tetrahedron is triangulated only if its four corners are finite, so no wall
+    is built where observed samples meet unobserved ones (TsdfVolume.extract).  A vertex may remain that no face uses."""
     if not (torch.is_tensor(grid) and grid.is_cuda):
         raise RuntimeError("extract_surface runs on the GPU only: the grid must be a device tensor (no CPU fallback)")
     if grid.dtype != torch.float32 or grid.dim() != 3:
@@ -297,7 +316,7 @@ def extract_surface(grid: torch.Tensor, bounds, level: float) -> Mesh:
     scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
     totals = torch.empty(2, device=dev, dtype=torch.int32)
     a = _lib.MtetArgs(Nx=Nx, Ny=Ny, Nz=Nz, level=float(level), lo=(C.c_float * 3)(*lo), hi=(C.c_float * 3)(*hi), grid=ptr(grid),
-                      tab=_tables())
+                      tab=_tables(), flags=_lib.MTET_SKIP_NONFINITE if observed_only else 0)
     check(TIMER.run("mtet_count", lambda: lib.upnerf_mtet_count(C.byref(a), ptr(scratch), ptr(totals), st), units=grid.numel()),
           "upnerf_mtet_count")
     V, F = (int(x) for x in totals.cpu())  # the one host read: the mesh is allocated exactly
@@ -373,3 +392,220 @@ def colour_vertices(system, mesh: Mesh, img_id: int, slab: float, chunk: Optiona
                           encode_feat=hp["nerf.feat_dim"] > 0, validation=True, embed_rows={k: v[:R] for k, v in rows.items()})
         out[r0:r0 + R].copy_(res[f"s_rgb_{typ}"])
     return out
+
+
+# ---- depth-map fusion: a truncated signed distance volume ------------------------------------------------------------------------
+
+WEIGHT_MODES = {"count": 0, "opacity": 1}
+
+
+def _per_view(x, n, what):
+    """`x` for each of n views: a list whose entries are arrays or sequences themselves holds one entry per view; anything else
+    (one K as a tensor, an array or (fx, fy, cx, cy); one (W, H)) is shared by all."""
+    if isinstance(x, (list, tuple)) and len(x) and (torch.is_tensor(x[0]) or isinstance(x[0], (np.ndarray, list, tuple))):
+        if len(x) != n:
+            raise ValueError(f"{what}: {len(x)} entries for {n} views")
+        return list(x)
+    return [x] * n
+
+
+def _intrinsics(K):
+    if torch.is_tensor(K) or isinstance(K, np.ndarray):
+        Km = np.asarray(torch.as_tensor(K).detach().cpu(), dtype=np.float64)
+        return float(Km[0, 0]), float(Km[1, 1]), float(Km[0, 2]), float(Km[1, 2])
+    fx, fy, cx, cy = K
+    return float(fx), float(fy), float(cx), float(cy)
+
+
+class TsdfVolume:
+    """A truncated signed distance volume on the Nx x Ny x Nz grid points of `bounds` (the grid extract_surface meshes), on the
+    device: `tsdf` [Nz, Ny, Nx] (the running mean of min(1, sdf / trunc); 1 where nothing was seen), `weight` (the summed view
+    weights, 0 = never observed) and, with colour=True, `rgb` [Nz, Ny, Nx, 3] with `rgb_weight`, a weight volume of the colour's
+    own (colour is fused only within `trunc` of the observed surface).  The arithmetic is defined in include/upnerf_hip.h
+    (upnerf_tsdf_integrate); there is no CPU path."""
+
+    def __init__(self, bounds, resolution: Sequence[int], trunc: float, colour: bool = True, device="cuda"):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("TsdfVolume lives on the GPU only (no CPU fallback)")
+        self.bounds = _bounds(bounds)
+        Nx, Ny, Nz = (int(n) for n in resolution)
+        if min(Nx, Ny, Nz) < 2:
+            raise ValueError(f"resolution is the number of grid points per axis (two at least), got {tuple(resolution)}")
+        self.resolution = (Nx, Ny, Nz)
+        self.trunc = float(trunc)
+        if not (self.trunc > 0 and np.isfinite(self.trunc)):
+            raise ValueError(f"trunc must be positive and finite, got {trunc}")
+        self.tsdf = torch.ones(Nz, Ny, Nx, device=dev, dtype=torch.float32)
+        self.weight = torch.zeros(Nz, Ny, Nx, device=dev, dtype=torch.float32)
+        self.rgb = torch.zeros(Nz, Ny, Nx, 3, device=dev, dtype=torch.float32) if colour else None
+        self.rgb_weight = torch.zeros(Nz, Ny, Nx, device=dev, dtype=torch.float32) if colour else None
+        self.n_views = 0
+
+    @torch.no_grad()
+    def integrate(self, depth, c2w, K, img_wh, rgb=None, opacity=None, min_opacity: float = 0.5, weight_mode: str = "count") -> None:
+        """Fold one view or a list of views into the volume, in order, _lib.TSDF_MAX_VIEWS per launch (the result does not
+        depend on how the list is cut).  depth: [H * W] (or [H, W]) fp32 device tensor of distances along unit rays, or a list
+        of them; c2w: [3, 4] or [n, 3, 4] (or a list); K: 3 x 3 or (fx, fy, cx, cy), img_wh = (W, H): one for all views or a
+        list; rgb [H * W, 3] and opacity [H * W] per view, optional.  A pixel whose opacity is below `min_opacity` is not a
+        measurement; weight_mode "count": a view counts 1, "opacity": its pixel's opacity (needs the maps)."""
+        if weight_mode not in WEIGHT_MODES:
+            raise ValueError(f"weight_mode is one of {tuple(WEIGHT_MODES)}, got {weight_mode!r}")
+        depths = list(depth) if isinstance(depth, (list, tuple)) else [depth]
+        n = len(depths)
+        if n < 1:
+            raise ValueError("no view to integrate")
+        poses = torch.as_tensor(c2w) if not isinstance(c2w, (list, tuple)) else torch.stack([torch.as_tensor(p) for p in c2w])
+        poses = poses.detach().to(dtype=torch.float32).cpu().reshape(-1, 3, 4)
+        if poses.shape[0] != n:
+            raise ValueError(f"c2w: {poses.shape[0]} poses for {n} views")
+        Ks, whs = _per_view(K, n, "K"), _per_view(img_wh, n, "img_wh")
+        rgbs = list(rgb) if isinstance(rgb, (list, tuple)) else [rgb] * n
+        ops = list(opacity) if isinstance(opacity, (list, tuple)) else [opacity] * n
+        if len(rgbs) != n or len(ops) != n:
+            raise ValueError("rgb and opacity hold one map per view")
+        dev = self.tsdf.device
+        views, keep = [], []
+        for i in range(n):
+            W, H = int(whs[i][0]), int(whs[i][1])
+            maps = []
+            for name, t, width in (("depth", depths[i], 1), ("opacity", ops[i], 1), ("rgb", rgbs[i], 3)):
+                if t is None:
+                    maps.append(None)
+                    continue
+                if not (torch.is_tensor(t) and t.is_cuda):
+                    raise RuntimeError(f"TsdfVolume.integrate runs on the GPU only: {name} must be a device tensor (no CPU fallback)")
+                if t.dtype != torch.float32 or t.numel() != H * W * width or t.device != dev:
+                    raise ValueError(f"{name} of view {i} is a fp32 tensor of {H} x {W}{' x 3' if width == 3 else ''} values on {dev}")
+                maps.append(t.detach().contiguous())
+            keep.append(maps)
+            fx, fy, cx, cy = _intrinsics(Ks[i])
+            views.append(_lib.TsdfView(c2w=(C.c_float * 12)(*poses[i].reshape(-1).tolist()), fx=fx, fy=fy, cx=cx, cy=cy, W=W, H=H,
+                                       depth=ptr(maps[0]), opacity=ptr(maps[1]), rgb=ptr(maps[2])))
+        Nx, Ny, Nz = self.resolution
+        lo, hi = self.bounds
+        for v0 in range(0, n, _lib.TSDF_MAX_VIEWS):
+            batch = views[v0:v0 + _lib.TSDF_MAX_VIEWS]
+            a = _lib.TsdfIntegrateArgs(Nx=Nx, Ny=Ny, Nz=Nz, n_views=len(batch), lo=(C.c_float * 3)(*lo), hi=(C.c_float * 3)(*hi),
+                                       trunc=self.trunc, min_opacity=float(min_opacity), weight_mode=WEIGHT_MODES[weight_mode],
+                                       tsdf=ptr(self.tsdf), weight=ptr(self.weight), rgb=ptr(self.rgb), rgb_weight=ptr(self.rgb_weight))
+            for j, v in enumerate(batch):
+                a.views[j] = v
+            check(TIMER.run("tsdf_integrate", lambda: lib.upnerf_tsdf_integrate(C.byref(a), stream()), units=self.tsdf.numel()),
+                  "upnerf_tsdf_integrate")
+        self.n_views += n
+
+    @torch.no_grad()
+    def surface_grid(self, min_weight: float = 1.0) -> torch.Tensor:
+        """[Nz, Ny, Nx]: -tsdf where weight >= min_weight (positive behind the surface), NaN where too few views looked: what
+        extract_surface(..., 0.0, observed_only=True) meshes (upnerf_tsdf_surface)."""
+        out = torch.empty_like(self.tsdf)
+        a = _lib.TsdfSurfaceArgs(n=self.tsdf.numel(), min_weight=float(min_weight), tsdf=ptr(self.tsdf), weight=ptr(self.weight),
+                                 out=ptr(out))
+        check(lib.upnerf_tsdf_surface(C.byref(a), stream()), "upnerf_tsdf_surface")
+        return out
+
+    @torch.no_grad()
+    def sample_colour(self, points: torch.Tensor) -> torch.Tensor:
+        """[V, 3] fused colour at `points` [V, 3]: trilinear over the corners that have a colour, mid-grey where none has
+        (upnerf_tsdf_sample)."""
+        if self.rgb is None:
+            raise ValueError("this volume was built with colour=False")
+        if not (torch.is_tensor(points) and points.is_cuda):
+            raise RuntimeError("TsdfVolume.sample_colour runs on the GPU only: points must be a device tensor (no CPU fallback)")
+        pts = points.detach().to(torch.float32).reshape(-1, 3).contiguous()
+        V = pts.shape[0]
+        out = torch.empty(V, 3, device=pts.device, dtype=torch.float32)
+        if V == 0:
+            return out
+        Nx, Ny, Nz = self.resolution
+        lo, hi = self.bounds
+        a = _lib.TsdfSampleArgs(Nx=Nx, Ny=Ny, Nz=Nz, V=V, lo=(C.c_float * 3)(*lo), hi=(C.c_float * 3)(*hi), rgb=ptr(self.rgb),
+                                rgb_weight=ptr(self.rgb_weight), points=ptr(pts), out=ptr(out))
+        check(lib.upnerf_tsdf_sample(C.byref(a), stream()), "upnerf_tsdf_sample")
+        return out
+
+    def extract(self, min_weight: float = 1.0) -> Mesh:
+        """The zero level of the fused distance as a Mesh: surface_grid, then extract_surface(..., 0.0, observed_only=True), so
+        the normals point at the cameras and nothing is built where no view looked; colours from the fused colour volume."""
+        mesh = extract_surface(self.surface_grid(min_weight), self.bounds, 0.0, observed_only=True)
+        if self.rgb is not None:
+            mesh.colours = self.sample_colour(mesh.vertices)
+        return mesh
+
+
+@torch.no_grad()
+def fuse_views(system, bounds, resolution: Sequence[int], img_ids: Optional[Sequence[int]] = None, trunc: Optional[float] = None,
+               downscale: int = 1, chunk: Optional[int] = None, min_opacity: float = 0.5) -> TsdfVolume:
+    """A TsdfVolume of the scene as its training cameras see it.  For every training image of `img_ids` (default: all): the
+    refined pose (as bounds_from_cameras obtains it), the rays of the whole frame at 1 / `downscale` of its size
+    (novel_view.path_rays, the dataset's Ks, all_imgs_wh, nears and fars), rendered by the public render_rays as
+    colour_vertices renders (sched_mult = 1, validation's sample counts, the image's own appearance row as `embed_rows`),
+    `chunk` rays at a time (default val.chunk_size); depth = `s_depth_*`, colour = `s_rgb_*`, opacity = the row sum of
+    `s_weights_*`; then TsdfVolume.integrate, a launch per TSDF_MAX_VIEWS views.  trunc: default 3 voxel diagonals.
+    Raises while the candidate schedule has not started (sched_mult == 0), as render_path does."""
+    from .novel_view import _per_image, path_rays
+    from .rendering import render_rays
+    hp, ds = system.hparams, system.train_dataset
+    if system.get_schedule_mult(system._host_progress) == 0:
+        raise ValueError("fuse_views renders the static depth and colour s_depth_* / s_rgb_*, which do not exist while the "
+                         "candidate schedule has not started (sched_mult == 0): this checkpoint is too early in training")
+    dev = next(system.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError("fuse_views runs on the GPU only (no CPU fallback)")
+    lo, hi = _bounds(bounds)
+    res = tuple(int(n) for n in resolution)
+    if trunc is None:
+        trunc = 3.0 * sum(((h - l) / max(n - 1, 1)) ** 2 for l, h, n in zip(lo, hi, res)) ** 0.5
+    downscale, chunk = int(downscale), int(chunk or hp["val.chunk_size"])
+    if downscale < 1 or chunk < 1:
+        raise ValueError("downscale and chunk are positive")
+    poses = _refined_training_poses(system, "integrate views of your own into a TsdfVolume").to(dev)
+    N = poses.shape[0]
+    ids = list(range(N)) if img_ids is None else [int(i) for i in img_ids]
+    if not ids or min(ids) < 0 or max(ids) >= N:
+        raise ValueError(f"img_ids must be training image indices in [0, {N})")
+    if getattr(ds, "Ks", None) is None or getattr(ds, "all_imgs_wh", None) is None:
+        raise ValueError("the dataset carries no intrinsics / image sizes (Ks, all_imgs_wh)")
+    typ = "fine" if system.fine else "coarse"
+    keys = [k for k in system.embeddings if k.endswith("_a")]
+    vol = TsdfVolume((lo, hi), res, trunc, colour=True, device=dev)
+    white_back = getattr(ds, "white_back", False)
+    pending = []  # (depth, rgb, opacity, pose, K, wh) of the views rendered and not yet folded in
+
+    def flush():
+        if pending:
+            d, c, o, p, k, wh = zip(*pending)
+            vol.integrate(list(d), torch.stack(p), list(k), list(wh), rgb=list(c), opacity=list(o), min_opacity=min_opacity)
+            pending.clear()
+
+    for i in ids:
+        fx, fy, cx, cy = _intrinsics(np.asarray(_per_image(ds, "Ks", i), dtype=np.float64))
+        W, H = (int(x) // downscale for x in ds.all_imgs_wh[i])
+        if min(W, H) < 1:
+            raise ValueError(f"image {i} has no pixel left at downscale {downscale}")
+        intr = (fx / downscale, fy / downscale, cx / downscale, cy / downscale)
+        near, far = _per_image(ds, "nears", i), _per_image(ds, "fars", i)
+        nf = torch.tensor([[float(hp["nerf.near"]) if near is None else float(near), float(hp["nerf.far"]) if far is None else float(far)]],
+                          device=dev, dtype=torch.float32)
+        c2w = poses[i:i + 1].contiguous()
+        n = W * H
+        depth = torch.empty(n, device=dev, dtype=torch.float32)
+        rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
+        opacity = torch.empty(n, device=dev, dtype=torch.float32)
+        rows = {k: system.embeddings[k].weight.detach()[i].expand(min(chunk, n), -1).contiguous() for k in keys}
+        for r0 in range(0, n, chunk):
+            R = min(chunk, n - r0)
+            rays, _ = path_rays(c2w, nf, (W, H), intr, r0, R)
+            out = render_rays(models=system.models, embeddings=system.embeddings, rays=rays, img_idx=None, sched_mult=1, sched_phase=2,
+                              N_samples=hp["nerf.N_samples"], use_disp=hp["nerf.use_disp"], perturb=0,
+                              N_importance=hp["nerf.N_importance"], white_back=white_back, encode_feat=hp["nerf.feat_dim"] > 0,
+                              validation=True, embed_rows={k: v[:R] for k, v in rows.items()})
+            depth[r0:r0 + R].copy_(out[f"s_depth_{typ}"])
+            rgb[r0:r0 + R].copy_(out[f"s_rgb_{typ}"])
+            opacity[r0:r0 + R].copy_(out[f"s_weights_{typ}"].reshape(R, -1).sum(1))
+        pending.append((depth, rgb, opacity, poses[i], intr, (W, H)))
+        if len(pending) == _lib.TSDF_MAX_VIEWS:  # (device memory: the maps of one launch's views, not of the whole scene)
+            flush()
+    flush()
+    return vol
