@@ -368,9 +368,10 @@ def two_key_path(n_frames=3, wh=(8, 6)):
 def frame_rays_and_rows(system, path, f):
     """The rays of frame f and its blended embedding rows, as render_path makes them."""
     from upnerf_amd import novel_view as nv
+    from upnerf_amd.static_scene import static_keys
     c2w, nf = nv.path_poses(path.key_c2w.cuda(), path.key_near_far.cuda(), path.u.cuda(), path.mode)
     n = path.img_wh[0] * path.img_wh[1]
-    keys = nv._table_keys(system, system.get_schedule_mult(system._host_progress))
+    keys = static_keys(system, system.get_schedule_mult(system._host_progress))
     tables = [(system.embeddings[k].weight.detach().contiguous(), None) for k in keys]
     rays, rows = nv.path_rays(c2w, nf, path.img_wh, path.K, f * n, n, tables=tables, i0=path.i0.cuda(), i1=path.i1.cuda(),
                               t=path.t.cuda())

@@ -378,3 +378,43 @@ def test_through_images_uses_the_refined_poses_and_writes_frames(systems, tmp_pa
     from PIL import Image
     back = np.asarray(Image.open(writer.path("path", 2, "rgb")))
     assert np.array_equal(back, out["rgb"][2].cpu().numpy())
+
+
+def test_a_training_view_is_the_same_picture_by_three_routes(systems, monkeypatch):
+    """Image i seen from its own refined pose under its own appearance: frame 0 of a path through it (render_path), the colour
+    map fuse_views renders of it, and render_static on the path_rays of that pose are the same rays, rows and kernels -- bit for
+    bit, with chunks of 20 rows over 48-pixel frames (they straddle the frame boundary; the last one is partial)."""
+    from upnerf_amd import geometry
+    from upnerf_amd import static_scene as ss
+    from upnerf_amd.novel_view import CameraPath, path_rays, render_path
+    s = copy.deepcopy(systems[0.8])
+    assert s.get_schedule_mult(s._host_progress) == 1
+    g = torch.Generator().manual_seed(21)
+    ds = s.train_dataset
+    ang = torch.linspace(-0.4, 0.4, 6)
+    ds.poses = torch.zeros(6, 3, 4)
+    ds.poses[:, 0, 0] = ds.poses[:, 2, 2] = torch.cos(ang)
+    ds.poses[:, 0, 2], ds.poses[:, 2, 0], ds.poses[:, 1, 1] = torch.sin(ang), -torch.sin(ang), 1.0
+    ds.poses[:, :, 3] = torch.rand(6, 3, generator=g) * 0.2
+    ds.nears, ds.fars = [0.1 + 0.01 * k for k in range(6)], [5.0 - 0.1 * k for k in range(6)]
+    ds.Ks = [np.array([[7.5 + k, 0, 3.6], [0, 7.0 + k, 2.8], [0, 0, 1]]) for k in range(6)]
+    ds.all_imgs_wh = torch.tensor([[8, 6]] * 6)
+    with torch.no_grad():
+        s.se3_refine.weight.copy_(torch.randn(6, 6, generator=g) * 1e-2)
+    i, j, n = 4, 1, 48
+    path = CameraPath.through_images(s, [i, j], n_frames=2)
+    by_path = render_path(s, path, chunk=20, outputs=("rgb_float",))["rgb_float"][0]
+    assert tuple(by_path.shape) == (n, 3) and torch.isfinite(by_path).all() and float(by_path.std()) > 0
+    fused = []
+    integrate = geometry.TsdfVolume.integrate
+    monkeypatch.setattr(geometry.TsdfVolume, "integrate", lambda self, depth, *a, rgb=None, **kw: (fused.extend(rgb), integrate(self, depth, *a, rgb=rgb, **kw))[1])
+    geometry.fuse_views(s, ((-1.0, -1.0, -3.0), (1.0, 1.0, 0.5)), (8, 8, 8), img_ids=[i], chunk=20)
+    assert len(fused) == 1
+    pose = ss.refined_training_poses(s, [i]).cuda().contiguous()
+    nf = torch.tensor([ss.near_far(s, i)], dtype=torch.float32).cuda()
+    rays, _ = path_rays(pose, nf, (8, 6), ds.Ks[i], 0, n)
+    with torch.no_grad():
+        own = ss.render_static(s, rays, ss.appearance_rows(s, ss.static_keys(s, 1), i, n), 1)["s_rgb_fine"]
+    assert torch.equal(by_path, fused[0]) and torch.equal(by_path, own)
+    other = render_path(s, CameraPath.through_images(s, [j, i], n_frames=2), chunk=20, outputs=("rgb_float",))["rgb_float"][0]
+    assert not torch.equal(by_path, other)  # (the comparison tells two images apart)

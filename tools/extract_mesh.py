@@ -28,7 +28,7 @@ import time
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 
 def parser():
@@ -64,22 +64,9 @@ def main(argv=None):
     res = tuple(a.resolution * 3 if len(a.resolution) == 1 else a.resolution)
     if not torch.cuda.is_available():
         raise SystemExit("extract_mesh.py runs on the GPU; none is visible")
-    from upnerf_amd import checkpoint, config, geometry
-    from upnerf_amd.nerf_system import NeRFSystem, SyntheticDataset
-    ckpt = checkpoint.read_checkpoint(a.ckpt) if a.ckpt else None
-    if a.config:
-        system = NeRFSystem(config.get_from_path(a.config))
-    else:
-        if "hyper_parameters" not in ckpt:
-            raise SystemExit("the checkpoint carries no hyper-parameters: give --config")
-        if a.from_cameras is not None:
-            raise SystemExit("--from-cameras needs the dataset's poses: give --config, or --bounds")
-        sd = ckpt.get("state_dict", ckpt)
-        system = NeRFSystem(dict(ckpt["hyper_parameters"]), SyntheticDataset(sd["se3_refine.weight"].shape[0]))
-    system.setup()
-    if ckpt is not None:
-        checkpoint.load_checkpoint(system, ckpt, resume=False)
-    system.cuda()
+    from _system import load_system
+    from upnerf_amd import geometry
+    system = load_system(a.config, a.ckpt, need_dataset=a.from_cameras is not None)
     t0 = time.perf_counter()
     bounds = (geometry.bounds_from_cameras(system, a.from_cameras) if a.from_cameras is not None
               else (tuple(a.bounds[:3]), tuple(a.bounds[3:])))

@@ -23,7 +23,7 @@ import time
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 
 def parser():
@@ -59,15 +59,10 @@ def main(argv=None):
     a = check_args(parser().parse_args(argv))
     if not torch.cuda.is_available():
         raise SystemExit("render_path.py renders on the GPU; none is visible")
-    from upnerf_amd import checkpoint, config
-    from upnerf_amd.nerf_system import NeRFSystem
+    from _system import load_system
     from upnerf_amd.novel_view import CameraPath, render_path
     from upnerf_amd.visualization import ImageWriter
-    hparams = config.get_from_path(a.config)
-    system = NeRFSystem(hparams)
-    system.setup()
-    checkpoint.load_checkpoint(system, a.ckpt, resume=False)
-    system.cuda()
+    system = load_system(a.config, a.ckpt)
     path = CameraPath.through_images(system, a.images, a.frames, mode=a.mode, loop=a.loop)
     if a.downscale > 1:
         n = a.downscale

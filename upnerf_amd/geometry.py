@@ -29,6 +29,9 @@ import torch
 from . import _lib
 from ._lib import check, lib, ptr, stream
 from .ops import TIMER
+from .novel_view import path_rays
+from .static_scene import (appearance_rows, box, c_float3, field_of, intrinsics, near_far, per_image, plane, refined_training_poses,
+                           render_static, require_cuda, static_keys)
 
 __all__ = ["TETS", "EDGES", "TET_EDGES", "TRI_TABLE", "edge_owner", "Mesh", "read_ply", "density_grid", "grid_columns",
            "extract_surface", "colour_vertices", "bounds_from_cameras", "refine_normals", "TsdfVolume", "fuse_views"]
@@ -93,13 +96,6 @@ def _tables() -> "_lib.MtetTables":
             for k, e in enumerate(tri):
                 t.tris[case][1 + 3 * j + k] = e
     return t
-
-
-def _bounds(bounds):
-    lo, hi = (tuple(float(v) for v in b) for b in bounds)
-    if len(lo) != 3 or len(hi) != 3:
-        raise ValueError("bounds is ((x0, y0, z0), (x1, y1, z1))")
-    return lo, hi
 
 
 # ---- meshes and PLY files (host code) -------------------------------------------------------------------------------------------
@@ -171,38 +167,16 @@ def read_ply(path: str) -> Mesh:
 
 # ---- camera bounds (host code) --------------------------------------------------------------------------------------------------
 
-def _refined_training_poses(system, otherwise: str) -> torch.Tensor:
-    """[N, 3, 4] refined camera-to-world poses of all training images: the dataset's poses composed with the trained se(3) rows
-    (pose_align.refined_poses, the HIP pose kernel).  otherwise: what the caller can do instead, for the error message."""
-    from .novel_view import _per_image
-    from .pose_align import refined_poses
-    ds = system.train_dataset
-    w = system.se3_refine.weight.detach()
-    N = w.shape[0]
-    if getattr(ds, "poses_dict", None) is not None:
-        raw = [torch.as_tensor(np.asarray(_per_image(ds, "poses_dict", i)), dtype=torch.float32) for i in range(N)]
-    elif getattr(ds, "poses", None) is not None:
-        raw = [torch.as_tensor(np.asarray(ds.poses[i]), dtype=torch.float32) for i in range(N)]
-    else:
-        raise ValueError(f"the training dataset carries no poses (poses_dict / poses): {otherwise}")
-    return refined_poses(w, torch.stack([p.reshape(-1, 4)[:3] for p in raw]))
-
-
 def bounds_from_cameras(system, margin: float, poses=None):
     """((x0, y0, z0), (x1, y1, z1)): the box round the refined training camera centres and the points at `far` on their optical
     axes (a camera looks down its -z axis: centre - far * R[:, 2]), grown by `margin` on every side.
 
     `far` per image is the dataset's `fars` where it has them, hparams["nerf.far"] otherwise.  poses: [N, 3, 4] refined
     camera-to-world poses to use instead of refining the dataset's with the trained se(3) rows (which runs the HIP pose kernel)."""
-    from .novel_view import _per_image
-    ds, hp = system.train_dataset, system.hparams
     if poses is None:
-        poses = _refined_training_poses(system, "pass bounds yourself")
+        poses = refined_training_poses(system, otherwise="pass bounds yourself")
     c2w = np.asarray(torch.as_tensor(poses).detach().cpu(), dtype=np.float64).reshape(-1, 3, 4)
-    fars = []
-    for i in range(c2w.shape[0]):
-        f = _per_image(ds, "fars", i)
-        fars.append(float(hp["nerf.far"]) if f is None else float(f))
+    fars = [plane(system, "far", i) for i in range(c2w.shape[0])]
     centre = c2w[:, :, 3]
     ahead = centre - np.asarray(fars)[:, None] * c2w[:, :, 2]
     pts = np.concatenate([centre, ahead])
@@ -217,16 +191,15 @@ def bounds_from_cameras(system, margin: float, poses=None):
 def grid_columns(bounds, resolution: Sequence[int], col0: int, count: int, S: Optional[int] = None, device="cuda"):
     """(o [count, 3], d [count, 3], z [count, S]) of grid columns [col0, col0 + count) (upnerf_grid_columns): column y * Nx + x
     is the ray o = (x, y, 0), d = (0, 0, 1) whose depths are the z coordinates, the last one repeated up to S >= Nz."""
-    lo, hi = _bounds(bounds)
+    lo, hi = box(bounds)
     Nx, Ny, Nz = (int(n) for n in resolution)
     S = max(Nz, MIN_SAMPLES) if S is None else int(S)
     dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("libupnerf_hip operates on device memory only (grid_columns got a CPU device)")
+    require_cuda("grid_columns", dev)
     o = torch.empty(count, 3, device=dev, dtype=torch.float32)
     d = torch.empty(count, 3, device=dev, dtype=torch.float32)
     z = torch.empty(count, S, device=dev, dtype=torch.float32)
-    a = _lib.GridColumnsArgs(Nx=Nx, Ny=Ny, Nz=Nz, S=S, lo=(C.c_float * 3)(*lo), hi=(C.c_float * 3)(*hi), col0=int(col0),
+    a = _lib.GridColumnsArgs(Nx=Nx, Ny=Ny, Nz=Nz, S=S, lo=c_float3(lo), hi=c_float3(hi), col0=int(col0),
                              count=int(count), o=ptr(o), d=ptr(d), z=ptr(z))
     check(lib.upnerf_grid_columns(C.byref(a), stream()), "upnerf_grid_columns")
     return o, d, z
@@ -242,8 +215,7 @@ def _field_sigma(model, o: torch.Tensor, d: torch.Tensor, z: torch.Tensor) -> to
     P = model.packed().detach().contiguous()
     plan = rd._plan(pk, R, S)  # density only, no gradient: the tiling, and with it the rows x0 is allocated with
     PF, P16, _, wexp, wnorm = rd._weights(pk, P, plan)
-    hp = getattr(model, "host_progress", None)
-    progress = float(model.progress.data) if hp is None else float(torch.tensor(hp, dtype=torch.float32))
+    progress = model.host_progress_value()
     sigma = torch.empty(R, S, device=dev, dtype=torch.float32)
     x0 = torch.empty(plan.Mp, _lib.X0, device=dev, dtype=torch.float32)
     fa = _lib.FieldFwdArgs(R=R, S=S, use_cand=0, use_rgb=0, rays_o=ptr(o), rays_d=ptr(d), z=ptr(z),
@@ -263,15 +235,8 @@ def density_grid(system, bounds, resolution: Sequence[int], field: str = "fine",
     The grid is evaluated as rays, one per (x, y) column (grid_columns), `chunk` columns at a time (default: about a million
     samples), so device memory is the chunk's workspace and the result whatever the resolution.  The values do not depend on
     `chunk`.  Columns shorter than the field kernels' 32 samples are padded and the padding dropped."""
-    if field not in ("fine", "coarse"):
-        raise ValueError(f"field is 'fine' or 'coarse', got {field!r}")
-    model = system.models.get(f"nerf_{field}")
-    if model is None:
-        raise ValueError(f"the system has no {field} field")
-    dev = next(model.parameters()).device
-    if dev.type != "cuda":
-        raise RuntimeError("density_grid runs on the GPU only (no CPU fallback)")
-    lo, hi = _bounds(bounds)
+    model, dev = field_of(system, field, "density_grid")
+    lo, hi = box(bounds)
     Nx, Ny, Nz = (int(n) for n in resolution)
     if min(Nx, Ny, Nz) < 1:
         raise ValueError(f"resolution is the number of grid points per axis, got {tuple(resolution)}")
@@ -302,11 +267,10 @@ def extract_surface(grid: torch.Tensor, bounds, level: float, observed_only: boo
     observed_only: a non-finite sample means "nobody looked here", not "outside" (UPNERF_MTET_SKIP_NONFINITE): an edge is
     crossed only between two finite samples and a tetrahedron is triangulated only if its four corners are finite, so no wall
     is built where observed samples meet unobserved ones (TsdfVolume.extract).  A vertex may remain that no face uses."""
-    if not (torch.is_tensor(grid) and grid.is_cuda):
-        raise RuntimeError("extract_surface runs on the GPU only: the grid must be a device tensor (no CPU fallback)")
+    require_cuda("extract_surface", grid)
     if grid.dtype != torch.float32 or grid.dim() != 3:
         raise ValueError("the grid is a fp32 tensor [Nz, Ny, Nx]")
-    lo, hi = _bounds(bounds)
+    lo, hi = box(bounds)
     grid = grid.detach().contiguous()
     Nz, Ny, Nx = grid.shape
     dev, st = grid.device, stream()
@@ -315,7 +279,7 @@ def extract_surface(grid: torch.Tensor, bounds, level: float, observed_only: boo
         check(int(nbytes), f"upnerf_mtet_scratch({Nx}, {Ny}, {Nz})")
     scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
     totals = torch.empty(2, device=dev, dtype=torch.int32)
-    a = _lib.MtetArgs(Nx=Nx, Ny=Ny, Nz=Nz, level=float(level), lo=(C.c_float * 3)(*lo), hi=(C.c_float * 3)(*hi), grid=ptr(grid),
+    a = _lib.MtetArgs(Nx=Nx, Ny=Ny, Nz=Nz, level=float(level), lo=c_float3(lo), hi=c_float3(hi), grid=ptr(grid),
                       tab=_tables(), flags=_lib.MTET_SKIP_NONFINITE if observed_only else 0)
     check(TIMER.run("mtet_count", lambda: lib.upnerf_mtet_count(C.byref(a), ptr(scratch), ptr(totals), st), units=grid.numel()),
           "upnerf_mtet_count")
@@ -365,31 +329,21 @@ def colour_vertices(system, mesh: Mesh, img_id: int, slab: float, chunk: Optiona
     """[V, 3] fp32 static colour (`s_rgb_fine`; `s_rgb_coarse` without a fine field) of every vertex, rendered by the public
     render_rays along vertex_rays(mesh, slab) at sched_mult = 1 with the appearance row of training image `img_id` (passed as
     `embed_rows`, as novel_view.render_path does), `chunk` rays at a time (default val.chunk_size)."""
-    from .rendering import render_rays
-    hp = system.hparams
     dev = next(system.parameters()).device
-    if dev.type != "cuda" or not mesh.vertices.is_cuda:
-        raise RuntimeError("colour_vertices runs on the GPU only (no CPU fallback)")
+    require_cuda("colour_vertices", dev, mesh.vertices)
     typ = "fine" if system.fine else "coarse"
     rays = vertex_rays(mesh, slab)
     V = rays.shape[0]
     out = torch.empty(V, 3, device=dev, dtype=torch.float32)
-    chunk = int(chunk or hp["val.chunk_size"])
+    chunk = int(chunk or system.hparams["val.chunk_size"])
     if chunk < 1:
         raise ValueError(f"chunk must be positive, got {chunk}")
-    keys = [k for k in system.embeddings if k.endswith("_a")]
-    rows = {}
-    for k in keys:
-        w = system.embeddings[k].weight.detach()
-        if not 0 <= int(img_id) < w.shape[0]:
-            raise ValueError(f"img_id must be a training image index in [0, {w.shape[0]})")
-        rows[k] = w[int(img_id)].expand(min(chunk, max(V, 1)), -1).contiguous()
+    # No check of the system's own schedule, unlike render_path and fuse_views: the colour head is asked for at sched_mult = 1
+    # whatever the checkpoint's progress, so an early checkpoint colours its mesh (with what that head has learnt so far).
+    rows = appearance_rows(system, static_keys(system, 1), img_id, min(chunk, max(V, 1)))
     for r0 in range(0, V, chunk):
         R = min(chunk, V - r0)
-        res = render_rays(models=system.models, embeddings=system.embeddings, rays=rays[r0:r0 + R], img_idx=None, sched_mult=1,
-                          sched_phase=2, N_samples=hp["nerf.N_samples"], use_disp=hp["nerf.use_disp"], perturb=0,
-                          N_importance=hp["nerf.N_importance"], white_back=getattr(system.train_dataset, "white_back", False),
-                          encode_feat=hp["nerf.feat_dim"] > 0, validation=True, embed_rows={k: v[:R] for k, v in rows.items()})
+        res = render_static(system, rays[r0:r0 + R], {k: v[:R] for k, v in rows.items()}, 1)
         out[r0:r0 + R].copy_(res[f"s_rgb_{typ}"])
     return out
 
@@ -409,14 +363,6 @@ def _per_view(x, n, what):
     return [x] * n
 
 
-def _intrinsics(K):
-    if torch.is_tensor(K) or isinstance(K, np.ndarray):
-        Km = np.asarray(torch.as_tensor(K).detach().cpu(), dtype=np.float64)
-        return float(Km[0, 0]), float(Km[1, 1]), float(Km[0, 2]), float(Km[1, 2])
-    fx, fy, cx, cy = K
-    return float(fx), float(fy), float(cx), float(cy)
-
-
 class TsdfVolume:
     """A truncated signed distance volume on the Nx x Ny x Nz grid points of `bounds` (the grid extract_surface meshes), on the
     device: `tsdf` [Nz, Ny, Nx] (the running mean of min(1, sdf / trunc); 1 where nothing was seen), `weight` (the summed view
@@ -426,9 +372,8 @@ class TsdfVolume:
 
     def __init__(self, bounds, resolution: Sequence[int], trunc: float, colour: bool = True, device="cuda"):
         dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("TsdfVolume lives on the GPU only (no CPU fallback)")
-        self.bounds = _bounds(bounds)
+        require_cuda("TsdfVolume", dev)
+        self.bounds = box(bounds)
         Nx, Ny, Nz = (int(n) for n in resolution)
         if min(Nx, Ny, Nz) < 2:
             raise ValueError(f"resolution is the number of grid points per axis (two at least), got {tuple(resolution)}")
@@ -473,20 +418,19 @@ class TsdfVolume:
                 if t is None:
                     maps.append(None)
                     continue
-                if not (torch.is_tensor(t) and t.is_cuda):
-                    raise RuntimeError(f"TsdfVolume.integrate runs on the GPU only: {name} must be a device tensor (no CPU fallback)")
+                require_cuda(f"TsdfVolume.integrate: {name}", t)
                 if t.dtype != torch.float32 or t.numel() != H * W * width or t.device != dev:
                     raise ValueError(f"{name} of view {i} is a fp32 tensor of {H} x {W}{' x 3' if width == 3 else ''} values on {dev}")
                 maps.append(t.detach().contiguous())
             keep.append(maps)
-            fx, fy, cx, cy = _intrinsics(Ks[i])
+            fx, fy, cx, cy = intrinsics(Ks[i])
             views.append(_lib.TsdfView(c2w=(C.c_float * 12)(*poses[i].reshape(-1).tolist()), fx=fx, fy=fy, cx=cx, cy=cy, W=W, H=H,
                                        depth=ptr(maps[0]), opacity=ptr(maps[1]), rgb=ptr(maps[2])))
         Nx, Ny, Nz = self.resolution
         lo, hi = self.bounds
         for v0 in range(0, n, _lib.TSDF_MAX_VIEWS):
             batch = views[v0:v0 + _lib.TSDF_MAX_VIEWS]
-            a = _lib.TsdfIntegrateArgs(Nx=Nx, Ny=Ny, Nz=Nz, n_views=len(batch), lo=(C.c_float * 3)(*lo), hi=(C.c_float * 3)(*hi),
+            a = _lib.TsdfIntegrateArgs(Nx=Nx, Ny=Ny, Nz=Nz, n_views=len(batch), lo=c_float3(lo), hi=c_float3(hi),
                                        trunc=self.trunc, min_opacity=float(min_opacity), weight_mode=WEIGHT_MODES[weight_mode],
                                        tsdf=ptr(self.tsdf), weight=ptr(self.weight), rgb=ptr(self.rgb), rgb_weight=ptr(self.rgb_weight))
             for j, v in enumerate(batch):
@@ -511,8 +455,7 @@ class TsdfVolume:
         (upnerf_tsdf_sample)."""
         if self.rgb is None:
             raise ValueError("this volume was built with colour=False")
-        if not (torch.is_tensor(points) and points.is_cuda):
-            raise RuntimeError("TsdfVolume.sample_colour runs on the GPU only: points must be a device tensor (no CPU fallback)")
+        require_cuda("TsdfVolume.sample_colour", points)
         pts = points.detach().to(torch.float32).reshape(-1, 3).contiguous()
         V = pts.shape[0]
         out = torch.empty(V, 3, device=pts.device, dtype=torch.float32)
@@ -520,7 +463,7 @@ class TsdfVolume:
             return out
         Nx, Ny, Nz = self.resolution
         lo, hi = self.bounds
-        a = _lib.TsdfSampleArgs(Nx=Nx, Ny=Ny, Nz=Nz, V=V, lo=(C.c_float * 3)(*lo), hi=(C.c_float * 3)(*hi), rgb=ptr(self.rgb),
+        a = _lib.TsdfSampleArgs(Nx=Nx, Ny=Ny, Nz=Nz, V=V, lo=c_float3(lo), hi=c_float3(hi), rgb=ptr(self.rgb),
                                 rgb_weight=ptr(self.rgb_weight), points=ptr(pts), out=ptr(out))
         check(lib.upnerf_tsdf_sample(C.byref(a), stream()), "upnerf_tsdf_sample")
         return out
@@ -544,23 +487,20 @@ def fuse_views(system, bounds, resolution: Sequence[int], img_ids: Optional[Sequ
     `chunk` rays at a time (default val.chunk_size); depth = `s_depth_*`, colour = `s_rgb_*`, opacity = the row sum of
     `s_weights_*`; then TsdfVolume.integrate, a launch per TSDF_MAX_VIEWS views.  trunc: default 3 voxel diagonals.
     Raises while the candidate schedule has not started (sched_mult == 0), as render_path does."""
-    from .novel_view import _per_image, path_rays
-    from .rendering import render_rays
     hp, ds = system.hparams, system.train_dataset
-    if system.get_schedule_mult(system._host_progress) == 0:
+    if system.get_schedule_mult(system._host_progress) == 0:  # (here, not in render_static: the text names the maps THIS function cannot give yet)
         raise ValueError("fuse_views renders the static depth and colour s_depth_* / s_rgb_*, which do not exist while the "
                          "candidate schedule has not started (sched_mult == 0): this checkpoint is too early in training")
     dev = next(system.parameters()).device
-    if dev.type != "cuda":
-        raise RuntimeError("fuse_views runs on the GPU only (no CPU fallback)")
-    lo, hi = _bounds(bounds)
+    require_cuda("fuse_views", dev)
+    lo, hi = box(bounds)
     res = tuple(int(n) for n in resolution)
     if trunc is None:
         trunc = 3.0 * sum(((h - l) / max(n - 1, 1)) ** 2 for l, h, n in zip(lo, hi, res)) ** 0.5
     downscale, chunk = int(downscale), int(chunk or hp["val.chunk_size"])
     if downscale < 1 or chunk < 1:
         raise ValueError("downscale and chunk are positive")
-    poses = _refined_training_poses(system, "integrate views of your own into a TsdfVolume").to(dev)
+    poses = refined_training_poses(system, otherwise="integrate views of your own into a TsdfVolume").to(dev)
     N = poses.shape[0]
     ids = list(range(N)) if img_ids is None else [int(i) for i in img_ids]
     if not ids or min(ids) < 0 or max(ids) >= N:
@@ -568,9 +508,8 @@ def fuse_views(system, bounds, resolution: Sequence[int], img_ids: Optional[Sequ
     if getattr(ds, "Ks", None) is None or getattr(ds, "all_imgs_wh", None) is None:
         raise ValueError("the dataset carries no intrinsics / image sizes (Ks, all_imgs_wh)")
     typ = "fine" if system.fine else "coarse"
-    keys = [k for k in system.embeddings if k.endswith("_a")]
+    keys = static_keys(system, 1)
     vol = TsdfVolume((lo, hi), res, trunc, colour=True, device=dev)
-    white_back = getattr(ds, "white_back", False)
     pending = []  # (depth, rgb, opacity, pose, K, wh) of the views rendered and not yet folded in
 
     def flush():
@@ -580,27 +519,21 @@ def fuse_views(system, bounds, resolution: Sequence[int], img_ids: Optional[Sequ
             pending.clear()
 
     for i in ids:
-        fx, fy, cx, cy = _intrinsics(np.asarray(_per_image(ds, "Ks", i), dtype=np.float64))
         W, H = (int(x) // downscale for x in ds.all_imgs_wh[i])
         if min(W, H) < 1:
             raise ValueError(f"image {i} has no pixel left at downscale {downscale}")
-        intr = (fx / downscale, fy / downscale, cx / downscale, cy / downscale)
-        near, far = _per_image(ds, "nears", i), _per_image(ds, "fars", i)
-        nf = torch.tensor([[float(hp["nerf.near"]) if near is None else float(near), float(hp["nerf.far"]) if far is None else float(far)]],
-                          device=dev, dtype=torch.float32)
+        intr = tuple(v / downscale for v in intrinsics(per_image(ds, "Ks", i)))
+        nf = torch.tensor([near_far(system, i)], device=dev, dtype=torch.float32)
         c2w = poses[i:i + 1].contiguous()
         n = W * H
         depth = torch.empty(n, device=dev, dtype=torch.float32)
         rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
         opacity = torch.empty(n, device=dev, dtype=torch.float32)
-        rows = {k: system.embeddings[k].weight.detach()[i].expand(min(chunk, n), -1).contiguous() for k in keys}
+        rows = appearance_rows(system, keys, i, min(chunk, n))
         for r0 in range(0, n, chunk):
             R = min(chunk, n - r0)
             rays, _ = path_rays(c2w, nf, (W, H), intr, r0, R)
-            out = render_rays(models=system.models, embeddings=system.embeddings, rays=rays, img_idx=None, sched_mult=1, sched_phase=2,
-                              N_samples=hp["nerf.N_samples"], use_disp=hp["nerf.use_disp"], perturb=0,
-                              N_importance=hp["nerf.N_importance"], white_back=white_back, encode_feat=hp["nerf.feat_dim"] > 0,
-                              validation=True, embed_rows={k: v[:R] for k, v in rows.items()})
+            out = render_static(system, rays, {k: v[:R] for k, v in rows.items()}, 1)
             depth[r0:r0 + R].copy_(out[f"s_depth_{typ}"])
             rgb[r0:r0 + R].copy_(out[f"s_rgb_{typ}"])
             opacity[r0:r0 + R].copy_(out[f"s_weights_{typ}"].reshape(R, -1).sum(1))

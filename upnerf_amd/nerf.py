@@ -67,6 +67,12 @@ class NeRF(nn.Module):
         # fill launch per model and step bought nothing; state_dict() / checkpoints / the nn.Module forward flush first.
         self._progress_stale = True
 
+    def host_progress_value(self) -> float:
+        """`progress` as the host sees it: the mirror kept by set_progress, rounded through fp32; code that writes
+        `progress.data` directly (the reference's way) leaves the mirror None and pays a device read here."""
+        hp = self.host_progress
+        return float(self.progress.data) if hp is None else float(torch.tensor(hp, dtype=torch.float32))
+
     def flush_progress(self):
         """Bring the device parameter `progress` up to date with the host mirror (state_dict, checkpoints, module forward)."""
         if getattr(self, "_progress_stale", False) and self.host_progress is not None:

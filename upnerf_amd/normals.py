@@ -27,6 +27,7 @@ import torch
 from . import _lib
 from ._lib import check, lib, ptr, stream
 from .ops import TIMER
+from .static_scene import field_of, require_cuda
 
 __all__ = ["density_gradient", "field_density_gradient", "normal_composite", "sample_points", "reuse_fragments", "TILE"]
 
@@ -62,18 +63,12 @@ def _fragments(model) -> Tuple[torch.Tensor, torch.Tensor]:
     return out
 
 
-def _progress(model) -> float:
-    hp = getattr(model, "host_progress", None)
-    return float(model.progress.data) if hp is None else float(torch.tensor(hp, dtype=torch.float32))
-
-
 @torch.no_grad()
 def field_density_gradient(model, points: torch.Tensor, wk_xyz=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(sigma [M], grad [M, 3]) of one NeRF module at `points` [M, 3] (fp32 device tensor): upnerf_density_grad with the
     module's packed parameters.  wk_xyz: the ten band weights; default: those of the module's progress."""
     from .rendering import band_weights
-    if not (torch.is_tensor(points) and points.is_cuda):
-        raise RuntimeError("libupnerf_hip operates on device memory only (density_gradient got CPU points)")
+    require_cuda("density_gradient", points)
     if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
         raise ValueError("points is a fp32 tensor [M, 3]")
     points = points.detach().contiguous()
@@ -84,7 +79,7 @@ def field_density_gradient(model, points: torch.Tensor, wk_xyz=None) -> Tuple[to
         return sigma, grad
     pk = model.packer
     if wk_xyz is None:
-        wk_xyz = band_weights(model.xyz_L, _progress(model), model.c2f)
+        wk_xyz = band_weights(model.xyz_L, model.host_progress_value(), model.c2f)
     PF, PT = _fragments(model)
     a = _lib.DensityGradArgs(M=M, points=ptr(points), P=ptr(PF), PT=ptr(PT), wk_xyz=(C.c_float * 10)(*wk_xyz), sigma=ptr(sigma),
                              grad=ptr(grad))
@@ -97,14 +92,7 @@ def density_gradient(system, points: torch.Tensor, field: str = "fine") -> Tuple
     """(sigma [M], grad [M, 3]): the shared density (sigma_s, after the softplus) of the `field` ("fine" or "coarse") network
     at the world points `points` [M, 3] and its gradient d sigma / d x there, with the BARF band weights of the model's
     current progress (as geometry.density_grid takes them).  GPU only; raises what density_grid raises."""
-    if field not in ("fine", "coarse"):
-        raise ValueError(f"field is 'fine' or 'coarse', got {field!r}")
-    model = system.models.get(f"nerf_{field}")
-    if model is None:
-        raise ValueError(f"the system has no {field} field")
-    dev = next(model.parameters()).device
-    if dev.type != "cuda":
-        raise RuntimeError("density_gradient runs on the GPU only (no CPU fallback)")
+    model, dev = field_of(system, field, "density_gradient")
     points = torch.as_tensor(points)
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError("points is a tensor [M, 3]")
@@ -115,9 +103,7 @@ def density_gradient(system, points: torch.Tensor, field: str = "fine") -> Tuple
 def normal_composite(grad: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """[R, 3]: normalise(sum_i w[r, i] * (-grad[r, i] / |grad[r, i]|)) (upnerf_normal_composite).  grad [R * S, 3] or [R, S, 3],
     w [R, S]: fp32 device tensors.  Terms with a zero or non-finite gradient count as zero; a zero sum gives (0, 0, 0)."""
-    for t in (grad, w):
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise RuntimeError("libupnerf_hip operates on device memory only (normal_composite got a CPU tensor)")
+    require_cuda("normal_composite", grad, w)
     if w.dim() != 2 or grad.numel() != 3 * w.numel() or grad.shape[-1] != 3:
         raise ValueError(f"expected grad [R * S, 3] and w [R, S]; got {tuple(grad.shape)} and {tuple(w.shape)}")
     R, S = w.shape

@@ -22,6 +22,7 @@ import torch
 from . import _lib
 from ._lib import check, lib, ptr, stream
 from .ops import TIMER
+from .static_scene import intrinsics, near_far, per_image, refined_training_poses, render_static, require_cuda, static_keys
 
 __all__ = ["CameraPath", "plan_path", "path_poses", "path_rays", "render_path", "MODES"]
 
@@ -72,16 +73,6 @@ def plan_path(n_frames: int, img_ids: Optional[Sequence[int]] = None, loop: bool
             torch.from_numpy(t))
 
 
-def _per_image(ds, name: str, idx: int):
-    """Entry of a per-image collection of the dataset for TRAINING image `idx`: scene datasets key theirs by image id
-    (`img_ids_train[idx]`), anything else is indexed by `idx`."""
-    v = getattr(ds, name, None)
-    if v is None:
-        return None
-    ids = getattr(ds, "img_ids_train", None)
-    return v[ids[idx]] if (ids is not None and isinstance(v, dict)) else v[idx]
-
-
 @dataclass
 class CameraPath:
     """Keyframes and the per-frame plan of a rendered sequence, all host tensors (render_path uploads them once)."""
@@ -125,30 +116,16 @@ class CameraPath:
         Keyframes are the REFINED training poses (pose_align.refined_poses of the trained se(3) rows and the dataset's
         poses), near / far the dataset's `nears` / `fars` (hparams nerf.near / nerf.far where it has none); the appearance
         follows the path (plan_path).  `K` and `img_wh` default to those of the first keyframe image."""
-        from .pose_align import refined_poses
         ids = [int(i) for i in img_ids]
-        ds, hp = system.train_dataset, system.hparams
-        w = system.se3_refine.weight
-        if not ids or min(ids) < 0 or max(ids) >= w.shape[0]:
-            raise ValueError(f"img_ids must be training image indices in [0, {w.shape[0]})")
-        if getattr(ds, "poses_dict", None) is not None:
-            poses = [torch.as_tensor(np.asarray(_per_image(ds, "poses_dict", i)), dtype=torch.float32) for i in ids]
-        elif getattr(ds, "poses", None) is not None:
-            poses = [torch.as_tensor(np.asarray(ds.poses[i]), dtype=torch.float32) for i in ids]
-        else:
-            raise ValueError("the training dataset carries no poses (poses_dict / poses): use CameraPath.from_poses")
-        poses = torch.stack([p.reshape(-1, 4)[:3] for p in poses])
-        sel = torch.as_tensor(ids, device=w.device)
-        keys = refined_poses(w.detach()[sel], poses).cpu()
-        nf = []
-        for i in ids:
-            n, f = _per_image(ds, "nears", i), _per_image(ds, "fars", i)
-            nf.append((float(hp["nerf.near"]) if n is None else float(n), float(hp["nerf.far"]) if f is None else float(f)))
-        nf = torch.tensor(nf, dtype=torch.float32)
+        ds, N = system.train_dataset, system.se3_refine.weight.shape[0]
+        if not ids or min(ids) < 0 or max(ids) >= N:
+            raise ValueError(f"img_ids must be training image indices in [0, {N})")
+        keys = refined_training_poses(system, ids, "use CameraPath.from_poses").cpu()
+        nf = torch.tensor([near_far(system, i) for i in ids], dtype=torch.float32)
         if loop:
             keys, nf = torch.cat([keys, keys[:1]]), torch.cat([nf, nf[:1]])
         if K is None:
-            K = _per_image(ds, "Ks", ids[0])
+            K = per_image(ds, "Ks", ids[0])
         if img_wh is None:
             wh = getattr(ds, "all_imgs_wh", None)
             img_wh = None if wh is None else tuple(int(x) for x in wh[ids[0]])
@@ -175,8 +152,7 @@ def _dev32(x: torch.Tensor, device, dtype=torch.float32) -> torch.Tensor:
 
 def path_poses(key_c2w: torch.Tensor, key_nf: torch.Tensor, u: torch.Tensor, mode="catmull"):
     """(c2w [F, 3, 4], near_far [F, 2]) at path parameters `u` [F] between the keyframes (upnerf_path_poses; device tensors)."""
-    if not key_c2w.is_cuda:
-        raise RuntimeError("libupnerf_hip operates on device memory only (path_poses got CPU tensors)")
+    require_cuda("path_poses", key_c2w)
     dev = key_c2w.device
     key_c2w, key_nf, u = _dev32(key_c2w, dev).reshape(-1, 3, 4), _dev32(key_nf, dev).reshape(-1, 2), _dev32(u, dev).reshape(-1)
     K, F = key_c2w.shape[0], u.numel()
@@ -197,15 +173,10 @@ def path_rays(c2w: torch.Tensor, nf: torch.Tensor, img_wh, K, row0: int, R: int,
     c2w [F, 3, 4], nf [F, 2] device tensors; K = 3 x 3 intrinsics or (fx, fy, cx, cy); tables: (table [N, dim], out or None)
     pairs, blended between rows i0[f] and i1[f] (int32 [F]) with weight t[f] -- indices outside the table are clamped into
     it by the kernel.  `rays` / `out`: preallocated buffers with at least R rows (their first R rows are written)."""
-    if not c2w.is_cuda:
-        raise RuntimeError("libupnerf_hip operates on device memory only (path_rays got CPU tensors)")
+    require_cuda("path_rays", c2w)
     dev = c2w.device
     W, H = int(img_wh[0]), int(img_wh[1])
-    if torch.is_tensor(K) or isinstance(K, np.ndarray):
-        Km = np.asarray(torch.as_tensor(K).cpu(), dtype=np.float64)
-        fx, fy, cx, cy = Km[0, 0], Km[1, 1], Km[0, 2], Km[1, 2]
-    else:
-        fx, fy, cx, cy = K
+    fx, fy, cx, cy = intrinsics(K)
     F = c2w.shape[0]
     if rays is None:
         rays = torch.empty(R, 8, device=dev, dtype=torch.float32)
@@ -213,8 +184,8 @@ def path_rays(c2w: torch.Tensor, nf: torch.Tensor, img_wh, K, row0: int, R: int,
         raise ValueError(f"rays must be [>= {R}, 8]")
     if len(tables) > _lib.PATH_MAX_TABLES:
         raise ValueError(f"at most {_lib.PATH_MAX_TABLES} embedding tables per launch, got {len(tables)}")
-    a = _lib.PathRaysArgs(F=F, H=H, W=W, n_tables=len(tables), row0=int(row0), R=int(R), fx=float(fx), fy=float(fy),
-                          cx=float(cx), cy=float(cy), c2w=ptr(c2w), nf=ptr(nf), i0=ptr(i0), i1=ptr(i1), t=ptr(t), rays=ptr(rays))
+    a = _lib.PathRaysArgs(F=F, H=H, W=W, n_tables=len(tables), row0=int(row0), R=int(R), fx=fx, fy=fy, cx=cx, cy=cy,
+                          c2w=ptr(c2w), nf=ptr(nf), i0=ptr(i0), i1=ptr(i1), t=ptr(t), rays=ptr(rays))
     outs = []
     for j, (table, out) in enumerate(tables):
         if table.dim() != 2 or (i0 is None or i1 is None or t is None):
@@ -231,11 +202,6 @@ def path_rays(c2w: torch.Tensor, nf: torch.Tensor, img_wh, K, row0: int, R: int,
         outs.append(out[:R])
     check(TIMER.run("path_rays", lambda: lib.upnerf_path_rays(C.byref(a), stream()), units=R), "upnerf_path_rays")
     return rays[:R], outs
-
-
-def _table_keys(system, sched_mult) -> list:
-    """The embedding tables the phase reads: appearance always, candidate while the schedule has not finished."""
-    return [k for k in system.embeddings if k.endswith("_a") or (k.endswith("_c") and sched_mult < 1)]
 
 
 @torch.no_grad()
@@ -257,14 +223,13 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
     white_back, else 0) at depth `far` -- not what the full render would have composited from density below the grid's level.
     One host read per chunk (the hit count); a chunk without hits launches no field kernel.  LAST_STATS holds the sequence's
     number of rays and hits.  None: nothing of this runs."""
-    from .rendering import render_rays
     from .visualization import depth_image, min_max_of, normal_image, rgb_image
     unknown = set(outputs) - {"rgb", "depth", "rgb_float", "normal", "normal_float"}
     if unknown:
         raise ValueError(f"unknown outputs {sorted(unknown)} (rgb, depth, rgb_float, normal, normal_float)")
     hp = system.hparams
     sched_mult = system.get_schedule_mult(system._host_progress)
-    if sched_mult == 0:
+    if sched_mult == 0:  # (here, not in render_static: the text names the outputs THIS function cannot give yet)
         raise ValueError("render_path renders the static colour s_rgb_*, which does not exist while the candidate schedule has "
                          "not started (sched_mult == 0): this checkpoint is too early in training")
     dev = next(system.parameters()).device
@@ -280,9 +245,8 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
     chunk = min(chunk, total)
     c2w, nf = path_poses(path.key_c2w.to(dev), path.key_near_far.to(dev), path.u.to(dev), path.mode)
     i0, i1, t = path.i0.to(dev), path.i1.to(dev), path.t.to(dev)
-    Kh = path.K.double()
-    intr = (float(Kh[0, 0]), float(Kh[1, 1]), float(Kh[0, 2]), float(Kh[1, 2]))
-    keys = _table_keys(system, sched_mult)
+    intr = intrinsics(path.K)
+    keys = static_keys(system, sched_mult)
     weights = [system.embeddings[k].weight.detach().contiguous() for k in keys]
     # the workspace of every chunk, allocated once: 32 B of rays and sum(dim) * 4 B of rows per ray of the chunk
     ws = {"rays": torch.empty(chunk, 8, device=dev, dtype=torch.float32)}
@@ -360,11 +324,7 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
                 rays, rows, index, n_hit = oc.compact_rays(occupancy, full, rows, ws=occ_ws)
                 LAST_STATS["hits"] += n_hit
             if occ_ws is None or n_hit > 0:
-                res = render_rays(models=system.models, embeddings=system.embeddings, rays=rays, img_idx=None, sched_mult=sched_mult,
-                                  sched_phase=2 if sched_mult == 1 else 1, N_samples=hp["nerf.N_samples"],
-                                  use_disp=hp["nerf.use_disp"], perturb=0, N_importance=hp["nerf.N_importance"], white_back=white_back,
-                                  encode_feat=hp["nerf.feat_dim"] > 0, validation=True, embed_rows=dict(zip(keys, rows)),
-                                  **({"normals": True} if want_normal else {}))
+                res = render_static(system, rays, dict(zip(keys, rows)), sched_mult, normals=want_normal)
                 rgb, depth = res[f"s_rgb_{typ}"], res[f"s_depth_{typ}"]
                 normal = res[f"normal_{typ}"] if want_normal else None
             else:

@@ -20,25 +20,15 @@ import torch
 from . import _lib
 from ._lib import check, lib, ptr, stream
 from .ops import TIMER
+from .static_scene import box, c_float3, require_cuda
 
 __all__ = ["OccupancyGrid", "ray_spans", "compact_hits", "compact_rays", "scatter_results", "BRICK"]
 
 BRICK = 8  # cells per brick edge (OCC_BRICK)
 
 
-def _bounds(bounds):
-    lo, hi = (tuple(float(v) for v in b) for b in bounds)
-    if len(lo) != 3 or len(hi) != 3:
-        raise ValueError("bounds is ((x0, y0, z0), (x1, y1, z1))")
-    if not all(h > l for l, h in zip(lo, hi)):
-        raise ValueError(f"bounds must have hi > lo on every axis, got {lo} .. {hi}")
-    return lo, hi
-
-
-def _device_only(what: str, *tensors):
-    for t in tensors:
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise RuntimeError(f"libupnerf_hip operates on device memory only ({what} got a CPU tensor)")
+def _bounds(bounds):  # hi > lo on every axis, or the cells have no size
+    return box(bounds, strict=True)
 
 
 def _unpack(words: torch.Tensor, n: int) -> torch.Tensor:
@@ -88,7 +78,7 @@ class OccupancyGrid:
         """From a [Nz, Ny, Nx] fp32 device grid of densities at grid points (density_grid): cell occupied iff a corner is finite
         and >= level, then `dilate` rounds of 26-neighbour dilation.  `level` has no default: the useful threshold depends on
         the scene's scale (see extract_surface)."""
-        _device_only("OccupancyGrid.from_density", grid)
+        require_cuda("OccupancyGrid.from_density", grid)
         if grid.dtype != torch.float32 or grid.dim() != 3:
             raise ValueError("the grid is a fp32 tensor [Nz, Ny, Nx]")
         level = float(level)
@@ -101,7 +91,7 @@ class OccupancyGrid:
     @classmethod
     def from_cells(cls, cells: torch.Tensor, bounds, dilate: int = 0) -> "OccupancyGrid":
         """From a [Cz, Cy, Cx] bool or uint8 device tensor (non-zero = occupied)."""
-        _device_only("OccupancyGrid.from_cells", cells)
+        require_cuda("OccupancyGrid.from_cells", cells)
         if cells.dtype not in (torch.bool, torch.uint8) or cells.dim() != 3:
             raise ValueError("the cells are a bool or uint8 tensor [Cz, Cy, Cx]")
         cells = cells.detach().to(torch.uint8).contiguous()
@@ -133,7 +123,7 @@ class OccupancyGrid:
 
 
 def _rays(what: str, rays: torch.Tensor) -> torch.Tensor:
-    _device_only(what, rays)
+    require_cuda(what, rays)
     if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or rays.shape[0] < 1:
         raise ValueError("rays are a fp32 tensor [R, 8] (o | d | near | far) with R >= 1")
     return rays.contiguous()
@@ -152,7 +142,7 @@ def ray_spans(occ: OccupancyGrid, rays: torch.Tensor, out: Optional[Tuple[torch.
         raise ValueError(f"t0, t1 are fp32 and hit is uint8, each with at least {R} entries")
     Cx, Cy, Cz = occ.dims
     lo, hi = occ.bounds
-    a = _lib.OccSpansArgs(Cx=Cx, Cy=Cy, Cz=Cz, R=R, lo=(C.c_float * 3)(*lo), hi=(C.c_float * 3)(*hi), words=ptr(occ.words),
+    a = _lib.OccSpansArgs(Cx=Cx, Cy=Cy, Cz=Cz, R=R, lo=c_float3(lo), hi=c_float3(hi), words=ptr(occ.words),
                           rays=ptr(rays), t0=ptr(t0), t1=ptr(t1), hit=ptr(hit))
     check(TIMER.run("occ_spans", lambda: lib.upnerf_occ_spans(C.byref(a), stream()), units=R), "upnerf_occ_spans")
     return t0[:R], t1[:R], hit[:R]
@@ -172,7 +162,7 @@ def compact_hits(rays: torch.Tensor, t0: torch.Tensor, t1: torch.Tensor, hit: to
     """(rays_c [n_hit, 8], [rows_c [n_hit, dim]], index int32 [n_hit], n_hit) -- the rows with hit != 0 in ascending order
     (upnerf_occ_compact), near / far of the ray rows replaced by t0 / t1.  One host read: the hit count."""
     rays = _rays("compact_hits", rays)
-    _device_only("compact_hits", t0, t1, hit, *rows)
+    require_cuda("compact_hits", t0, t1, hit, *rows)
     R, dev = rays.shape[0], rays.device
     if t0.dtype != torch.float32 or t1.dtype != torch.float32 or hit.dtype not in (torch.uint8, torch.bool):
         raise ValueError("t0, t1 are fp32 [R] and hit is uint8 [R]")
@@ -206,7 +196,7 @@ def compact_hits(rays: torch.Tensor, t0: torch.Tensor, t1: torch.Tensor, hit: to
 def compact_rays(occ: OccupancyGrid, rays: torch.Tensor, rows: Sequence[torch.Tensor] = (), ws: Optional[dict] = None):
     """ray_spans and compact_hits: (rays_c, rows_c, index, n_hit) of the rays that touch an occupied cell."""
     rays = _rays("compact_rays", rays)
-    _device_only("compact_rays", *rows)
+    require_cuda("compact_rays", *rows)
     if ws is None:
         ws = compact_workspace(rays.shape[0], [t.shape[1] for t in rows], rays.device)
     t0, t1, hit = ray_spans(occ, rays, out=(ws["t0"], ws["t1"], ws["hit"]))
@@ -220,7 +210,7 @@ def scatter_results(index: torch.Tensor, rays: torch.Tensor, rgb_c: Optional[tor
     `index` names, the background colour and the ray's own far on every other row (upnerf_occ_scatter).  n_hit = len(index);
     with n_hit == 0 rgb_c / depth_c may be None.  want_depth defaults to `depth_c is not None`."""
     rays = _rays("scatter_results", rays)
-    _device_only("scatter_results", index, *[t for t in (rgb_c, depth_c) if t is not None])
+    require_cuda("scatter_results", index, *[t for t in (rgb_c, depth_c) if t is not None])
     R, dev, n = rays.shape[0], rays.device, index.numel()
     if index.dtype != torch.int32 or n > R:
         raise ValueError("index is int32 [n_hit] with n_hit <= R")
