@@ -101,7 +101,7 @@ def test_every_plan_is_one_description():
     n = raised = 0
     for fm, ws, bits, train, kind, (W, D) in itertools.product(pp.MODES, ("f32", "f16", "f24"), itertools.product((0, 1), repeat=5),
                                                               (False, True), PASSES, FIELDS):
-        sw = dict(zip(BOOLS, bits), FIELD_MODE=fm, WGRAD_STORE=ws, HMASK_SCALE=1)
+        sw = dict(zip(BOOLS, bits), FIELD_MODE=fm, WGRAD_STORE=ws)
         bad_f24 = ws == "f24" and not sw["WGRAD_CHAIN"]
         seen = {}  # use16 -> (the plan's forms as a tuple, what forms_check returned): the forms are checked once per class ...
         for R, S in SHAPES:
@@ -127,6 +127,6 @@ def test_every_plan_is_one_description():
 
 
 def test_unknown_field_mode_raises():
-    sw = dict(zip(BOOLS, (1,) * 5), FIELD_MODE="bf16", WGRAD_STORE="f32", HMASK_SCALE=1)
+    sw = dict(zip(BOOLS, (1,) * 5), FIELD_MODE="bf16", WGRAD_STORE="f32")
     with pytest.raises(ValueError, match=r"unknown FIELD_MODE 'bf16' \(one of \('f16x3', 'f32', 'f16'\)\)"):
         pp.plan_pass(256, 128, 8, 5, 33, 1, True, True, False, True, **sw)

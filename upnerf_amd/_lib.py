@@ -16,7 +16,7 @@ from .pass_plan import (AUXK, RR_PART_STRIDE, TILE_PART_STRIDE, WG_F16_FRAG, WG_
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UPNERF_LIB") or os.path.join(_HERE, "libupnerf_hip.so")  # UPNERF_LIB: diagnostic builds only
 MAX_D = 8
-TILE_ROWS, CK = int(os.environ.get("UPNERF_TILE_ROWS", 64)), 16  # env: diagnostic builds only
+CK = 16
 
 _fp = C.c_void_p
 

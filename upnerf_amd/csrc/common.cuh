@@ -385,42 +385,11 @@ __device__ __forceinline__ float wave_sum(float v) {
 // activations and pre-activation gradients: ~30 GB per step), are stored and loaded NON-TEMPORALLY: they then do not push the
 // data that IS re-read out of the 4 MB L2s and the Infinity Cache -- the weight fragments every field workgroup streams, the
 // weight-gradient slabs the next launch sums.  Measured (round 3, graph-replayed step, three alternating runs): 18.27 -> 17.79 ms.
-// -DUPNERF_NO_NT restores plain accesses.
-//
-// Experiment switches that change RESULTS (timing-only builds: wrong or missing outputs) compile only in a build that says it is
-// an experiment (`make variant` passes -DUPNERF_EXPERIMENT); a stray -D in the product build is a compile error, not a silently
-// wrong library.
-#if (defined(UPNERF_EXP_HALFROW) || defined(UPNERF_EXP_NOSTORE) || defined(UPNERF_EXP_SAMEB) || defined(RR_EXP_NOSTORE) || \
-     defined(RR_EXP_NODMA) || defined(RR_EXP_NOEPI) || defined(RR_EXP_NOMMA) || defined(RR_EXP_NOBARRIER) || defined(RR_EXP_NOLDS) || defined(RR_EXP_PLAINLOAD) || defined(WG_EXP_NOLOAD) || defined(WG_EXP_NOSTAGE) || defined(WG_EXP_NOMMA) || defined(WP_EXP_NOREAD) || defined(WP_EXP_NOMMA) || defined(TR_EXP_NOLOAD) || defined(TR_EXP_NOMMA) || defined(TR_EXP_NOSTORE)) && !defined(UPNERF_EXPERIMENT)
-#error "UPNERF_EXP_* / RR_EXP_* switches produce wrong results: build them with -DUPNERF_EXPERIMENT (make variant), never into libupnerf_hip.so"
-#endif
-#ifdef UPNERF_NO_NT
-#define NT_LOAD(p) (*(p))
-#define NT_STORE(p, v) (*(p) = (v))
-#elif defined(UPNERF_ST_POLICY)
-// A/B of the cache policy of the streaming stores (make variant EXP=-DUPNERF_ST_POLICY=n): 1 = sc1 (write-through, the line is
-// DROPPED from the XCD's L2 -- plain and nt stores keep it: MI355X_MICROARCH.md, fence table, 'stores of each flavour'),
-// 2 = sc0 sc1, 3 = sc1 nt.  Inline asm: hipcc does not count these stores in vmcnt (its own waits only get stricter) and the
-// data registers are protected by the trailing s_nop (cdna_hip_programming.md 5.7).
-template <class T>
-__device__ __forceinline__ void store_policy(T* p, const T& v) {
-#if UPNERF_ST_POLICY == 1
-#define UPNERF_ST_BITS "sc1"
-#elif UPNERF_ST_POLICY == 2
-#define UPNERF_ST_BITS "sc0 sc1"
-#else
-#define UPNERF_ST_BITS "sc1 nt"
-#endif
-  if constexpr (sizeof(T) == 16) asm volatile("global_store_dwordx4 %0, %1, off " UPNERF_ST_BITS "\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-  else if constexpr (sizeof(T) == 8) asm volatile("global_store_dwordx2 %0, %1, off " UPNERF_ST_BITS "\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-  else __builtin_nontemporal_store(v, p);
-}
-#define NT_LOAD(p) __builtin_nontemporal_load(p)
-#define NT_STORE(p, v) store_policy((p), (v))
-#else
+// Plain accesses were the state before; write-through policies for the stores (sc1, sc0 sc1, sc1 nt, which drop the line from the XCD's
+// L2) measured 2.53 / 2.49, 2.53 / 2.50, 2.51 / 2.48 against 2.49 / 2.47 ms per forward / backward launch: the L2 lines
+// the stores occupy are not what evicts the weights.
 #define NT_LOAD(p) __builtin_nontemporal_load(p)
 #define NT_STORE(p, v) __builtin_nontemporal_store((v), (p))
-#endif
 
 // ---- fixed-order reduction of weight-gradient slabs (upnerf_wgrad*): the work of ONE 512-thread block `bid` of the reduce
 // grid, callable from the reduce kernel and from the prologue of the NEXT weight-gradient kernel (upnerf_wgrad16 with a pending record).

@@ -19,7 +19,6 @@
 // stores, per-row scalars (one LDS read per lane instead of one per register).
 #pragma once
 #include "common.cuh"
-#include <type_traits>
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -128,51 +127,21 @@ __device__ __forceinline__ void mma16_step(f32x16 (&acc)[MT][NT], const h8 (&xh)
 // before the MFMAs of block t issue (AHEAD x MFMA time >= L2 latency); the activation fragments (LDS, ~100 cycles) stay
 // one block ahead.  One ring revolution is unrolled, so every ring index is a compile-time register name; sched_barrier
 // fences keep the requests ABOVE the matrix work (hipcc otherwise sinks them to their first use).
-// weight-fragment load.  Experiments (make variant): UPNERF_W_NT = non-temporal (L1-bypassing) loads; UPNERF_EXP_SAMEB = every
-// k-block reads the FIRST block of its n-tile (wrong results: the kernel with its weight stream served from L1)
-#if defined(UPNERF_W_NT)
-#define W_LOAD(p, t) __builtin_nontemporal_load((const h8*)((p) + (size_t)(t) * 2048))
-#define W_LOAD_LO(p, t) __builtin_nontemporal_load((const h8*)((p) + (size_t)(t) * 2048 + 1024))
-#elif defined(UPNERF_EXP_SAMEB)
-#define W_LOAD(p, t) (*(const h8*)((p) + (size_t)((t) & 1) * 2048))
-#define W_LOAD_LO(p, t) (*(const h8*)((p) + (size_t)((t) & 1) * 2048 + 1024))
-#else
+// weight-fragment load: plain, through L1.  Non-temporal (L1-bypassing) loads cost +35 % of the launch at any prefetch depth and K
+// order, and every workgroup walking K from its own starting block did not help: 2.43 / 2.54 against 2.39 / 2.46 ms.
 #define W_LOAD(p, t) (*(const h8*)((p) + (size_t)(t) * 2048))
 #define W_LOAD_LO(p, t) (*(const h8*)((p) + (size_t)(t) * 2048 + 1024))
-#endif
-// `piece(t)` (optional) runs once per k-block, in the request section of block t -- behind the weight requests of block
-// t + AHEAD and the operand reads of block t + 1, in front of the MFMAs of block t: the place of work that rides under the
-// contraction (the previous stage's activation stores, one 1 KiB piece per k-block: field16.hip:PlaneStore).
-struct NoPiece {
-  __device__ __forceinline__ void operator()(int) const {}
-};
-template <int NP, int W, int T, int AHEAD, int MT, int NT, class PIECE = NoPiece>
+template <int NP, int W, int T, int AHEAD, int MT, int NT>
 __device__ __forceinline__ void mma16_lds(f32x16 (&acc)[MT][NT], const char* Ph, const char* Pl, int row0, int kA0,
-                                          const char* __restrict__ Wf, int Kp16, int n0, int kB0, int lane,
-                                          PIECE&& piece = PIECE()) {
+                                          const char* __restrict__ Wf, int Kp16, int n0, int kB0, int lane) {
   constexpr int SETS = (AHEAD + 1 > T) ? T : AHEAD + 1;  // ring size; the ring runs SETS - 1 blocks ahead
   constexpr int AH = SETS - 1;
-#ifdef UPNERF_EXP_SETPRIO
-  struct Prio { __device__ Prio() { __builtin_amdgcn_s_setprio(UPNERF_EXP_SETPRIO); } __device__ ~Prio() { __builtin_amdgcn_s_setprio(0); } } prio_;
-#endif
-#ifndef F16_FORCE_UNROLLED_K
-#define F16_FORCE_UNROLLED_K 0
-#endif
-  if constexpr (F16_FORCE_UNROLLED_K || SETS % 2 != 0 || T % SETS != 0) {
+  if constexpr (SETS % 2 != 0 || T % SETS != 0) {
     // ring sizes that do not divide the loop (two blocks ahead = three sets): the whole K loop unrolled, every ring index a
     // compile-time constant.  The lane's row offsets are made opaque first: hipcc would otherwise hoist all T LDS addresses
     // out of the caller's layer loop and spill them.
     int li = lane & 31, lh = lane >> 5;
     asm volatile("" : "+v"(li), "+v"(lh));
-#ifdef UPNERF_EXP_KROT
-    // experiment (round 6): every workgroup walks the K dimension from its own starting block -- the CUs of an XCD then ask the L2
-    // for DIFFERENT fragments at any moment instead of all for the same one (same products, another summation order)
-    static_assert((T & (T - 1)) == 0, "rotation: power-of-two trip counts");
-    const int rot = __builtin_amdgcn_readfirstlane((blockIdx.x >> 3) & (T - 1));
-#define KR(t) (((t) + rot) & (T - 1))
-#else
-#define KR(t) (t)
-#endif
     const char* bpu[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) bpu[nt] = Wf + ((size_t)((n0 >> 5) + nt) * Kp16 + (kB0 >> 4)) * 2048 + (li + 32 * lh) * 16;
@@ -180,14 +149,14 @@ __device__ __forceinline__ void mma16_lds(f32x16 (&acc)[MT][NT], const char* Ph,
     auto ldw = [&](int t) {
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
-        uwh[t % SETS][nt] = W_LOAD(bpu[nt], KR(t));
-        if constexpr (NP == 2) uwl[t % SETS][nt] = W_LOAD_LO(bpu[nt], KR(t));
+        uwh[t % SETS][nt] = W_LOAD(bpu[nt], t);
+        if constexpr (NP == 2) uwl[t % SETS][nt] = W_LOAD_LO(bpu[nt], t);
       }
     };
     auto ldx = [&](int t) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
-        const int o = poff<W>(row0 + 32 * mt + li, kA0 + 16 * KR(t) + 8 * lh);
+        const int o = poff<W>(row0 + 32 * mt + li, kA0 + 16 * t + 8 * lh);
         uxh[t & 1][mt] = *(const h8*)(Ph + o);
         if constexpr (NP == 2) uxl[t & 1][mt] = *(const h8*)(Pl + o);
       }
@@ -199,16 +168,12 @@ __device__ __forceinline__ void mma16_lds(f32x16 (&acc)[MT][NT], const char* Ph,
     for (int t = 0; t < T; ++t) {
       if (t + AH < T) ldw(t + AH);
       if (t + 1 < T) ldx(t + 1);
-      piece(t);
       __builtin_amdgcn_sched_barrier(0);
       mma16_step<NP>(acc, uxh[t & 1], uxl[t & 1], uwh[t % SETS], uwl[t % SETS]);
       __builtin_amdgcn_sched_barrier(0);
     }
-#undef KR
     return;
   }
-  static_assert(F16_FORCE_UNROLLED_K || SETS % 2 != 0 || T % SETS != 0 || std::is_same<typename std::remove_reference<PIECE>::type, NoPiece>::value,
-                "per-k-block pieces: unrolled K loops only");
   const int i = lane & 31, hh = lane >> 5;
   const char* bp[NT];
   int arow[MT];

@@ -17,7 +17,6 @@
 //   * trunk / final activations and all pre-activation gradients are stored straight from the accumulators (16 bytes per
 //     lane and quad), the 128-wide head activations from the planes.
 #include "common16.cuh"
-#include <type_traits>
 
 // Tiling (template parameters TILE, NW): 64 samples x 4 waves, two workgroups per CU: a wave owns 64 columns x all 64 rows
 // (MT = 2, NT = 2); every workgroup pulls a layer's whole weight matrix from L2 (4 KB per sample and layer in the f16x3 mode).
@@ -25,17 +24,13 @@
 // kernels with LDS-staged weights are csrc/field16rr.hip.
 #define ACT_STORE(p, v) NT_STORE(p, v)  // activations / gradients for a later kernel (common.cuh: streaming accesses)
 #define F16_TILE 64
-#ifndef F16_WAVES
-#define F16_WAVES 4  // waves of a 64-sample workgroup (experiment: 8 = one 32-column tile per wave, four waves per SIMD)
-#endif
+// waves of a 64-sample workgroup (eight -- one 32-column tile per wave, four waves per SIMD at 128 registers -- were tried and dropped)
+#define F16_WAVES 4
 // two workgroups per CU = 2 waves per SIMD; hipcc takes the second __launch_bounds__ argument as the minimum number of
 // waves per SIMD
 #define F16_WAVES_PER_EU 2
-// f16 mode (one plane: 42-48 KB of LDS per 64-sample workgroup): a third workgroup per CU fits if a wave stays within 168 registers
-#ifndef F16_WAVES_PER_EU_F16
-#define F16_WAVES_PER_EU_F16 2
-#endif
-#define F16_EU(NP, TILE) ((TILE) == 64 && F16_WAVES == 8 ? 4 : ((NP) == 1 && (TILE) == 64 ? F16_WAVES_PER_EU_F16 : F16_WAVES_PER_EU))
+// (f16 mode, one plane: 42-48 KB of LDS per 64-sample workgroup would allow a third workgroup per CU, 168 registers per wave do not:
+// 200-320 bytes of spills per lane, Trevi step 21.6 -> 24.2 ms -- DESIGN.md 4.6.)
 // Weight fragments are requested this many 16-deep k-blocks ahead of the MFMAs that consume them.  Measured with the stamps
 // build (per wave and trunk layer): f16 mode 10.4k cycles per K loop one block ahead = 650 cycles per k-block = the L2
 // latency, 8.1k three ahead and 8.3k seven ahead -- from there on the loop is bound by the bytes the CU can pull from L2
@@ -46,25 +41,10 @@
 #ifndef F16_AHEAD_X3
 #define F16_AHEAD_X3 2
 #endif
-#ifndef F16_STORE_IN_LOOP
-// Activation stores as one 1 KiB piece per k-block INSIDE the next layer's K loop (PlaneStore).  Built, parity-green,
-// measured slower (round 5, alternating runs on one box: forward launch 2.61 / 2.58 ms against 2.52 / 2.54 behind the loop): the K loop
-// already keeps the CU's vector-memory path at the rate it sustains under this mix, a store per k-block lengthens it by what the
-// burst behind the loop costs and the epilogue still waits for its barriers.  0 = behind the loop (shipped); 1 = the experiment;
-// 2 (round 6) = the experiment with the piece's LDS words read one k-block ahead of their store.  In the trunk probe -- whose
-// workgroups are exact copies of each other and stay in phase -- 2 beats the burst (2.465 against 2.585 ms); in this kernel, whose
-// two workgroups per CU drift apart through their encoding and head stages and so already overlap one's burst with the other's K
-// loop, it does not: forward launch 2.431 (2) / 2.449 (1) against 2.374 ms, alternating on one box (profiles/r06_ab_stores_in_loop.txt).
-#define F16_STORE_IN_LOOP 0
-#endif
-// the backward head stage's sums of the per-row scalars: 1 = one wave, a row per lane, butterfly (round 6); 0 = four threads walking
-// the tile's 64 rows while the other 252 wait at the barrier behind them
-#ifndef F16_BH_SCALAR_SUMS_WAVE
-#define F16_BH_SCALAR_SUMS_WAVE 1
-#endif
-#ifndef F16_JOIN_HEADS
-#define F16_JOIN_HEADS 1  // the first layers of the colour and the candidate head in one K loop when both run (0: one after the other, for A/B runs)
-#endif
+// The activation stores go out in a burst BEHIND the K loop that read the planes.  One 1 KiB piece per k-block INSIDE the next layer's
+// K loop was built, parity-green and measured slower: forward launch 2.431 / 2.449 against 2.374 ms, alternating on one box
+// (profiles/r06_ab_stores_in_loop.txt) -- the two workgroups of a CU drift apart and already overlap one's burst with
+// the other's K loop.
 #ifndef F16_AHEAD_F16
 #define F16_AHEAD_F16 5  // (with non-temporal stores: 19.63 ms per Trevi step against 19.78 at three ahead; round 3)
 #endif
@@ -162,9 +142,6 @@ __device__ __forceinline__ void tile_store16(const char* Ph, const char* Pl, int
   static_assert(TILE * GPR % THREADS == 0, "whole passes of the workgroup");
   constexpr int B = (BATCH == 0 || BATCH > ITER) ? ITER : BATCH;
   static_assert(ITER % B == 0, "whole batches");
-#if F16_WAVES == 8 || defined(F16_OPAQUE_STORE)
-  asm volatile("" : "+v"(tid));  // (128-register build: keep hipcc from hoisting every row address out of the caller's layer loop)
-#endif
   const bool whole = m0 + TILE <= M;
 #pragma unroll 1
   for (int it0 = 0; it0 < ITER; it0 += B) {
@@ -186,9 +163,6 @@ __device__ __forceinline__ void tile_store16(const char* Ph, const char* Pl, int
                   mix16<0>(wh[j][1], un, mix16<0>(wl[j][1], un, 0.f)), mix16<1>(wh[j][1], un, mix16<1>(wl[j][1], un, 0.f))};
       else
         v = f32x4{mix16<0>(wh[j][0], un, 0.f), mix16<1>(wh[j][0], un, 0.f), mix16<0>(wh[j][1], un, 0.f), mix16<1>(wh[j][1], un, 0.f)};
-#ifdef UPNERF_EXP_HALFROW
-      if (NCOLS == 256 && g >= UPNERF_EXP_HALFROW) continue;
-#endif
       if (whole || m0 + row < M) {
         if constexpr (STREAM) ACT_STORE((f32x4*)&dst[(size_t)(m0 + row) * ldg + 4 * g], v);
         else *(f32x4*)&dst[(size_t)(m0 + row) * ldg + 4 * g] = v;  // re-read by this workgroup soon (x0 at the skip layer)
@@ -201,71 +175,6 @@ __device__ __forceinline__ void tile_store16(const char* Ph, const char* Pl, int
                                              int ldg, int m0, int M, int tid) {
   tile_store16<NP, W, TILE, THREADS, NCOLS, BATCH, STREAM>(Ph, Pl, c0, unscale, unscale, dst, ldg, m0, M, tid);
 }
-
-// tile_store16 of a full-width (W-column) tensor cut into its 1 KiB pieces -- piece t = the workgroup's store pass t of
-// tile_store16: rows 4 t .. 4 t + 3 at 256 threads -- for issue INSIDE the K loop of the next contraction, one piece per k-block
-// (common16.cuh:mma16_lds `piece`): that loop reads the same planes, nothing writes them before its closing barrier, and the wave
-// that is held by a store's issue (~260 cycles) leaves the matrix pipe to its SIMD partner instead of idling it
-// together with all eight waves of the CU in a burst of sixteen stores behind the loop.  Whole tiles only (no row guard: no control flow in the K loop --
-// a branch there makes hipcc's vmcnt bookkeeping conservative and drains the weight ring).
-template <int NP, int W, int TILE, int THREADS>
-struct PlaneStore {
-  static constexpr int GPR = W >> 2, ITER = TILE * GPR / THREADS;
-  const char *Ph, *Pl;
-  float* __restrict__ dst;  // row m0 of the tensor
-  float un0, un1;
-  int tid;
-  u32x2_t ch, cl;
-  __device__ __forceinline__ void read(int it, u32x2_t& h, u32x2_t& l) const {
-    const int idx = tid + it * THREADS, row = idx / GPR, g = idx % GPR;
-    const int o = poff<W>(row, 4 * g);
-    h = *(const u32x2_t*)(Ph + o);
-    if constexpr (NP == 2) l = *(const u32x2_t*)(Pl + o);
-  }
-  __device__ __forceinline__ PlaneStore(const char* ph, const char* pl, float* d, float u0, float u1, int t)
-      : Ph(ph), Pl(pl), dst(d), un0(u0), un1(u1), tid(t) {
-    // (opaque per layer: the pieces' row offsets are layer-invariant, hipcc hoisted all sixteen address pairs out of the layer
-    // loop, spilled them and reloaded them inside the K loop -- scratch loads, i.e. vmcnt waits behind the stores)
-    asm volatile("" : "+v"(tid));
-  }
-#if F16_STORE_IN_LOOP == 2
-  // Round 6: the piece's LDS words are read ONE K-BLOCK AHEAD of their conversion and store (operator()(t) stores piece t - 1 and reads
-  // piece t; flush(ITER - 1) behind the loop): the store's LDS round trip passes under the previous k-block's MFMAs instead of standing
-  // in front of this one's.  In the trunk probe (tools/repro/pair_trunk_probe.hip, mode 12) that turns the in-loop stores from a loss
-  // (2.70 against 2.585 ms) into a gain (2.465).
-  __device__ __forceinline__ void flush(int it) const {
-    const int idx = tid + it * THREADS, row = idx / GPR, g = idx % GPR;
-    const float un = row < TILE / 2 ? un0 : un1;
-    f32x4 v;
-    if constexpr (NP == 2)
-      v = f32x4{mix16<0>(ch[0], un, mix16<0>(cl[0], un, 0.f)), mix16<1>(ch[0], un, mix16<1>(cl[0], un, 0.f)),
-                mix16<0>(ch[1], un, mix16<0>(cl[1], un, 0.f)), mix16<1>(ch[1], un, mix16<1>(cl[1], un, 0.f))};
-    else
-      v = f32x4{mix16<0>(ch[0], un, 0.f), mix16<1>(ch[0], un, 0.f), mix16<0>(ch[1], un, 0.f), mix16<1>(ch[1], un, 0.f)};
-    ACT_STORE((f32x4*)&dst[(size_t)row * W + 4 * g], v);
-  }
-  __device__ __forceinline__ void operator()(int it) {
-    if (it > 0) flush(it - 1);
-    read(it, ch, cl);
-  }
-#else
-  __device__ __forceinline__ void flush(int) const {}
-  __device__ __forceinline__ void operator()(int it) {
-    // (read, convert and store in one go: carrying the next piece's LDS words across the MFMAs cost the forward kernel, which
-    // sits at 256 registers, 47 spilled registers)
-    read(it, ch, cl);
-    const int idx = tid + it * THREADS, row = idx / GPR, g = idx % GPR;
-    const float un = row < TILE / 2 ? un0 : un1;
-    f32x4 v;
-    if constexpr (NP == 2)
-      v = f32x4{mix16<0>(ch[0], un, mix16<0>(cl[0], un, 0.f)), mix16<1>(ch[0], un, mix16<1>(cl[0], un, 0.f)),
-                mix16<0>(ch[1], un, mix16<0>(cl[1], un, 0.f)), mix16<1>(ch[1], un, mix16<1>(cl[1], un, 0.f))};
-    else
-      v = f32x4{mix16<0>(ch[0], un, 0.f), mix16<1>(ch[0], un, 0.f), mix16<0>(ch[1], un, 0.f), mix16<1>(ch[1], un, 0.f)};
-    ACT_STORE((f32x4*)&dst[(size_t)row * W + 4 * g], v);
-  }
-#endif
-};
 
 // tile_store16 for a half-width tensor that also adds every stored row to the accumulator of the row's ray slot (sums[slot],
 // this thread's four columns; slot_s[row] < NS): the per-tile part of upnerf_ray_sum (see upnerf_field_bwd_args.tile_part).
@@ -313,9 +222,8 @@ __device__ __forceinline__ void tile_copy16(const char* Ph, int e, int e2, uint1
                                             int m0, int M, int tid) {
   constexpr int GPR = W >> 3, ITER = TILE * GPR / THREADS;
   if (tid < TILE / 64 && m0 + 64 * tid < M) dexp[m0 / 64 + tid] = tid == 0 ? e : e2;
-#if F16_WAVES == 8  // (128-register build; in the default build the hoisted, partly spilled offsets measured FASTER than recomputing them)
-  asm volatile("" : "+v"(tid));
-#endif
+  // tid is made opaque only in the calls without an exponent table; elsewhere the row offsets hipcc hoists out of the layer loop
+  // (and partly spills) measured FASTER than recomputing them
   if (dexp == nullptr) asm volatile("" : "+v"(tid));
 #pragma unroll
   for (int it = 0; it < ITER; ++it) {
@@ -393,7 +301,7 @@ __device__ __forceinline__ void put_quad(char* Ph, char* Pl, int row, int col, c
 
 // ------------------------------------------------------------------------------------------------------------------
 template <int NP, int TILE, int NW>
-__global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_fwd_kernel(upnerf_layout L, upnerf_field_fwd_args a) {
+__global__ __launch_bounds__(64 * NW, F16_WAVES_PER_EU) void field16_fwd_kernel(upnerf_layout L, upnerf_field_fwd_args a) {
   constexpr int W = 256, W2 = 128, THREADS = 64 * NW;
   constexpr int AH = NP == 2 ? F16_AHEAD_X3 : F16_AHEAD_F16;  // weight k-blocks in flight (common16.cuh:mma16_lds)
   __shared__ __attribute__((aligned(16))) char planes[NP * TILE * W * 2];
@@ -419,11 +327,7 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_fwd_kernel(
   char* Pl = planes + (NP - 1) * TILE * W * 2;  // NP == 1: never dereferenced
   using TW = WaveTile16<W, TILE, NW>;
   using TH = WaveTile16<W2, TILE, NW>;
-#if F16_WAVES == 8 || defined(F16_SCALAR_WAVE)
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: no 64-bit per-lane bases)
-#else
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#endif
   const int li = lane & 31, hh = lane >> 5;
   const int S = a.S, M = a.R * a.S, m0 = blockIdx.x * TILE;
   const float* __restrict__ P = a.P;
@@ -433,11 +337,6 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_fwd_kernel(
   const int hn0 = TH::n0(wave), hrow0 = TH::row0(wave);
   const int D = L.D;
   STAMP_DECL;
-#ifdef UPNERF_EXP_ASYMPRIO
-  // experiment: ONE of the two waves that share a SIMD (odd hardware wave slot) runs at a raised priority for the whole kernel --
-  // does an asymmetric pair settle into complementary phases (one workgroup's K loop beside the other's epilogue)?
-  if (__builtin_amdgcn_s_getreg(6148 /* HW_REG_HW_ID, wave_id[3:0] */) & 1) __builtin_amdgcn_s_setprio(UPNERF_EXP_ASYMPRIO);
-#endif
   if (tid == 0) {
 #pragma unroll
     for (int l = 0; l < UPNERF_MAX_D; ++l) {
@@ -565,17 +464,9 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_fwd_kernel(
 
   // fp32 copy of trunk activation h_lidx for the weight gradients, from the planes (with fp16 storage only the last layer)
   auto store_h32 = [&](int lidx, float un0, float un1) {
-#ifndef UPNERF_EXP_NOSTORE
     if (a.h && (!a.h_last_only || lidx == D - 1))
       tile_store16<NP, W, TILE, THREADS, W>(Ph, Pl, 0, un0, un1, a.h + (a.h_last_only ? 0 : (size_t)lidx * M * W), W, m0, M, tid);
-#endif
   };
-  // fp32 activation stores inside the K loops (PlaneStore): whole tiles of a training pass that stores every layer
-#ifdef UPNERF_EXP_NOSTORE
-  const bool h_in_loop = false;
-#else
-  const bool h_in_loop = F16_STORE_IN_LOOP && a.h && !a.h_last_only && (M % TILE) == 0 && NW == 4;
-#endif
   // ---- trunk (nerf.py:84-87)
   STAMP(7);  // sample positions + encoding + x0 store
   // exponents of the two row halves of the planes (rows [0, TILE/2) and [TILE/2, TILE)): the lockstep stages keep them equal
@@ -599,20 +490,13 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_fwd_kernel(
       }
       mma16_glb<NP, UPNERF_X0>(acc, ap, ecur, P16 + 4 * (size_t)wl, (UPNERF_X0 + W) / 16, n0, 0, lane);
       mma16_lds<NP, W, W / 16, AH>(acc, Ph, Pl, row0, 0, P16 + 4 * (size_t)wl, (UPNERF_X0 + W) / 16, n0, UPNERF_X0, lane);
-    } else if (h_in_loop) {
-      // h_{l-1} leaves from the planes this K loop reads, one 1 KiB piece per k-block (PlaneStore)
-      PlaneStore<NP, W, TILE, THREADS> ps(Ph, Pl, a.h + ((size_t)(l - 1) * M + m0) * W, pow2f(-ehalf[0]), pow2f(-ehalf[1]), tid);
-      static_assert(PlaneStore<NP, W, TILE, THREADS>::ITER == W / 16, "one store piece per k-block");
-      mma16_lds<NP, W, W / 16, AH>(acc, Ph, Pl, row0, 0, P16 + 4 * (size_t)wl, W / 16, n0, 0, lane, ps);
-      ps.flush(W / 16 - 1);
     } else {
       mma16_lds<NP, W, W / 16, AH>(acc, Ph, Pl, row0, 0, P16 + 4 * (size_t)wl, W / 16, n0, 0, lane);
     }
     STAMP(1);
     // h_{l-1} leaves from the planes this K loop has just read, in whole lines, behind the loop's last wait for a weight
-    // fragment: the epilogue, two barriers and the plane write pass before the wave waits for a load again (the skip layer,
-    // ragged last tiles and fp16-stored operands; everything else went out inside the K loop)
-    if (l >= 1 && !(h_in_loop && l != L.skip)) store_h32(l - 1, pow2f(-ehalf[0]), pow2f(-ehalf[1]));
+    // fragment: the epilogue, two barriers and the plane write pass before the wave waits for a load again
+    if (l >= 1) store_h32(l - 1, pow2f(-ehalf[0]), pow2f(-ehalf[1]));
     // the bias row comes from the LDS copy made at kernel start: a global load here would open every epilogue with an L2
     // round trip, and its wait would also wait for the stores just issued (vmcnt retires in order)
     f32x4 bl[TW::NT][4];
@@ -667,15 +551,9 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_fwd_kernel(
     acc_zero(acc);
     f32x4 be[TW::NT][4];
     load_cols(be, P + L.be, n0, hh);
-    if (h_in_loop) {
-      PlaneStore<NP, W, TILE, THREADS> ps(Ph, Pl, a.h + ((size_t)(D - 1) * M + m0) * W, pow2f(-ehalf[0]), pow2f(-ehalf[1]), tid);
-      mma16_lds<NP, W, W / 16, AH>(acc, Ph, Pl, row0, 0, P16 + 4 * (size_t)L.we, W / 16, n0, 0, lane, ps);
-      ps.flush(W / 16 - 1);
-    } else {
-      mma16_lds<NP, W, W / 16, AH>(acc, Ph, Pl, row0, 0, P16 + 4 * (size_t)L.we, W / 16, n0, 0, lane);
-      asm volatile("" ::: "memory");  // the bias loads above stay above the stores below
-      store_h32(D - 1, pow2f(-ehalf[0]), pow2f(-ehalf[1]));
-    }
+    mma16_lds<NP, W, W / 16, AH>(acc, Ph, Pl, row0, 0, P16 + 4 * (size_t)L.we, W / 16, n0, 0, lane);
+    asm volatile("" ::: "memory");  // the bias loads above stay above the stores below
+    store_h32(D - 1, pow2f(-ehalf[0]), pow2f(-ehalf[1]));
     acc_fma_bias_h<false>(acc, pow2f(-(ehalf[0] + wexp[8])), pow2f(-(ehalf[1] + wexp[8])), be);
     const float wm = acc_absmax(acc);
     if (lane == 0) smax[wave] = wm;
@@ -713,7 +591,7 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_fwd_kernel(
   float mr = 0.0f, mc = 0.0f;
   // both heads on (the schedule's middle phase): their first layers contract the same 256 columns of e -- ONE K loop (common16.cuh:
   // mma16_lds_pair; per accumulator bitwise the two loops it replaces)
-  const bool pair = F16_JOIN_HEADS && a.use_rgb && a.use_cand && TH::NT == 1;
+  const bool pair = a.use_rgb && a.use_cand && TH::NT == 1;
   if (pair) {
     f32x16 acc2[TH::MT][2];
     acc_zero(acc2);
@@ -819,7 +697,7 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_fwd_kernel(
 // ------------------------------------------------------------------------------------------------------------------
 // Backward data-gradient chain (autograd of nerf.py:80-124), stage for stage as field.hip:field_bwd_kernel.
 template <int NP, int TILE, int NW>
-__global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_bwd_kernel(upnerf_layout L, upnerf_field_bwd_args a) {
+__global__ __launch_bounds__(64 * NW, F16_WAVES_PER_EU) void field16_bwd_kernel(upnerf_layout L, upnerf_field_bwd_args a) {
   constexpr int W = 256, W2 = 128, THREADS = 64 * NW;
   constexpr int AH = NP == 2 ? F16_AHEAD_X3 : F16_AHEAD_F16;
   constexpr int MAXRAYS = 3;            // rays a 64-sample tile can touch when S >= 32
@@ -839,7 +717,7 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_bwd_kernel(
   __shared__ int loff_s[UPNERF_MAX_D];  // t_w[l] (see the forward kernel: no runtime index into the by-value struct)
   __shared__ int wexp_s[WEXP_SLOTS];    // weight exponents (see the forward kernel: no global load in front of a contraction)
   // per-tile partial sums (a.tile_part, 64-sample tiles only): ray slot of every row; cross-wave reduction scratch
-  constexpr int TPW = (TILE == F16_TILE && NW == 4) ? NW : 1;  // (the 8-wave experiment of the 64-sample tile: no partial sums)
+  constexpr int TPW = (TILE == F16_TILE && NW == 4) ? NW : 1;
   __shared__ int slot_s[TILE];
   __shared__ __attribute__((aligned(16))) float red_s[TPW][32][24];
   const bool tp = TILE == F16_TILE && NW == 4 && a.tile_part != nullptr;
@@ -852,11 +730,7 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_bwd_kernel(
   using TW = WaveTile16<W, TILE, NW>;
   using TH = WaveTile16<W2, TILE, NW>;
   using TX = WaveTile16<UPNERF_X0, TILE, NW>;
-#if F16_WAVES == 8 || defined(F16_SCALAR_WAVE)
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: no 64-bit per-lane bases)
-#else
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#endif
   const int li = lane & 31, hh = lane >> 5;
   const int S = a.S, M = a.R * a.S, m0 = blockIdx.x * TILE, D = L.D;
   const float* __restrict__ P = a.P;
@@ -868,11 +742,6 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_bwd_kernel(
   const int ray0 = m0 / S;
   const unsigned long long* __restrict__ hm = (const unsigned long long*)a.hmask + (size_t)blockIdx.x * THREADS + tid;
   const size_t hm_stride = (size_t)gridDim.x * THREADS;
-#ifdef UPNERF_EXP_ASYMPRIO
-  // experiment: ONE of the two waves that share a SIMD (odd hardware wave slot) runs at a raised priority for the whole kernel --
-  // does an asymmetric pair settle into complementary phases (one workgroup's K loop beside the other's epilogue)?
-  if (__builtin_amdgcn_s_getreg(6148 /* HW_REG_HW_ID, wave_id[3:0] */) & 1) __builtin_amdgcn_s_setprio(UPNERF_EXP_ASYMPRIO);
-#endif
 
   if (tid == 64) {
 #pragma unroll
@@ -1076,7 +945,7 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_bwd_kernel(
       }
       __syncthreads();
       if (k < 4) *(f32x4*)&part[(k == 0 ? 0 : W2 * k) + 4 * g] = readout(k);
-#if F16_BH_SCALAR_SUMS_WAVE
+      // (four threads walking the tile's 64 rows instead left the other 252 waiting at the barrier behind them: round 6)
       if (wave == NW - 1) {  // sums of the per-row scalars (d b_csig, d b_r2): one row per lane, a butterfly over the wave (fixed order)
         static_assert(TILE == 64 || TPW == 1, "one row per lane");
         float v[4] = {dpc_s[lane], dprgb_s[lane][0], dprgb_s[lane][1], dprgb_s[lane][2]};
@@ -1089,15 +958,6 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_bwd_kernel(
           part[4 * W2 + 4 + lane] = 0.0f;  // pad
         }
       }
-#else
-      if (tid >= THREADS - 4) {  // sums of the per-row scalars: d b_csig, d b_r2 (four threads walking the 64 rows)
-        const int c = tid - (THREADS - 4);
-        float sacc = 0.0f;
-        for (int r = 0; r < TILE; ++r) sacc += c == 0 ? dpc_s[r] : dprgb_s[r][c - 1];
-        part[4 * W2 + c] = sacc;
-        part[4 * W2 + 4 + c] = 0.0f;  // pad
-      }
-#endif
       __syncthreads();
 #pragma unroll
       for (int c = 0; c < MAXRAYS; ++c) {
@@ -1204,9 +1064,7 @@ __global__ __launch_bounds__(64 * NW, F16_EU(NP, TILE)) void field16_bwd_kernel(
   acc_zero(accx);
   int ehalf[2] = {ecur, ecur};
   auto store_gz32 = [&](int lidx, float un0, float un1) {
-#ifndef UPNERF_EXP_NOSTORE
     if (a.gz_h) tile_store16<NP, W, TILE, THREADS, W>(Ph, Pl, 0, un0, un1, a.gz_h + (size_t)lidx * M * W, W, m0, M, tid);
-#endif
   };
   if (D == 1) store_gz32(0, pow2f(-ecur), pow2f(-ecur));
   {

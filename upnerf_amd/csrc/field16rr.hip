@@ -110,17 +110,9 @@ __device__ __forceinline__ float wave_max_rr(float m) {
 // ASM: per kernel.  Measured (alternating runs on one box, 8192 rays, `profiles/r06_ab_rr_dma.txt`): the BACKWARD kernel gains 4.4 %
 // (2.304 -> 2.202 ms; slab loop 300k -> 277k cycles per wave), the FORWARD kernel loses 1.7 % (1.989 -> 2.023 ms: its contraction gets
 // faster, 1081 -> 892 cycles per slab, and its barrier waits longer) -- so the forward kernel keeps the builtin.
-// RR_EXP_DMA_BUILTIN / RR_EXP_DMA_ASM force one form in both kernels (A/B builds).
 template <bool ASM>
 __device__ __forceinline__ void lds_dma16(const void* g, const void* lds) {
-#if defined(RR_EXP_DMA_BUILTIN)
-  constexpr bool use_asm = false;
-#elif defined(RR_EXP_DMA_ASM)
-  constexpr bool use_asm = true;
-#else
-  constexpr bool use_asm = ASM;
-#endif
-  if constexpr (!use_asm) {
+  if constexpr (!ASM) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
   } else {
     const unsigned d = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((__attribute__((address_space(3))) const char*)lds));
@@ -133,10 +125,6 @@ __device__ __forceinline__ void lds_dma16(const void* g, const void* lds) {
 // (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt_hi[15:14]).  A switch statement here compiled into a chain of
 // ~10 taken branches per call (round 4 stamps: ~400 cycles per slab).
 __device__ __forceinline__ void wait_vmcnt(int n) {
-#ifdef RR_SAFE_WAIT  // diagnostic: drain everything (A/B against the counted waits)
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  return;
-#endif
   n = __builtin_amdgcn_readfirstlane(n > 31 ? 31 : (n < 0 ? 0 : n));
 #define RR_WE(N) "s_waitcnt vmcnt(" #N ")\n\ts_branch 1f\n\t"
   asm volatile(
@@ -234,34 +222,22 @@ struct Ring {
     // vector-memory path takes it (~60 cycles each when eight waves issue together), and a blocked wave issues no MFMA.  The
     // lagging waves start a tile with the previous tile's epilogue anyway; their SIMD partners go straight to the matrix
     // work.  A leading wave waits for nothing of its own: the barrier behind the lagging waves' counted wait covers it.
-#ifndef RR_DMA_ALL
-#define RR_DMA_ALL 0  // 1 (experiment): all eight waves request (two pieces each per 16 KB slab) instead of the lagging four (four each)
-#endif
-    if (nreq < nslab && (RR_DMA_ALL || wave >= NW / 2)) {
-      constexpr int ND = RR_DMA_ALL ? NW : NW / 2;
+    // (All eight waves requesting, two pieces each per 16 KB slab instead of four: no difference -- profiles/r06_ab_rr_dma.txt.)
+    if (nreq < nslab && wave >= NW / 2) {
+      constexpr int ND = NW / 2;
       const int2 e = slab_s[nreq];
       const int off = __builtin_amdgcn_readfirstlane(e.x), kb = __builtin_amdgcn_readfirstlane(e.y);
       const int per = (kb + ND - 1) / ND;
       const char* g = src + (size_t)off + lane * 16;
       char* d = ring + slot * RR_SLOT;
       asm volatile("" ::: "memory");
-#ifndef RR_EXP_NODMA
 #pragma unroll 1
       for (int q = 0; q < per; ++q) {
-        int ch = (RR_DMA_ALL ? wave : wave - ND) + ND * q;
+        int ch = wave - ND + ND * q;
         ch = ch < kb ? ch : kb - 1;  // surplus waves repeat the last chunk (same bytes to the same place)
-#ifdef RR_EXP_PLAINLOAD  // timing experiment (wrong results): the same bytes by ordinary loads whose results are dropped
-        const f32x4 v = *(const volatile f32x4*)(g + (size_t)ch * 2048);
-        asm volatile("" ::"v"(v));
-#else
         lds_dma16<ASM_DMA>(g + (size_t)ch * 2048, d + ch * 1024);
-#endif
       }
       vmc += per;
-#else
-      (void)g;
-      (void)d;
-#endif
       asm volatile("" ::: "memory");
     }
     if (nreq < nslab) ++nreq;
@@ -293,9 +269,7 @@ struct Ring {
     wait_vmcnt(vmc - mark(slot + 1));
     RR_STAMP(0);  // wait for the pair's DMA (and, in order, for every older store)
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS traffic (transposer, previous fragments) is done
-#ifndef RR_EXP_NOBARRIER
     __builtin_amdgcn_s_barrier();
-#endif
     RR_STAMP(1);  // barrier
     asm volatile("" ::: "memory");
     issue(ring, (slot + 2) & 3);
@@ -303,13 +277,7 @@ struct Ring {
     RR_STAMP(2);  // DMA issue
     __builtin_amdgcn_sched_barrier(0);
   }
-  __device__ __forceinline__ void count(int n) {
-#ifdef RR_EXP_NOSTORE
-    (void)n;  // (the experiment issues no stores; the sign-bit DMAs count themselves through count_dma)
-#else
-    vmc += n;
-#endif
-  }
+  __device__ __forceinline__ void count(int n) { vmc += n; }
   __device__ __forceinline__ void count_dma(int n) { vmc += n; }
 };
 
@@ -321,29 +289,19 @@ __device__ __forceinline__ void kpart(f32x16& acc, const char* p, const h8 (&o)[
   static_assert(T <= N, "operand array");
   constexpr int SETS = PF + 1;
   h8 af[SETS];
-#ifdef RR_EXP_NOLDS  // timing experiment: no weight-fragment reads
-#pragma unroll
-  for (int t = 0; t < SETS; ++t) af[t] = o[0];
-#define RR_LDSREAD(dst, addr) asm volatile("" ::"v"(addr))
-#else
 #define RR_LDSREAD(dst, addr) dst = *(const h8*)(addr)
-#endif
 #pragma unroll
   for (int t = 0; t < PF && t < T; ++t) RR_LDSREAD(af[t], p + t * 1024);
 #pragma unroll
   for (int t = 0; t < T; ++t) {
     if (t + PF < T) RR_LDSREAD(af[(t + PF) % SETS], p + (t + PF) * 1024);
     __builtin_amdgcn_sched_barrier(0);
-#ifndef RR_EXP_NOMMA
     if (FIRST && t == 0) {  // C = 0 as an inline constant: no 16-register clear in front of the tile
       const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[t % SETS], o[t], z, 0, 0, 0);
     } else {
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[t % SETS], o[t], acc, 0, 0, 0);
     }
-#else
-    asm volatile("" ::"v"(af[t % SETS]), "v"(o[t]));
-#endif
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -385,11 +343,7 @@ __device__ __forceinline__ void stg_flush(const char* stg, int lane, float* __re
   for (int i = 0; i < 4; ++i) {
     const int row = 8 * i + (lane >> 3);
     const f32x4 v = *(const f32x4*)(stg + row * 128 + ((c ^ (row & 7)) << 4));
-#ifndef RR_EXP_NOSTORE
     if (dst) NT_STORE((f32x4*)(dst + (size_t)row * ld + col0 + 4 * c), v);  // (dst == nullptr: the sums only; the caller counts no stores)
-#else
-    asm volatile("" ::"v"(v));
-#endif
     if (part) {
       const float k = row < rb ? 1.0f : 0.0f;
       s0 += v * k;
@@ -526,9 +480,6 @@ __device__ __forceinline__ void operand_dots(const h8 (&op)[N], int e, const flo
 // one operand fragment (k-block blk of this wave's 32-row tile) -> the fragment-ordered fp16 tensor: 1 KiB per instruction
 // (fb: k-blocks per 32-row tile of the tensor -- 16 for a 256-wide one, 8 for a 128-wide one)
 __device__ __forceinline__ void frag_store(uint16_t* __restrict__ base, size_t tile32, int blk, int lane, const h8& v, int fb = 16) {
-#ifdef RR_EXP_NOSTORE  // timing experiment (wrong results): no activation / gradient stores at all
-  return;
-#endif
   NT_STORE((f32x4*)((char*)base + (tile32 * fb + blk) * 1024 + lane * 16), __builtin_bit_cast(f32x4, v));
 }
 
@@ -583,22 +534,16 @@ __device__ __forceinline__ void run_tiles(RG& rg, char* lds, bool lag, MMA mma, 
   static_for<0, NT>([&](auto J) {
     constexpr int j = decltype(J)::value, slot = j & 3;
     rg.begin(lds, slot);
-#ifndef RR_EXP_NOEPI
     if constexpr (j > 0) {
       if (lag) epi(std::integral_constant<int, (j > 0 ? j - 1 : 0)>{});
     }
-#endif
     RR_STAMP_RG(rg, 5);
     mma(lds + slot * RR_SLOT + rg.lane * 16);
     RR_STAMP_RG(rg, 4);
-#ifndef RR_EXP_NOEPI
     if (!lag) epi(J);
-#endif
     RR_STAMP_RG(rg, 5);
   });
-#ifndef RR_EXP_NOEPI
   if (lag) epi(std::integral_constant<int, NT - 1>{});
-#endif
 }
 
 // ================================================================================================================================
@@ -905,9 +850,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void rr16_fwd_kernel(upnerf_layout
           RR_STAMP_RG(rg, 8);  // fragment / row stores
         });
     if (train) {
-#ifndef RR_EXP_NOSTORE
       NT_STORE((u32x4_t*)((char*)a.hmask + (((size_t)l * nt32 + t32) * 64 + lane) * 16), words);
-#endif
       rg.count(1);
       if (lane == 0) a.hexp[(size_t)l * nt32 + t32] = eo;  // (one lane: not counted)
     }
@@ -988,9 +931,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void rr16_fwd_kernel(upnerf_layout
             tile_out<NW, 0, jp>(rg, to, blk, Nh, stg, t32, lane);
           });
       if (train) {
-#ifndef RR_EXP_NOSTORE
         NT_STORE((u32x4_t*)((char*)a.hmask + (((size_t)(D + 2) * nt32 + t32) * 64 + lane) * 16), words);
-#endif
         rg.count(1);
       }
       if (train && a.r1_16 && lane == 0) a.r1exp[t32] = e_R;
@@ -1033,9 +974,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void rr16_fwd_kernel(upnerf_layout
               tile_out<NW, 0, jp>(rg, to, blk, Nh, stg, t32, lane);
             });
         if (train) {
-#ifndef RR_EXP_NOSTORE
           NT_STORE((u32x4_t*)((char*)a.hmask + (((size_t)D * nt32 + t32) * 64 + lane) * 16), words);
-#endif
           rg.count(1);
         }
         if (train && a.g1_16 && lane == 0) a.g1exp[t32] = e_G;
@@ -1069,9 +1008,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void rr16_fwd_kernel(upnerf_layout
               tile_out<NW, 0, jp>(rg, to, blk, Bh, stg, t32, lane);
             });
         if (train) {
-#ifndef RR_EXP_NOSTORE
           NT_STORE((u32x4_t*)((char*)a.hmask + (((size_t)(D + 1) * nt32 + t32) * 64 + lane) * 16), words);
-#endif
           rg.count(1);
         }
         if (a.g2_16 && lane == 0) a.g2exp[t32] = e_G2;

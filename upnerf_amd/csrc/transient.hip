@@ -36,11 +36,7 @@ __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __bui
 // the register ring -- `wait_any` 0.59 of the wave cycles at `mfma_busy` 0.30, unchanged by a three-deep ring.  The values are
 // summed into a number nobody reads (kept alive by an empty asm at the end of the kernel).  A different workgroup -> XCD mapping
 // only lowers the coverage: nothing depends on it.
-#ifndef TR_WARM
-#define TR_WARM 1
-#endif
 __device__ __forceinline__ float warm_lines(const float* __restrict__ w, int nfloats, int lane_id, int nlanes) {
-  if (!TR_WARM) return 0.f;
   const int lines = nfloats >> 5;
   float s = w[(size_t)(lane_id < lines ? lane_id : lines - 1) << 5];  // unconditional: no branch, no wait (see the kernels' last line)
   for (int l = lane_id + nlanes; l < lines; l += nlanes) s += w[(size_t)l << 5];  // (launches of fewer than 96 workgroups only)
@@ -94,11 +90,7 @@ __device__ __forceinline__ void layer_fwd(const float* Xs, const float* __restri
       const int gn = g + u + 3 < G ? g + u + 3 : G - 1;
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-#ifdef TR_EXP_NOLOAD
-        b[(u + 3) & 3][t] = f32x4{1.f, 2.f, 3.f, (float)gn};
-#else
         b[(u + 3) & 3][t] = *(const f32x4*)(wp[t] + 16 * gn);
-#endif
       }
       __builtin_amdgcn_sched_barrier(0);
       const f32x4 a = *(const f32x4*)(xp + 16 * (g + u));
@@ -106,11 +98,7 @@ __device__ __forceinline__ void layer_fwd(const float* Xs, const float* __restri
       for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-#ifdef TR_EXP_NOMMA
-          acc[t][j] += a[j] * b[u][t][j];
-#else
           acc[t] = mfma4(a[j], b[u][t][j], acc[t]);
-#endif
         }
     }
   }
@@ -126,15 +114,11 @@ __device__ __forceinline__ void layer_fwd(const float* Xs, const float* __restri
     if constexpr (NT == 4) {
       const f32x4 o = {v[0], v[1], v[2], v[3]};
       *(f32x4*)&Ys[row * TR_LD + col0] = o;
-#ifndef TR_EXP_NOSTORE
       if (gout && m0 + row < R) *(f32x4*)&gout[(size_t)(m0 + row) * ldg + col0] = o;
-#endif
     } else {
       const f32x2 o = {v[0], v[1]};
       *(f32x2*)&Ys[row * TR_LD + col0] = o;
-#ifndef TR_EXP_NOSTORE
       if (gout && m0 + row < R) *(f32x2*)&gout[(size_t)(m0 + row) * ldg + col0] = o;
-#endif
     }
   }
 }

@@ -52,27 +52,13 @@ __device__ __forceinline__ h4 tr_read(const char* base, int byteoff) {
 // Round 6: the loads of a register set stay where the source puts them -- right behind the barrier, in front of the contraction.  Left
 // to itself hipcc SINKS them (they have no consumer until the next staging) to the END of the contraction: the ISA of round 5's build
 // had the requests of set 0 behind the staging of set 1 and `s_waitcnt vmcnt(0)` in front of that staging -- one register set in flight
-// instead of two, 32 KB per CU instead of 64.  WG_NO_PIN: the old placement, for A/B builds.
+// instead of two, 32 KB per CU instead of 64.
 // Measured (alternating runs on one box, profiles/r06_ab_wgrad_pin.txt): the fp16-operand kernels (wgrad_f16p_kernel, configs[3]) gain
 // 0.9 % on the Trevi step with two resp. four sets really in flight; the f16x3 kernel (three MFMAs per product) LOSES 0.6 % on the
 // headline step -- its stream is held by the clock the part keeps under matrix work + memory traffic (profiles/r06_wgrad_planes.txt),
 // not by the bytes in flight, and the sunk requests interleave better with its MFMAs.  So: pinned in wgrad_f16p_kernel
-// (WG_PIN_LOADS_P), not in wgrad_f16x3_kernel (WG_PIN_LOADS: -DWG_PIN_X3 turns it on, -DWG_NO_PIN turns both off).
-#if defined(WG_PIN_X3) && !defined(WG_NO_PIN)
-#define WG_PIN_LOADS __builtin_amdgcn_sched_barrier(0)
-#else
-#define WG_PIN_LOADS
-#endif
-#ifdef WG_NO_PIN
-#define WG_PIN_LOADS_P
-#else
+// (WG_PIN_LOADS_P), not in wgrad_f16x3_kernel.
 #define WG_PIN_LOADS_P __builtin_amdgcn_sched_barrier(0)
-#endif
-#ifdef UPNERF_EXP_HALFROW
-#define HALFROW_OK(T, c4) (!((T) == 256 && (c4) >= UPNERF_EXP_HALFROW))
-#else
-#define HALFROW_OK(T, c4) true
-#endif
 // HASV: a 1-wide head that reads the same B rows rides along (upnerf_wgrad_desc.v): vsum[k] += v[m] B[m][k] in fp32 on the
 // rows as they pass through the staging registers, sum of v beside it; per-split partials to vslabs[split][K + 4].
 template <int NP, int MTW, int NTW, bool HASV = false>
@@ -166,14 +152,14 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16x3_kernel(int M, int N
 #pragma unroll
     for (int q = 0; q < A4; ++q) {
       const int idx = tid + q * FX_THREADS, row = idx / (TN / 4), c4 = idx - row * (TN / 4);
-      const f32x4 v = (mc + row < mend && nblk + 4 * c4 < N && HALFROW_OK(TN, c4)) ? ra[q] : z4;
+      const f32x4 v = (mc + row < mend && nblk + 4 * c4 < N) ? ra[q] : z4;
       bsum += v;
       split_store(base, base + SZA, v, sa, row, 4 * c4);
     }
 #pragma unroll
     for (int q = 0; q < B4; ++q) {
       const int idx = tid + q * FX_THREADS, row = idx / (TK / 4), c4 = idx - row * (TK / 4);
-      const f32x4 v = (mc + row < mend && kblk + 4 * c4 < K && HALFROW_OK(TK, c4)) ? rb[q] : z4;
+      const f32x4 v = (mc + row < mend && kblk + 4 * c4 < K) ? rb[q] : z4;
       split_store(base + 2 * SZA, base + 2 * SZA + SZB, v, sb, row, 4 * c4);
       if constexpr (HASV) {
         const float vm = mc + row < mend ? rv[q] : 0.0f;
@@ -228,8 +214,7 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16x3_kernel(int M, int N
   constexpr bool TWO_SETS = MT * NT * 16 <= 64 || FX_CHUNK == 16;
   if constexpr (TWO_SETS) {
     // rows beyond mend are staged as zeros, so an odd number of chunks simply contracts one all-zero chunk
-    // (WG_EXP_*: timing experiments with wrong results -- what is left of the launch without the loads / the staging (which is
-    // also the only consumer of the loads: nothing waits for them any more) / the MFMAs; tools/bench_wgrad.py)
+    // (What is left of the launch without the loads -- staging + MFMAs alone -- is quoted at the loads above: 0.276 of 0.381 ms.)
     // Straight-line on purpose.  Round 5 tried to run the two jobs of an interval (contract the staged chunk | stage the next one)
     // in opposite orders in waves 0-3 and 4-7, so that one wave of a SIMD converts while its partner owns the matrix pipe
     // (MI355X_MICROARCH.md 'Two waves per SIMD' item 9): (a) both orders written out under one wave-uniform branch inside the
@@ -237,34 +222,18 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16x3_kernel(int M, int N
     // -- same launch time as before (0.550 against 0.545 ms stand-alone incl. the reduction); (c) a branch around two whole loops:
     // 47 spills; (d) the loop of (b) with the operand loads hidden in inline asm and hand-counted waits: hipcc re-used the loads'
     // destination registers for the contraction's operand reads while the loads were in flight (seen in the ISA; never run).
-    gload(ra0, rb0, rv0, mbeg);
-    WG_PIN_LOADS;  // (set 0 is requested BEFORE set 1: the wait in front of the first staging then counts four younger loads)
+    gload(ra0, rb0, rv0, mbeg);  // (set 0 is requested BEFORE set 1: the wait in front of the first staging then counts four younger loads)
     gload(ra1, rb1, rv1, mbeg + FX_CHUNK);
-    WG_PIN_LOADS;
 #pragma unroll 1
     for (int mc = mbeg; mc < mend; mc += 2 * FX_CHUNK) {
-#ifndef WG_EXP_NOSTAGE
       lstore(ra0, rb0, rv0, 0, mc);
-#endif
       __syncthreads();
-#ifndef WG_EXP_NOLOAD
       gload(ra0, rb0, rv0, mc + 2 * FX_CHUNK);
-      WG_PIN_LOADS;
-#endif
-#ifndef WG_EXP_NOMMA
       contract(0);
-#endif
-#ifndef WG_EXP_NOSTAGE
       lstore(ra1, rb1, rv1, 1, mc + FX_CHUNK);
-#endif
       __syncthreads();
-#ifndef WG_EXP_NOLOAD
       gload(ra1, rb1, rv1, mc + 3 * FX_CHUNK);
-      WG_PIN_LOADS;
-#endif
-#ifndef WG_EXP_NOMMA
       contract(1);
-#endif
     }
   } else {
     int buf = 0;
@@ -330,156 +299,6 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16x3_kernel(int M, int N
       for (int j = 1; j < G; ++j) t += redt[j * Q];
       vslabs[(size_t)split * (TK + 4) + TK] = t;
     }
-  }
-}
-
-// ---- 256 x 256 block on FOUR waves, one per SIMD (round 5; f16x3 arithmetic only) ------------------------------------------------
-// The eight-wave kernel above runs its chunk as [stage | barrier | operand reads | MFMAs] with all waves in lockstep: the two
-// waves of a SIMD share the matrix pipe while both contract and leave it idle while both convert, and nothing covers the LDS
-// latency of the operand reads (round 4's elimination: staging + MFMAs alone 0.276 ms, loads + MFMAs alone 0.222, everything
-// 0.381; MFMA busy 0.46).  hipcc would not give the two halves different orders (see that kernel's loop), so this kernel removes
-// the sharing instead: ONE wave per SIMD owns the pipe and 512 registers -- a 128 x 128 quarter of the block in 256 accumulator
-// registers, TWO operand-fragment sets (the reads of chunk c + 1 are issued in front of the MFMAs of chunk c), two register sets
-// of fp32 rows in flight -- and its own instruction stream interleaves the conversion of chunk c + 2 with the MFMAs of chunk c
-// (an MFMA holds the vector issue for 8 of its 32 cycles).  Four LDS images (chunk c + 2 is written while c and c + 1 are read),
-// one barrier per 16-row chunk.  Same arithmetic, same summation order inside a slab as the eight-wave kernel's (a row's products
-// are added in row order either way), so the slabs -- and everything downstream -- are bitwise those of that kernel.
-#define W4_THREADS 256
-template <int NP>
-__global__ __launch_bounds__(W4_THREADS, 1) void wgrad_f16x3_w4_kernel(int M, int N, int K, const float* __restrict__ A, int lda,
-                                                                     const float* __restrict__ B, int ldb,
-                                                                     const int* __restrict__ expo_a, const int* __restrict__ expo_b,
-                                                                     float* __restrict__ slabs, float* __restrict__ bslabs,
-                                                                     int rows_per_split, upnerf_wgrad_pending prev) {
-  static_assert(NP == 2, "the one-MFMA form has its own kernel family (wgrad_f16p_kernel)");
-  constexpr int TN = 256, TK = 256, CH = 16, NBUF = 4;
-  constexpr int SZ = 2 * CH * 256;          // bytes per plane (two 128-column panels of 16 rows)
-  constexpr int BUF = 4 * SZ;               // [A hi | A lo | B hi | B lo]
-  constexpr int R4 = CH * TN / 4 / W4_THREADS;  // 16-byte pieces of A (and of B) per thread and chunk: 4
-  constexpr int MT = 4, NT = 4;
-  __shared__ __attribute__((aligned(16))) char lds[NBUF * BUF];  // 128 KB
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 31, hh = lane >> 5;
-  const int n0 = (wave >> 1) * 128, k0 = (wave & 1) * 128;
-  const int split = blockIdx.x;
-  const int mbeg = split * rows_per_split;
-  const int mend = (mbeg + rows_per_split < M) ? mbeg + rows_per_split : M;
-  if (prev.nsplit > 0) {  // the first prev.rblocks workgroups sum the slabs of the previous launch of the run
-    const int wg = blockIdx.x;
-    if (wg < prev.rblocks) {
-      wgrad_reduce_body<4>(wg, tid, prev, (f32x4(*)[64])lds);
-      __syncthreads();
-    }
-  }
-  const int ea = expo_a[0], eb = expo_b[0];
-  const float sa = ldexpf(1.0f, ea), sb = ldexpf(1.0f, eb);
-  f32x16 acc[MT][NT];
-  acc_zero(acc);
-  f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
-  const int mlast = mend > mbeg ? mend - 1 : (mbeg < M ? mbeg : M - 1);
-  // this thread's pieces: row r0 + 4 q of the chunk, columns 4 c4 .. 4 c4 + 3 (64 threads per 256-column row)
-  const int r0 = tid >> 6, c4 = tid & 63;
-  const bool cola = 4 * c4 < N, colb = 4 * c4 < K;
-  const float* __restrict__ pa = A + (cola ? 4 * c4 : 0);
-  const float* __restrict__ pb = B + (colb ? 4 * c4 : 0);
-  f32x4 ra[2][R4], rb[2][R4];
-  auto gload = [&](f32x4 (&xa)[R4], f32x4 (&xb)[R4], int mc) {
-#pragma unroll
-    for (int q = 0; q < R4; ++q) {
-      const int m = mc + r0 + 4 * q < mlast ? mc + r0 + 4 * q : mlast;
-      xa[q] = WG_LOAD((const f32x4*)&pa[(size_t)m * lda]);
-      xb[q] = WG_LOAD((const f32x4*)&pb[(size_t)m * ldb]);
-    }
-  };
-  auto split_store = [&](char* hi, char* lo, f32x4 v, float sc, int off) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 hh2 __attribute__((ext_vector_type(2)));
-    const f2 x0 = f2{v[0], v[1]} * sc, x1 = f2{v[2], v[3]} * sc;
-    const hh2 h0 = __builtin_convertvector(x0, hh2), h1 = __builtin_convertvector(x1, hh2);
-    *(h4*)(hi + off) = __builtin_shufflevector(h0, h1, 0, 1, 2, 3);
-    const hh2 l0 = __builtin_convertvector(x0 - __builtin_convertvector(h0, f2), hh2);
-    const hh2 l1 = __builtin_convertvector(x1 - __builtin_convertvector(h1, f2), hh2);
-    *(h4*)(lo + off) = __builtin_shufflevector(l0, l1, 0, 1, 2, 3);
-  };
-  auto lstore = [&](const f32x4 (&xa)[R4], const f32x4 (&xb)[R4], int buf, int mc) {
-    char* base = lds + buf * BUF;
-    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < R4; ++q) {
-      const int row = r0 + 4 * q, off = himg<CH>(row, 4 * c4);
-      const bool in = mc + row < mend;
-      const f32x4 va = (in && cola) ? xa[q] : z4, vb = (in && colb) ? xb[q] : z4;
-      bsum += va;
-      split_store(base, base + SZ, va, sa, off);
-      split_store(base + 2 * SZ, base + 3 * SZ, vb, sb, off);
-    }
-  };
-  const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
-  const int trow = 8 * (g >> 1) + tq, tcol = 16 * (g & 1) + 4 * tp;
-  h8 fah[2][MT], fal[2][MT], fbh[2][NT], fbl[2][NT];
-  auto readfrag = [&](h8 (&ah)[MT], h8 (&al)[MT], h8 (&bh)[NT], h8 (&bl)[NT], int buf) {
-    const char* base = lds + buf * BUF;
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-      const int o0 = himg<CH>(trow, n0 + 32 * t + tcol), o1 = himg<CH>(trow + 4, n0 + 32 * t + tcol);
-      ah[t] = __builtin_shufflevector(tr_read(base, o0), tr_read(base, o1), 0, 1, 2, 3, 4, 5, 6, 7);
-      al[t] = __builtin_shufflevector(tr_read(base + SZ, o0), tr_read(base + SZ, o1), 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int o0 = himg<CH>(trow, k0 + 32 * t + tcol), o1 = himg<CH>(trow + 4, k0 + 32 * t + tcol);
-      bh[t] = __builtin_shufflevector(tr_read(base + 2 * SZ, o0), tr_read(base + 2 * SZ, o1), 0, 1, 2, 3, 4, 5, 6, 7);
-      bl[t] = __builtin_shufflevector(tr_read(base + 3 * SZ, o0), tr_read(base + 3 * SZ, o1), 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-  };
-  auto mma = [&](const h8 (&ah)[MT], const h8 (&al)[MT], const h8 (&bh)[NT], const h8 (&bl)[NT]) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-      }
-  };
-  // chunk c lives in image c % 4, fragment set c % 2; its rows travelled in register set c % 2 (rows past mend are staged as zeros)
-  gload(ra[0], rb[0], mbeg);
-  gload(ra[1], rb[1], mbeg + CH);
-  lstore(ra[0], rb[0], 0, mbeg);
-  gload(ra[0], rb[0], mbeg + 2 * CH);
-  __syncthreads();
-  readfrag(fah[0], fal[0], fbh[0], fbl[0], 0);
-  lstore(ra[1], rb[1], 1, mbeg + CH);
-  gload(ra[1], rb[1], mbeg + 3 * CH);
-  __syncthreads();
-#pragma unroll 1
-  for (int mc = mbeg; mc < mend; mc += 4 * CH) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {  // chunk c = (mc - mbeg) / CH + u: its images / sets are compile-time names
-      readfrag(fah[(u + 1) & 1], fal[(u + 1) & 1], fbh[(u + 1) & 1], fbl[(u + 1) & 1], (u + 1) & 3);  // chunk c + 1
-      mma(fah[u & 1], fal[u & 1], fbh[u & 1], fbl[u & 1]);                                              // chunk c
-      lstore(ra[u & 1], rb[u & 1], (u + 2) & 3, mc + (u + 2) * CH);                                      // chunk c + 2
-      gload(ra[u & 1], rb[u & 1], mc + (u + 4) * CH);                                                    // chunk c + 4
-      __syncthreads();
-    }
-  }
-  const float unscale = ldexpf(1.0f, -(ea + eb));
-  float* slab = slabs + (size_t)split * TN * TK;
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = n0 + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hh;
-        slab[n * TK + k0 + 32 * nt + li] = acc[mt][nt][r] * unscale;
-      }
-  if (bslabs) {  // column sums of A: thread t owns columns 4 * (t % 64) ..+3 of rows t / 64 + 4 q; the four threads sharing them meet in LDS
-    __syncthreads();
-    f32x4* red = (f32x4*)lds;
-    red[tid] = bsum;
-    __syncthreads();
-    if (tid < 64) *(f32x4*)&bslabs[(size_t)split * TN + 4 * tid] = ((red[tid] + red[tid + 64]) + red[tid + 128]) + red[tid + 192];
   }
 }
 
@@ -765,7 +584,7 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16p_kernel(int M, int N,
 #pragma unroll
   for (int u = 0; u < NS; ++u) {
     gload(ra[u], xa[u], rbp[u], xb[u], rbf[u], la[u], lb[u], rvv[u], mbeg + u * FX_CHUNK);
-    WG_PIN_LOADS_P;  // (the sets are requested in order, and stay where the source puts them: see WG_PIN_LOADS)
+    WG_PIN_LOADS_P;  // (the sets are requested in order, and stay where the source puts them)
   }
 #pragma unroll 1
   for (int mc = mbeg; mc < mend; mc += NS * FX_CHUNK) {
@@ -931,9 +750,6 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_planes_kernel(int M, cons
         nxa = aexp[mn >> 6];
         nxb = bexp[mn >> 6];
       }
-#ifdef WP_EXP_NOREAD  // timing experiment (wrong results): the DMA stream and the per-chunk synchronisation alone
-      continue;
-#endif
       const char* base = lds + (c % WP_SLOTS) * WP_SLOT;
       // 2^((ea - xa) + (eb - xb)) as fp16: both tile exponents folded into the B fragments
       int fe = (ea - xa) + (eb - xb);
@@ -979,17 +795,9 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_planes_kernel(int M, cons
         }
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-#ifndef WP_EXP_NOMMA  // timing experiment (wrong results): everything but the matrix work
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bh, acc[mt][nt], 0, 0, 0);
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bl, acc[mt][nt], 0, 0, 0);
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mt], bh, acc[mt][nt], 0, 0, 0);
-#else
-          acc[mt][nt][0] += (float)ah[mt][0] * (float)bh[0] + (float)al[mt][1] * (float)bl[1];
-#ifdef WP_EXP_SLEEP  // ... and the wave idles for the time its three MFMAs would hold the pipe when it has it to itself (96 cycles)
-          __builtin_amdgcn_s_sleep(1);
-          asm volatile("s_nop 15\n\ts_nop 15");
-#endif
-#endif
         }
       }
     }
@@ -1034,14 +842,6 @@ int launch_p(const Launch& L) {
   return (int)hipGetLastError();
 }
 
-#ifndef WG_NO_W4
-// 0 (make variant EXP=-DWG_NO_W4=0): the 256 x 256 block on wgrad_f16x3_w4_kernel (four waves, one per SIMD).  Built in round 5,
-// bitwise the eight-wave kernel's slabs (tests/test_hip_kernels.py runs green on either), measured SLOWER: 0.406 / 0.146 ms against
-// 0.366 / 0.135 ms stand-alone (786 432 / 262 144 rows, launch + reduction, tools/bench_wgrad.py) and 239.8 k against 244.1 k rays/s
-// on the step: a single in-order wave per SIMD hides neither the operand reads' LDS latency nor the conversion under its own MFMAs
-// as well as two waves hide them for each other.  1 = the eight-wave kernel (shipped).
-#define WG_NO_W4 1
-#endif
 // fp32 rows (UPNERF_WG_F32), split (planes 0 / 2) or rounded (planes 1) on load
 template <int MTW, int NTW, bool HASV = false>
 int launch(const Launch& L) {
@@ -1065,11 +865,8 @@ int launch_kind(const Launch& L, int TN, int TK) {
   switch (d.A.kind) {
     case UPNERF_WG_F32:
       if (d.v) return launch<4, 4, true>(L);
-      if (TN == 256 && TK == 256 && d.planes == 2 && d.N <= 256 && d.K <= 256 && !WG_NO_W4) {  // one wave per SIMD (wgrad_f16x3_w4_kernel)
-        hipLaunchKernelGGL((wgrad_f16x3_w4_kernel<2>), dim3(d.nsplit), dim3(W4_THREADS), 0, L.st, d.M, d.N, d.K, (const float*)d.A.p, d.A.ld,
-                           (const float*)d.B.p, d.B.ld, d.expo_a, d.expo_b, d.slabs, L.bslabs, L.rows, L.prev);
-        return (int)hipGetLastError();
-      }
+      // (A four-wave kernel for the 256 x 256 block, one wave per SIMD with a 128 x 128 quarter each, gave bitwise the same slabs and
+      // was SLOWER: 0.406 / 0.146 against 0.366 / 0.135 ms stand-alone, 239.8 k against 244.1 k rays/s on the step -- DESIGN.md 4.8.)
       if (TN == 256 && TK == 256) return launch<4, 4>(L);
       if (TN == 256 && TK == 128) return launch<4, 2>(L);
       if (TN == 256 && TK == 64) return launch<4, 1>(L);

@@ -39,7 +39,7 @@ PassPlan = namedtuple("PassPlan", "M Mp use16 rr tile_rows rows_capacity planes 
 
 
 def plan_pass(W, W2, D, R, S, mode, use_cand, use_rgb, rgb_joint, train, *, FIELD_MODE, WGRAD_STORE, FIELD_RR, TILE_PARTIALS,
-              WGRAD_CHAIN, JOIN_HEADS, VEC_RIDE, HMASK_SCALE) -> PassPlan:
+              WGRAD_CHAIN, JOIN_HEADS, VEC_RIDE) -> PassPlan:
     if FIELD_MODE not in MODES:
         raise ValueError(f"unknown FIELD_MODE {FIELD_MODE!r} (one of {MODES})")
     use16 = FIELD_MODE != "f32" and W == 256 and S >= 32  # the f16 matrix-core kernels (csrc/field16*.hip); otherwise fp32 MFMA
@@ -93,7 +93,7 @@ def plan_pass(W, W2, D, R, S, mode, use_cand, use_rgb, rgb_joint, train, *, FIEL
         "h": ((1 if store16 else D, M, W) if not (store16 and rr) else None) if train else None,
         "e": e, "e16": e16, "eexp": eexp,
         # ReLU decisions, 64 bits per lane and tile (rr: 128 per lane)
-        "hmask": (((D + 3) * Mp * 4 if rr else (D + 1) * ((M + 127) // 128) * 512 * HMASK_SCALE,)) if train else None,
+        "hmask": (((D + 3) * Mp * 4 if rr else (D + 1) * ((M + 127) // 128) * 512,)) if train else None,
         # running max|.| of the stored tensors (scales of the weight gradients): [0, 16) this pass, [16, 32) the backward kernel
         "mx32": (32,) if train else None,
         "g1": g1, "g1_16": g1_16, "g1exp": g1exp, "g2": g2, "g2_16": g2_16, "g2exp": g2exp, "r1": r1, "r1_16": r1_16, "r1exp": r1exp,
