@@ -1134,11 +1134,14 @@ def test_ray_aux_with_aligned_misaligned_and_absent_appearance_rows(hip, R):
     assert float((cpu(aux) - ref0).abs().max()) < 2e-6 and float(cpu(aux)[:, 27:].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("R", [37, 1024])
+@pytest.mark.parametrize("R", [1, 17, 37, 65, 129, 1024])
 def test_fused_transient_net_matches_torch(hip, R):
     """csrc/transient.hip (the whole TransientNet as one forward and one backward launch + one grouped weight-gradient launch)
     against the same module evaluated by plain torch ops in fp64 on the CPU (models/transient_net.py:27-38): outputs and every
-    gradient, a ragged last tile (R % 16 != 0), and against the per-layer HIP path it replaces."""
+    gradient, a ragged last tile (R % 16 != 0), and against the per-layer HIP path it replaces.  R = 1 .. 129 take the grouped
+    weight-gradient launch across its R // 64 split boundaries (no split, one, two) with ragged tiles, through the wrapper's
+    slicing of the three heads' rows and the two-block write of wt's gradient; the kernels themselves are held stage by stage in
+    tests/test_hip_transient.py."""
     import upnerf_amd.transient_net as tn
     from upnerf_amd import synth
     torch.manual_seed(5)
