@@ -1257,6 +1257,65 @@ typedef struct {
 } upnerf_tsdf_sample_args;
 int upnerf_tsdf_sample(const upnerf_tsdf_sample_args* a, void* stream);
 
+/* ---- DINO ViT descriptors and their PCA (csrc/dino.hip, upnerf_amd/dino.py): the pieces of a pre-norm vision
+ * transformer that upnerf_linear does not cover, and the moments of the descriptor PCA.  Added under ABI 11: new symbols only.
+ * Every entry point: arguments refused on the host before anything is launched, nothing allocated, no host read-back, no atomics
+ * and a fixed summation order (the same bits every run), all launches on `stream`.
+ *
+ * upnerf_vit_patches: rows[t][(c * 8 + ky) * 8 + kx] = ((v / 255 or v) - mean[c]) / std[c] with v = pixel (ty * stride + ky,
+ * tx * stride + kx) of channel c, t = ty * w0 + tx, h0 = 1 + (H - 8) / stride, w0 likewise: the operand of the patch projection
+ * as a GEMM against the flattened [D][3 * 8 * 8] convolution weight.  u8 != 0: the image is uint8 and divided by 255 first;
+ * else fp32, taken as already in [0, 1].  Pixels right of or below the last full patch are never read. */
+#define UPNERF_VIT_PATCH 8
+#define UPNERF_VIT_HEAD_DIM 64
+typedef struct {
+  int32_t H, W, stride, u8;
+  const void* image;         /* [H][W][3] uint8 or fp32 */
+  float mean[3], std[3];
+  float* rows;               /* [h0 * w0][192] */
+} upnerf_vit_patches_args;
+int upnerf_vit_patches(const upnerf_vit_patches_args* a, void* stream);
+
+/* upnerf_vit_embed: tok[0][:] = cls[:] + pos[0][:]; tok[n][:] += pos[n][:] for 1 <= n < N (rows 1.. hold the patch projection). */
+int upnerf_vit_embed(int N, int D, const float* cls, const float* pos, float* tok, void* stream);
+
+/* upnerf_layernorm: y[m][:] = (x[m][:] - mean) / sqrt(var + eps) * gamma + beta, var the mean of the squared CENTRED values.
+ * D <= 1024, D % 4 == 0 (else UPNERF_EUNSUP); one wave per row, the row in registers, the two sums in fp64.  y may be x. */
+int upnerf_layernorm(int M, int D, const float* x, int ldx, const float* gamma, const float* beta, float eps, float* y, int ldy,
+                     void* stream);
+
+/* upnerf_vit_attention: out[n][h * 64 + :] = softmax_j(scale * q[n][h] . k[j][h]) v[j][h], n, j < N, for each head h < heads.
+ * q, k, v: row n of head h starts at p + n * ld + h * 64 (for a fused [N][3 D] qkv buffer: q = qkv, k = qkv + D, v = qkv + 2 D,
+ * ld = 3 D); pointers 16-byte aligned, strides multiples of 4.  head_dim must be 64 (UPNERF_EUNSUP).  Streaming softmax: no
+ * N x N buffer exists; N is arbitrary.  out must not overlap q, k or v. */
+typedef struct {
+  int32_t N, heads, head_dim, reserved_;
+  const float* q; const float* k; const float* v;
+  int64_t ldq, ldk, ldv;
+  float scale, reserved2_;
+  float* out;                /* [N][ldo], columns [0, heads * 64) written */
+  int64_t ldo;
+} upnerf_vit_attention_args;
+int upnerf_vit_attention(const upnerf_vit_attention_args* a, void* stream);
+
+/* upnerf_vit_gelu: x = x / 2 * erfc(-x / sqrt(2)) in place (the exact erf form of GELU), n elements.
+ * upnerf_vit_residual: x += y, n elements. */
+int upnerf_vit_gelu(float* x, long long n, void* stream);
+int upnerf_vit_residual(float* x, const float* y, long long n, void* stream);
+
+/* upnerf_pca_fit: the moments of the PCA of T descriptor rows of width D (D <= 1024), each row divided by its L2 norm as it is
+ * read (no epsilon: a zero row gives NaN, as the division it restates).  mean[D] (fp32) = the column mean; gram[D][D] (fp64) =
+ * sum_t (u_t - mean)(u_t - mean)^T with the fp64 mean: fp64 partials per chunk of 1024 rows into `scratch`
+ * (upnerf_pca_fit_scratch(T, D) doubles), summed in chunk order by a second pass.  The eigenproblem is the caller's. */
+typedef struct {
+  int32_t T, D;
+  const float* x; int64_t ldx;
+  float* mean;               /* [D] */
+  double* gram;              /* [D][D] */
+} upnerf_pca_fit_args;
+long long upnerf_pca_fit_scratch(int T, int D);
+int upnerf_pca_fit(const upnerf_pca_fit_args* a, double* scratch, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

@@ -202,6 +202,21 @@ class LpipsScratchArgs(C.Structure):
                 ("act0_elems", C.c_int64), ("act1_elems", C.c_int64), ("part_elems", C.c_int64)]
 
 
+class VitPatchesArgs(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("stride", C.c_int32), ("u8", C.c_int32), ("image", _fp),
+                ("mean", C.c_float * 3), ("std", C.c_float * 3), ("rows", _fp)]
+
+
+class VitAttentionArgs(C.Structure):
+    _fields_ = [("N", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32), ("reserved_", C.c_int32),
+                ("q", _fp), ("k", _fp), ("v", _fp), ("ldq", C.c_int64), ("ldk", C.c_int64), ("ldv", C.c_int64),
+                ("scale", C.c_float), ("reserved2_", C.c_float), ("out", _fp), ("ldo", C.c_int64)]
+
+
+class PcaFitArgs(C.Structure):
+    _fields_ = [("T", C.c_int32), ("D", C.c_int32), ("x", _fp), ("ldx", C.c_int64), ("mean", _fp), ("gram", _fp)]
+
+
 class SceneImage(C.Structure):
     _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("x0", C.c_int32), ("x1", C.c_int32),
                 ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
@@ -434,9 +449,17 @@ _SIGNATURES = {
     "upnerf_tsdf_integrate": [C.POINTER(TsdfIntegrateArgs), _p],
     "upnerf_tsdf_surface": [C.POINTER(TsdfSurfaceArgs), _p],
     "upnerf_tsdf_sample": [C.POINTER(TsdfSampleArgs), _p],
+    "upnerf_vit_patches": [C.POINTER(VitPatchesArgs), _p],
+    "upnerf_vit_embed": [_i, _i, _p, _p, _p, _p],
+    "upnerf_layernorm": [_i, _i, _p, _i, _p, _p, _f, _p, _i, _p],
+    "upnerf_vit_attention": [C.POINTER(VitAttentionArgs), _p],
+    "upnerf_vit_gelu": [_p, C.c_longlong, _p],
+    "upnerf_vit_residual": [_p, _p, C.c_longlong, _p],
+    "upnerf_pca_fit_scratch": [_i, _i],
+    "upnerf_pca_fit": [C.POINTER(PcaFitArgs), _p, _p],
 }
 _LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
-             "upnerf_occ_compact_scratch")
+             "upnerf_occ_compact_scratch", "upnerf_pca_fit_scratch")
 MAX_SCALARS = 96
 EXPORTS = tuple(_SIGNATURES)
 
