@@ -160,3 +160,17 @@ def test_pack_without_the_feature_layer_places_the_colour_matrix_as_it_stands():
     (m.packer.pack(p) * torch.arange(L.total, dtype=torch.float32)).sum().backward()
     g = p["rgb_share_layer.0.weight"].grad
     assert torch.equal(g[3, :5], torch.arange(L.wr1 + 3 * (W + AUXK), L.wr1 + 3 * (W + AUXK) + 5, dtype=torch.float32))
+
+
+@pytest.mark.parametrize("W,D,skips", [(256, 8, [4]), (256, 8, []), (256, 8, [1]), (64, 4, []), (256, 1, []), (64, 1, [])])
+def test_layout_struct_is_layout_offsets_field_by_field(W, D, skips):
+    """The struct the kernels take holds pass_plan.layout_offsets' integers (which the weight-gradient schedule reads), layers
+    beyond D zero."""
+    from upnerf_amd import _lib, pass_plan
+    from upnerf_amd.packing import NerfPacker
+    pk = NerfPacker(W, D, skips, 63, 27, 384, 48, 16)
+    want = pass_plan.layout_offsets(W, D, skips[0] if skips else -1)
+    assert pk.offsets == want and {f for f, _ in _lib.Layout._fields_} == set(want._fields)
+    for f, v in want._asdict().items():
+        got = getattr(pk.L, f)
+        assert (list(got) == list(v) + [0] * (_lib.MAX_D - D)) if isinstance(v, tuple) else got == v, f

@@ -10,13 +10,12 @@ import os
 
 import torch
 
-from .pass_plan import (AUXK, RR_PART_STRIDE, TILE_PART_STRIDE, WG_F16_FRAG, WG_F16_TILE, WG_F24, WG_F32, WG_PLANES,  # noqa: F401
-                        X0)
+from .pass_plan import (AUXK, CK, RR_PART_STRIDE, TILE_PART_STRIDE, WG_F16_FRAG, WG_F16_TILE, WG_F24, WG_F32,  # noqa: F401
+                        WG_PLANES, X0)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UPNERF_LIB") or os.path.join(_HERE, "libupnerf_hip.so")  # UPNERF_LIB: diagnostic builds only
 MAX_D = 8
-CK = 16
 
 _fp = C.c_void_p
 

@@ -19,6 +19,7 @@ import torch.nn.functional as F
 
 from . import zero_pool
 from ._lib import AUXK, CK, MAX_D, X0, Frag16Desc, FragDesc, Layout
+from .pass_plan import layout_offsets
 
 
 def _align(n, a=4):
@@ -125,38 +126,14 @@ class NerfPacker:
         self.skip = active[0] if active else -1
         self.feat_dim, self.A, self.C, self.in_dir = feat_dim, appearance_dim, candidate_dim, in_dir
         self.has_cand = candidate_dim > 0
+        # the offsets as plain integers (pass_plan.wgrad_schedule reads these), and the same in the struct the kernels take
+        self.offsets = layout_offsets(W, D, self.skip)
         L = Layout()
-        L.W, L.D, L.skip = W, D, self.skip
-        off = 0
-
-        def take(n):
-            nonlocal off
-            o = off
-            off += _align(n)
-            return o
-
-        W2 = self.W2
-        for l in range(D):
-            k = X0 if l == 0 else (X0 + W if l == self.skip else W)
-            L.w[l] = take(W * k)
-        for l in range(D):
-            L.b[l] = take(W)
-        L.we, L.be = take(W * W), take(W)
-        L.wsig, L.bsig = take(W), take(4)
-        L.wc1, L.bc1 = take(W2 * (W + CK)), take(W2)
-        L.wc2, L.bc2 = take(W2 * W2), take(W2)
-        L.wcsig, L.bcsig = take(W2), take(4)
-        L.wr1, L.br1 = take(W2 * (W + AUXK)), take(W2)
-        L.wr2, L.br2 = take(4 * W2), take(4)
-        L.total = off
-        off = 0
-        for l in range(D):
-            L.t_w[l] = take((X0 if l == 0 else W) * W)
-        L.t_skipx = take(X0 * W)
-        L.t_we = take(W * W)
-        L.t_head = take(W * W)
-        L.t_wc2 = take(W2 * W2)
-        L.t_total = off
+        for k, v in self.offsets._asdict().items():
+            if isinstance(v, tuple):  # one per layer
+                getattr(L, k)[:D] = v
+            else:
+                setattr(L, k, v)
         self.L = L
 
     # ------------------------------------------------------------------ forward-form buffer

@@ -1,12 +1,16 @@
-"""What one field pass stores and in which form, decided ONCE: rendering._FieldPass allocates its forward and backward buffers
-from this plan and takes the operand forms of its weight gradients from it; geometry's density-only pass takes its tiling from it.
-Host arithmetic only -- neither the library nor a device is touched, a plan can be built (and tested) anywhere."""
+"""One host-side description of a field pass, decided ONCE.  plan_pass: what the pass stores and in which form --
+rendering._FieldPass allocates its forward and backward buffers from the plan and reads its weight gradients' operands from it;
+geometry's density-only pass takes its tiling from it.  layout_offsets: where every parameter block sits in the packed buffer P
+(packing.NerfPacker fills the kernels' layout struct from it).  wgrad_schedule: the launches that write the gradient of P, against
+which operands and into which block -- _FieldPass.backward executes that list and holds no offset or exponent slot of its own.
+Host arithmetic only -- neither the library nor a device is touched, all three can be built (and tested) anywhere."""
 from __future__ import annotations
 
 from collections import namedtuple
+from functools import lru_cache
 
 # constants of include/upnerf_hip.h that size a pass (_lib re-exports them beside the structs)
-X0, AUXK = 64, 80
+X0, AUXK, CK = 64, 80, 16
 WG_F32, WG_F16_TILE, WG_F16_FRAG, WG_F24, WG_PLANES = range(5)  # UPNERF_WG_*: how a weight-gradient operand is stored
 TILE_PART_STRIDE = 1288  # UPNERF_TILE_PART_STRIDE
 RR_PART_STRIDE = 512  # UPNERF_RR_PART_STRIDE
@@ -123,3 +127,104 @@ def plan_pass(W, W2, D, R, S, mode, use_cand, use_rgb, rgb_joint, train, *, FIEL
             ops.update({k: Operand(WG_F32, W2, k) for k, on in (("gz_g1", cand), ("gz_r1", col)) if on})
     return PassPlan(M, Mp, use16, rr, RR_TILE if rr else 64, Mp if rr else 0, 1 if FIELD_MODE == "f16" else 2, store16, store24, ntile,
                     e_frag, joined, rg16, g2f, partials, ride, buffers, ops)
+
+
+# ---- where the parameter blocks sit: include/upnerf_hip.h:upnerf_layout, field by field (w, b, t_w: one offset per layer)
+LayoutOffsets = namedtuple("LayoutOffsets", "W D skip w b we be wsig bsig wc1 bc1 wc2 bc2 wcsig bcsig wr1 br1 wr2 br2 total "
+                                            "t_w t_skipx t_we t_head t_wc2 t_total")
+
+
+def layout_offsets(W, D, skip=-1) -> LayoutOffsets:
+    """Offsets (floats) of the blocks of P and of the transposed copies PT: laid end to end in the order of the struct, each
+    starting on a multiple of 4.  skip: the layer that also reads the encoding (its matrix is [W][X0 + W]), -1 = none."""
+    W2 = W // 2
+
+    def end_to_end(sizes):
+        offs, off = [], 0
+        for n in sizes:
+            offs.append(off)
+            off += (n + 3) // 4 * 4
+        return offs, off
+
+    kin = [X0 if l == 0 else X0 + W if l == skip else W for l in range(D)]
+    o, total = end_to_end([W * k for k in kin] + [W] * D + [W * W, W, W, 4, W2 * (W + CK), W2, W2 * W2, W2, W2, 4,
+                                                         W2 * (W + AUXK), W2, 4 * W2, 4])
+    t, t_total = end_to_end([(X0 if l == 0 else W) * W for l in range(D)] + [X0 * W, W * W, W * W, W2 * W2])
+    return LayoutOffsets(W, D, skip, tuple(o[:D]), tuple(o[D:2 * D]), *o[2 * D:], total, tuple(t[:D]), *t[D:], t_total)
+
+
+# ---- the weight-gradient launches of a pass
+# Slots of the two [16] tables of running maxima (upnerf_field_fwd_args.amax: the B operands, upnerf_field_bwd_args.gmax: the A
+# operands) and of the exponents upnerf_scale_exponents makes of them.  Trunk layer l: slot l in both (h_l, gz_l); behind them:
+ExpSlots = namedtuple("ExpSlots", "final g1 g2 r1 joined x0")  # e / gz_e, g1 / gz_g1, gz_g2, r1 / gz_r1, [gz_r1 | gz_g1], x0
+
+
+def exp_slots(D) -> ExpSlots:
+    return ExpSlots(D, D + 1, D + 2, D + 3, D + 4, D + 4)  # (joined is a slot of gmax, x0 one of amax)
+
+
+# What a Launch is: MAT upnerf_wgrad16 (dW [N][ldo] = A^T B, db = column sums of A), VEC / VEC_FRAG upnerf_vec_wgrad / its twin
+# for operand fragments (a 1- or 3-wide head `v` against the rows of B), PART the same result out of the backward kernel's per-tile
+# sums (upnerf_tile_part_finish writes it, no launch of its own), RAY upnerf_wgrad over rays (fp32; per-ray sums A against the
+# per-ray inputs B).
+MAT, VEC, VEC_FRAG, PART, RAY = "mat", "vec", "vec_frag", "part", "ray"
+# A, B: (name in PassPlan.operands, layer or None) -- RAY: (buffer of the backward pass, None), (saved input, None); v: the head's
+# buffer [M] or [M][4], N of them used; ea / eb: exponent slots of A / B (MAT only); dW, db, dW2, db2: offsets into dP (floats);
+# n2 > 0: rows [n2, N) go to dW2 / ldo2 / db2; ride: the VEC record of a 1-wide head that rides on this MAT launch, or None
+Launch = namedtuple("Launch", "kind A B v N K ea eb dW ldo db n2 dW2 ldo2 db2 ride", defaults=(0, None, 0, None, None))
+# trunk: the layers, the final layer and the shared density head; part: None, or the (candidate, colour) PART records (None: that
+# head is off); cand, rgb: the heads' own launches (the joined first layers are the candidate segment's), () where a head is off
+Schedule = namedtuple("Schedule", "trunk part cand rgb")
+
+
+def wgrad_schedule(plan: PassPlan, L, skip, use_cand, use_rgb) -> Schedule:
+    """Every launch of a training pass that writes into dP, in launch order; each parameter block of the heads that are on is
+    written by exactly one of them.  L: the layout's offsets (LayoutOffsets, or anything hashable with its fields)."""
+    frag = frozenset(k for k, o in plan.operands.items() if o.kind == WG_F16_FRAG)
+    return _schedule(plan.joined, plan.ride, plan.partials == "tile", frag, L, skip, bool(use_cand), bool(use_rgb))
+
+
+@lru_cache(maxsize=None)
+def _schedule(joined, ride, tile_part, frag, L, skip, cand, rgb) -> Schedule:
+    W, W2, D, E = L.W, L.W // 2, L.D, exp_slots(L.D)
+
+    def mat(A, N, B, K, ea, eb, dW, ldo, db, **kw):
+        return Launch(MAT, A, B, None, N, K, ea, eb, dW, ldo, db, **kw)
+
+    def vec(v, nvec, X, K, dW, db, part=False):
+        return Launch(PART if part else VEC_FRAG if X in frag else VEC, None, (X, None), v, nvec, K, None, None, dW, K, db)
+
+    trunk = []
+    for l in range(D):
+        if l == 0:
+            trunk.append(mat(("gz", 0), W, ("x0", None), X0, 0, E.x0, L.w[0], X0, L.b[0]))
+        elif l == skip:  # [W][X0 + W]: the encoding's columns, then the previous layer's
+            trunk.append(mat(("gz", l), W, ("x0", None), X0, l, E.x0, L.w[l], X0 + W, L.b[l]))
+            trunk.append(mat(("gz", l), W, ("h", l - 1), W, l, l - 1, L.w[l] + X0, X0 + W, None))
+        else:
+            trunk.append(mat(("gz", l), W, ("h", l - 1), W, l, l - 1, L.w[l], W, L.b[l]))
+    # the shared density head reads the final layer's B operand: where the plan says so its gradient rides on that launch
+    sig = vec("dpre_s", 1, "h_last", W, L.wsig, L.bsig)
+    trunk.append(mat(("gz_e", None), W, ("h_last", None), W, E.final, D - 1, L.we, W, L.be, ride=sig if ride else None))
+    if not ride:
+        trunk.append(sig)
+    csig = vec("dpre_c", 1, "g2", W2, L.wcsig, L.bcsig, tile_part)
+    rgb2 = vec("dpre_rgb", 3, "r1", W2, L.wr2, L.br2, tile_part)
+    e = ("e", None)
+    c, r = [], []
+    if cand:
+        if joined:  # rows [0, W2) -> wr1 / br1 (colour head), rows [W2, W) -> wc1 / bc1 (candidate head)
+            c.append(mat(("gz_rg", None), W, e, W, E.joined, E.final, L.wr1, W + AUXK, L.br1, n2=W2, dW2=L.wc1, ldo2=W + CK,
+                         db2=L.bc1))
+        else:
+            c.append(mat(("gz_g1", None), W2, e, W, E.g1, E.final, L.wc1, W + CK, L.bc1))
+        c.append(Launch(RAY, ("rs_c", None), ("c_rows", None), None, W2, CK, None, None, L.wc1 + W, W + CK, None))
+        c.append(mat(("gz_g2", None), W2, ("g1", None), W2, E.g2, E.g1, L.wc2, W2, L.bc2))
+        c += [] if tile_part else [csig]
+    if rgb:
+        if not joined:
+            r.append(mat(("gz_r1", None), W2, e, W, E.r1, E.final, L.wr1, W + AUXK, L.br1))
+        r.append(Launch(RAY, ("rs_r", None), ("aux", None), None, W2, AUXK, None, None, L.wr1 + W, W + AUXK, None))
+        r += [] if tile_part else [rgb2]
+    part = (csig if cand else None, rgb2 if rgb else None) if tile_part else None
+    return Schedule(tuple(trunk), part, tuple(c), tuple(r))
