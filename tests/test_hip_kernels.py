@@ -1588,10 +1588,11 @@ def test_hip_pack_matches_torch_pack_forward_and_backward(hip, W, D, cand, feat)
 
 
 # ------------------------------------------------------------------------------------------ parameter re-layout
-@pytest.mark.parametrize("W,D", [(256, 8), (64, 4)])
-def test_frag_copy_matches_torch_packing(hip, W, D):
+@pytest.mark.parametrize("W,D,skips", [pytest.param(256, 8, [4], id="256-8"), pytest.param(64, 4, [4], id="64-4"),
+                                       pytest.param(256, 8, [], id="256-8-noskip"), pytest.param(256, 8, [1], id="256-8-skip1")])
+def test_frag_copy_matches_torch_packing(hip, W, D, skips):
     from upnerf_amd.packing import NerfPacker
-    pk = NerfPacker(W, D, [4], 63, 27, 384, 48, 16)
+    pk = NerfPacker(W, D, skips, 63, 27, 384, 48, 16)
     P = gen((pk.L.total,), 60).cuda()
     assert torch.equal(pk.frag_hip(P), pk.frag(P))
     ref = pk.frag_t(pk.pack_t(P))

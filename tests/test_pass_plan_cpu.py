@@ -1,7 +1,8 @@
 """The plan of a field pass (upnerf_amd/pass_plan.py) over the full product of switches, pass kinds and shapes: every logical
 tensor in exactly one storage form, nothing planned that the pass does not need, whole tiles behind the register-resident
 kernels, operand kinds that follow the storage.  Its weight-gradient schedule over the same product and every skip position:
-each parameter block of the layout written exactly once, by launches whose operands the plan holds in a form the kernel takes.
+each parameter block of the layout written exactly once and at the pitch the table of blocks (param_blocks) states, by launches
+whose operands the plan holds in a form the kernel takes.
 Host arithmetic only: no library, no device."""
 import itertools
 
@@ -212,6 +213,17 @@ def coverage_check(sched, L, use_cand, use_rgb):
     assert bad.size == 0, (bad[:8], count[bad[:8]], expect[bad[:8]])
 
 
+def pitches_check(sched, L):
+    """Every matrix-shaped destination (MAT, RAY; the second row block of a split launch too) lies inside one block of the table
+    of parameter blocks and is written at that block's pitch."""
+    tab = [(pp.block_offset(L, b), b) for b in pp.param_blocks(L.W, L.D, L.skip)]
+    for r in records(sched):
+        if r.kind in (pp.MAT, pp.RAY):
+            for dW, ldo, rows in ((r.dW, r.ldo, r.n2 or r.N),) + (((r.dW2, r.ldo2, r.N - r.n2),) if r.n2 else ()):
+                o, b = max((x for x in tab if x[0] <= dW), key=lambda x: x[0])
+                assert ldo == b.ld and b.matrix and rows == b.used_rows and (dW - o) + r.K <= b.ld, (r, b.field)
+
+
 def operands_check(p, sched, W):
     """Every operand is planned in a form the launch takes (include/upnerf_hip.h: UPNERF_WG_*, upnerf_wgrad_desc.v, upnerf_vec_wgrad
     and its twin)."""
@@ -299,6 +311,7 @@ def test_every_schedule_writes_each_block_once():
             assert sched is pp.wgrad_schedule(p, L, skip, use_cand, use_rgb)  # built once
             if (sched, L, use_cand, use_rgb) not in covered:  # (a property of the schedule alone)
                 coverage_check(sched, L, use_cand, use_rgb)
+                pitches_check(sched, L)
                 covered.add((sched, L, use_cand, use_rgb))
             operands_check(p, sched, W)
             decisions_check(p, sched, L, use_cand, use_rgb)

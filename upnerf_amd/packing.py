@@ -12,44 +12,44 @@ and the kernels only ever see the [W/2][W] product; autograd differentiates the 
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 from typing import Dict
 
 import torch
 import torch.nn.functional as F
 
 from . import zero_pool
-from ._lib import AUXK, CK, MAX_D, X0, Frag16Desc, FragDesc, Layout
-from .pass_plan import layout_offsets
+from ._lib import CK, MAX_D, Frag16Desc, FragDesc, Layout, PackDesc
+from .pass_plan import (EXP_C1, EXP_C2, EXP_FINAL, EXP_HEAD_T, EXP_R1, block_offset, block_size, blocks_by_field, layout_offsets,
+                        param_blocks, t_blocks)
 
-
-def _align(n, a=4):
-    return (n + a - 1) // a * a
+# One copy of the pack launch: `rows` x `cols` floats from column col0 of the parameter `name` (row pitch src_ld) to column
+# dst_col0 of `block` (None: the scratch area behind P); form: "both", or the one direction ("fwd" / "bwd") it belongs to
+_Copy = namedtuple("_Copy", "name col0 rows cols src_ld block dst_col0 form")
 
 
 class _PackFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, packer, names, *tensors):
-        from ._lib import PackDesc, check, lib, ptr, stream
-        L, W, W2, Fd = packer.L, packer.W, packer.W2, packer.feat_dim
+        from ._lib import check, lib, ptr, stream
+        L, W, W2, Fd, ldr = packer.L, packer.W, packer.W2, packer.feat_dim, packer.block["wr1"].ld
         p = {n: t.detach().contiguous() for n, t in zip(names, tensors)}
         dev = tensors[0].device
         if not packer.encode_feat:  # no feature layer to fold into the colour head: the pack launch is the whole job
             buf = zero_pool.zeros(L.total, dev)
-            descs = packer._pack_descs(p, lambda n: p[n].data_ptr())
-            arr = (PackDesc * len(descs))(*descs)
-            check(lib.upnerf_pack(ptr(buf), arr, len(descs), 0, stream()), "upnerf_pack")
+            arr = packer._pack_descs(lambda n: p[n].data_ptr())
+            check(lib.upnerf_pack(ptr(buf), arr, len(arr), 0, stream()), "upnerf_pack")
             ctx.packer, ctx.names, ctx.buf = packer, names, None
             ctx.shapes = [tuple(t.shape) for t in tensors]
             return buf
         buf = zero_pool.zeros(L.total + W2 * Fd, dev)  # P followed by a copy of W_r1[:, :F]
         st = stream()
-        descs = packer._pack_descs(p, lambda n: p[n].data_ptr(), L.total)
-        arr = (PackDesc * len(descs))(*descs)
-        check(lib.upnerf_pack(ptr(buf), arr, len(descs), 0, st), "upnerf_pack")
+        arr = packer._pack_descs(lambda n: p[n].data_ptr(), L.total)
+        check(lib.upnerf_pack(ptr(buf), arr, len(arr), 0, st), "upnerf_pack")
         base = buf.data_ptr()
         wrF = base + 4 * L.total
         # folded colour layer: W_r1[:, :F] . W_feat -> wr1[:, :W];  W_r1[:, :F] . b_feat + b_r1 -> br1
-        check(lib.upnerf_linear(W2, W, Fd, wrF, Fd, ptr(p["feat_share_layer.weight"]), W, None, base + 4 * L.wr1, W + AUXK, 2,
+        check(lib.upnerf_linear(W2, W, Fd, wrF, Fd, ptr(p["feat_share_layer.weight"]), W, None, base + 4 * L.wr1, ldr, 2,
                                 st), "upnerf_linear")
         # W_r1[:, :F] . b_feat + b_r1 -> br1: one small matrix-vector launch straight into P (r3 ADVICE: rocBLAS gemv made the
         # summation order -- and with it the bitwise replay == eager contract -- depend on the rocBLAS version, and created its
@@ -63,10 +63,10 @@ class _PackFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dP):
-        from ._lib import PackDesc, check, lib, ptr, stream
+        from ._lib import check, lib, ptr, stream
         from .ops import wgrad_blocks_into, wgrad_into
         packer, names, buf = ctx.packer, ctx.names, ctx.buf
-        L, W, W2, Fd = packer.L, packer.W, packer.W2, packer.feat_dim
+        L, W, W2, Fd, ldr = packer.L, packer.W, packer.W2, packer.feat_dim, packer.block["wr1"].ld
         dP = dP.contiguous()
         dev = dP.device
         st = stream()
@@ -77,9 +77,8 @@ class _PackFn(torch.autograd.Function):
         for n, s_, k in zip(names, ctx.shapes, sizes):
             grads[n] = flat[off:off + k].view(s_)
             off += k
-        descs = packer._pack_descs(grads, lambda n: grads[n].data_ptr())
-        arr = (PackDesc * len(descs))(*descs)
-        check(lib.upnerf_pack(ptr(dP), arr, len(descs), 1, st), "upnerf_pack")
+        arr = packer._pack_descs(lambda n: grads[n].data_ptr())
+        check(lib.upnerf_pack(ptr(dP), arr, len(arr), 1, st), "upnerf_pack")
         if not packer.encode_feat:
             return (None, None) + tuple(grads[n] for n in names)
         feat_w, feat_b = ctx.saved_tensors
@@ -88,16 +87,16 @@ class _PackFn(torch.autograd.Function):
         g_wr = grads["rgb_share_layer.0.weight"]          # [W2][F + 27 + A]
         in_rgb = g_wr.shape[1]
         # d W_r1[:, :F] = gfold . W_feat^T + gbr1 (x) b_feat
-        check(lib.upnerf_linear(W2, Fd, W, base + 4 * L.wr1, W + AUXK, ptr(feat_w), W, None, ptr(g_wr), in_rgb, 0, st),
+        check(lib.upnerf_linear(W2, Fd, W, base + 4 * L.wr1, ldr, ptr(feat_w), W, None, ptr(g_wr), in_rgb, 0, st),
               "upnerf_linear")
         # (the second term, g_wr[:, :F] += gbr1 (x) b_feat, rides on the matrix-vector launch below: upnerf_matvec_rank1)
         # d W_feat = W_r1[:, :F]^T . gfold ; d b_feat = W_r1[:, :F]^T . gbr1 ; d b_r1 = gbr1
         wrF = buf[L.total:].view(W2, Fd)
         g_fw = grads["feat_share_layer.weight"]
         if Fd > 256:
-            wgrad_blocks_into(W2, wrF, Fd, Fd, dP, W + AUXK, W, g_fw.data_ptr(), W, None, dev, b_off=L.wr1)
+            wgrad_blocks_into(W2, wrF, Fd, Fd, dP, ldr, W, g_fw.data_ptr(), W, None, dev, b_off=L.wr1)
         else:
-            wgrad_into(W2, wrF, Fd, Fd, dP, W + AUXK, W, g_fw.data_ptr(), W, None, dev, b_off=L.wr1)
+            wgrad_into(W2, wrF, Fd, Fd, dP, ldr, W, g_fw.data_ptr(), W, None, dev, b_off=L.wr1)
         check(lib.upnerf_matvec_rank1(W2, Fd, ptr(wrF), Fd, ptr(gbr1), ptr(grads["feat_share_layer.bias"]), ptr(g_wr), in_rgb,
                                       ptr(feat_b), st), "upnerf_matvec_rank1")
         return (None, None) + tuple(grads[n] for n in names)
@@ -126,7 +125,9 @@ class NerfPacker:
         self.skip = active[0] if active else -1
         self.feat_dim, self.A, self.C, self.in_dir = feat_dim, appearance_dim, candidate_dim, in_dir
         self.has_cand = candidate_dim > 0
-        # the offsets as plain integers (pass_plan.wgrad_schedule reads these), and the same in the struct the kernels take
+        # the blocks of P and of the transposed set (pass_plan states them once), their offsets as plain integers
+        # (pass_plan.wgrad_schedule reads these), and the same in the struct the kernels take
+        self.blocks, self.tblocks, self.block = (f(W, D, self.skip) for f in (param_blocks, t_blocks, blocks_by_field))
         self.offsets = layout_offsets(W, D, self.skip)
         L = Layout()
         for k, v in self.offsets._asdict().items():
@@ -135,117 +136,97 @@ class NerfPacker:
             else:
                 setattr(L, k, v)
         self.L = L
+        self._copies = self._source_map()
+        self._pack_forms, self._frag_descs = {f: self._pack_template(f) for f in ("fwd", "bwd")}, self._make_frag_descs()
+
+    # layout field -> the reference parameter a block is a plain copy of (w, b: per layer; wr1, br1: _source_map)
+    PARAM = {"we": "xyz_encoding_final.weight", "be": "xyz_encoding_final.bias", "wsig": "share_sigma.0.weight",
+             "bsig": "share_sigma.0.bias", "wc1": "candidate_encoding.0.weight", "bc1": "candidate_encoding.0.bias",
+             "wc2": "candidate_encoding.2.weight", "bc2": "candidate_encoding.2.bias", "wcsig": "candidate_sigma.0.weight",
+             "bcsig": "candidate_sigma.0.bias", "wr2": "rgb_share_layer.2.weight", "br2": "rgb_share_layer.2.bias"}
+
+    def _source_map(self):
+        """Which columns of which reference parameter are copied where: [_Copy] in the order of the pack launch's descriptors (a
+        layer's matrix and bias together, then block order).  form "fwd": the contiguous copy of W_r1[:, :F] the fold reads, to a
+        scratch area behind P (block None); "bwd": d b_r1 = d br1, which forward is the mat-vec's output, not a copy."""
+        wr, naux = "rgb_share_layer.0.weight", self.in_dir + self.A
+        Fd = self.feat_dim if self.encode_feat else self.W  # columns of W_r1 in front of [PE(dir) | appearance]
+        out = []
+        for b in sorted(self.blocks, key=lambda b: self.D if b.layer is None else b.layer):
+            if b.field == "wr1" and self.encode_feat:  # the side columns; [:, :W] is the fold's
+                out += [_Copy(wr, Fd, b.rows, naux, Fd + naux, b, b.part("dir").col0, "both"),
+                        _Copy(wr, 0, b.rows, Fd, Fd + naux, None, 0, "fwd")]
+            elif b.field == "wr1":  # W_r1 = [W | PE(dir) | appearance] as it stands
+                out.append(_Copy(wr, 0, b.rows, Fd + naux, Fd + naux, b, 0, "both"))
+            elif b.field == "br1":
+                out.append(_Copy("rgb_share_layer.0.bias", 0, 1, b.cols, b.cols, b, 0, "bwd" if self.encode_feat else "both"))
+            elif self.has_cand or not self.PARAM.get(b.field, "").startswith("candidate"):  # its parts, side by side
+                name = self.PARAM.get(b.field) or f"xyz_encoding_{b.layer + 1}.0.{'weight' if b.field == 'w' else 'bias'}"
+                c0 = 0
+                for part in b.parts:
+                    if c0 and out[-1].dst_col0 + out[-1].cols == part.col0:  # no padding between the two: one copy
+                        out[-1] = out[-1]._replace(cols=out[-1].cols + part.cols)
+                    else:
+                        out.append(_Copy(name, c0, b.used_rows, part.cols, b.cols, b, part.col0, "both"))
+                    c0 += part.cols
+        return out
 
     # ------------------------------------------------------------------ forward-form buffer
     def pack(self, p: Dict[str, torch.Tensor]) -> torch.Tensor:
         """p: name -> parameter (reference names, e.g. 'xyz_encoding_1.0.weight').  Returns P [L.total]."""
-        W, W2, D, L = self.W, self.W2, self.D, self.L
-        dev, dt = p["xyz_encoding_1.0.weight"].device, torch.float32
+        dev = p["xyz_encoding_1.0.weight"].device
+        folded = {}
+        if self.encode_feat:  # the fold (module docstring): [W/2][W] in front of wr1's side columns, and br1
+            wrF = p["rgb_share_layer.0.weight"][:, :self.feat_dim]
+            folded = {"wr1": wrF @ p["feat_share_layer.weight"],
+                      "br1": (wrF @ p["feat_share_layer.bias"] + p["rgb_share_layer.0.bias"])[None]}
         pieces = []
-
-        def put(t, n):
-            t = t.reshape(-1)
-            pad = _align(n) - t.numel()
-            assert t.numel() == n and pad >= 0
-            pieces.append(F.pad(t, (0, pad)) if pad else t)
-
-        for l in range(D):
-            w = p[f"xyz_encoding_{l + 1}.0.weight"]
-            if l == 0:
-                put(F.pad(w, (0, 1)), W * X0)
-            elif l == self.skip:
-                put(torch.cat([F.pad(w[:, :63], (0, 1)), w[:, 63:]], 1), W * (X0 + W))
-            else:
-                put(w, W * W)
-        for l in range(D):
-            put(p[f"xyz_encoding_{l + 1}.0.bias"], W)
-        put(p["xyz_encoding_final.weight"], W * W)
-        put(p["xyz_encoding_final.bias"], W)
-        put(p["share_sigma.0.weight"], W)
-        put(F.pad(p["share_sigma.0.bias"], (0, 3)), 4)
-        if self.has_cand:
-            put(p["candidate_encoding.0.weight"], W2 * (W + CK))
-            put(p["candidate_encoding.0.bias"], W2)
-            put(p["candidate_encoding.2.weight"], W2 * W2)
-            put(p["candidate_encoding.2.bias"], W2)
-            put(p["candidate_sigma.0.weight"], W2)
-            put(F.pad(p["candidate_sigma.0.bias"], (0, 3)), 4)
-        else:
-            for n in (W2 * (W + CK), W2, W2 * W2, W2, W2, 4):
-                put(torch.zeros(n, device=dev, dtype=dt), n)
-        Fd = self.feat_dim if self.encode_feat else W
-        wr = p["rgb_share_layer.0.weight"]  # [W2][F + 27 + A]  (encode_feat = False: [W2][W + 27 + A])
-        fold = wr[:, :Fd] @ p["feat_share_layer.weight"] if self.encode_feat else wr[:, :W]  # [W2][W]
-        aux_w = F.pad(wr[:, Fd:], (0, AUXK - (self.in_dir + self.A))) if self.A else \
-            F.pad(wr[:, Fd:], (0, AUXK - self.in_dir))
-        put(torch.cat([fold, aux_w], 1), W2 * (W + AUXK))
-        put(wr[:, :Fd] @ p["feat_share_layer.bias"] + p["rgb_share_layer.0.bias"] if self.encode_feat
-            else p["rgb_share_layer.0.bias"], W2)
-        put(F.pad(p["rgb_share_layer.2.weight"], (0, 0, 0, 1)), 4 * W2)
-        put(F.pad(p["rgb_share_layer.2.bias"], (0, 1)), 4)
+        for b in self.blocks:
+            cols = [(0, folded[b.field])] if b.field in folded else []
+            cols += [(c.dst_col0, p[c.name].reshape(-1, c.src_ld)[:, c.col0:c.col0 + c.cols])
+                     for c in self._copies if c.block is b and c.form != "bwd"]
+            if not cols:  # a head the model does not have
+                pieces.append(torch.zeros(block_size(b), device=dev, dtype=torch.float32))
+                continue
+            row, end = [], 0
+            for c0, t in cols:  # (in column order) zero columns between the parts, behind the last one, then zero rows
+                row.append(F.pad(t, (c0 - end, 0)))
+                end = c0 + t.shape[1]
+            m = F.pad(torch.cat(row, 1), (0, b.ld - end)).reshape(-1)
+            pieces.append(F.pad(m, (0, block_size(b) - m.numel())))
         P = torch.cat(pieces)
-        assert P.numel() == L.total
+        assert P.numel() == self.L.total
         return P
 
     # ------------------------------------------------------------------ HIP pack (product path on the GPU)
-    def _pack_descs(self, p: Dict[str, torch.Tensor], base_of, scratch_off=None):
-        """Copy descriptors of pack().  `base_of(name)` gives the device pointer a descriptor starts from (the parameter,
-        or its gradient buffer for the backward); `scratch_off`: where the contiguous copy of W_r1[:, :F] goes (forward
-        only; its gradient comes from the fold, not from a copy)."""
-        from ._lib import PackDesc
-        W, W2, D, L, Fd = self.W, self.W2, self.D, self.L, self.feat_dim
-        out = []
+    def _pack_template(self, form):
+        """One direction's copy descriptors as bytes (the packer stays copyable), pointers as byte offsets; what fills them per call."""
+        cs = [c for c in self._copies if c.form in ("both", form)]
+        arr = (PackDesc * len(cs))(*[
+            PackDesc(4 * c.col0, c.rows, c.cols, c.src_ld, block_offset(self.L, c.block) + c.dst_col0 if c.block else 0,
+                     c.block.ld if c.block else c.cols, 0) for c in cs])
+        return bytes(arr), [(i, c.name, 4 * c.col0) for i, c in enumerate(cs)], [i for i, c in enumerate(cs) if c.block is None]
 
-        def add(name, col0, rows, cols, dst_off, dst_ld, acc=0):
-            t = p[name]
-            ld = t.shape[1] if t.dim() == 2 else t.numel()
-            out.append(PackDesc(base_of(name) + 4 * col0, rows, cols, ld if t.dim() == 2 else cols, dst_off, dst_ld, acc))
-
-        for l in range(D):
-            n = f"xyz_encoding_{l + 1}.0"
-            if l == 0:
-                add(n + ".weight", 0, W, 63, L.w[0], X0)
-            elif l == self.skip:
-                add(n + ".weight", 0, W, 63, L.w[l], X0 + W)
-                add(n + ".weight", 63, W, W, L.w[l] + X0, X0 + W)
-            else:
-                add(n + ".weight", 0, W, W, L.w[l], W)
-            add(n + ".bias", 0, 1, W, L.b[l], W)
-        add("xyz_encoding_final.weight", 0, W, W, L.we, W)
-        add("xyz_encoding_final.bias", 0, 1, W, L.be, W)
-        add("share_sigma.0.weight", 0, 1, W, L.wsig, W)
-        add("share_sigma.0.bias", 0, 1, 1, L.bsig, 1)
-        if self.has_cand:
-            add("candidate_encoding.0.weight", 0, W2, W + CK, L.wc1, W + CK)
-            add("candidate_encoding.0.bias", 0, 1, W2, L.bc1, W2)
-            add("candidate_encoding.2.weight", 0, W2, W2, L.wc2, W2)
-            add("candidate_encoding.2.bias", 0, 1, W2, L.bc2, W2)
-            add("candidate_sigma.0.weight", 0, 1, W2, L.wcsig, W2)
-            add("candidate_sigma.0.bias", 0, 1, 1, L.bcsig, 1)
-        naux = self.in_dir + self.A
-        if not self.encode_feat:  # W_r1 = [W | PE(dir) | appearance] columns go where the folded matrix and its side columns sit
-            add("rgb_share_layer.0.weight", 0, W2, W + naux, L.wr1, W + AUXK)
-            add("rgb_share_layer.0.bias", 0, 1, W2, L.br1, W2)
-        else:
-            add("rgb_share_layer.0.weight", Fd, W2, naux, L.wr1 + W, W + AUXK)   # [PE(dir) | appearance] columns
-            if scratch_off is not None:
-                add("rgb_share_layer.0.weight", 0, W2, Fd, scratch_off, Fd)       # contiguous copy of W_r1[:, :F]
-            else:  # backward: d b_r1 = d br1 (forward, br1 = W_r1[:, :F] b_feat + b_r1 is the mat-vec's output, not a copy)
-                add("rgb_share_layer.0.bias", 0, 1, W2, L.br1, W2)
-        add("rgb_share_layer.2.weight", 0, 3, W2, L.wr2, W2)
-        add("rgb_share_layer.2.bias", 0, 1, 3, L.br2, 3)
-        return out
+    def _pack_descs(self, base_of, scratch_off=None):
+        """Copy descriptors of pack() as the array upnerf_pack takes.  `base_of(name)` gives the device pointer a descriptor starts
+        from (the parameter, or its gradient buffer for the backward); `scratch_off`: where the contiguous copy of W_r1[:, :F]
+        goes (forward only; its gradient comes from the fold, not from a copy)."""
+        tmpl, fill, scratch = self._pack_forms["bwd" if scratch_off is None else "fwd"]
+        arr = (PackDesc * len(fill)).from_buffer_copy(tmpl)
+        for i, name, byte0 in fill:
+            arr[i].ptr = base_of(name) + byte0
+        for i in scratch:
+            arr[i].dst_off = scratch_off
+        return arr
 
     PACK_NAMES_BASE = ["share_sigma.0.weight", "share_sigma.0.bias", "xyz_encoding_final.weight", "xyz_encoding_final.bias",
                        "feat_share_layer.weight", "feat_share_layer.bias", "rgb_share_layer.0.weight",
                        "rgb_share_layer.0.bias", "rgb_share_layer.2.weight", "rgb_share_layer.2.bias"]
-    PACK_NAMES_CAND = ["candidate_encoding.0.weight", "candidate_encoding.0.bias", "candidate_encoding.2.weight",
-                       "candidate_encoding.2.bias", "candidate_sigma.0.weight", "candidate_sigma.0.bias"]
 
     def pack_names(self):
         base = [n for n in self.PACK_NAMES_BASE if self.encode_feat or not n.startswith("feat_share_layer")]
         names = [f"xyz_encoding_{l + 1}.0.{k}" for l in range(self.D) for k in ("weight", "bias")] + base
-        return names + (self.PACK_NAMES_CAND if self.has_cand else [])
+        return names + [n for n in self.PARAM.values() if n.startswith("candidate") and self.has_cand]
 
     def pack_hip(self, p: Dict[str, torch.Tensor]) -> torch.Tensor:
         """pack() with HIP kernels and a hand-written backward: 4 launches instead of ~45 (and ~10 instead of ~50 in the
@@ -254,33 +235,27 @@ class NerfPacker:
         return _PackFn.apply(self, names, *[p[n] for n in names])
 
     # ------------------------------------------------------------------ one-launch HIP re-layout (product path)
+    EXP_FINAL, EXP_C1, EXP_C2, EXP_R1, EXP_HEAD_T = EXP_FINAL, EXP_C1, EXP_C2, EXP_R1, EXP_HEAD_T  # (pass_plan's; trunk layer l: id l)
+
+    def _make_frag_descs(self):
+        """(forward descriptors, n, transposed descriptors, n) for upnerf_frag_copy and, with the exponent ids, for upnerf_frag16.
+        Forward: every matrix block onto itself.  Transposed: every feed of every block of PT, the trunk's by layer and source
+        column (a skip layer's encoding columns first) and then the struct's order -- the kernels index the row norms
+        upnerf_frag16 returns by descriptor."""
+        L = self.L
+        fwd = [(block_offset(L, b), b.ld, 0, b.rows, b.ld, block_offset(L, b), b.ld, 0, b.exp) for b in self.blocks if b.matrix]
+        feeds = sorted(((t, f) for t in self.tblocks for f in t.feeds),
+                       key=lambda tf: (self.D, 0) if tf[1].src.layer is None else (tf[1].src.layer, tf[1].col0))
+        bwd = [(block_offset(L, f.src) + f.col0, f.src.ld, 1, f.cols, f.src.rows, block_offset(L, t), t.ld, f.dst_col0, f.exp)
+               for t, f in feeds]
+        mk = lambda T, lst, n: (T * len(lst))(*[T(*d[:n]) for d in lst])
+        return {T: (mk(T, fwd, n), len(fwd), mk(T, bwd, n), len(bwd)) for T, n in ((FragDesc, 8), (Frag16Desc, 9))}
+
     def _descs(self):
-        """(forward descriptors, transposed descriptors) for upnerf_frag_copy, built once."""
-        if getattr(self, "_desc_cache", None) is None:
-            W, W2, D, L = self.W, self.W2, self.D, self.L
-            fwd, bwd = [], []
-            kp = lambda l: X0 if l == 0 else (X0 + W if l == self.skip else W)
-            for l in range(D):
-                fwd.append((L.w[l], kp(l), 0, W, kp(l), L.w[l], kp(l), 0))
-            fwd.append((L.we, W, 0, W, W, L.we, W, 0))
-            fwd.append((L.wc1, W + CK, 0, W2, W + CK, L.wc1, W + CK, 0))
-            fwd.append((L.wc2, W2, 0, W2, W2, L.wc2, W2, 0))
-            fwd.append((L.wr1, W + AUXK, 0, W2, W + AUXK, L.wr1, W + AUXK, 0))
-            for l in range(D):
-                if l == 0:
-                    bwd.append((L.w[0], X0, 1, X0, W, L.t_w[0], W, 0))
-                elif l == self.skip:
-                    bwd.append((L.w[l], X0 + W, 1, X0, W, L.t_skipx, W, 0))
-                    bwd.append((L.w[l] + X0, X0 + W, 1, W, W, L.t_w[l], W, 0))
-                else:
-                    bwd.append((L.w[l], W, 1, W, W, L.t_w[l], W, 0))
-            bwd.append((L.we, W, 1, W, W, L.t_we, W, 0))
-            bwd.append((L.wr1, W + AUXK, 1, W, W2, L.t_head, W, 0))
-            bwd.append((L.wc1, W + CK, 1, W, W2, L.t_head, W, W2))
-            bwd.append((L.wc2, W2, 1, W2, W2, L.t_wc2, W2, 0))
-            mk = lambda lst: (FragDesc * len(lst))(*[FragDesc(*t) for t in lst])
-            self._desc_cache = (mk(fwd), len(fwd), mk(bwd), len(bwd))
-        return self._desc_cache
+        return self._frag_descs[FragDesc]
+
+    def _descs16(self):
+        return self._frag_descs[Frag16Desc]
 
     @torch.no_grad()
     def frag_hip(self, P: torch.Tensor) -> torch.Tensor:
@@ -301,26 +276,6 @@ class NerfPacker:
         return out
 
     # ------------------------------------------------------------------ f16x3 re-layout (product path, W = 256)
-    EXP_FINAL, EXP_C1, EXP_C2, EXP_R1, EXP_HEAD_T = 8, 9, 10, 11, 12  # exponent ids; trunk layer l uses id l
-
-    def _descs16(self):
-        if getattr(self, "_desc16_cache", None) is None:
-            D = self.D
-            fd, nf, bd, nb = self._descs()
-            fid = list(range(D)) + [self.EXP_FINAL, self.EXP_C1, self.EXP_C2, self.EXP_R1]
-            bid = []
-            for l in range(D):
-                bid += [l, l] if l == self.skip else [l]
-            bid += [self.EXP_FINAL, self.EXP_HEAD_T, self.EXP_HEAD_T, self.EXP_C2]
-            assert len(fid) == nf and len(bid) == nb
-
-            def mk(src, n, ids):
-                fields = [f for f, _ in FragDesc._fields_]
-                return (Frag16Desc * n)(*[Frag16Desc(*[getattr(src[i], f) for f in fields], ids[i]) for i in range(n)])
-
-            self._desc16_cache = (mk(fd, nf, fid), nf, mk(bd, nb, bid), nb)
-        return self._desc16_cache
-
     @torch.no_grad()
     def frag16_hip(self, P: torch.Tensor, perm: bool = False):
         """(P16, PT16, wexp, wnorm): every matrix of P (and its transposed copy) as scaled fp16 (hi, lo) MFMA fragments with
@@ -350,54 +305,30 @@ class NerfPacker:
     @torch.no_grad()
     def frag(self, P: torch.Tensor) -> torch.Tensor:
         """Kernel-side copy of P: matrices in fragment order, vectors (biases, 1/3-wide heads) unchanged."""
-        W, W2, D, L = self.W, self.W2, self.D, self.L
         out = P.clone()
-        for l in range(D):
-            self._frag_into(out, P, L.w[l], W, X0 if l == 0 else (X0 + W if l == self.skip else W))
-        self._frag_into(out, P, L.we, W, W)
-        self._frag_into(out, P, L.wc1, W2, W + CK)
-        self._frag_into(out, P, L.wc2, W2, W2)
-        self._frag_into(out, P, L.wr1, W2, W + AUXK)
+        for b in self.blocks:
+            if b.matrix:
+                self._frag_into(out, P, block_offset(self.L, b), b.rows, b.ld)
         return out
 
     @torch.no_grad()
     def frag_t(self, PT: torch.Tensor) -> torch.Tensor:
-        W, W2, D, L = self.W, self.W2, self.D, self.L
         out = PT.clone()
-        for l in range(D):
-            self._frag_into(out, PT, L.t_w[l], X0 if l == 0 else W, W)
-        self._frag_into(out, PT, L.t_skipx, X0, W)
-        self._frag_into(out, PT, L.t_we, W, W)
-        self._frag_into(out, PT, L.t_head, W, W)
-        self._frag_into(out, PT, L.t_wc2, W2, W2)
+        for t in self.tblocks:
+            self._frag_into(out, PT, block_offset(self.L, t), t.rows, t.ld)
         return out
 
     # ------------------------------------------------------------------ transposed copies (no grad)
     @torch.no_grad()
     def pack_t(self, P: torch.Tensor) -> torch.Tensor:
-        W, W2, D, L = self.W, self.W2, self.D, self.L
-        PT = torch.empty(L.t_total, device=P.device, dtype=P.dtype)
-
-        def mat(o, n, k):
-            return P[o:o + n * k].view(n, k)
-
-        def putT(o, m):  # m: [rows][cols] written row-major at PT[o:]
-            PT[o:o + m.numel()] = m.reshape(-1)
-
-        for l in range(D):
-            if l == 0:
-                putT(L.t_w[0], mat(L.w[0], W, X0).t())
-            elif l == self.skip:
-                w = mat(L.w[l], W, X0 + W)
-                putT(L.t_skipx, w[:, :X0].t())
-                putT(L.t_w[l], w[:, X0:].t())
-            else:
-                putT(L.t_w[l], mat(L.w[l], W, W).t())
-        if self.skip < 0:
-            PT[L.t_skipx:L.t_skipx + X0 * W] = 0
-        putT(L.t_we, mat(L.we, W, W).t())
-        wr1 = mat(L.wr1, W2, W + AUXK)[:, :W]
-        wc1 = mat(L.wc1, W2, W + CK)[:, :W]
-        putT(L.t_head, torch.cat([wr1.t(), wc1.t()], 1))
-        putT(L.t_wc2, mat(L.wc2, W2, W2).t())
+        PT = torch.empty(self.L.t_total, device=P.device, dtype=P.dtype)
+        for t in self.tblocks:
+            o = block_offset(self.L, t)
+            dst = PT[o:o + t.rows * t.ld].view(t.rows, t.ld)
+            if not t.feeds:
+                dst.zero_()
+            for f in t.feeds:
+                so = block_offset(self.L, f.src)
+                src = P[so:so + f.src.rows * f.src.ld].view(f.src.rows, f.src.ld)
+                dst[:, f.dst_col0:f.dst_col0 + f.src.rows] = src[:, f.col0:f.col0 + f.cols].t()
         return PT

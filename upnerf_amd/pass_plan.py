@@ -1,13 +1,15 @@
 """One host-side description of a field pass, decided ONCE.  plan_pass: what the pass stores and in which form --
 rendering._FieldPass allocates its forward and backward buffers from the plan and reads its weight gradients' operands from it;
-geometry's density-only pass takes its tiling from it.  layout_offsets: where every parameter block sits in the packed buffer P
-(packing.NerfPacker fills the kernels' layout struct from it).  wgrad_schedule: the launches that write the gradient of P, against
-which operands and into which block -- _FieldPass.backward executes that list and holds no offset or exponent slot of its own.
-Host arithmetic only -- neither the library nor a device is touched, all three can be built (and tested) anywhere."""
+geometry's density-only pass takes its tiling from it.  param_blocks / t_blocks: the blocks of the packed buffer P and of its
+transposed copies, layout_offsets: where each sits (packing.NerfPacker derives all it does from these).  wgrad_schedule: the
+launches that write the gradient of P, against which operands and into which block -- _FieldPass.backward executes that list and
+holds no offset or exponent slot of its own.  Host arithmetic only -- neither the library nor a device is touched, all of it can
+be built (and tested) anywhere."""
 from __future__ import annotations
 
 from collections import namedtuple
 from functools import lru_cache
+from itertools import accumulate
 
 # constants of include/upnerf_hip.h that size a pass (_lib re-exports them beside the structs)
 X0, AUXK, CK = 64, 80, 16
@@ -129,27 +131,96 @@ def plan_pass(W, W2, D, R, S, mode, use_cand, use_rgb, rgb_joint, train, *, FIEL
                     e_frag, joined, rg16, g2f, partials, ride, buffers, ops)
 
 
-# ---- where the parameter blocks sit: include/upnerf_hip.h:upnerf_layout, field by field (w, b, t_w: one offset per layer)
+# ---- the parameter blocks: include/upnerf_hip.h:upnerf_layout stated ONCE -- offsets, packing, fragment copies, transposed copies
+# and the destinations of the weight gradients are all read off these two tables
+IN_XYZ, IN_DIR, A_DIM = 63, 27, 48  # used columns of the encodings and of the appearance embedding
+EXP_FINAL, EXP_C1, EXP_C2, EXP_R1, EXP_HEAD_T = 8, 9, 10, 11, 12  # upnerf_frag16's exponent ids of the matrices; trunk layer l: id l
+Part = namedtuple("Part", "name col0 cols")  # used columns [col0, col0 + cols) of a block and what they multiply
+
+
+class Block(namedtuple("Block", "field layer rows cols ld matrix parts exp used_rows")):
+    """One block of P, [rows][ld] floats rounded up to 4: the layout field it fills (layer: of `w` / `b`), `cols` used columns in
+    `parts` (every other column, and the rows from used_rows on, are zero padding), matrix: stored as MFMA fragments on the
+    kernel side under exponent id `exp`; a vector stays as it is."""
+    __slots__ = ()
+
+    def part(self, name) -> Part:
+        return next(p for p in self.parts if p.name == name)
+
+
+# A block of the transposed set PT, [rows][ld]: feed f puts f.src[:, f.col0 : f.col0 + f.cols]^T at columns [f.dst_col0, + f.src.rows)
+TBlock = namedtuple("TBlock", "field layer rows ld feeds")
+Feed = namedtuple("Feed", "src col0 cols dst_col0 exp")
+
+
+def block_size(b) -> int:
+    return (b.rows * b.ld + 3) // 4 * 4
+
+
+def block_offset(L, b) -> int:
+    """Where block b (of either table) starts in the layout L (LayoutOffsets or the kernels' struct)."""
+    return getattr(L, b.field) if b.layer is None else getattr(L, b.field)[b.layer]
+
+
+@lru_cache(maxsize=None)
+def param_blocks(W, D, skip=-1):
+    """The blocks of P in the order of the struct.  skip: the layer that also reads the encoding, -1 = none."""
+    W2 = W // 2
+
+    def mat(field, layer, rows, exp, *parts):  # parts: (name, used columns, columns taken)
+        ps, c0 = [], 0
+        for name, cols, width in parts:
+            ps.append(Part(name, c0, cols))
+            c0 += width
+        return Block(field, layer, rows, sum(p.cols for p in ps), c0, True, tuple(ps), exp, rows)
+
+    def vec(field, layer, cols, rows=1, used=1):
+        return Block(field, layer, rows, cols, cols, False, (Part(field, 0, cols),), None, used)
+
+    x, h = ("x", IN_XYZ, X0), ("h", W, W)
+    trunk = [mat("w", l, W, l, *((x,) if l == 0 else (x, h) if l == skip else (h,))) for l in range(D)]
+    return tuple(trunk + [vec("b", l, W) for l in range(D)] + [
+        mat("we", None, W, EXP_FINAL, h), vec("be", None, W), vec("wsig", None, W), vec("bsig", None, 1),
+        mat("wc1", None, W2, EXP_C1, ("e", W, W), ("c", CK, CK)), vec("bc1", None, W2),
+        mat("wc2", None, W2, EXP_C2, ("g1", W2, W2)), vec("bc2", None, W2), vec("wcsig", None, W2), vec("bcsig", None, 1),
+        mat("wr1", None, W2, EXP_R1, ("e", W, W), ("dir", IN_DIR, IN_DIR), ("a", A_DIM, AUXK - IN_DIR)), vec("br1", None, W2),
+        vec("wr2", None, W2, rows=4, used=3), vec("br2", None, 3)])
+
+
+@lru_cache(maxsize=None)
+def blocks_by_field(W, D, skip=-1) -> dict:
+    """param_blocks by layout field: one Block, or for `w` / `b` one per layer."""
+    blocks = param_blocks(W, D, skip)
+    return {**{b.field: b for b in blocks}, "w": blocks[:D], "b": blocks[D:2 * D]}
+
+
+@lru_cache(maxsize=None)
+def t_blocks(W, D, skip=-1):
+    """The blocks of PT in the order of the struct's t_* fields.  t_skipx is always there and fed only under a skip."""
+    W2, B = W // 2, blocks_by_field(W, D, skip)
+    own = [(b, b.parts[-1].col0) for b in B["w"]]  # a layer's transposed copy: the columns of its last part, padding included
+    xs = B["w"][skip] if 0 < skip < D else None
+    return tuple([TBlock("t_w", b.layer, b.ld - c0, W, (Feed(b, c0, b.ld - c0, 0, b.exp),)) for b, c0 in own] + [
+        TBlock("t_skipx", None, X0, W, (Feed(xs, 0, xs.part("h").col0, 0, xs.exp),) if xs else ()),
+        TBlock("t_we", None, W, W, (Feed(B["we"], 0, W, 0, EXP_FINAL),)),
+        TBlock("t_head", None, W, W, (Feed(B["wr1"], 0, W, 0, EXP_HEAD_T), Feed(B["wc1"], 0, W, W2, EXP_HEAD_T))),
+        TBlock("t_wc2", None, W2, W2, (Feed(B["wc2"], 0, W2, 0, EXP_C2),))])
+
+
 LayoutOffsets = namedtuple("LayoutOffsets", "W D skip w b we be wsig bsig wc1 bc1 wc2 bc2 wcsig bcsig wr1 br1 wr2 br2 total "
                                             "t_w t_skipx t_we t_head t_wc2 t_total")
 
 
+@lru_cache(maxsize=None)
 def layout_offsets(W, D, skip=-1) -> LayoutOffsets:
-    """Offsets (floats) of the blocks of P and of the transposed copies PT: laid end to end in the order of the struct, each
-    starting on a multiple of 4.  skip: the layer that also reads the encoding (its matrix is [W][X0 + W]), -1 = none."""
-    W2 = W // 2
+    """Offsets (floats) of the blocks of P and of the transposed copies PT: laid end to end in the order of the two tables, each
+    starting on a multiple of 4 (w, b, t_w: one offset per layer)."""
+    def end_to_end(blocks):
+        ends = list(accumulate(block_size(b) for b in blocks))
+        return [0] + ends[:-1], ends[-1]
 
-    def end_to_end(sizes):
-        offs, off = [], 0
-        for n in sizes:
-            offs.append(off)
-            off += (n + 3) // 4 * 4
-        return offs, off
-
-    kin = [X0 if l == 0 else X0 + W if l == skip else W for l in range(D)]
-    o, total = end_to_end([W * k for k in kin] + [W] * D + [W * W, W, W, 4, W2 * (W + CK), W2, W2 * W2, W2, W2, 4,
-                                                         W2 * (W + AUXK), W2, 4 * W2, 4])
-    t, t_total = end_to_end([(X0 if l == 0 else W) * W for l in range(D)] + [X0 * W, W * W, W * W, W2 * W2])
+    o, total = end_to_end(param_blocks(W, D, skip))
+    t, t_total = end_to_end(t_blocks(W, D, skip))
     return LayoutOffsets(W, D, skip, tuple(o[:D]), tuple(o[D:2 * D]), *o[2 * D:], total, tuple(t[:D]), *t[D:], t_total)
 
 
@@ -194,37 +265,34 @@ def _schedule(joined, ride, tile_part, frag, L, skip, cand, rgb) -> Schedule:
     def vec(v, nvec, X, K, dW, db, part=False):
         return Launch(PART if part else VEC_FRAG if X in frag else VEC, None, (X, None), v, nvec, K, None, None, dW, K, db)
 
+    B = blocks_by_field(W, D, skip)
     trunk = []
-    for l in range(D):
-        if l == 0:
-            trunk.append(mat(("gz", 0), W, ("x0", None), X0, 0, E.x0, L.w[0], X0, L.b[0]))
-        elif l == skip:  # [W][X0 + W]: the encoding's columns, then the previous layer's
-            trunk.append(mat(("gz", l), W, ("x0", None), X0, l, E.x0, L.w[l], X0 + W, L.b[l]))
-            trunk.append(mat(("gz", l), W, ("h", l - 1), W, l, l - 1, L.w[l] + X0, X0 + W, None))
-        else:
-            trunk.append(mat(("gz", l), W, ("h", l - 1), W, l, l - 1, L.w[l], W, L.b[l]))
+    for l, b in enumerate(B["w"]):  # one launch per column part: the encoding's columns, the previous layer's
+        for p in b.parts:
+            X, K, eb = (("x0", None), X0, E.x0) if p.name == "x" else (("h", l - 1), W, l - 1)
+            trunk.append(mat(("gz", l), W, X, K, l, eb, L.w[l] + p.col0, b.ld, L.b[l] if p is b.parts[0] else None))
     # the shared density head reads the final layer's B operand: where the plan says so its gradient rides on that launch
     sig = vec("dpre_s", 1, "h_last", W, L.wsig, L.bsig)
-    trunk.append(mat(("gz_e", None), W, ("h_last", None), W, E.final, D - 1, L.we, W, L.be, ride=sig if ride else None))
+    trunk.append(mat(("gz_e", None), W, ("h_last", None), W, E.final, D - 1, L.we, B["we"].ld, L.be, ride=sig if ride else None))
     if not ride:
         trunk.append(sig)
     csig = vec("dpre_c", 1, "g2", W2, L.wcsig, L.bcsig, tile_part)
     rgb2 = vec("dpre_rgb", 3, "r1", W2, L.wr2, L.br2, tile_part)
-    e = ("e", None)
+    e, wc1, wc2, wr1 = ("e", None), B["wc1"], B["wc2"], B["wr1"]
     c, r = [], []
     if cand:
         if joined:  # rows [0, W2) -> wr1 / br1 (colour head), rows [W2, W) -> wc1 / bc1 (candidate head)
-            c.append(mat(("gz_rg", None), W, e, W, E.joined, E.final, L.wr1, W + AUXK, L.br1, n2=W2, dW2=L.wc1, ldo2=W + CK,
+            c.append(mat(("gz_rg", None), W, e, W, E.joined, E.final, L.wr1, wr1.ld, L.br1, n2=W2, dW2=L.wc1, ldo2=wc1.ld,
                          db2=L.bc1))
         else:
-            c.append(mat(("gz_g1", None), W2, e, W, E.g1, E.final, L.wc1, W + CK, L.bc1))
-        c.append(Launch(RAY, ("rs_c", None), ("c_rows", None), None, W2, CK, None, None, L.wc1 + W, W + CK, None))
-        c.append(mat(("gz_g2", None), W2, ("g1", None), W2, E.g2, E.g1, L.wc2, W2, L.bc2))
+            c.append(mat(("gz_g1", None), W2, e, W, E.g1, E.final, L.wc1, wc1.ld, L.bc1))
+        c.append(Launch(RAY, ("rs_c", None), ("c_rows", None), None, W2, CK, None, None, L.wc1 + wc1.part("c").col0, wc1.ld, None))
+        c.append(mat(("gz_g2", None), W2, ("g1", None), W2, E.g2, E.g1, L.wc2, wc2.ld, L.bc2))
         c += [] if tile_part else [csig]
     if rgb:
         if not joined:
-            r.append(mat(("gz_r1", None), W2, e, W, E.r1, E.final, L.wr1, W + AUXK, L.br1))
-        r.append(Launch(RAY, ("rs_r", None), ("aux", None), None, W2, AUXK, None, None, L.wr1 + W, W + AUXK, None))
+            r.append(mat(("gz_r1", None), W2, e, W, E.r1, E.final, L.wr1, wr1.ld, L.br1))
+        r.append(Launch(RAY, ("rs_r", None), ("aux", None), None, W2, AUXK, None, None, L.wr1 + wr1.part("dir").col0, wr1.ld, None))
         r += [] if tile_part else [rgb2]
     part = (csig if cand else None, rgb2 if rgb else None) if tile_part else None
     return Schedule(tuple(trunk), part, tuple(c), tuple(r))
