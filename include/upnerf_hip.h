@@ -1316,6 +1316,73 @@ typedef struct {
 long long upnerf_pca_fit_scratch(int T, int D);
 int upnerf_pca_fit(const upnerf_pca_fit_args* a, double* scratch, void* stream);
 
+/* ---- DPT-Large inverse depth (csrc/dpt.hip, upnerf_amd/dpt.py): the convolutional decoder and the resizes
+ * around the network; the backbone is the ViT entry points above.  Added under ABI 11: new symbols only.  Every entry point:
+ * arguments refused on the host before anything is launched, nothing allocated, no host read-back, no atomics and a fixed
+ * summation order (the same bits every run), all launches on `stream`.
+ *
+ * Maps are NHWC: pixel (y, x) of an H x W map with C channels is the C floats at p + (y * W + x) * ld (ld >= C: a row stride), so
+ * the token rows of the backbone are maps and every 1 x 1 convolution is upnerf_linear.
+ *
+ * upnerf_conv3x3: y = [relu]( conv(pre_relu ? relu(x) : x, w) + bias + res ), kernel 3 x 3, padding 1 (zeros, of the map AFTER the
+ * pre-ReLU), stride 1 or 2 (else UPNERF_EUNSUP); output (H - 1) / stride + 1 by (W - 1) / stride + 1.  w is [C_out][3][3][C_in]
+ * (ky, kx, ci; the checkpoint's [C_out][C_in][3][3] relaid once by the caller).  C_in, C_out: multiples of 32 up to 1024 (else
+ * UPNERF_EUNSUP).  bias [C_out] and res (an output-sized map, row stride ldr) may be NULL.  Pointers 16-byte aligned, strides
+ * multiples of 4.  y must not overlap x; res may overlap neither (UPNERF_EINVAL).  An implicit GEMM on the fp32-input MFMA: exact
+ * fp32 products summed as one fp32 chain in the order (ky, kx, ci). */
+typedef struct {
+  int32_t H, W, C_in, C_out, stride, pre_relu, relu, reserved_;
+  const float* x; int64_t ldx;
+  const float* w;
+  const float* bias;
+  const float* res; int64_t ldr;
+  float* y; int64_t ldy;
+} upnerf_conv3x3_args;
+int upnerf_conv3x3(const upnerf_conv3x3_args* a, void* stream);
+
+/* upnerf_upsample2x: bilinear, H x W -> 2 H x 2 W, align_corners=True, in torch's arithmetic: fp32 scale = (in - 1) / (out - 1)
+ * (0 for in = 1), src = scale * dst, i0 = (int)src, i1 = min(i0 + 1, in - 1).  16-byte accesses when C, the strides and the
+ * pointers allow it, element-wise otherwise.  y must not overlap x. */
+typedef struct {
+  int32_t H, W, C, reserved_;
+  const float* x; int64_t ldx;
+  float* y; int64_t ldy;
+} upnerf_upsample2x_args;
+int upnerf_upsample2x(const upnerf_upsample2x_args* a, void* stream);
+
+/* upnerf_depth_to_space: the scatter half of a transposed convolution whose kernel equals its stride s (2 or 4, else
+ * UPNERF_EUNSUP): y[(py * s + dy, px * s + dx)][c] = x[(py, px)][(dy * s + dx) * C + c] + bias[c], x the H x W map with s * s * C
+ * columns that upnerf_linear makes against the weight relaid to [(dy, dx, c_out)][c_in].  bias may be NULL.  y must not overlap x. */
+typedef struct {
+  int32_t H, W, C, s;
+  const float* x; int64_t ldx;
+  const float* bias;
+  float* y; int64_t ldy;
+} upnerf_depth_to_space_args;
+int upnerf_depth_to_space(const upnerf_depth_to_space_args* a, void* stream);
+
+/* upnerf_resize_cubic: [h][w][C] -> [H][W][C] (contiguous, C = 1 or 3, else UPNERF_EUNSUP), cubic convolution with A = -0.75,
+ * half-pixel centres (src = (dst + 0.5) * in / out - 0.5 in fp32), the four taps per axis clamped to the image, no antialiasing:
+ * cv2's INTER_CUBIC on a float image and torch's bicubic with align_corners=False.  u8 != 0: x is uint8 and divided by 255 as it
+ * is read.  affine != 0: (v - mean[c]) / std[c] on the way out (std > 0, else UPNERF_EINVAL). */
+typedef struct {
+  int32_t h, w, H, W, C, u8, affine, reserved_;
+  const void* x;
+  float mean[3], std[3];
+  float* y;
+} upnerf_resize_cubic_args;
+int upnerf_resize_cubic(const upnerf_resize_cubic_args* a, void* stream);
+
+/* upnerf_vit_patches16: rows[t][(c * P + ky) * P + kx] = image[(ty * P + ky, tx * P + kx)][c], t = ty * (W / P) + tx, P = patch
+ * (1..64): the operand rows of a P x P patch convolution at stride P from an fp32 [H][W][3] image, taken as it is (the general-
+ * patch sibling of upnerf_vit_patches).  Pixels right of or below the last full patch are never read. */
+typedef struct {
+  int32_t H, W, patch, reserved_;
+  const float* image;        /* [H][W][3] */
+  float* rows;               /* [(H / P) * (W / P)][3 * P * P] */
+} upnerf_vit_patches16_args;
+int upnerf_vit_patches16(const upnerf_vit_patches16_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

@@ -216,6 +216,32 @@ class PcaFitArgs(C.Structure):
     _fields_ = [("T", C.c_int32), ("D", C.c_int32), ("x", _fp), ("ldx", C.c_int64), ("mean", _fp), ("gram", _fp)]
 
 
+class Conv3x3Args(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("C_in", C.c_int32), ("C_out", C.c_int32), ("stride", C.c_int32),
+                ("pre_relu", C.c_int32), ("relu", C.c_int32), ("reserved_", C.c_int32), ("x", _fp), ("ldx", C.c_int64), ("w", _fp),
+                ("bias", _fp), ("res", _fp), ("ldr", C.c_int64), ("y", _fp), ("ldy", C.c_int64)]
+
+
+class Upsample2xArgs(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("reserved_", C.c_int32), ("x", _fp), ("ldx", C.c_int64),
+                ("y", _fp), ("ldy", C.c_int64)]
+
+
+class DepthToSpaceArgs(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("s", C.c_int32), ("x", _fp), ("ldx", C.c_int64),
+                ("bias", _fp), ("y", _fp), ("ldy", C.c_int64)]
+
+
+class ResizeCubicArgs(C.Structure):
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("u8", C.c_int32),
+                ("affine", C.c_int32), ("reserved_", C.c_int32), ("x", _fp), ("mean", C.c_float * 3), ("std", C.c_float * 3),
+                ("y", _fp)]
+
+
+class VitPatches16Args(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("patch", C.c_int32), ("reserved_", C.c_int32), ("image", _fp), ("rows", _fp)]
+
+
 class SceneImage(C.Structure):
     _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("x0", C.c_int32), ("x1", C.c_int32),
                 ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
@@ -456,6 +482,11 @@ _SIGNATURES = {
     "upnerf_vit_residual": [_p, _p, C.c_longlong, _p],
     "upnerf_pca_fit_scratch": [_i, _i],
     "upnerf_pca_fit": [C.POINTER(PcaFitArgs), _p, _p],
+    "upnerf_conv3x3": [C.POINTER(Conv3x3Args), _p],
+    "upnerf_upsample2x": [C.POINTER(Upsample2xArgs), _p],
+    "upnerf_depth_to_space": [C.POINTER(DepthToSpaceArgs), _p],
+    "upnerf_resize_cubic": [C.POINTER(ResizeCubicArgs), _p],
+    "upnerf_vit_patches16": [C.POINTER(VitPatches16Args), _p],
 }
 _LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
              "upnerf_occ_compact_scratch", "upnerf_pca_fit_scratch")

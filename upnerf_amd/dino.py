@@ -19,7 +19,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, vit
 from .ops import TIMER
 
 # ---- the network: dino_vits8 -----------------------------------------------------------------------------------------
@@ -32,9 +32,7 @@ KEYS = dict(cls="cls_token",                         # [1, 1, D]
             pos="pos_embed",                         # [1, 1 + P * P, D]
             pe_w="patch_embed.proj.weight",          # [D, 3, 8, 8]
             pe_b="patch_embed.proj.bias")            # [D]
-BLOCK_KEYS = (("norm1.weight", "D"), ("norm1.bias", "D"), ("attn.qkv.weight", "3D,D"), ("attn.qkv.bias", "3D"),
-              ("attn.proj.weight", "D,D"), ("attn.proj.bias", "D"), ("norm2.weight", "D"), ("norm2.bias", "D"),
-              ("mlp.fc1.weight", "4D,D"), ("mlp.fc1.bias", "4D"), ("mlp.fc2.weight", "D,4D"), ("mlp.fc2.bias", "D"))
+BLOCK_KEYS = vit.BLOCK_KEYS  # per block: norm1, attn.qkv, attn.proj, norm2, mlp.fc1, mlp.fc2 (weight and bias each)
 # ---- the extractor: ViTExtractor(model_type="dino_vits8", stride=4).extract_descriptors(x, layer=9, facet="key", bin=False,
 #      include_cls=False) ----------------------------------------------------------------------------------------------
 #   the patch convolution runs at `stride` without padding; the descriptor is the KEY third of blocks[layer].attn.qkv's
@@ -198,26 +196,6 @@ class DinoViT:
                                    hid=e(N, self.hidden))
         return self._bufs[key]
 
-    # -- single launches ---------------------------------------------------------------------------------------------
-    def _linear(self, name, M, N, K, A, lda, W, b, Cout, ldc):
-        st = _lib.stream()
-        _lib.check(TIMER.run(name, lambda: _lib.lib.upnerf_linear(M, N, K, A, lda, _lib.ptr(W), K, _lib.ptr(b), Cout, ldc, 0, st),
-                             units=2 * M * N * K), "upnerf_linear")  # (units: FLOP)
-
-    def _layernorm(self, M, x, w, b, y):
-        st = _lib.stream()
-        _lib.check(TIMER.run("dino_layernorm", lambda: _lib.lib.upnerf_layernorm(
-            M, self.D, _lib.ptr(x), self.D, _lib.ptr(w), _lib.ptr(b), MODEL["ln_eps"], _lib.ptr(y), self.D, st)), "upnerf_layernorm")
-
-    def _attention(self, N, qkv, out):
-        D = self.D
-        a = _lib.VitAttentionArgs(N=N, heads=self.heads, head_dim=MODEL["head_dim"], q=qkv.data_ptr(), k=qkv.data_ptr() + 4 * D,
-                                  v=qkv.data_ptr() + 8 * D, ldq=3 * D, ldk=3 * D, ldv=3 * D, scale=MODEL["head_dim"] ** -0.5,
-                                  out=_lib.ptr(out), ldo=D)
-        st = _lib.stream()
-        _lib.check(TIMER.run("dino_attention", lambda: _lib.lib.upnerf_vit_attention(C.byref(a), st), units=4 * N * N * D),
-                   "upnerf_vit_attention")
-
     def descriptors(self, image: torch.Tensor) -> torch.Tensor:
         """image: [H][W][3] on the device, uint8 (divided by 255 on the way in) or fp32 already in [0, 1]; it is normalised with
         the ImageNet statistics as its pixels are gathered.  Returns the key descriptors of block `layer`, [h0][w0][D] fp32."""
@@ -243,29 +221,15 @@ class DinoViT:
                                  rows=_lib.ptr(rows))
         pa.mean[:], pa.std[:] = PREPROCESS["mean"], PREPROCESS["std"]
         _lib.check(TIMER.run("dino_patches", lambda: lib.upnerf_vit_patches(C.byref(pa), st)), "upnerf_vit_patches")
-        self._linear("dino_patch_proj", T, D, Kp, _lib.ptr(rows), Kp, self.pe_w, self.pe_b, tok.data_ptr() + 4 * D, D)
+        vit.linear("dino_patch_proj", T, D, Kp, _lib.ptr(rows), Kp, self.pe_w, self.pe_b, tok.data_ptr() + 4 * D, D)
         _lib.check(TIMER.run("dino_embed", lambda: lib.upnerf_vit_embed(N, D, _lib.ptr(self.cls), _lib.ptr(pos), _lib.ptr(tok), st)),
                    "upnerf_vit_embed")
-        for blk in self.blocks[:self.layer]:
-            self._layernorm(N, tok, blk["norm1.weight"], blk["norm1.bias"], xn)
-            self._linear("dino_qkv", N, 3 * D, D, _lib.ptr(xn), D, blk["attn.qkv.weight"], blk["attn.qkv.bias"], _lib.ptr(qkv), 3 * D)
-            self._attention(N, qkv, att)
-            self._linear("dino_proj", N, D, D, _lib.ptr(att), D, blk["attn.proj.weight"], blk["attn.proj.bias"], _lib.ptr(xn), D)
-            _lib.check(TIMER.run("dino_residual", lambda: lib.upnerf_vit_residual(_lib.ptr(tok), _lib.ptr(xn), N * D, st)),
-                       "upnerf_vit_residual")
-            self._layernorm(N, tok, blk["norm2.weight"], blk["norm2.bias"], xn)
-            self._linear("dino_fc1", N, self.hidden, D, _lib.ptr(xn), D, blk["mlp.fc1.weight"], blk["mlp.fc1.bias"], _lib.ptr(hid),
-                         self.hidden)
-            _lib.check(TIMER.run("dino_gelu", lambda: lib.upnerf_vit_gelu(_lib.ptr(hid), N * self.hidden, st)), "upnerf_vit_gelu")
-            self._linear("dino_fc2", N, D, self.hidden, _lib.ptr(hid), self.hidden, blk["mlp.fc2.weight"], blk["mlp.fc2.bias"],
-                         _lib.ptr(att), D)
-            _lib.check(TIMER.run("dino_residual", lambda: lib.upnerf_vit_residual(_lib.ptr(tok), _lib.ptr(att), N * D, st)),
-                       "upnerf_vit_residual")
+        vit.run_blocks(self.blocks[:self.layer], N, D, self.heads, self.hidden, tok, xn, qkv, att, hid, "dino")
         last = self.blocks[self.layer]
-        self._layernorm(N, tok, last["norm1.weight"], last["norm1.bias"], xn)
+        vit.layernorm("dino_layernorm", N, D, tok, last["norm1.weight"], last["norm1.bias"], xn, MODEL["ln_eps"])
         out = torch.empty(h0, w0, D, dtype=torch.float32, device=image.device)
         # the key rows in (d, head) order, from token row 1 on: the descriptor map in its final layout
-        self._linear("dino_key", T, D, D, xn.data_ptr() + 4 * D, D, self.key_w, self.key_b, _lib.ptr(out), D)
+        vit.linear("dino_key", T, D, D, xn.data_ptr() + 4 * D, D, self.key_w, self.key_b, _lib.ptr(out), D)
         return out
 
     def pca_moments(self, desc: torch.Tensor):
