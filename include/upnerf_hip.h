@@ -1383,6 +1383,57 @@ typedef struct {
 } upnerf_vit_patches16_args;
 int upnerf_vit_patches16(const upnerf_vit_patches16_args* a, void* stream);
 
+/* ---- a baked scene: rays marched through a colour-density grid, the field never touched (csrc/baked.hip).
+ * Added under ABI 11: new symbols only.  Arguments refused on the host before anything is launched, nothing allocated, no host
+ * read-back, no atomics, one launch on `stream`; the same bits every run and however the rays are cut into launches.
+ *
+ * Geometry: that of the occupancy grid above.  `rgbs` [Cz+1][Cy+1][Cx+1][4] holds r, g, b, sigma at the grid points (16-byte
+ * aligned); `words` are the upnerf_occ_words(Cx, Cy, Cz) words of a grid in which every cell with a clear bit has eight
+ * corners that are (0, 0, 0, 0): the bits say where the integrand is zero and never change the picture.
+ *
+ * One thread per ray row o | d | near | far (d need not be unit length).  All fp32:
+ *   K = ceilf((far - near) / step), held to UPNERF_BAKED_MAX_SAMPLES; t_k = fmaf(k + 0.5, step, near), k = 0 .. K-1;
+ *   p = fmaf(t_k, d, o) per axis; g = (p - lo) * inv per axis, inv = (float)(C / ((double)hi - (double)lo));
+ *   a sample with an axis on which NOT (0 <= g <= C) contributes nothing; i = min((int)floorf(g), C - 1), f = g - i;
+ *   v = the trilinear blend of the eight corners of cell i, four channels: along x first, then y, then z, each blend
+ *   fmaf(f, b - a, a);
+ *   delta = step * sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx))); e = expf(-delta * v.sigma); alpha = 1 - e; w = T * alpha;
+ *   rgb += w * v.rgb (fmaf), depth = fmaf(w, t_k, depth), opacity += w; T *= 1 - alpha; in sample order, T starts at 1;
+ *   stop > 0: the ray ends after the sample that brought T below `stop`;
+ *   at the end rgb = fmaf(1 - opacity, background, rgb), depth = fmaf(1 - opacity, far, depth).
+ * A ray with a NaN or an infinity among its eight numbers, or with NOT (far > near), is a miss: rgb = background, depth = far, opacity = 0.
+ * Samples are skipped only where their OWN cell, computed as above, has a clear bit (or lies in a brick with a clear bit, or
+ * outside the box): the result is, bit for bit, that of visiting every sample. */
+#define UPNERF_BAKED_MAX_SAMPLES 4194304
+typedef struct {
+  int32_t Cx, Cy, Cz, R;
+  float lo[3], hi[3];        /* hi > lo, finite */
+  float step;                /* > 0, finite */
+  float background;          /* finite */
+  float stop;                /* >= 0, < 1; 0 = never */
+  int32_t reserved_;
+  const float* rgbs;         /* [Cz+1][Cy+1][Cx+1][4], 16-byte aligned */
+  const uint32_t* words;     /* [upnerf_occ_words(Cx, Cy, Cz)] */
+  const float* rays;         /* [R][8], 16-byte aligned */
+  float* rgb;                /* [R][3] */
+  float* depth;              /* [R] */
+  float* opacity;            /* [R] */
+} upnerf_baked_render_args;
+int upnerf_baked_render(const upnerf_baked_render_args* a, void* stream);
+
+/* upnerf_baked_pack: the grid of a baked scene from its parts.  rgbs[n] = (rgb[n], sigma[n]) where sigma[n] is finite, > 0 and
+ * >= level, else (0, 0, 0, 0); `rgb` NULL: colour (0, 0, 0).  kept[n] (optional) = 1 / 0 accordingly.  One thread per point. */
+typedef struct {
+  int64_t n;
+  float level;               /* not NaN */
+  int32_t reserved_;
+  const float* sigma;        /* [n] */
+  const float* rgb;          /* [n][3] or NULL */
+  float* rgbs;               /* [n][4], 16-byte aligned */
+  uint8_t* kept;             /* [n] or NULL */
+} upnerf_baked_pack_args;
+int upnerf_baked_pack(const upnerf_baked_pack_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

@@ -1,0 +1,123 @@
+"""Render rate of camera-path frames from a baked scene (upnerf_amd/baked.py) beside the two routes through the
+field, on the frames of tools/bench_path.py.
+
+    python tools/bench_baked.py [--resolution 128 128 128] [--level SIGMA] [--step 0.02] [--frames 8] [--width 200] [--height 200]
+                                [--chunk 16384] [--progress 0.8] [--images 763] [--reps 3] [--out profiles/baked_render.json]
+
+The system is bench.py's (two 8 x 256 fields, 64 + 128 samples, 763 images, seeded weights), the path and the box those of
+bench_path.py --occupancy.  In one process, after a warm-up of every mode, `--reps` rounds of  plain render_path / render_path
+with the occupancy grid of the same density at the same level / render_path with the baked scene  run alternately (a drift of
+the clocks touches every mode alike; wall clock around a device synchronisation, the median of each).  Written: the bake time
+(density, colour and packing; wall clock), frames/s and rays/s of each mode beside its hit share, the grid's bytes, the marcher's
+own time per launch (HIP events), and the PSNR of the baked frames against the plain ones at this resolution, step and level.
+The weights are random: the hit share and the PSNR say nothing about a trained scene."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+BOUNDS = ((-2.5, -2.5, -5.5), (2.5, 2.5, 0.5))  # in front of the cameras (bench_path.py)
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--resolution", type=int, nargs=3, default=(128, 128, 128), metavar=("NX", "NY", "NZ"))
+    ap.add_argument("--level", type=float, default=None, help="density below which a grid point is dropped (default: the 0.75 quantile of the grid's density, a random field's scale being arbitrary)")
+    ap.add_argument("--step", type=float, default=0.02, help="sample spacing of the baked render")
+    ap.add_argument("--frames", type=int, default=8)
+    ap.add_argument("--width", type=int, default=200)
+    ap.add_argument("--height", type=int, default=200)
+    ap.add_argument("--keys", type=int, default=4)
+    ap.add_argument("--chunk", type=int, default=16384)
+    ap.add_argument("--progress", type=float, default=0.8)
+    ap.add_argument("--images", type=int, default=763)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--bake-image", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "baked_render.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_baked.py measures on the GPU; none is visible")
+    import bench
+    from upnerf_amd import novel_view
+    from upnerf_amd.baked import BakedScene
+    from upnerf_amd.geometry import density_grid
+    from upnerf_amd.novel_view import CameraPath, render_path
+    from upnerf_amd.occupancy import OccupancyGrid
+    from upnerf_amd.ops import TIMER
+    dev = torch.device("cuda", 0)
+    sysm = bench.build_system(dev, a.progress, n_images=a.images)
+    sysm.hparams["val.chunk_size"] = a.chunk
+    W, H, F = a.width, a.height, a.frames
+    ang = torch.linspace(-0.3, 0.3, a.keys)  # keyframes on a small arc around the origin, looking down -z (bench_path.py)
+    c2w = torch.zeros(a.keys, 3, 4)
+    c2w[:, 0, 0] = c2w[:, 2, 2] = torch.cos(ang)
+    c2w[:, 0, 2], c2w[:, 2, 0], c2w[:, 1, 1] = torch.sin(ang), -torch.sin(ang), 1.0
+    c2w[:, :, 3] = torch.stack([0.2 * torch.sin(ang), torch.zeros(a.keys), 0.2 * (1 - torch.cos(ang))], 1)
+    K = torch.tensor([[0.8 * W, 0, W / 2], [0, 0.8 * W, H / 2], [0, 0, 1.0]])
+    path = CameraPath.from_poses(c2w, (0.1, 5.0), F, appearance=(a.bake_image, a.bake_image), img_wh=(W, H), K=K)  # ONE appearance: the baked one
+    rays = F * H * W
+    res = tuple(a.resolution)
+    view = (0.0, 0.0, -1.0)  # the cameras of this path look down -z; the synthetic dataset has no poses to average
+    grid = density_grid(sysm, BOUNDS, res)
+    if a.level is None:  # a quarter of the points kept (a stated rule, not a tuned number: the field is random)
+        a.level = float(torch.quantile(grid.reshape(-1)[::max(1, grid.numel() // 1_000_000)].float(), 0.75))
+    bake = lambda: BakedScene.build(sysm, BOUNDS, res, a.level, img_id=a.bake_image, view_dir=view)
+    bake()  # warm-up
+    bake_s = statistics.median(wall(bake) for _ in range(a.reps))
+    scene = bake()
+    occ = OccupancyGrid.from_density(grid, BOUNDS, a.level, dilate=1)
+    modes = {"plain": {}, "occupancy": {"occupancy": occ}, "baked": {"baked": scene, "baked_step": a.step}}
+    share, frames = {}, {}
+    for k, kw in modes.items():  # warm-up of every mode; the float frames for the PSNR
+        frames[k] = render_path(sysm, path, outputs=("rgb_float",), **kw)["rgb_float"].clamp(0, 1)
+        share[k] = novel_view.LAST_STATS["hits"] / rays if k == "occupancy" else None
+    direct = scene.render(novel_view.path_rays(*novel_view.path_poses(path.key_c2w.to(dev), path.key_near_far.to(dev), path.u.to(dev), path.mode),
+                                               (W, H), path.K, 0, H * W)[0], a.step)
+    share["baked"] = float((direct["opacity"] > 0).float().mean())  # frame 0: rays that met a kept sample
+    times = {k: [] for k in modes}
+    for _ in range(a.reps):
+        for k, kw in modes.items():
+            times[k].append(wall(lambda: render_path(sysm, path, outputs=("rgb",), **kw)))
+    TIMER.reset()
+    TIMER.enabled, TIMER.only = True, {"baked_render"}
+    render_path(sysm, path, outputs=("rgb",), **modes["baked"])
+    kern = {n: {"ms_per_launch": v["avg_ms"], "launches": v["launches"], "rays_per_launch": v["units_per_launch"]} for n, v in TIMER.summary().items()}
+    TIMER.enabled, TIMER.only = False, None
+    TIMER.reset()
+    psnr = lambda x, y: float(-10 * torch.log10(((x - y) ** 2).mean().clamp_min(1e-20)))
+    runs = {}
+    for k, ts in times.items():
+        dt = statistics.median(ts)
+        runs[k] = {"frames_per_s": F / dt, "rays_per_s": rays / dt, "hit_share": share[k], "seconds": sorted(ts)}
+    out = {"metric": "camera-path frames: plain render_path, with an occupancy grid, from a baked scene (rgb output; random weights)",
+           "frames": F, "img_wh": [W, H], "chunk": a.chunk, "progress": a.progress, "reps": a.reps, "resolution": list(res),
+           "level": a.level, "step": a.step, "bounds": [list(b) for b in BOUNDS], "view_dir": list(view), "bake_image": a.bake_image,
+           "bake_seconds": bake_s, "grid_bytes": scene.nbytes, "occupied_share": scene.fraction,
+           "sigma_min": float(grid.min()), "sigma_max": float(grid.max()), "runs": runs, "kernels": kern,
+           "psnr_baked_vs_plain_db": psnr(frames["baked"], frames["plain"]), "psnr_occupancy_vs_plain_db": psnr(frames["occupancy"], frames["plain"]),
+           "baked_over_plain": runs["baked"]["rays_per_s"] / runs["plain"]["rays_per_s"],
+           "baked_over_occupancy": runs["baked"]["rays_per_s"] / runs["occupancy"]["rays_per_s"]}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

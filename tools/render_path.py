@@ -4,12 +4,20 @@ appearance moving from photograph to photograph (upnerf_amd/novel_view.py; DESIG
     python tools/render_path.py --config scene.yaml --ckpt last.ckpt --images 3 17 42 --frames 120 --out DIR
                                 [--mode linear|catmull] [--downscale N] [--depth] [--normals] [--loop] [--chunk ROWS]
                                 [--occupancy NX NY NZ --level SIGMA [--dilate K] [--bounds X0 Y0 Z0 X1 Y1 Z1 | --margin M]]
+                                [--baked NX NY NZ --level SIGMA --step DT [--bake-image ID] [--save-baked F | --load-baked F]]
 
 --occupancy skips empty space: the fine field's density is sampled on NX x NY x NZ grid points over the box (--bounds, or the
 box round the refined cameras and their far points grown by --margin), cells with a corner >= --level (grown by --dilate
 rounds) are kept, and only the rays that touch such a cell are rendered, over the part of the ray that does.  A skipped pixel
 shows the background, NOT what the full render would have composited from density below --level: --level (no default, as in
 tools/extract_mesh.py) and --dilate trade speed for that.
+
+--baked renders a PREVIEW without the field: the fine field is sampled once into a colour-density grid of NX x NY x NZ points over
+the same box (points below --level are dropped), with the appearance of training image --bake-image (default: the first of
+--images) and for ONE viewing direction, the mean optical axis of the training cameras -- a baked scene has no view dependence
+and one appearance -- and every frame is marched from that grid with samples --step apart (upnerf_amd/baked.py).
+--save-baked writes the grid to an .npz, --load-baked renders from one (then NX NY NZ and --level are those of the file).
+--depth works, --normals and --occupancy do not.
 
 Writes PNG files only -- DIR/path/step_<frame, 8 digits>/rgb.png (and depth.png with --depth, normal.png with
 --normals: the world-space normal map, (n + 1) / 2, mid-grey where nothing was hit).  No video encoder is installed
@@ -44,14 +52,32 @@ def parser():
     ap.add_argument("--dilate", type=int, default=1, help="rounds of 26-neighbour dilation of the kept cells")
     ap.add_argument("--bounds", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="box of the occupancy grid")
     ap.add_argument("--margin", type=float, default=0.5, help="without --bounds: the box round the cameras and their far points, grown by this")
+    ap.add_argument("--baked", type=int, nargs=3, metavar=("NX", "NY", "NZ"), help="render from a colour-density grid of this many grid points instead of the field")
+    ap.add_argument("--step", type=float, default=None, help="sample spacing of the baked render along a ray (required with --baked / --load-baked; no default)")
+    ap.add_argument("--bake-image", type=int, default=None, help="training image whose appearance is baked (default: the first of --images)")
+    ap.add_argument("--save-baked", default=None, help="write the baked grid to this .npz")
+    ap.add_argument("--load-baked", default=None, help="render from the baked grid of this .npz instead of baking")
     return ap
 
 
 def check_args(a):
     if a.occupancy is not None and a.level is None:
         raise SystemExit("--occupancy needs --level: the useful density threshold depends on the scene's scale")
-    if a.occupancy is None and (a.level is not None or a.bounds is not None):
-        raise SystemExit("--level and --bounds belong to --occupancy")
+    baked = a.baked is not None or a.load_baked is not None
+    if a.baked is not None and a.load_baked is not None:
+        raise SystemExit("--baked bakes a grid, --load-baked reads one: give one of them")
+    if a.baked is not None and a.level is None:
+        raise SystemExit("--baked needs --level: the useful density threshold depends on the scene's scale")
+    if baked and a.step is None:
+        raise SystemExit("a baked render needs --step: the sample spacing depends on the scene's scale")
+    if baked and (a.occupancy is not None or a.normals):
+        raise SystemExit("a baked render has no --normals and carries its own occupancy bits (no --occupancy)")
+    if not baked and (a.step is not None or a.bake_image is not None or a.save_baked is not None):
+        raise SystemExit("--step, --bake-image and --save-baked belong to --baked")
+    if a.load_baked is not None and (a.save_baked is not None or a.level is not None or a.bounds is not None):
+        raise SystemExit("--load-baked takes the grid, its box and its level from the file")
+    if a.occupancy is None and a.baked is None and (a.level is not None or a.bounds is not None):
+        raise SystemExit("--level and --bounds belong to --occupancy or --baked")
     return a
 
 
@@ -80,8 +106,24 @@ def main(argv=None):
         occ = OccupancyGrid.build(system, bounds, a.occupancy, a.level, dilate=a.dilate)
         extra = {"occupied_share": occ.fraction, "bounds": [list(bounds[0]), list(bounds[1])], "level": a.level, "dilate": a.dilate,
                  "occupancy_seconds": time.perf_counter() - tb}
+    scene = None
+    if a.baked is not None or a.load_baked is not None:
+        from upnerf_amd import geometry
+        from upnerf_amd.baked import BakedScene
+        tb = time.perf_counter()
+        if a.load_baked is not None:
+            scene = BakedScene.load(a.load_baked, next(system.parameters()).device)
+        else:
+            bounds = (tuple(a.bounds[:3]), tuple(a.bounds[3:])) if a.bounds else geometry.bounds_from_cameras(system, a.margin)
+            scene = BakedScene.build(system, bounds, a.baked, a.level, img_id=a.images[0] if a.bake_image is None else a.bake_image)
+            if a.save_baked is not None:
+                scene.save(a.save_baked)
+        torch.cuda.synchronize()
+        extra = {"baked_resolution": list(scene.resolution), "bounds": [list(scene.bounds[0]), list(scene.bounds[1])], "level": scene.level,
+                 "step": a.step, "occupied_share": scene.fraction, "baked_bytes": scene.nbytes, "bake_seconds": time.perf_counter() - tb}
     t0 = time.perf_counter()
-    render_path(system, path, chunk=a.chunk, outputs=("rgb",) + (("depth",) if a.depth else ()) + (("normal",) if a.normals else ()), sink=writer, occupancy=occ)
+    render_path(system, path, chunk=a.chunk, outputs=("rgb",) + (("depth",) if a.depth else ()) + (("normal",) if a.normals else ()), sink=writer, occupancy=occ,
+                baked=scene, baked_step=a.step)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if occ is not None:

@@ -370,6 +370,17 @@ class OccScatterArgs(C.Structure):
                 ("rays", _fp), ("rgb_c", _fp), ("depth_c", _fp), ("rgb", _fp), ("depth", _fp)]
 
 
+class BakedRenderArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("R", C.c_int32), ("lo", C.c_float * 3),
+                ("hi", C.c_float * 3), ("step", C.c_float), ("background", C.c_float), ("stop", C.c_float), ("reserved_", C.c_int32),
+                ("rgbs", _fp), ("words", _fp), ("rays", _fp), ("rgb", _fp), ("depth", _fp), ("opacity", _fp)]
+
+
+class BakedPackArgs(C.Structure):
+    _fields_ = [("n", C.c_int64), ("level", C.c_float), ("reserved_", C.c_int32), ("sigma", _fp), ("rgb", _fp), ("rgbs", _fp),
+                ("kept", _fp)]
+
+
 class DensityGradArgs(C.Structure):
     _fields_ = [("M", C.c_int32), ("reserved_", C.c_int32), ("points", _fp), ("P", _fp), ("PT", _fp), ("wk_xyz", C.c_float * 10),
                 ("sigma", _fp), ("grad", _fp)]
@@ -487,6 +498,8 @@ _SIGNATURES = {
     "upnerf_depth_to_space": [C.POINTER(DepthToSpaceArgs), _p],
     "upnerf_resize_cubic": [C.POINTER(ResizeCubicArgs), _p],
     "upnerf_vit_patches16": [C.POINTER(VitPatches16Args), _p],
+    "upnerf_baked_render": [C.POINTER(BakedRenderArgs), _p],
+    "upnerf_baked_pack": [C.POINTER(BakedPackArgs), _p],
 }
 _LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
              "upnerf_occ_compact_scratch", "upnerf_pca_fit_scratch")

@@ -1,0 +1,259 @@
+"""A baked scene: the static field sampled ONCE into a colour-density grid, and frames marched from that grid without touching
+the field -- a preview renderer that costs a few memory reads per sample instead of an 8 x 256 network.
+
+    bounds = bounds_from_cameras(system, margin=0.5)
+    scene = BakedScene.build(system, bounds, (256, 256, 256), level=10.0, img_id=3)
+    out = render_path(system, path, baked=scene, baked_step=0.01)      # or scene.render(rays, step=0.01)
+    scene.save("scene.npz"); scene = BakedScene.load("scene.npz", "cuda")
+
+The grid holds r, g, b, sigma at the Nx x Ny x Nz points of `density_grid`; a point whose sigma is below `level` (or not finite)
+is stored as (0, 0, 0, 0), and the occupancy bits are those of the kept sigmas (`OccupancyGrid.from_density` at the smallest
+positive fp32, no dilation): an unoccupied cell has eight exact zeros and contributes exactly nothing, so the bits only say where
+the integrand is zero and never change the picture.  Colour is the static colour head at sched_mult = 1 with ONE appearance row
+and for ONE viewing direction: a baked scene has NO view dependence.  The marcher is `upnerf_baked_render` (csrc/baked.hip;
+include/upnerf_hip.h states its arithmetic).  There is no CPU path."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, lib, ptr, stream
+from .ops import TIMER
+from .static_scene import box, c_float3, field_of, refined_training_poses, require_cuda
+
+__all__ = ["BakedScene", "field_colour", "TINY"]
+
+TINY = float(np.float32(2.0 ** -149))  # the smallest positive fp32: the level at which the kept sigmas are packed into bits
+
+
+def _field_rgb(model, o: torch.Tensor, d: torch.Tensor, z: torch.Tensor, view: torch.Tensor, a_rows: Optional[torch.Tensor]):
+    """(sigma_s [R, S], rgb [R, S, 3]) of `model` at o + d z, the colour for the viewing directions `view` [R, 3] and the
+    appearance rows `a_rows` [R, dim]: the sibling of geometry._field_sigma with the colour head on (use_rgb = 1, r1 = NULL:
+    inference, nothing stored for a backward pass).  The side input of the colour head is built by upnerf_ray_aux as
+    rendering._FieldPass builds it, from `view` -- the grid-column rays o, d still place the samples."""
+    from . import rendering as rd
+    pk, L = model.packer, model.packer.L
+    R, S = z.shape
+    dev, st = z.device, stream()
+    P = model.packed().detach().contiguous()
+    plan = rd._plan(pk, R, S, 2, False, True)  # mode 2, colour head, no gradient
+    PF, P16, _, wexp, wnorm = rd._weights(pk, P, plan)
+    progress = model.host_progress_value()
+    buf = rd._alloc(plan, "aux", dev)
+    wk = (C.c_float * 4)(*rd.band_weights(model.dir_L, progress, model.c2f))
+    check(lib.upnerf_ray_aux(R, ptr(view), ptr(a_rows), wk, None, ptr(buf["aux"]), st), "upnerf_ray_aux")
+    buf.update(rd._alloc(plan, "field", dev))
+    fa = rd._args(_lib.FieldFwdArgs, buf, R=R, S=S, use_cand=0, use_rgb=1, rays_o=ptr(o), rays_d=ptr(d), z=ptr(z),
+                  wk_xyz=(C.c_float * 10)(*rd.band_weights(model.xyz_L, progress, model.c2f)), P=ptr(PF), P16=ptr(P16),
+                  wexp=ptr(wexp), planes=plan.planes, tile_rows=plan.tile_rows, wnorm=ptr(wnorm), rows_capacity=plan.rows_capacity)
+    fn = lib.upnerf_field_fwd_f16x3 if plan.use16 else lib.upnerf_field_fwd
+    check(TIMER.run("baked_colour", lambda: fn(C.byref(L), C.byref(fa), st), units=R * S), "upnerf_field_fwd")
+    return buf["sigma_s"].view(R, S), buf["rgb"].view(R, S, 3)
+
+
+def _appearance(system, model, field: str, img_id, rows, dev) -> Optional[torch.Tensor]:
+    """The one appearance row [1, dim] of a bake, or None for a field without an appearance embedding."""
+    if not model.encode_appearance:
+        return None
+    if (img_id is None) == (rows is None):
+        raise ValueError("give either img_id (a training image's appearance) or rows (an appearance row of your own)")
+    w = system.embeddings[f"{field}_a"].weight.detach()
+    if rows is not None:
+        row = torch.as_tensor(rows, dtype=torch.float32).to(dev).reshape(1, -1)
+        if row.shape[1] != w.shape[1]:
+            raise ValueError(f"rows is one appearance row of width {w.shape[1]}, got {row.shape[1]}")
+        return row.contiguous()
+    if not 0 <= int(img_id) < w.shape[0]:
+        raise ValueError(f"img_id must be a training image index in [0, {w.shape[0]})")
+    return w[int(img_id)].reshape(1, -1).to(torch.float32).contiguous()
+
+
+def mean_optical_axis(system) -> torch.Tensor:
+    """[3] the normalised mean optical axis of the refined training cameras (a camera looks down its -z axis)."""
+    poses = refined_training_poses(system, otherwise="pass view_dir yourself")
+    axis = -poses[:, :, 2].double().mean(0)
+    n = float(axis.norm())
+    if not n > 0 or not np.isfinite(n):
+        raise ValueError("the training cameras' optical axes cancel: pass view_dir yourself")
+    return (axis / n).to(torch.float32)
+
+
+@torch.no_grad()
+def field_colour(system, bounds, resolution: Sequence[int], view_dir, img_id=None, rows=None, field: str = "fine",
+                 chunk: Optional[int] = None) -> torch.Tensor:
+    """[Nz, Ny, Nx, 3] fp32 device tensor: the static colour head (sched_mult = 1) of the `field` network at the grid points of
+    `density_grid`, for the viewing direction `view_dir` (normalised here) and one appearance row, `chunk` grid columns at a
+    time.  The values do not depend on `chunk`."""
+    from .geometry import MIN_SAMPLES, grid_columns
+    model, dev = field_of(system, field, "field_colour")
+    lo, hi = box(bounds)
+    Nx, Ny, Nz = (int(n) for n in resolution)
+    if min(Nx, Ny, Nz) < 1:
+        raise ValueError(f"resolution is the number of grid points per axis, got {tuple(resolution)}")
+    v = torch.as_tensor(view_dir, dtype=torch.float64).reshape(3)
+    n = float(v.norm())
+    if not n > 0 or not np.isfinite(n):
+        raise ValueError("view_dir is a direction: three finite numbers, not all zero")
+    v = (v / n).to(torch.float32).to(dev)
+    a_row = _appearance(system, model, field, img_id, rows, dev)
+    S = max(Nz, MIN_SAMPLES)
+    cols = Nx * Ny
+    chunk = int(chunk) if chunk is not None else max(1, (1 << 20) // S)
+    if chunk < 1:
+        raise ValueError(f"chunk must be positive, got {chunk}")
+    chunk = min(chunk, cols)
+    out = torch.empty(Nz, cols, 3, device=dev, dtype=torch.float32)
+    view = v.expand(chunk, 3).contiguous()
+    a_rows = a_row.expand(chunk, -1).contiguous() if a_row is not None else None
+    for c0 in range(0, cols, chunk):
+        n = min(chunk, cols - c0)
+        o, d, z = grid_columns((lo, hi), (Nx, Ny, Nz), c0, n, S, device=dev)
+        _, rgb = _field_rgb(model, o, d, z, view[:n], a_rows[:n] if a_rows is not None else None)
+        out[:, c0:c0 + n].copy_(rgb[:, :Nz].transpose(0, 1))
+    return out.view(Nz, Ny, Nx, 3)
+
+
+def _render_args(rays, step, background, stop):
+    step, background, stop = float(step), float(background), float(stop)
+    if not (step > 0 and np.isfinite(step)):
+        raise ValueError(f"step is a positive, finite length in units of t, got {step}")
+    if not np.isfinite(background):
+        raise ValueError(f"background is a finite grey level, got {background}")
+    if not 0 <= stop < 1:
+        raise ValueError(f"stop is a transmittance in [0, 1) (0: never), got {stop}")
+    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or rays.shape[0] < 1:
+        raise ValueError("rays are a fp32 tensor [R, 8] (o | d | near | far) with R >= 1")
+    return step, background, stop
+
+
+class BakedScene:
+    """`rgbs` [Nz, Ny, Nx, 4] fp32 on the device (r, g, b, sigma at the grid points, pruned at `level`), the box it spans and
+    the OccupancyGrid of its kept sigmas."""
+
+    def __init__(self, rgbs: torch.Tensor, bounds, level: float):
+        from .occupancy import OccupancyGrid
+        require_cuda("BakedScene", rgbs)
+        if rgbs.dtype != torch.float32 or rgbs.dim() != 4 or rgbs.shape[3] != 4 or not rgbs.is_contiguous():
+            raise ValueError("rgbs is a contiguous fp32 tensor [Nz, Ny, Nx, 4]")
+        self.rgbs = rgbs
+        self.bounds = box(bounds, strict=True)
+        self.level = float(level)
+        self.occupancy = OccupancyGrid.from_density(rgbs[..., 3].contiguous(), self.bounds, level=TINY, dilate=0)
+
+    # ---- construction ------------------------------------------------------------------------------------------------------
+
+    @classmethod
+    @torch.no_grad()
+    def from_grids(cls, sigma: torch.Tensor, rgb: Optional[torch.Tensor], bounds, level: float = 0.0) -> "BakedScene":
+        """From a density grid [Nz, Ny, Nx] and a colour grid [Nz, Ny, Nx, 3] (None: black) of the caller's own, fp32 on the
+        device.  A point is kept iff its sigma is finite, positive and >= level; every other point becomes (0, 0, 0, 0)
+        (upnerf_baked_pack)."""
+        require_cuda("BakedScene.from_grids", sigma, *([rgb] if rgb is not None else []))
+        if sigma.dtype != torch.float32 or sigma.dim() != 3 or min(sigma.shape) < 2:
+            raise ValueError("sigma is a fp32 tensor [Nz, Ny, Nx] with two points per axis at least")
+        if rgb is not None and (rgb.dtype != torch.float32 or tuple(rgb.shape) != tuple(sigma.shape) + (3,)):
+            raise ValueError("rgb is a fp32 tensor [Nz, Ny, Nx, 3]")
+        level = float(level)
+        if level != level:
+            raise ValueError("level is not a number")
+        sigma = sigma.detach().contiguous()
+        rgb = rgb.detach().contiguous() if rgb is not None else None
+        rgbs = torch.empty(tuple(sigma.shape) + (4,), device=sigma.device, dtype=torch.float32)
+        a = _lib.BakedPackArgs(n=sigma.numel(), level=level, sigma=ptr(sigma), rgb=ptr(rgb), rgbs=ptr(rgbs), kept=None)
+        check(TIMER.run("baked_pack", lambda: lib.upnerf_baked_pack(C.byref(a), stream()), units=sigma.numel()), "upnerf_baked_pack")
+        return cls(rgbs, bounds, level)
+
+    @classmethod
+    @torch.no_grad()
+    def build(cls, system, bounds, resolution: Sequence[int], level: float, img_id=None, rows=None, view_dir=None,
+              field: str = "fine", chunk: Optional[int] = None) -> "BakedScene":
+        """Bake the static scene of `system`: sigma = geometry.density_grid, colour = field_colour with the appearance row of
+        training image `img_id` (or `rows`, a row of the caller's own) for the viewing direction `view_dir` (default: the
+        normalised mean optical axis of the refined training cameras).  `level` has no default: the useful threshold depends on
+        the scene's scale (see extract_surface).  `resolution` counts grid POINTS per axis, two at least."""
+        from .geometry import density_grid
+        if min(int(n) for n in resolution) < 2:
+            raise ValueError(f"resolution is the number of grid points per axis (two at least), got {tuple(resolution)}")
+        if view_dir is None:
+            view_dir = mean_optical_axis(system)
+        sigma = density_grid(system, bounds, resolution, field=field, chunk=chunk)
+        rgb = field_colour(system, bounds, resolution, view_dir, img_id=img_id, rows=rows, field=field, chunk=chunk)
+        return cls.from_grids(sigma, rgb, bounds, level)
+
+    # ---- rendering ---------------------------------------------------------------------------------------------------------
+
+    def render(self, rays: torch.Tensor, step: float, background: float = 0.0, stop: float = 0.0, out: Optional[dict] = None) -> dict:
+        """{"rgb" [R, 3], "depth" [R], "opacity" [R]} of [R, 8] device rays (upnerf_baked_render): samples every `step` of t
+        from near + step / 2, alpha-composited front to back; what the ray does not hit shows `background` at depth `far`.
+        stop > 0 ends a ray once its transmittance falls below it.  out: preallocated buffers of at least R rows."""
+        require_cuda("BakedScene.render", rays)
+        step, background, stop = _render_args(rays, step, background, stop)
+        rays = rays.contiguous()
+        if rays.data_ptr() % 16:
+            rays = rays.clone()
+        R, dev = rays.shape[0], rays.device
+        if out is None:
+            out = {"rgb": torch.empty(R, 3, device=dev), "depth": torch.empty(R, device=dev), "opacity": torch.empty(R, device=dev)}
+        for k, shape in (("rgb", (3,)), ("depth", ()), ("opacity", ())):
+            t = out[k]
+            if t.dtype != torch.float32 or t.shape[0] < R or tuple(t.shape[1:]) != shape or t.device != dev:
+                raise ValueError("the outputs are fp32 [>= R, 3], [>= R] and [>= R] on the rays' device")
+        Cx, Cy, Cz = self.occupancy.dims
+        lo, hi = self.bounds
+        a = _lib.BakedRenderArgs(Cx=Cx, Cy=Cy, Cz=Cz, R=R, lo=c_float3(lo), hi=c_float3(hi), step=step, background=background,
+                                 stop=stop, rgbs=ptr(self.rgbs), words=ptr(self.occupancy.words), rays=ptr(rays),
+                                 rgb=ptr(out["rgb"]), depth=ptr(out["depth"]), opacity=ptr(out["opacity"]))
+        check(TIMER.run("baked_render", lambda: lib.upnerf_baked_render(C.byref(a), stream()), units=R), "upnerf_baked_render")
+        return {k: out[k][:R] for k in ("rgb", "depth", "opacity")}
+
+    # ---- files -------------------------------------------------------------------------------------------------------------
+
+    def save(self, path: str) -> None:
+        """An .npz holding the grid, the bounds and the level; the bits are rebuilt on load."""
+        save_arrays(path, self.rgbs.detach().cpu().numpy(), self.bounds, self.level)
+
+    @classmethod
+    def load(cls, path: str, device="cuda") -> "BakedScene":
+        rgbs, bounds, level = load_arrays(path)
+        return cls(torch.from_numpy(rgbs).to(device).contiguous(), bounds, level)
+
+    # ---- accessors ---------------------------------------------------------------------------------------------------------
+
+    @property
+    def resolution(self):
+        Nz, Ny, Nx, _ = self.rgbs.shape
+        return Nx, Ny, Nz
+
+    @property
+    def nbytes(self) -> int:
+        """Device bytes of the grid and its bits."""
+        return self.rgbs.numel() * 4 + self.occupancy.words.numel() * 4
+
+    @property
+    def fraction(self) -> float:
+        """Occupied share of the cells."""
+        return self.occupancy.fraction
+
+
+def save_arrays(path: str, rgbs: np.ndarray, bounds, level: float) -> None:
+    rgbs = np.asarray(rgbs)
+    if rgbs.dtype != np.float32 or rgbs.ndim != 4 or rgbs.shape[3] != 4:
+        raise ValueError("rgbs is a fp32 array [Nz, Ny, Nx, 4]")
+    lo, hi = box(bounds, strict=True)
+    with open(path, "wb") as fh:  # (a file object: numpy appends no .npz of its own to the name)
+        np.savez(fh, rgbs=rgbs, bounds=np.asarray([lo, hi], np.float64), level=np.float64(level))
+
+
+def load_arrays(path: str):
+    """(rgbs fp32 [Nz, Ny, Nx, 4], bounds, level) of a file BakedScene.save wrote; anything else raises ValueError."""
+    with np.load(path) as f:
+        if set(f.files) != {"rgbs", "bounds", "level"}:
+            raise ValueError(f"{path}: not a baked scene (arrays {sorted(f.files)})")
+        rgbs, bounds, level = f["rgbs"], f["bounds"], float(f["level"])
+    if rgbs.dtype != np.float32 or rgbs.ndim != 4 or rgbs.shape[3] != 4 or bounds.shape != (2, 3) or min(rgbs.shape[:3]) < 2:
+        raise ValueError(f"{path}: not a baked scene (rgbs {rgbs.dtype} {rgbs.shape}, bounds {bounds.shape})")
+    return np.ascontiguousarray(rgbs), box(bounds.tolist(), strict=True), level

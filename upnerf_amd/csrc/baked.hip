@@ -1,0 +1,246 @@
+// A baked scene: the static field sampled once into a colour-density grid (r, g, b, sigma per grid point, 16 bytes), and rays
+// marched through that grid without touching the field (include/upnerf_hip.h states the arithmetic).
+//   upnerf_baked_pack    sigma [n] and rgb [n][3] -> rgbs [n][4]; a point whose sigma is below the level, not positive or not
+//                        finite becomes (0, 0, 0, 0), so a cell none of whose corners kept a sigma holds eight exact zeros.
+//   upnerf_baked_render  one thread per ray, one wave per workgroup (a chunk of 16 384 rays is 256 workgroups: one per CU).  The
+//                        samples sit on a lattice the ray alone fixes, t_k = fmaf(k + 0.5, step, near): every sample is computed
+//                        from its index.  Every fp32 operation between k and the grid coordinate g is monotone (a rounding never
+//                        reverses an order), so g is monotone in k on every axis -- and with it the cell, the brick and the side
+//                        of the box a sample falls on.  Skipping rests on that alone: where sample k lies in an empty region (outside
+//                        the box on one axis; a brick with a clear bit; a cell with a clear bit), a later sample k' is PROPOSED
+//                        from the plane through which the ray leaves the region, and the jump is taken only if sample k', located
+//                        by the same arithmetic as any sample, lies in the SAME region: then so does every sample between them.  A
+//                        refused proposal costs one step.  No span, no epsilon, nothing a rounding could move across an edge: the
+//                        picture is, bit for bit, the one that visits every sample (tests/test_hip_baked.py runs both).
+//                        A visited sample reads its eight corners as eight 16-byte loads; the rays of a wave are 64 neighbouring
+//                        pixels of an image row and read neighbouring corners.  All per-ray state is in registers; no LDS.
+// All stores are ordinary vector stores from plain C++.
+#include "common.cuh"
+#include "grid.cuh"
+
+#include <math.h>
+
+namespace {
+
+#define BAKED_THREADS 64
+
+struct BakedGrid {
+  int C[3];        // cells per axis
+  float lo[3], inv[3], Cf[3];
+  int64_t sy, sz;  // strides of the point grid, in points
+};
+
+// sample k of a ray: its t, its grid coordinates, and where it falls
+struct BakedSample {
+  float t, g[3];
+  int i[3];     // cell per axis (inside only)
+  int side[3];  // 0: inside the slab of the axis, -1: g < 0, +1: g > C, 2: not a number
+  bool inside;
+};
+
+__host__ __device__ __forceinline__ BakedSample baked_locate(const BakedGrid& G, const float* o, const float* d, float near,
+                                                             float step, int k) {
+  BakedSample s;
+  s.t = fmaf((float)k + 0.5f, step, near);
+  s.inside = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float p = fmaf(s.t, d[a], o[a]);
+    const float g = (p - G.lo[a]) * G.inv[a];
+    s.g[a] = g;
+    s.side[a] = g < 0.0f ? -1 : (g > G.Cf[a] ? 1 : (g >= 0.0f ? 0 : 2));
+    if (s.side[a] != 0) s.inside = false;
+    const int i = (int)floorf(s.side[a] == 0 ? g : 0.0f);
+    s.i[a] = i < G.C[a] - 1 ? i : G.C[a] - 1;
+  }
+  return s;
+}
+
+// the sample index proposed for a t at which the ray leaves a region: the last sample before it, less one; < 0: none
+__host__ __device__ __forceinline__ int baked_propose(float t_exit, float near, float step, int K) {
+  const float x = floorf((t_exit - near) / step - 0.5f) - 1.0f;
+  if (!(x > 0.0f)) return -1;
+  return x < (float)(K - 1) ? (int)x : K - 1;
+}
+
+struct BakedOut {
+  float rgb[3], depth, opacity;
+};
+
+// the march of one ray row (host and device: the host build is what a CPU program checks against the fp64 restatement)
+__host__ __device__ __forceinline__ BakedOut baked_march(const upnerf_baked_render_args& A, const BakedGrid& G, const OccDims& dm,
+                                                         const float* row, bool use_bits) {
+  const float o[3] = {row[0], row[1], row[2]}, d[3] = {row[3], row[4], row[5]};
+  const float near = row[6], far = row[7];
+  BakedOut out;
+  out.rgb[0] = out.rgb[1] = out.rgb[2] = 0.0f;
+  out.depth = 0.0f;
+  out.opacity = 0.0f;
+  bool ok = far > near;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ok = ok && isfinite(row[j]);
+  if (ok) {
+    const float nk = ceilf((far - near) / A.step);
+    const int K = nk < (float)UPNERF_BAKED_MAX_SAMPLES ? (int)nk : UPNERF_BAKED_MAX_SAMPLES;
+    const float delta = A.step * sqrtf(fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0])));
+    const uint32_t* fine = A.words;
+    const uint32_t* brick = A.words + dm.fine_words;
+    const f32x4* pts = (const f32x4*)A.rgbs;
+    float T = 1.0f;
+    int k = 0;
+    while (k < K) {
+      const BakedSample s = baked_locate(G, o, d, near, A.step, k);
+      int next = k + 1;
+      if (!s.inside) {
+        // outside on an axis along which the ray does not come back: every later sample is outside too
+        bool gone = false;
+        float t_in = -INFINITY;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          if (s.side[a] == 1 || s.side[a] == -1) {
+            const bool away = s.side[a] > 0 ? d[a] >= 0.0f : d[a] <= 0.0f;
+            if (away) gone = true;
+            else t_in = fmaxf(t_in, ((s.side[a] > 0 ? G.lo[a] + G.Cf[a] / G.inv[a] : G.lo[a]) - o[a]) / d[a]);
+          }
+        }
+        if (gone) break;
+        if (use_bits) {
+          const int kp = baked_propose(t_in, near, A.step, K);
+          if (kp > k) {
+            const BakedSample q = baked_locate(G, o, d, near, A.step, kp);
+            bool same = false;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) same = same || ((s.side[a] == 1 || s.side[a] == -1) && q.side[a] == s.side[a]);
+            if (same) next = kp + 1;
+          }
+        }
+        k = next;
+        continue;
+      }
+      if (use_bits) {
+        const int bx = s.i[0] / OCC_BRICK, by = s.i[1] / OCC_BRICK, bz = s.i[2] / OCC_BRICK;
+        int shift = -1;  // the empty region the sample lies in: 3 = its brick, 0 = its cell, -1 = none
+        if (!occ_bit(brick, ((int64_t)bz * dm.By + by) * dm.Bx + bx)) shift = 3;
+        else if (!occ_bit(fine, ((int64_t)s.i[2] * dm.Cy + s.i[1]) * dm.Cx + s.i[0])) shift = 0;
+        if (shift >= 0) {
+          float t_out = INFINITY;
+#pragma unroll
+          for (int a = 0; a < 3; ++a) {
+            if (d[a] == 0.0f) continue;
+            const int r = s.i[a] >> shift;
+            int plane = d[a] > 0.0f ? (r + 1) << shift : r << shift;
+            plane = plane < G.C[a] ? plane : G.C[a];
+            t_out = fminf(t_out, ((G.lo[a] + (float)plane / G.inv[a]) - o[a]) / d[a]);
+          }
+          const int kp = baked_propose(t_out, near, A.step, K);
+          if (kp > k) {
+            const BakedSample q = baked_locate(G, o, d, near, A.step, kp);
+            if (q.inside && (q.i[0] >> shift) == (s.i[0] >> shift) && (q.i[1] >> shift) == (s.i[1] >> shift) &&
+                (q.i[2] >> shift) == (s.i[2] >> shift))
+              next = kp + 1;
+          }
+          k = next;
+          continue;
+        }
+      }
+      // the sample counts: trilinear blend of the eight corners, x first, then y, then z
+      const int64_t base = ((int64_t)s.i[2] * G.sz + (int64_t)s.i[1] * G.sy) + s.i[0];
+      const float fx = s.g[0] - (float)s.i[0], fy = s.g[1] - (float)s.i[1], fz = s.g[2] - (float)s.i[2];
+      const f32x4 c000 = pts[base], c100 = pts[base + 1];
+      const f32x4 c010 = pts[base + G.sy], c110 = pts[base + G.sy + 1];
+      const f32x4 c001 = pts[base + G.sz], c101 = pts[base + G.sz + 1];
+      const f32x4 c011 = pts[base + G.sz + G.sy], c111 = pts[base + G.sz + G.sy + 1];
+      float v[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float x00 = fmaf(fx, c100[c] - c000[c], c000[c]), x10 = fmaf(fx, c110[c] - c010[c], c010[c]);
+        const float x01 = fmaf(fx, c101[c] - c001[c], c001[c]), x11 = fmaf(fx, c111[c] - c011[c], c011[c]);
+        const float y0 = fmaf(fy, x10 - x00, x00), y1 = fmaf(fy, x11 - x01, x01);
+        v[c] = fmaf(fz, y1 - y0, y0);
+      }
+      const float e = expf(-delta * v[3]);
+      const float alpha = 1.0f - e;
+      const float w = T * alpha;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) out.rgb[c] = fmaf(w, v[c], out.rgb[c]);
+      out.depth = fmaf(w, s.t, out.depth);
+      out.opacity += w;
+      T *= 1.0f - alpha;
+      if (A.stop > 0.0f && T < A.stop) break;
+      k = next;
+    }
+  }
+  const float rest = 1.0f - out.opacity;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out.rgb[c] = fmaf(rest, A.background, out.rgb[c]);
+  out.depth = fmaf(rest, far, out.depth);
+  return out;
+}
+
+__global__ __launch_bounds__(BAKED_THREADS) void baked_render_kernel(upnerf_baked_render_args a, BakedGrid G, OccDims dm) {
+  const int r = blockIdx.x * BAKED_THREADS + threadIdx.x;
+  if (r >= a.R) return;
+  const f32x4* rp = (const f32x4*)(a.rays + (int64_t)r * 8);  // (rows of 32 bytes in a buffer the host found 16-byte aligned)
+  const f32x4 r0 = rp[0], r1 = rp[1];
+  const float row[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+  const BakedOut out = baked_march(a, G, dm, row, true);
+  float* c = a.rgb + (int64_t)r * 3;
+  c[0] = out.rgb[0], c[1] = out.rgb[1], c[2] = out.rgb[2];
+  a.depth[r] = out.depth;
+  a.opacity[r] = out.opacity;
+}
+
+__global__ __launch_bounds__(NTHREADS) void baked_pack_kernel(upnerf_baked_pack_args a) {
+  const int64_t n = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
+  if (n >= a.n) return;
+  const float s = a.sigma[n];
+  const bool keep = isfinite(s) && s > 0.0f && s >= a.level;
+  f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (keep) {
+    if (a.rgb) v.x = a.rgb[n * 3], v.y = a.rgb[n * 3 + 1], v.z = a.rgb[n * 3 + 2];
+    v.w = s;
+  }
+  ((f32x4*)a.rgbs)[n] = v;
+  if (a.kept) a.kept[n] = keep ? 1 : 0;
+}
+
+bool baked_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// the arguments a launch may be given, and the grid as the kernel reads it
+bool baked_grid(const upnerf_baked_render_args* a, BakedGrid* G, OccDims* dm) {
+  if (!a || !occ_dims(a->Cx, a->Cy, a->Cz, dm) || a->R <= 0) return false;
+  if (!a->rgbs || !a->words || !a->rays || !a->rgb || !a->depth || !a->opacity) return false;
+  if (!baked_aligned16(a->rgbs) || !baked_aligned16(a->rays)) return false;
+  if (!(a->step > 0.0f) || !isfinite(a->step) || !isfinite(a->background) || !(a->stop >= 0.0f && a->stop < 1.0f)) return false;
+  const int C[3] = {a->Cx, a->Cy, a->Cz};
+  for (int k = 0; k < 3; ++k) {
+    if (!(a->hi[k] > a->lo[k]) || !isfinite(a->hi[k]) || !isfinite(a->lo[k])) return false;
+    G->C[k] = C[k];
+    G->Cf[k] = (float)C[k];
+    G->lo[k] = a->lo[k];
+    G->inv[k] = (float)((double)C[k] / ((double)a->hi[k] - (double)a->lo[k]));
+    if (!(G->inv[k] > 0.0f) || !isfinite(G->inv[k])) return false;
+  }
+  G->sy = (int64_t)a->Cx + 1;
+  G->sz = G->sy * ((int64_t)a->Cy + 1);
+  return true;
+}
+
+}  // namespace
+
+extern "C" int upnerf_baked_render(const upnerf_baked_render_args* a, void* stream) {
+  BakedGrid G;
+  OccDims dm;
+  if (!baked_grid(a, &G, &dm)) return UPNERF_EINVAL;
+  hipLaunchKernelGGL(baked_render_kernel, dim3((a->R + BAKED_THREADS - 1) / BAKED_THREADS), dim3(BAKED_THREADS), 0,
+                     (hipStream_t)stream, *a, G, dm);
+  return (int)hipGetLastError();
+}
+
+extern "C" int upnerf_baked_pack(const upnerf_baked_pack_args* a, void* stream) {
+  if (!a || a->n <= 0 || !a->sigma || !a->rgbs || !baked_aligned16(a->rgbs) || a->level != a->level) return UPNERF_EINVAL;
+  const int64_t blocks = (a->n + NTHREADS - 1) / NTHREADS;
+  if (blocks > 0x7fffffff) return UPNERF_EUNSUP;
+  hipLaunchKernelGGL(baked_pack_kernel, dim3((unsigned)blocks), dim3(NTHREADS), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}

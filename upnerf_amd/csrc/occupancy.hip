@@ -17,32 +17,13 @@
 //                       and gets the background and its own far.  One thread per row, a binary search of the index.
 // All stores are ordinary vector stores from plain C++.
 #include "common.cuh"
+#include "grid.cuh"
 #include "scan.cuh"
 
 #include <limits.h>
 #include <math.h>
 
 namespace {
-
-#define OCC_BRICK 8
-
-struct OccDims {
-  int Cx, Cy, Cz, Bx, By, Bz;
-  int64_t cells, bricks, fine_words, brick_words;
-};
-
-bool occ_dims(int Cx, int Cy, int Cz, OccDims* d) {
-  if (Cx < 1 || Cy < 1 || Cz < 1) return false;
-  const int64_t cells = (int64_t)Cx * Cy * Cz;
-  if ((int64_t)Cx * Cy > INT_MAX || cells > INT_MAX) return false;
-  d->Cx = Cx, d->Cy = Cy, d->Cz = Cz;
-  d->Bx = (Cx + OCC_BRICK - 1) / OCC_BRICK, d->By = (Cy + OCC_BRICK - 1) / OCC_BRICK, d->Bz = (Cz + OCC_BRICK - 1) / OCC_BRICK;
-  d->cells = cells;
-  d->bricks = (int64_t)d->Bx * d->By * d->Bz;
-  d->fine_words = (cells + 31) / 32;
-  d->brick_words = (d->bricks + 31) / 32;
-  return true;
-}
 
 // ---- build -----------------------------------------------------------------------------------------------------------------------
 
@@ -145,8 +126,6 @@ __host__ __device__ __forceinline__ int occ_cell_of(const OccAxis& a, double p, 
   else if (i < c1 && p >= occ_plane(a, i + 1)) ++i;
   return i;
 }
-
-__host__ __device__ __forceinline__ bool occ_bit(const uint32_t* words, int64_t b) { return (words[b >> 5] >> (b & 31)) & 1u; }
 
 __host__ __device__ __forceinline__ int occ_imin(int a, int b) { return a < b ? a : b; }
 

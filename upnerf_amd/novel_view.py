@@ -207,7 +207,7 @@ def path_rays(c2w: torch.Tensor, nf: torch.Tensor, img_wh, K, row0: int, R: int,
 @torch.no_grad()
 def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: Sequence[str] = ("rgb",),
                 depth_range: Optional[Tuple[float, float]] = None, sink: Optional[Callable] = None,
-                occupancy=None) -> Dict[str, torch.Tensor]:
+                occupancy=None, baked=None, baked_step: Optional[float] = None) -> Dict[str, torch.Tensor]:
     """Render every frame of `path` with the static fields of `system` (perturb = 0, no gradient, validation's sample counts).
 
     outputs: any of "rgb" (uint8 [F, H, W, 3] of `s_rgb_fine`, `s_rgb_coarse` without a fine field), "depth" (uint8
@@ -222,7 +222,15 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
     [near, far], and the results scattered back (upnerf_occ_scatter); a ray that touches nothing shows the BACKGROUND (1 with
     white_back, else 0) at depth `far` -- not what the full render would have composited from density below the grid's level.
     One host read per chunk (the hit count); a chunk without hits launches no field kernel.  LAST_STATS holds the sequence's
-    number of rays and hits.  None: nothing of this runs."""
+    number of rays and hits.  None: nothing of this runs.
+    baked: a `baked.BakedScene`, with `baked_step` (the sample spacing in units of t; no default).  The frames come from
+    `baked.render` on the rays upnerf_path_rays makes and the fields are never evaluated: no view dependence, ONE appearance (the
+    one the scene was baked with: the path's blend is not looked at), outputs "rgb", "depth" and "rgb_float" only.  Asking for a
+    normal map, or passing `occupancy` as well (the scene carries its own bits), raises ValueError."""
+    if baked is not None:
+        return _render_path_baked(system, path, chunk, outputs, depth_range, sink, occupancy, baked, baked_step)
+    if baked_step is not None:
+        raise ValueError("baked_step belongs to baked=")
     from .visualization import depth_image, min_max_of, normal_image, rgb_image
     unknown = set(outputs) - {"rgb", "depth", "rgb_float", "normal", "normal_float"}
     if unknown:
@@ -349,4 +357,70 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
                 g += cnt
                 if p0 + cnt == n:
                     finish(f)
+    return out
+
+
+def _render_path_baked(system, path: CameraPath, chunk, outputs, depth_range, sink, occupancy, baked, baked_step):
+    """render_path(..., baked=scene, baked_step=dt): the frames of `path` from the baked scene's grid alone."""
+    from .baked import BakedScene
+    from .visualization import depth_image, min_max_of, rgb_image
+    if not isinstance(baked, BakedScene):
+        raise ValueError("baked is a baked.BakedScene")
+    if occupancy is not None:
+        raise ValueError("occupancy and baked exclude each other: a baked scene carries the bits of its own grid")
+    if baked_step is None:
+        raise ValueError("baked needs baked_step, the sample spacing in units of t (it has no default: it depends on the scene's scale)")
+    unknown = set(outputs) - {"rgb", "depth", "rgb_float"}
+    if unknown:
+        raise ValueError(f"a baked scene renders rgb, depth and rgb_float only, not {sorted(unknown)}")
+    dev = baked.rgbs.device
+    W, H = path.img_wh
+    F, n = path.n_frames, W * H
+    total = F * n
+    chunk = int(chunk or system.hparams["val.chunk_size"])
+    if chunk < 1:
+        raise ValueError(f"chunk must be positive, got {chunk}")
+    chunk = min(chunk, total)
+    c2w, nf = path_poses(path.key_c2w.to(dev), path.key_near_far.to(dev), path.u.to(dev), path.mode)
+    intr = intrinsics(path.K)
+    background = 1.0 if getattr(system.train_dataset, "white_back", False) else 0.0
+    want_depth = "depth" in outputs
+    rays_ws = torch.empty(chunk, 8, device=dev, dtype=torch.float32)
+    ws = {"rgb": torch.empty(chunk, 3, device=dev), "depth": torch.empty(chunk, device=dev), "opacity": torch.empty(chunk, device=dev)}
+    stage_rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    stage_depth = torch.empty(n, device=dev, dtype=torch.float32) if want_depth else None
+    out: Dict[str, torch.Tensor] = {}
+    if "rgb" in outputs:
+        out["rgb"] = torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
+    if want_depth:
+        out["depth"] = torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
+    if "rgb_float" in outputs:
+        out["rgb_float"] = torch.empty(F, n, 3, device=dev, dtype=torch.float32)
+    rng_dev = None  # frame 0's (min, max) depth on the device: one colour scale for the whole sequence
+    for g0 in range(0, total, chunk):
+        R = min(chunk, total - g0)
+        rays, _ = path_rays(c2w, nf, (W, H), intr, g0, R, rays=rays_ws)
+        res = baked.render(rays, baked_step, background=background, out=ws)
+        g = g0
+        while g < g0 + R:  # the chunk's rows, frame by frame
+            f, p0 = divmod(g, n)
+            cnt = min(n - p0, g0 + R - g)
+            stage_rgb[p0:p0 + cnt].copy_(res["rgb"][g - g0:g - g0 + cnt])
+            if want_depth:
+                stage_depth[p0:p0 + cnt].copy_(res["depth"][g - g0:g - g0 + cnt])
+            g += cnt
+            if p0 + cnt == n:
+                images = {}
+                if "rgb_float" in out:
+                    out["rgb_float"][f].copy_(stage_rgb)
+                if "rgb" in out:
+                    out["rgb"][f].copy_(rgb_image(stage_rgb, (W, H)))
+                    images["rgb"] = out["rgb"][f]
+                if want_depth:
+                    if depth_range is None and rng_dev is None:
+                        rng_dev = min_max_of(stage_depth)
+                    out["depth"][f].copy_(depth_image(stage_depth, (W, H), min_max=depth_range if depth_range is not None else rng_dev))
+                    images["depth"] = out["depth"][f]
+                if sink is not None:
+                    sink("path", f, images)
     return out
