@@ -12,28 +12,46 @@ def mat(P, off, n, k):
     return P[off:off + n * k].view(n, k)
 
 
-def posenc_w(x, L, wk):
-    freq = (2 ** torch.arange(L, dtype=torch.float32)).to(x.dtype) * torch.pi
-    arg = x[..., None] * freq
+def posenc_w(x, L, wk, arg32=False):
+    """arg32: the argument of every sin / cos is the kernels' own -- the fp32 product x * ldexpf(PI_F, k) of the fp32 value of x --
+    with the exact derivative (straight-through); sin and cos themselves are evaluated in x's precision."""
+    if arg32:
+        freq32 = (2 ** torch.arange(L, dtype=torch.float32)) * torch.pi
+        arg = x[..., None] * freq32.to(x.dtype)
+        arg = arg + ((x.detach().float()[..., None] * freq32).to(x.dtype) - arg).detach()
+    else:
+        freq = (2 ** torch.arange(L, dtype=torch.float32)).to(x.dtype) * torch.pi
+        arg = x[..., None] * freq
     enc = torch.stack([arg.sin(), arg.cos()], dim=-2) * torch.as_tensor(wk, dtype=x.dtype)
     return torch.cat([x, enc.reshape(*x.shape[:-1], -1)], -1)
 
 
-def ray_aux(rays_d, a_rows, wk_dir):
+def ray_aux(rays_d, a_rows, wk_dir, arg32=False):
     R = rays_d.shape[0]
-    pe = posenc_w(rays_d, 4, wk_dir)
+    pe = posenc_w(rays_d, 4, wk_dir, arg32)
     a = a_rows if a_rows is not None else torch.zeros(R, 48, dtype=rays_d.dtype)
     return torch.cat([pe, a, torch.zeros(R, AUXK - 75, dtype=rays_d.dtype)], 1)
 
 
-def field(P, pk, rays_o, rays_d, z, c_rows, aux, wk_xyz, use_cand, use_rgb, keep_pre=False):
+def field(P, pk, rays_o, rays_d, z, c_rows, aux, wk_xyz, use_cand, use_rgb, keep_pre=False, arg32=False, quant=None):
     """Returns dict with x0 [M,64], h [D][M,W], e, g1, g2, r1, sigma_s, sigma_c, rgb and (keep_pre) the
-    pre-activation tensors with retain_grad() set."""
+    pre-activation tensors with retain_grad() set.
+
+    arg32: a reference run in fp64 starts where the kernels start -- the sample positions o + d z and the encoding's arguments
+    take the values fp32 arithmetic gives them (one fp32 ulp of 2^9 pi x moves its sine by ~1e-4), with the exact derivatives
+    (straight-through, as composite's e32); everything behind x0 runs in the precision of the inputs.
+    quant: optional rounding applied to both operands of every matrix product (trunk, final layer, first and second head layers; the
+    vector heads, biases and accumulation stay as they are) -- the "f16" mode's arithmetic with a floating exponent per element."""
+    q = quant or (lambda t: t)
     L, W, W2, D = pk.L, pk.W, pk.W2, pk.D
     R, S = z.shape
     M = R * S
     xyz = (rays_o[:, None, :] + rays_d[:, None, :] * z[..., None]).reshape(M, 3)
-    x0 = F.pad(posenc_w(xyz, 10, wk_xyz), (0, 1))
+    if arg32:
+        o32, d32, z32 = (t.detach().float() for t in (rays_o, rays_d, z))
+        xyz32 = (o32[:, None, :] + d32[:, None, :] * z32[..., None]).reshape(M, 3)
+        xyz = xyz + (xyz32.to(xyz.dtype) - xyz).detach()
+    x0 = F.pad(posenc_w(xyz, 10, wk_xyz, arg32), (0, 1))
     out = {"x0": x0, "h": [], "pre_h": []}
     ray = torch.arange(M) // S
 
@@ -47,25 +65,25 @@ def field(P, pk, rays_o, rays_d, z, c_rows, aux, wk_xyz, use_cand, use_rgb, keep
         k = X0 if l == 0 else (X0 + W if l == pk.skip else W)
         w, b = mat(P, L.w[l], W, k), P[L.b[l]:L.b[l] + W]
         inp = torch.cat([x0, h], 1) if l == pk.skip else h
-        pre = keep(inp @ w.t() + b)
+        pre = keep(q(inp) @ q(w).t() + b)
         h = torch.relu(pre)
         out["pre_h"].append(pre)
         out["h"].append(h)
     pre_s = keep(h @ P[L.wsig:L.wsig + W] + P[L.bsig])
     out["pre_sig_s"], out["sigma_s"] = pre_s, F.softplus(pre_s)
-    e = keep(h @ mat(P, L.we, W, W).t() + P[L.be:L.be + W])
+    e = keep(q(h) @ q(mat(P, L.we, W, W)).t() + P[L.be:L.be + W])
     out["e"] = e
     if use_cand:
         wc1 = mat(P, L.wc1, W2, W + CK)
-        pre_g1 = keep(torch.cat([e, c_rows[ray]], 1) @ wc1.t() + P[L.bc1:L.bc1 + W2])
+        pre_g1 = keep(q(torch.cat([e, c_rows[ray]], 1)) @ q(wc1).t() + P[L.bc1:L.bc1 + W2])
         g1 = torch.relu(pre_g1)
-        pre_g2 = keep(g1 @ mat(P, L.wc2, W2, W2).t() + P[L.bc2:L.bc2 + W2])
+        pre_g2 = keep(q(g1) @ q(mat(P, L.wc2, W2, W2)).t() + P[L.bc2:L.bc2 + W2])
         g2 = torch.relu(pre_g2)
         pre_c = keep(g2 @ P[L.wcsig:L.wcsig + W2] + P[L.bcsig])
         out.update(pre_g1=pre_g1, g1=g1, pre_g2=pre_g2, g2=g2, pre_sig_c=pre_c, sigma_c=F.softplus(pre_c))
     if use_rgb:
         wr1 = mat(P, L.wr1, W2, W + AUXK)
-        pre_r1 = keep(torch.cat([e, aux[ray]], 1) @ wr1.t() + P[L.br1:L.br1 + W2])
+        pre_r1 = keep(q(torch.cat([e, aux[ray]], 1)) @ q(wr1).t() + P[L.br1:L.br1 + W2])
         r1 = torch.relu(pre_r1)
         pre_rgb = keep(r1 @ mat(P, L.wr2, 4, W2)[:3].t() + P[L.br2:L.br2 + 3])
         out.update(pre_r1=pre_r1, r1=r1, pre_rgb=pre_rgb, rgb=torch.sigmoid(pre_rgb))

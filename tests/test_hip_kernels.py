@@ -12,13 +12,12 @@ import os
 import pytest
 import torch
 
+import field_cases
 import kernel_space as ks
+from field_cases import TOL_ACT, TOL_GRAD, check_field_pass
 from golden_util import GOLDEN, Case, orc, rel_err
 
 pytestmark = pytest.mark.gpu
-
-TOL_ACT = 1e-5
-TOL_GRAD = 1e-4
 
 
 @pytest.fixture(scope="module")
@@ -584,33 +583,6 @@ def test_adam_matches_torch_optim(hip):
 
 
 # ------------------------------------------------------------------------------------------ fused field + composite
-def _setup_pass(c, typ, hip):
-    """Inputs of one field pass of golden case `c` (CPU tensors) + the packer."""
-    from test_packing_cpu import build_model
-    st = c.state(requires_grad=False)
-    b = c.batch()
-    idx = b["img_idx"]
-    pose = orc.compose_pair(orc.se3_exp(st["se3_refine"][idx]), b["c2w"]) if c.pose_opt else b["c2w"]
-    o, d = orc.get_rays(b["directions"], pose)
-    model = build_model(c, typ, st)
-    keep = {}
-    real = orc.schedule_mult
-    orc.schedule_mult = lambda p, s: c.sched
-    try:
-        with torch.no_grad():
-            orc.training_forward(st, c.cfgs(), b, c.hparams(), c.progress, u_list=c.u_list, keep=keep)
-    finally:
-        orc.schedule_mult = real
-    z = keep["z_coarse" if typ == "coarse" else "z_fine"].contiguous()
-    use_cand = bool(c.sched < 1 and model.encode_candidate)
-    use_rgb = bool(c.sched > 0)
-    mode = (1 if use_rgb else 0) if use_cand else (3 if c.sched < 1 else 2)
-    return dict(model=model, o=o.contiguous(), d=d.contiguous(), z=z, a_rows=st[f"embedding_{typ}_a"][idx],
-                c_rows=st[f"embedding_{typ}_c"][idx], use_cand=use_cand, use_rgb=use_rgb, mode=mode,
-                wk_xyz=hip["rendering"].band_weights(10, c.progress, c.c2f),
-                wk_dir=hip["rendering"].band_weights(4, c.progress, c.c2f))
-
-
 STAGE_CASES = [("cfg1_small", "coarse"), ("cfg2_phase0", "coarse"), ("cfg2_phase1", "fine"), ("cfg2_phase2", "fine"),
                ("small_nocand", "fine"), ("small_round_half", "fine"), ("small_allmasked", "coarse"),
                ("cfg2_trained_p08", "fine"), ("cfg2_trained_p045", "fine")]  # "trained-like" magnitudes, all bands on
@@ -626,149 +598,14 @@ def field_mode(hip, request):
     rd.FIELD_MODE = old
 
 
-# "f16" (BASELINE.json configs[3]: fp16 weights and activations, one MFMA per product, fp32 accumulate) is compared with the
-# same fp32 restatement at STATED relaxed gates: 11-bit operands through ten chained layers give ~1e-3 on activations
-# (max-normalised gate 1e-2).  Gradients: a ReLU whose pre-activation lies within 1e-3 of zero may decide the other way in
-# fp16, which changes single entries by their full size, so the gate is on the whole tensor -- relative L2 error 6e-2 --
-# plus a loose cap on any single entry (max-normalised 0.5).
-TOL_ACT_F16, TOL_GRAD_F16, TOL_GRAD_F16_MAX = 1e-2, 6e-2, 0.5
-# ... and, because an L2 gate that wide could hide a wrong ReLU-mask ROW (one sample's 256 mask bits of one layer are 1 / M of the
-# tensor), the masks are compared directly (r5 VERDICT item 6): the share of elements whose sign decision differs from the fp32
-# restatement's -- stored activation h_l > 0 in the forward pass, pre-activation gradient gz_l != 0 in the backward pass -- stays
-# below 1e-3 per layer, and no single sample row differs in more than an eighth of its bits (measured in round 6: worst share
-# 2.1e-4, worst row 2 of 256 bits; the fp32-accurate modes are held to 1e-4 and 4 of 256 bits -- measured 1.0e-5 and 1 bit, a
-# pre-activation within rounding of zero).
-MASK_FLIP_F16, MASK_FLIP_ROW_F16 = 1e-3, 1.0 / 8
-
-
+# (the comparison itself, its gates -- the relaxed ones of the "f16" mode and the limits on differing ReLU decisions among them --
+# and the inputs of a pass: tests/field_cases.py, shared with tests/test_hip_field_edges.py)
 @pytest.mark.parametrize("field_mode", ["f16x3", "f32", "f16"], indirect=True)
 @pytest.mark.parametrize("name,typ", STAGE_CASES)
 def test_field_pass_stage_by_stage(hip, name, typ, field_mode):
-    c = Case(name)
-    if field_mode != "f16x3" and c.cfgs()["nerf_coarse"].W != 256:
+    if field_mode != "f16x3" and Case(name).cfgs()["nerf_coarse"].W != 256:
         pytest.skip("64-wide fields run the fp32 kernels in either mode (and the f16 mode refuses them)")
-    TOL_ACT, TOL_GRAD = (TOL_ACT_F16, TOL_GRAD_F16) if field_mode == "f16" else (globals()["TOL_ACT"], globals()["TOL_GRAD"])
-    s = _setup_pass(c, typ, hip)
-    rd = hip["rendering"]
-    model, pk = s["model"], s["model"].packer
-    R, S = s["z"].shape
-    # ---- CPU: kernel-space forward with every pre-activation kept, random upstream gradients
-    P_ref = model.packed().detach().clone().requires_grad_(True)
-    o_ref, d_ref = s["o"].clone().requires_grad_(True), s["d"].clone().requires_grad_(True)
-    c_ref, a_ref = s["c_rows"].clone().requires_grad_(True), s["a_rows"].clone().requires_grad_(True)
-    aux_ref = ks.ray_aux(d_ref.detach(), a_ref, s["wk_dir"])
-    f = ks.field(P_ref, pk, o_ref, d_ref, s["z"], c_ref, aux_ref, s["wk_xyz"], s["use_cand"], s["use_rgb"], keep_pre=True)
-    out_ref = ks.composite(f, s["z"], s["mode"], s["use_rgb"], pk.W)
-    names = ["E_s", "G_c", "sum_sfeat", "t_weight", "c_depth", "s_depth", "rgb_map", "w_all", "w_s"]
-    ups = {n: gen(tuple(out_ref[n].shape), 50 + i) for i, n in enumerate(names) if n in out_ref}
-    sum((out_ref[n] * ups[n]).sum() for n in ups).backward()
-
-    # ---- GPU
-    model_g = model.cuda()
-    P_g = model_g.packed().detach().clone().requires_grad_(True)
-    assert rel_err(cpu(P_g), P_ref.detach()) < 1e-6
-    o_g, d_g = s["o"].cuda().requires_grad_(True), s["d"].cuda().requires_grad_(True)
-    c_g, a_g = s["c_rows"].cuda().requires_grad_(True), s["a_rows"].cuda().requires_grad_(True)
-    cfg = rd._PassCfg(pk, s["mode"], s["use_cand"], s["use_rgb"], s["wk_xyz"], s["wk_dir"])
-    outs = rd._FieldPass.apply(o_g, d_g, s["z"].cuda(), c_g, a_g, P_g, cfg)
-    node = next(t.grad_fn for t in outs if t.grad_fn is not None)
-    sv = node.saved
-    M = R * S
-    errs = {}
-
-    def cmp(tag, got, ref, tol):
-        g, r = cpu(got).reshape(-1).double(), ref.detach().reshape(-1).double()
-        e = rel_err(g, r)
-        if field_mode == "f16" and tol == TOL_GRAD:  # gradients in the fp16 mode: relative L2 + a cap on single entries
-            l2 = float((g - r).norm() / r.norm().clamp_min(1e-30))
-            ok_ = l2 < tol and e < TOL_GRAD_F16_MAX
-            e = l2
-        else:
-            ok_ = e < tol
-        if not ok_:
-            errs[tag] = float(f"{e:.3g}")
-        return ok_
-
-    def mask_cmp(tag, got, ref, by_zero):
-        """ReLU decisions of one layer against the restatement's: `by_zero` compares zero patterns (gradients: a masked element is an
-        exact zero on both sides), otherwise signs of the stored activations."""
-        g, r = cpu(got).reshape(M, -1), ref.detach().reshape(M, -1)
-        diff = ((g != 0) != (r != 0)) if by_zero else ((g > 0) != (r > 0))
-        share, worst_row = float(diff.float().mean()), float(diff.float().mean(1).max())
-        masks[tag] = (float(f"{share:.2e}"), float(f"{worst_row:.2e}"))
-        lim, lim_row = (MASK_FLIP_F16, MASK_FLIP_ROW_F16) if field_mode == "f16" else (1e-4, 1.0 / 64)
-        if not (share <= lim and worst_row <= lim_row):
-            errs["mask_" + tag] = masks[tag]
-            return False
-        return True
-
-    masks = {}
-    ok = True
-    ok &= cmp("x0", sv["x0"], f["x0"], 1e-3 if field_mode == "f16" else 2e-6)  # f16: stored from the fp16 plane the layers read
-    # f16 mode stores fp16 tiles + exponents (the register-resident kernels: operand fragments, one exponent per 32 rows)
-    hs = sv["h"] if sv.get("h16") is None else rd.dequant16(sv["h16"], sv["hexp"], frag=getattr(node, "rr", False))[:, :M]
-    for l in range(pk.D):
-        ok &= cmp(f"h{l}", hs[l], f["h"][l], TOL_ACT)
-        ok &= mask_cmp(f"h{l}", hs[l], f["h"][l], by_zero=False)
-    if sv.get("h16") is not None and sv.get("h") is not None:  # (the register-resident kernels keep no fp32 copy)
-        ok &= cmp("h_last_fp32", sv["h"][0], f["h"][pk.D - 1], TOL_ACT)
-    ok &= cmp("sigma_s", sv["sigma_s"], f["sigma_s"], TOL_ACT)
-    e_got = sv["e"] if sv.get("e") is not None else rd.dequant16(sv["e16"][None], sv["eexp"][None], frag=True)[0, :M]  # (rr: fragments only)
-    ok &= cmp("e", e_got, f["e"], TOL_ACT)
-    def stored(k):  # (rr: g2 / r1 may be held as fp16 fragments only)
-        return sv[k] if sv.get(k) is not None else rd.dequant16(sv[k + "_16"][None], sv[k + "exp"][None], frag=True)[0, :M]
-    if s["use_cand"]:
-        for k in ("g1", "g2", "sigma_c"):
-            ok &= cmp(k, stored(k), f[k], TOL_ACT)
-    if s["use_rgb"]:
-        ok &= cmp("aux", sv["aux"], aux_ref, 2e-6)
-        for k in ("r1", "rgb"):
-            ok &= cmp(k, stored(k), f[k], TOL_ACT)
-    for i, n in enumerate(names):
-        if n in out_ref:
-            ok &= cmp("out_" + n, outs[i], out_ref[n], TOL_ACT)
-    assert ok, "FWD over tolerance: " + repr(errs)
-
-    # ---- backward
-    sink = {}
-    rd._DEBUG_SINK = sink
-    try:
-        sum((outs[i] * ups[n].cuda()).sum() for i, n in enumerate(names) if n in ups).backward()
-    finally:
-        rd._DEBUG_SINK = None
-    ok = True
-    ok &= cmp("dpre_s", sink["dpre_s"], f["pre_sig_s"].grad, TOL_GRAD)
-    for l in range(pk.D):
-        ok &= cmp(f"gz_h{l}", sink["gz_h"][l], f["pre_h"][l].grad, TOL_GRAD)
-        ok &= mask_cmp(f"gz_h{l}", sink["gz_h"][l], f["pre_h"][l].grad, by_zero=True)
-    print(f"[masks] {name} {typ} {field_mode}: worst share {max(v[0] for v in masks.values()):.1e}, worst row {max(v[1] for v in masks.values()):.1e}")
-    ok &= cmp("gz_e", sink["gz_e"], f["e"].grad, TOL_GRAD)
-    if s["use_cand"]:
-        ok &= cmp("dpre_c", sink["dpre_c"], f["pre_sig_c"].grad, TOL_GRAD)
-        ok &= cmp("gz_g2", sink["gz_g2"], f["pre_g2"].grad, TOL_GRAD)
-        ok &= cmp("gz_g1", sink["gz_g1"], f["pre_g1"].grad, TOL_GRAD)
-        ok &= cmp("d_c_rows", c_g.grad, c_ref.grad, TOL_GRAD)
-    if s["use_rgb"]:
-        ok &= cmp("dpre_rgb", sink["dpre_rgb"][:, :3], f["pre_rgb"].grad, TOL_GRAD)
-        ok &= cmp("gz_r1", sink["gz_r1"], f["pre_r1"].grad, TOL_GRAD)
-        ok &= cmp("d_a_rows", a_g.grad, a_ref.grad, TOL_GRAD)
-    ok &= cmp("d_o", o_g.grad, o_ref.grad, TOL_GRAD)
-    ok &= cmp("d_d", d_g.grad, d_ref.grad, TOL_GRAD)
-    L = pk.L
-    W, W2 = pk.W, pk.W2
-    pieces = {"w0": (L.w[0], W * 64), "b0": (L.b[0], W), "we": (L.we, W * W), "be": (L.be, W), "wsig": (L.wsig, W),
-              "bsig": (L.bsig, 1)}
-    for l in range(1, pk.D):
-        pieces[f"w{l}"] = (L.w[l], W * (64 + W if l == pk.skip else W))
-        pieces[f"b{l}"] = (L.b[l], W)
-    if s["use_cand"]:
-        pieces.update(wc1=(L.wc1, W2 * (W + 16)), bc1=(L.bc1, W2), wc2=(L.wc2, W2 * W2), bc2=(L.bc2, W2),
-                      wcsig=(L.wcsig, W2), bcsig=(L.bcsig, 1))
-    if s["use_rgb"]:
-        pieces.update(wr1=(L.wr1, W2 * (W + 80)), br1=(L.br1, W2), wr2=(L.wr2, 3 * W2), br2=(L.br2, 3))
-    for k, (off, n) in pieces.items():
-        ok &= cmp("dP_" + k, P_g.grad[off:off + n], P_ref.grad[off:off + n], TOL_GRAD)
-    assert ok, "BWD over tolerance: " + repr(errs)
+    check_field_pass(hip, field_cases.load((name, typ)), field_mode, torch.float32, tag=f"{name} {typ}")
 
 
 def test_frag16_row_norms_bound_every_matrix(hip):
