@@ -1,25 +1,23 @@
 """The C-ABI shared library loads without a GPU and exports exactly the entry points include/upnerf_hip.h declares
-(no compute calls here).  Also: the binding refuses to work without the library (no fallback)."""
+(no compute calls here); every struct, signature and constant of the ctypes binding agrees with that header (tests/abi_check.py).
+Also: the binding refuses to work without the library (no fallback)."""
 import ctypes
 import os
-import re
 import subprocess
 
 import pytest
 
+import abi_check
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared():
-    src = open(os.path.join(ROOT, "include", "upnerf_hip.h")).read()
-    # entry points of the diagnostic build (-DUPNERF_STAMPS, libupnerf_hip_stamps.so) are not part of the shipped library
-    src = re.sub(r"#ifdef UPNERF_STAMPS.*?#endif", "", src, flags=re.S)
-    return sorted(set(re.findall(r"^(?:int|long long)\s+(upnerf_\w+)\s*\(", src, flags=re.M)))
+HEADER = os.path.join(ROOT, "include", "upnerf_hip.h")
+# constants of the header that no Python code needs (a new define lands here or in _lib, a mirrored one may not stay here)
+UNMIRRORED = ("EINVAL", "EUNSUP", "TILE_ROWS", "MAX_FRAG_DESC", "MAX_PACK_DESC", "VIT_PATCH", "VIT_HEAD_DIM", "BAKED_MAX_SAMPLES")
 
 
 def test_header_symbols_are_exported_and_bound():
     from upnerf_amd import _lib
-    names = declared()
+    names = sorted(abi_check.prototypes(HEADER))
     assert len(names) >= 15
     dll = ctypes.CDLL(_lib.LIB_PATH)
     for n in names:
@@ -28,31 +26,85 @@ def test_header_symbols_are_exported_and_bound():
     assert _lib.lib.upnerf_abi_version() == _lib.ABI_VERSION == 11
 
 
-def test_struct_sizes_match_the_c_layout():
-    """ctypes mirrors of the argument structs must have the size the C compiler gives them."""
-    import subprocess
-    import tempfile
+def test_every_struct_mirror_has_the_c_layout():
+    """Every ctypes.Structure of _lib against its typedef: sizeof, and offsetof and sizeof of every field."""
     from upnerf_amd import _lib
-    prog = r'''
-    #include <stdio.h>
-    #include "upnerf_hip.h"
-    int main(){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(upnerf_layout), sizeof(upnerf_field_fwd_args),
-      sizeof(upnerf_composite_fwd_args), sizeof(upnerf_composite_bwd_args), sizeof(upnerf_field_bwd_args),
-      sizeof(upnerf_loss_args), sizeof(upnerf_loss_grads), sizeof(upnerf_frag_desc), sizeof(upnerf_frag16_desc),
-      sizeof(upnerf_gather_rays_args), sizeof(upnerf_pack_desc), sizeof(upnerf_wgrad_group), sizeof(upnerf_embed_group),
-      sizeof(upnerf_embed_rows_group), sizeof(upnerf_rng), sizeof(upnerf_add_pair), sizeof(upnerf_wgrad_pending),
-      sizeof(upnerf_wgrad_desc), sizeof(upnerf_wgrad_operand)); return 0; }'''
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
-        sizes = [int(x) for x in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
-    mine = [ctypes.sizeof(t) for t in (_lib.Layout, _lib.FieldFwdArgs, _lib.CompositeFwdArgs, _lib.CompositeBwdArgs,
-                                       _lib.FieldBwdArgs, _lib.LossArgs, _lib.LossGrads, _lib.FragDesc, _lib.Frag16Desc,
-                                       _lib.GatherRaysArgs, _lib.PackDesc, _lib.WgradGroup, _lib.EmbedGroup,
-                                       _lib.EmbedRowsGroup, _lib.Rng, _lib.AddPair, _lib.WgradPending, _lib.WgradDesc,
-                                       _lib.WgradOperand)]
-    assert sizes == mine
+    classes = abi_check.struct_classes(_lib)
+    bad = abi_check.check_structs(classes, HEADER)
+    assert not bad, "\n".join(bad)
+    # the check looked at something: not fewer structs and fields than at the commit that introduced it
+    assert len(classes) >= 61 and sum(len(c._fields_) for c in classes) >= 757
+
+
+def test_every_signature_compiles_against_its_prototype():
+    from upnerf_amd import _lib
+    bad = abi_check.check_prototypes(_lib._SIGNATURES, _lib._LONGLONG, HEADER)
+    assert not bad, "\n".join(bad)
+    assert len(_lib._SIGNATURES) >= 98
+
+
+def test_every_constant_of_the_header_is_mirrored_or_listed():
+    from upnerf_amd import _lib
+    bad = abi_check.check_constants(vars(_lib), HEADER, UNMIRRORED)
+    assert not bad, "\n".join(bad)
+    assert len(abi_check.constants(HEADER)) >= 39
+
+
+MADE_UP = """#include <stdint.h>
+#define UPNERF_MAX_THINGS 4
+enum { UPNERF_KIND_A, UPNERF_KIND_B };
+typedef struct { int32_t n, reserved_; const float* t0; const float* t1; float* out; } upnerf_span_args;
+typedef struct { int32_t R, mode; const float* rgb; float* depth; } upnerf_shade_args;
+typedef struct { const float* g; int32_t off, n; } upnerf_item_desc;
+int upnerf_span(const upnerf_span_args* a, const float* rays, int n, void* stream);
+long long upnerf_span_scratch(int n);
+int upnerf_shade(const upnerf_shade_args* a, const upnerf_item_desc* items, int nitems, void* stream);
+"""
+
+
+def test_the_checker_reports_each_planted_error(tmp_path):
+    """A three-struct header and its mirrors, with one error planted at a time: each is reported, by struct and field or by
+    function.  (Neither the real header nor the library is touched.)"""
+    from ctypes import POINTER, Structure, c_float, c_int, c_int32, c_void_p
+    header = tmp_path / "upnerf_made_up.h"
+    header.write_text(MADE_UP)
+    i32, p = c_int32, c_void_p
+    mirror = lambda name, *fields: type(name, (Structure,), {"_fields_": list(fields)})
+    span = [("n", i32), ("reserved_", i32), ("t0", p), ("t1", p), ("out", p)]
+    shade = [("R", i32), ("mode", i32), ("rgb", p), ("depth", p)]
+    Span, Shade, Item = mirror("SpanArgs", *span), mirror("ShadeArgs", *shade), mirror("ItemDesc", ("g", p), ("off", i32), ("n", i32))
+    structs = lambda *cls: abi_check.check_structs(cls, str(header))
+    assert structs(Span, Shade, Item) == []
+    swapped = mirror("SpanArgs", *span[:2], span[3], span[2], span[4])  # t1 before t0: what sizeof alone cannot see
+    assert ctypes.sizeof(swapped) == ctypes.sizeof(Span)
+    bad = structs(swapped, Shade, Item)
+    assert len(bad) == 2 and "SpanArgs.t1" in bad[0] and "SpanArgs.t0" in bad[1], bad
+    bad = structs(mirror("SpanArgs", *span[:4], ("dst", p)), Shade, Item)  # renamed: the compiler's message, and the name left out
+    assert any("upnerf_span_args" in b and "dst" in b for b in bad) and "upnerf_span_args.out: not in the mirror SpanArgs" in bad, bad
+    dropped = mirror("ShadeArgs", shade[0], *shade[2:])  # padding takes the place of `mode`: no size and no offset moves
+    assert ctypes.sizeof(dropped) == ctypes.sizeof(Shade) and dropped.rgb.offset == Shade.rgb.offset
+    assert structs(Span, dropped, Item) == ["upnerf_shade_args.mode: not in the mirror ShadeArgs"]
+    assert structs(Span, Shade) == ["upnerf_item_desc: no ctypes class mirrors it"]
+    assert structs(Span, Shade, Item, mirror("Extra", ("n", i32))) == ["Extra: the header has no typedef upnerf_extra"]
+
+    good = {"upnerf_span": [POINTER(Span), POINTER(c_float), c_int, p], "upnerf_span_scratch": [c_int],
+            "upnerf_shade": [POINTER(Shade), POINTER(Item), c_int, p]}
+    protos = lambda longlong=("upnerf_span_scratch",), **over: abi_check.check_prototypes({**good, **over}, longlong, str(header))
+    assert protos() == []
+    for name, argtypes, what in (("upnerf_span", good["upnerf_span"][:3], "too few arguments"),                  # one short
+                                 ("upnerf_span", [POINTER(Span), c_int, c_int, p], "pointer from integer"),     # pointer as c_int
+                                 ("upnerf_shade", [POINTER(Shade), POINTER(Span), c_int, p], "incompatible pointer")):
+        bad = protos(**{name: argtypes})
+        assert len(bad) == 1 and bad[0].startswith(name + ": ") and what in bad[0], bad
+    bad = protos(longlong=())  # the 64-bit return bound as int: by the set, and by the narrowing assignment
+    assert len(bad) == 2 and all(b.startswith("upnerf_span_scratch: ") for b in bad), bad
+
+    consts = dict(MAX_THINGS=4, KIND_A=0, KIND_B=1)
+    assert abi_check.check_constants(consts, str(header), ()) == []
+    bad = abi_check.check_constants({**consts, "MAX_THINGS": 5}, str(header), ())
+    assert len(bad) == 1 and bad[0].startswith("MAX_THINGS: 5 in Python") and "is 4" in bad[0], bad
+    assert len(abi_check.check_constants({"MAX_THINGS": 4, "KIND_A": 0}, str(header), ())) == 1  # KIND_B: neither mirrored nor listed
+    assert len(abi_check.check_constants(consts, str(header), ("KIND_B",))) == 1  # listed as unmirrored, yet mirrored
 
 
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):

@@ -1,16 +1,14 @@
 """The baked scene without a GPU: the fp64 restatement (tests/baked_ref.py) against closed forms, the host-side refusals of
-upnerf_baked_render / upnerf_baked_pack and of the Python surface, the C layout of the two argument structs, and the arrays of
+upnerf_baked_render / upnerf_baked_pack and of the Python surface, and the arrays of
 a saved scene."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import baked_ref as br
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def constant_box(sigma, colour, shape=(6, 7, 8)):
@@ -126,16 +124,6 @@ def test_baked_pack_refuses_before_launch():
     for bad in (dict(n=0), dict(sigma=None), dict(rgbs=None), dict(rgbs=ctypes.c_void_p(8)), dict(level=float("nan"))):
         assert _lib.lib.upnerf_baked_pack(ctypes.byref(_lib.BakedPackArgs(**{**ok, **bad})), None) == -1
     assert _lib.lib.upnerf_baked_pack(None, None) == -1
-
-
-def test_struct_sizes_match_the_c_layout(tmp_path):
-    from upnerf_amd import _lib
-    src, exe = tmp_path / "s.c", tmp_path / "s"
-    src.write_text('#include <stdio.h>\n#include "upnerf_hip.h"\nint main(){ printf("%zu %zu\\n", sizeof(upnerf_baked_render_args), '
-                   'sizeof(upnerf_baked_pack_args)); return 0; }\n')
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    sizes = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert sizes == [ctypes.sizeof(_lib.BakedRenderArgs), ctypes.sizeof(_lib.BakedPackArgs)]
 
 
 def test_the_python_surface_refuses_on_the_host():

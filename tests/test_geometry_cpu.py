@@ -212,23 +212,3 @@ def test_sizing_call_refuses_what_does_not_fit_int32_without_a_gpu():
     a.tab = tab
     assert _lib.lib.upnerf_mtet_count(ctypes.byref(a), one, one, None) == -1
     assert _lib.lib.upnerf_mtet_count(None, one, one, None) == -1
-
-
-def test_new_argument_structs_have_the_c_layout(tmp_path):
-    import ctypes
-    import subprocess
-    from upnerf_amd import _lib
-    prog = r'''
-    #include <stdio.h>
-    #include <stddef.h>
-    #include "upnerf_hip.h"
-    int main(){ printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(upnerf_grid_columns_args), offsetof(upnerf_grid_columns_args, o),
-      sizeof(upnerf_mtet_tables), sizeof(upnerf_mtet_args), offsetof(upnerf_mtet_args, tab), offsetof(upnerf_mtet_args, n_vertices),
-      offsetof(upnerf_mtet_args, vertices)); return 0; }'''
-    src, exe = str(tmp_path / "s.c"), str(tmp_path / "s")
-    open(src, "w").write(prog)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
-    sizes = [int(x) for x in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
-    assert sizes == [ctypes.sizeof(_lib.GridColumnsArgs), _lib.GridColumnsArgs.o.offset, ctypes.sizeof(_lib.MtetTables),
-                     ctypes.sizeof(_lib.MtetArgs), _lib.MtetArgs.tab.offset, _lib.MtetArgs.n_vertices.offset,
-                     _lib.MtetArgs.vertices.offset]

@@ -1,12 +1,10 @@
 """SSIM without a GPU: the fp64 test reference (tests/ssim_ref.py) against an independent restatement and closed forms,
-the border rule it pins, the C layout of upnerf_ssim_args, the host-side refusals of upnerf_ssim and metrics.py, and the
+the border rule it pins, the host-side refusals of upnerf_ssim and metrics.py, and the
 psnr.pkl / ssim.pkl bookkeeping of the TTO results."""
 import ctypes
 import math
 import os
 import pickle
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -14,7 +12,6 @@ import torch
 
 import ssim_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _scipy_ssim_map(x, y):
@@ -70,23 +67,6 @@ def test_reflect_padding_is_the_border_rule(where):
     for other in ("replicate", "zeros"):
         assert float((refl - ssim_ref.ssim_map(a, b, pad_mode=other)).abs().max()) > 1e-3, other
     assert np.abs(refl[0, 0].numpy() - _scipy_ssim_map(a[0, 0].numpy(), b[0, 0].numpy())).max() < 1e-12
-
-
-def test_ssim_args_match_the_c_layout():
-    from upnerf_amd import _lib
-    prog = r'''
-    #include <stddef.h>
-    #include <stdio.h>
-    #include "upnerf_hip.h"
-    int main(){ printf("%zu %zu %zu %zu\n", sizeof(upnerf_ssim_args), offsetof(upnerf_ssim_args, pred_stride),
-                       offsetof(upnerf_ssim_args, ssim), offsetof(upnerf_ssim_args, map)); return 0; }'''
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
-        got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
-    S = _lib.SsimArgs
-    assert got == [ctypes.sizeof(S), S.pred_stride.offset, S.ssim.offset, S.map.offset]
 
 
 def _args(**kw):

@@ -423,8 +423,8 @@ _SIGNATURES = {
     "upnerf_wgrad16_scratch": [C.POINTER(WgradDesc)],
     "upnerf_wgrad16": [C.POINTER(WgradDesc), C.POINTER(WgradPending), _p],
     "upnerf_wgrad_finish": [_p, _p],
-    "upnerf_transient_fwd": [_p, _p],
-    "upnerf_transient_bwd": [_p, _p, _p],
+    "upnerf_transient_fwd": [C.POINTER(TransientArgs), _p],
+    "upnerf_transient_bwd": [C.POINTER(TransientArgs), C.POINTER(TransientGrads), _p],
     "upnerf_wgrad_grouped_scratch": [C.POINTER(WgradGroup), _i, _i],
     "upnerf_wgrad_grouped": [C.POINTER(WgradGroup), _i, _p, _i, _p],
     "upnerf_vec_wgrad": [_i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _i, _p],
