@@ -435,8 +435,10 @@ enum {
    * MFMA (HBM-bound); 1 (f16) = rounded to fp16, one MFMA per block (the "f16" field mode).  Any N and K. */
   UPNERF_WG_F32 = 0,
   /* fp16 bits [M][ld], value * 2^exp[m / 64]: the f16 field mode's fp16-STORED operands (upnerf_field_bwd_f16x3's gz16 /
-   * gzexp, h16 / hexp).  Brought to the tensor-wide exponent on load (exact power-of-two scaling in fp16), one MFMA per block,
-   * fp32 accumulate.  Reads 1 KB per sample and layer instead of 2.  ld, N, K multiples of 8; 256 x 256 blocks (B stored the
+   * gzexp, h16 / hexp).  Brought to the tensor-wide exponent on load: value * 2^(e_tensor - e_tile) rounded ONCE to fp16 -- exact
+   * while the result is a normal fp16 number, to 2^-25 (half a subnormal step) below 2^-14, for any exponent difference (a tile
+   * more than 2^24 below the tensor's maximum is rounded from the exact fp32 product; nothing is clamped).  This holds for every
+   * stored kind and plane below.  One MFMA per block, fp32 accumulate.  Reads 1 KB per sample and layer instead of 2.  ld, N, K multiples of 8; 256 x 256 blocks (B stored the
    * same way) and 256 x 64 (fp32 B). */
   UPNERF_WG_F16_TILE,
   /* the operand FRAGMENTS of the register-resident field kernels (upnerf_field_fwd_args.tile_rows = 256: [32-row tile]

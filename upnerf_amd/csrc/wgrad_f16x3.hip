@@ -431,20 +431,32 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16p_kernel(int M, int N,
       }
     }
   };
-  auto pw2h = [](int e) {  // 2^e as fp16 (e clamped to what fp16 holds; far-below-maximum tiles flush towards zero)
-    e = e > 15 ? 15 : (e < -24 ? -24 : e);
-    return (_Float16)ldexpf(1.0f, e);
+  // v * 2^e with ONE rounding to fp16.  While 2^e is an fp16 number (e >= -24) that is the fp16 product itself, exact unless it
+  // lands in the subnormal range.  A tile more than 2^24 below the tensor's maximum has no such factor: clamping e at -24 there would
+  // multiply the tile by 2^(-24 - e) too much, so those pieces (rare, and worth at most a subnormal each) go through fp32, where
+  // the product is exact, and are rounded once like the others.  e > 15 only meets all-zero tiles; the factor stays finite.
+  auto scale8 = [](h8 v, int e) {
+    if (e >= -24) {
+      const _Float16 f = (_Float16)ldexpf(1.0f, e > 15 ? 15 : e);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = v[j] * f;
+    } else {
+      const float g = ldexpf(1.0f, e < -64 ? -64 : e);  // (|v| 2^-41 already rounds to zero)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = (_Float16)((float)v[j] * g);
+    }
+    return v;
   };
-  // eight residual bytes -> fp16 residuals in units of 2^-e of the tensor: (byte - 128) / 32 * f, f = 2^(e_tensor - e_tile)
-  auto lo8 = [](u32x2_t w, _Float16 f) {
+  // eight residual bytes -> fp16 residuals in the TILE's units, (byte - 128) / 32: multiples of 2^-5 up to 8, exact in fp16 whether
+  // or not the two operations are contracted; scale8 then brings them to the tensor-wide exponent like the hi plane
+  auto lo8 = [](u32x2_t w) {
     typedef unsigned short us8 __attribute__((ext_vector_type(8)));
     us8 u;
 #pragma unroll
     for (int j = 0; j < 8; ++j) u[j] = (unsigned short)((w[j >> 2] >> (8 * (j & 3))) & 0xffu);
     h8 v = __builtin_convertvector(u, h8);
-    const _Float16 s = f * (_Float16)0.03125f, o = f * (_Float16)-4.0f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = v[j] * s + o;
+    for (int j = 0; j < 8; ++j) v[j] = v[j] * (_Float16)0.03125f + (_Float16)-4.0f;
     return v;
   };
   // mc: first row of the chunk the set holds (rows >= mend and columns past the matrix are staged as zeros)
@@ -481,15 +493,12 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16p_kernel(int M, int N,
       const float inv = ldexpf(1.0f, -xa[q]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) bsum[j] += (float)ra[q][j] * inv;
-      const _Float16 f = pw2h(ea - xa[q]);
-      h8 v = ra[q];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = v[j] * f;
+      const h8 v = scale8(ra[q], ea - xa[q]);
       if constexpr (NP == 2) {
-        const h8 vl = lo8(la[q], (_Float16)1.0f);
+        const h8 vl = lo8(la[q]);
 #pragma unroll
         for (int j = 0; j < 8; ++j) bsum[j] += (float)vl[j] * inv;
-        *(h8*)(base + SZA + himg<FX_CHUNK>(row, 8 * c8)) = lo8(la[q], f);
+        *(h8*)(base + SZA + himg<FX_CHUNK>(row, 8 * c8)) = scale8(vl, ea - xa[q]);
       }
       if constexpr (FRAG) {
         const int r = (tid % RPA) + RPA * q, s2 = tid / RPA, col = 16 * (s2 >> 1) + 4 * (s2 & 1);
@@ -503,7 +512,6 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16p_kernel(int M, int N,
 #pragma unroll
       for (int q = 0; q < B8; ++q) {
         const int idx = tid + q * FX_THREADS, row = idx / (TK / 8), c8 = idx - row * (TK / 8);
-        const _Float16 f = pw2h(eb - xb[q]);
         h8 v = rbp[q];
         if constexpr (HASV) {  // natural units: fp16 value * 2^-tile exponent, times the row's v (zero past mend: rbp is masked)
           const bool in = mc + (tid % RPB) + RPB * q < mend;
@@ -512,15 +520,14 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16p_kernel(int M, int N,
           for (int j = 0; j < 8; ++j) vsum[j] = fmaf((float)v[j], sc, vsum[j]);
           vtot += (in && tid < RPB) ? rv[q] : 0.0f;
         }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = v[j] * f;
+        v = scale8(v, eb - xb[q]);
         if constexpr (FRAG) {
           const int r = (tid % RPB) + RPB * q, s2 = tid / RPB, col = 16 * (s2 >> 1) + 4 * (s2 & 1);
           *(h4*)(base + OB + himg<FX_CHUNK>(r, col)) = __builtin_shufflevector(v, v, 0, 1, 2, 3);
           *(h4*)(base + OB + himg<FX_CHUNK>(r, col + 8)) = __builtin_shufflevector(v, v, 4, 5, 6, 7);
         } else {
           *(h8*)(base + OB + himg<FX_CHUNK>(row, 8 * c8)) = v;
-          if constexpr (NP == 2) *(h8*)(base + OB + SZB + himg<FX_CHUNK>(row, 8 * c8)) = lo8(lb[q], f);
+          if constexpr (NP == 2) *(h8*)(base + OB + SZB + himg<FX_CHUNK>(row, 8 * c8)) = scale8(lo8(lb[q]), eb - xb[q]);
         }
       }
     } else {
@@ -663,8 +670,8 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_f16p_kernel(int M, int N,
 // every wave copies its pieces of a 16-row chunk straight into the swizzled LDS image with global_load_lds_dwordx4 -- the XOR of the
 // image (himg) is applied on the SOURCE side, through the per-lane global address -- four chunks in a ring, three in flight (96 KB
 // per CU requested ahead of the matrix work, against 64 KB in registers in wgrad_f16x3_kernel), ONE counted s_waitcnt vmcnt + ONE
-// s_barrier per chunk.  The tile exponents are folded into the B fragments after the transposed read (v_pk_mul_f16 by a power of
-// two: exact unless the product sinks below fp16's range, i.e. is 2^-38 of the tensor's maximum), so the MFMA inputs are the ones
+// s_barrier per chunk.  The tile exponents are applied to the fragments after the transposed read, each operand's to its own (v_pk_mul_f16 by
+// a power of two: exact unless the product sinks below fp16's normal range, where it is rounded once), so the MFMA inputs are the ones
 // wgrad_f16x3_kernel builds from the fp32 rows: (hi + lo) 2^k splits into hi 2^k and lo 2^k.  Column sums of A (the bias gradient)
 // come from the A fragments: each of the four waves that share an n-range sums one of its four n-tiles.  M-range of a split: whole
 // 16-row chunks, whole 64-row tiles of exponents (the caller guarantees M % 64 == 0 and rows_per_split % 64 == 0).
@@ -751,10 +758,22 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_planes_kernel(int M, cons
         nxb = bexp[mn >> 6];
       }
       const char* base = lds + (c % WP_SLOTS) * WP_SLOT;
-      // 2^((ea - xa) + (eb - xb)) as fp16: both tile exponents folded into the B fragments
-      int fe = (ea - xa) + (eb - xb);
-      fe = fe > 15 ? 15 : (fe < -24 ? -24 : fe);
-      const _Float16 f = (_Float16)ldexpf(1.0f, fe);
+      // Each operand's fragments are brought to ITS tensor-wide exponent (wave-uniform branches: one tile per chunk).  Folding both
+      // differences into the B fragments pushed B's small elements into the subnormal range by A's difference, and clamping the
+      // sum at -24 scaled a tile further below the maximum than that by 2^(-24 - e) too much.
+      const int fa = ea - xa, fb = eb - xb;
+      auto scale8 = [](h8 v, int e) {  // v * 2^e with one rounding to fp16 (see wgrad_f16p_kernel)
+        if (e >= -24) {
+          const _Float16 f = (_Float16)ldexpf(1.0f, e > 15 ? 15 : e);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = v[j] * f;
+        } else {
+          const float g = ldexpf(1.0f, e < -64 ? -64 : e);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = (_Float16)((float)v[j] * g);
+        }
+        return v;
+      };
       h8 ah[MT], al[MT];
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
@@ -785,14 +804,16 @@ __global__ __launch_bounds__(FX_THREADS, 1) void wgrad_planes_kernel(int M, cons
           }
         bacc = fmaf(s, ldexpf(1.0f, -xa), bacc);
       }
+      if (fa != 0) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+          ah[mt] = scale8(ah[mt], fa);
+          al[mt] = scale8(al[mt], fa);
+        }
+      }
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
-        h8 bh = bhv[nt], bl = blv[nt];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          bh[j] = bh[j] * f;
-          bl[j] = bl[j] * f;
-        }
+        const h8 bh = scale8(bhv[nt], fb), bl = scale8(blv[nt], fb);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bh, acc[mt][nt], 0, 0, 0);
