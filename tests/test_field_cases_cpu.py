@@ -101,3 +101,129 @@ def test_fp16_operands_alone_leave_the_draw_inside_the_f16_gates(key):
     print(f"[fp16 operands vs fp64] {fc.label(key)}: activations {worst[0]:.1e} (gate {fc.TOL_ACT_F16:g}), gradients L2 {worst[1]:.1e} "
           f"({fc.TOL_GRAD_F16:g}), single entry {worst[2]:.2f} ({fc.TOL_GRAD_F16_MAX:g})")
     assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------------ preconditions of tests/test_hip_field_plans.py
+def _requested(key, variant, dtype, **kw):
+    s = fc.load(key)
+    ups = fc.variant_ups(variant, s)
+    ref = fc.restate(s, dtype, ups=ups, **kw) if kw else fc.reference(s, dtype, ups)
+    return s, ups, ref, fc.ref_grads(ref, s, fc.variant_leaves(variant, s))
+
+
+@pytest.mark.parametrize("key,variant", fc.BACKWARD_PAIRS, ids=lambda v: v if isinstance(v, str) else fc.label(v))
+def test_fp32_restatement_of_every_partial_backward_is_within_half_of_the_gates_of_the_fp64_one(key, variant):
+    """Every (case, variant) pair of the GPU file: the gradients the variant requests, fp32 restatement against fp64, within half
+    of TOL_GRAD (and, where P is requested, the trunk's gradient masks within half of the mask limits).  Every requested gradient
+    the variant's upstreams reach is non-zero (the dead-ray case keeps its exemption); one they do not reach is exactly zero in
+    both, which holds the kernels to an exact zero."""
+    s, ups, r64, g64 = _requested(key, variant, torch.float64)
+    _, _, r32, g32 = _requested(key, variant, torch.float32)
+    assert list(g32) == list(g64) and g64
+    M = s["z"].numel()
+    none, bad, worst = fc.unreached(s, ups), {}, 0.0
+    for k, t in g64.items():
+        if k in none:
+            assert float(t.abs().max()) == 0.0 and float(g32[k].abs().max()) == 0.0, k
+            continue
+        assert float(t.abs().max()) > 0 or s.get("dead") is not None, k
+        e = rel_err(g32[k], t)
+        worst = max(worst, e)
+        if not e <= 0.5 * fc.TOL_GRAD:
+            bad[k] = e
+    share = row = 0.0
+    if "P" in fc.variant_leaves(variant, s):
+        for l in range(s["model"].packer.D):
+            sh, rw = fc.mask_diff(r32.f["pre_h"][l].grad, r64.f["pre_h"][l].grad, M, True)
+            share, row = max(share, sh), max(row, rw)
+            if not (sh <= 0.5 * fc.MASK_FLIP and rw <= 0.5 * fc.MASK_FLIP_ROW):
+                bad[f"mask_gz_h{l}"] = (sh, rw)
+    print(f"[fp32 vs fp64] {fc.label(key)} {variant}: gradients {worst:.1e} (gate {fc.TOL_GRAD:g}), mask share {share:.1e} "
+          f"({fc.MASK_FLIP:g}), worst row {row:.1e} ({fc.MASK_FLIP_ROW:.1e}); unreached: {sorted(none & set(g64))}")
+    assert not bad, bad
+
+
+F16_PAIRS = [(k, v) for k, v in fc.BACKWARD_PAIRS if "f16" in fc.modes_of(k)]
+
+
+@pytest.mark.parametrize("key,variant", F16_PAIRS, ids=lambda v: v if isinstance(v, str) else fc.label(v))
+def test_fp16_operands_alone_leave_every_partial_backward_inside_the_f16_gates(key, variant):
+    """test_fp16_operands_alone_leave_the_draw_inside_the_f16_gates for the pairs the GPU file runs in the "f16" mode: a subset of
+    upstreams or leaves changes which samples carry the gradient, so each pair is its own draw."""
+    s, ups, _, g64 = _requested(key, variant, torch.float64)
+    _, _, _, gq = _requested(key, variant, torch.float64, quant=fc.round16)
+    bad, worst = {}, [0.0, 0.0]
+    for k, t in g64.items():
+        d, r = (gq[k] - t).reshape(-1), t.reshape(-1)
+        l2, mx = float(d.norm() / r.norm().clamp_min(1e-30)), rel_err(gq[k], t)
+        worst = [max(worst[0], l2), max(worst[1], mx)]
+        if not (l2 < fc.TOL_GRAD_F16 and mx < fc.TOL_GRAD_F16_MAX):
+            bad[k] = (l2, mx)
+    print(f"[fp16 operands vs fp64] {fc.label(key)} {variant}: gradients L2 {worst[0]:.1e} ({fc.TOL_GRAD_F16:g}), "
+          f"single entry {worst[1]:.2f} ({fc.TOL_GRAD_F16_MAX:g})")
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("key", fc.DENSITY_ONLY, ids=fc.label)
+def test_density_only_restatement_in_fp32_is_within_half_of_every_gate_of_the_fp64_one(key):
+    """The density-only passes: what the forward-only comparison reads off the restatement (x0, sigma_s, s_depth, w_s)."""
+    s = fc.load(key)
+    assert s["c_rows"] is None and s["a_rows"] is None and (s["mode"], s["use_cand"], s["use_rgb"]) == (2, False, False)
+    a32, a64 = fc.ref_stages(fc.reference(s, torch.float32), s)[0], fc.ref_stages(fc.reference(s, torch.float64), s)[0]
+    assert {k for k in a64 if k.startswith("out_")} == {"out_s_depth", "out_w_s"}
+    for k in ("x0", "sigma_s", "out_s_depth", "out_w_s"):
+        e = rel_err(a32[k][0].detach(), a64[k][0].detach())
+        print(f"[fp32 vs fp64] {fc.label(key)} {k}: {e:.1e}")
+        assert float(a64[k][0].abs().max()) > 0 and e <= 0.5 * (fc.TOL_X0 if k == "x0" else fc.TOL_ACT), (k, e)
+    with_rows = fc.load(key._replace(use_rgb=True, bare=False))  # (the rows do not reach the density)
+    assert torch.equal(fc.reference(with_rows, torch.float64).out["w_s"], a64["out_w_s"][0])
+
+
+def test_the_plan_cases_cover_what_they_claim():
+    ragged = lambda k: isinstance(k, fc.Synth) and (k.R * k.S) % 64 != 0
+    for v in fc.VARIANTS:
+        assert any(ragged(k) for k, w in fc.BACKWARD_PAIRS if w == v), v
+    dead = next(k for k in fc.SYNTH_256 if k.dead is not None)
+    assert {v for k, v in fc.BACKWARD_PAIRS if k == dead} & {"frozen_appearance", "frozen_pose", "frozen_candidate"}
+    assert {(k.W, k.R, k.S) for k in fc.DENSITY_ONLY} == {(256, 7, 40), (256, 3, 200), (256, 2, 257), (64, 5, 33)}
+    assert any(k.S % 32 for k in fc.DENSITY_ONLY) and any(k.dead is not None for k in fc.DENSITY_ONLY)
+    for k in fc.PLAN_CASES:  # the table's columns, per case: leaves and upstreams exist where a variant applies
+        s = fc.load(k)
+        assert fc.traits(k) == (s["mode"], s["use_cand"], s["use_rgb"]), k
+        outs = set(fc.reference(s, torch.float32).out)
+        for v in fc.variants_of(k):
+            ups = fc.variant_ups(v, s)
+            assert fc.variant_leaves(v, s) and (ups is None or set(ups) <= outs), (k, v)
+    # no pair is run in a mode that would refuse it, no 256-wide pair misses a mode
+    assert all(m == ["f16x3"] for m in map(fc.modes_of, fc.SYNTH_64 + fc.NOFEAT[:1] + fc.DENSITY_ONLY[3:]))
+    assert all(fc.modes_of(k) == fc.MODES for k in fc.SYNTH_256 + fc.NOFEAT[1:] + fc.DENSITY_ONLY[:3])
+    assert fc.modes_of(fc.SYNTH_SMALLEST) == ["f16x3", "f32"]
+
+
+def test_the_forward_only_plans_differ_from_the_training_plans():
+    """Host arithmetic only (pass_plan.plan_pass under the default switches): without `train` nothing the backward pass reads is
+    planned in any mode, and in the "f16" mode's register-resident kernels e (and g2) change form on at least one case used --
+    the GPU test then runs another store set and another compositing input than check_field_pass does."""
+    from upnerf_amd.pass_plan import plan_pass
+    sw = dict(WGRAD_STORE="f32", FIELD_RR=1, TILE_PARTIALS=1, WGRAD_CHAIN=1, JOIN_HEADS=1, VEC_RIDE=1)
+    differ = []
+    for key, fm in fc.FORWARD_RUNS + fc.DENSITY_RUNS:
+        s = fc.load(key)
+        pk, (R, S) = s["model"].packer, s["z"].shape
+        plans = [plan_pass(pk.W, pk.W2, pk.D, R, S, s["mode"], s["use_cand"], s["use_rgb"], bool(s.get("rgb_joint")), train,
+                           FIELD_MODE=fm, **sw) for train in (False, True)]
+        ev, tr = (p.buffers for p in plans)
+        gone = [k for k in ev if ev[k] is None and tr[k] is not None]
+        for k in ("hmask", "mx32", "d_sigma_s", "dpre_s"):
+            assert k in gone, (key, fm, k)
+        assert "h" in gone or "h16" in gone, (key, fm)
+        assert any(k in gone for k in ("gz_h", "gz16")), (key, fm)
+        for k in ("h", "h16", "hmask", "mx32", "gz_e", "gz_h", "gz16", "gz_rg", "gz_rg16", "gz_g1", "gz_g2", "gz_g2_16", "gz_r1",
+                  "d_sigma_s", "d_sigma_c", "d_rgb", "dpre_s", "dpre_c", "dpre_rgb", "tile_part", "ray_part", "g1", "g1_16", "r1", "r1_16"):
+            assert ev[k] is None, (key, fm, k)
+        if fm == "f16" and plans[0].e_frag != plans[1].e_frag:
+            differ.append(fc.label(key))
+        if fm != "f16":
+            assert not plans[0].e_frag and not plans[1].e_frag
+    print("[plans] e changes form between the training and the forward-only plan of the f16 mode on:", differ)
+    assert differ
