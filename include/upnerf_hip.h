@@ -1436,6 +1436,75 @@ typedef struct {
 } upnerf_baked_pack_args;
 int upnerf_baked_pack(const upnerf_baked_pack_args* a, void* stream);
 
+/* ---- a baked scene with view dependence: per grid point the coefficients of a real spherical-harmonic expansion of the colour
+ * over the viewing direction, evaluated for each ray's own direction (csrc/baked.hip).  Added under ABI 11: new
+ * symbols only.  Degree 1 or 2, nb = (degree + 1)^2 = 4 or 9 basis functions; degree 0 is upnerf_baked_render on `rgbs`.
+ *
+ * The record of a grid point, aligned to its own size -- the stored record is the definition:
+ *   degree 1: 32 bytes: 12 fp16 coefficients in bytes 0..23, fp32 sigma at byte 24;
+ *   degree 2: 64 bytes: 27 fp16 coefficients in bytes 0..53, fp32 sigma at byte 56;
+ * coefficients channel-major, k[c][j] is half c * nb + j (c = r, g, b; j = 0 .. nb-1); every other byte is zero; a dropped
+ * point is an all-zero record, so a cell with a clear bit has eight exact zeros of sigma as it has in `rgbs`.
+ *
+ * The basis of a unit direction (x, y, z), the constants rounded to fp32, every operation fp32:
+ *   Y0 = 0.28209479177387814;  Y1 = -0.4886025119029199 * y;  Y2 = 0.4886025119029199 * z;  Y3 = -0.4886025119029199 * x;
+ *   Y4 = 1.0925484305920792 * (x * y);  Y5 = -1.0925484305920792 * (y * z);
+ *   Y6 = 0.31539156525252005 * fmaf(2 z, z, -fmaf(x, x, y * y));  Y7 = -1.0925484305920792 * (x * z);
+ *   Y8 = 0.5462742152960396 * fmaf(x, x, -(y * y)).
+ *
+ * upnerf_baked_sh_render: upnerf_baked_render in everything (lattice, skipping, blend, compositing, misses) but the four
+ * channels of a corner.  Once per ray: len = sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx))) (delta = step * len, as above),
+ * (x, y, z) = d / len per component, Y_0 .. Y_{nb-1} as above.  Per corner of a visited sample: the halves converted exactly to
+ * fp32; col[c] = acc after acc = 0, acc = fmaf(Y_j, k[c][j], acc) for j = 0 .. nb-1 in that order; the corner is
+ * (col[0], col[1], col[2], sigma).  The trilinear blend is that of upnerf_baked_render; then the three blended colours are
+ * clamped, v = fminf(fmaxf(v, 0), 1), and composited as above.  (A ray with d = 0 has no direction: its colours clamp to 0 and
+ * its alpha is 0.) */
+typedef struct {
+  int32_t Cx, Cy, Cz, R;
+  float lo[3], hi[3];        /* hi > lo, finite */
+  float step;                /* > 0, finite */
+  float background;          /* finite */
+  float stop;                /* >= 0, < 1; 0 = never */
+  int32_t degree;            /* 1 or 2 */
+  const uint8_t* records;    /* [Cz+1][Cy+1][Cx+1][32 | 64], aligned to the record size */
+  const uint32_t* words;     /* [upnerf_occ_words(Cx, Cy, Cz)] */
+  const float* rays;         /* [R][8], 16-byte aligned */
+  float* rgb;                /* [R][3] */
+  float* depth;              /* [R] */
+  float* opacity;            /* [R] */
+} upnerf_baked_sh_render_args;
+int upnerf_baked_sh_render(const upnerf_baked_sh_render_args* a, void* stream);
+
+/* upnerf_sh_accumulate: one direction's share of a least-squares projection onto the basis.  With w[j] = W[j][k], column k of
+ * the fp32 pseudo-inverse of the [K][nb] basis matrix of the K directions (formed by the caller in fp64),
+ *   acc[p][c][j] = fmaf(w[j], rgb[p][c], first ? 0 : acc[p][c][j]),   j = 0 .. nb-1, c = 0 .. 2.
+ * Called for k = 0 .. K-1 in order (first != 0 for k = 0), the sum has one fixed order.  One thread per point. */
+typedef struct {
+  int64_t n;
+  int32_t nb;                /* 4 or 9 */
+  int32_t first;             /* != 0: write, do not accumulate */
+  float w[9];                /* w[0 .. nb-1], finite */
+  int32_t reserved_;
+  const float* rgb;          /* [n][3]: the colours for this direction */
+  float* acc;                /* [n][3][nb] */
+} upnerf_sh_accumulate_args;
+int upnerf_sh_accumulate(const upnerf_sh_accumulate_args* a, void* stream);
+
+/* upnerf_baked_sh_pack: the records of a baked scene from sigma and the accumulated coefficients.  A point is kept iff its sigma
+ * is finite, > 0 and >= level (the rule of upnerf_baked_pack) and all its 3 nb coefficients are finite.  Kept: each coefficient
+ * held to [-65504, 65504] (fminf(fmaxf(.))) and rounded to fp16, to nearest even; sigma copied; the other bytes zero.  Dropped:
+ * a zero record.  kept[n] (optional) = 1 / 0 accordingly.  One thread per point. */
+typedef struct {
+  int64_t n;
+  float level;               /* not NaN */
+  int32_t degree;            /* 1 or 2 */
+  const float* sigma;        /* [n] */
+  const float* acc;          /* [n][3][nb] */
+  uint8_t* records;          /* [n][32 | 64], aligned to the record size */
+  uint8_t* kept;             /* [n] or NULL */
+} upnerf_baked_sh_pack_args;
+int upnerf_baked_sh_pack(const upnerf_baked_sh_pack_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

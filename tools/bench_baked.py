@@ -3,6 +3,7 @@ field, on the frames of tools/bench_path.py.
 
     python tools/bench_baked.py [--resolution 128 128 128] [--level SIGMA] [--step 0.02] [--frames 8] [--width 200] [--height 200]
                                 [--chunk 16384] [--progress 0.8] [--images 763] [--reps 3] [--out profiles/baked_render.json]
+                                [--sh [--dirs 48] [--sh-out profiles/baked_sh_render.json]]
 
 The system is bench.py's (two 8 x 256 fields, 64 + 128 samples, 763 images, seeded weights), the path and the box those of
 bench_path.py --occupancy.  In one process, after a warm-up of every mode, `--reps` rounds of  plain render_path / render_path
@@ -10,7 +11,12 @@ with the occupancy grid of the same density at the same level / render_path with
 the clocks touches every mode alike; wall clock around a device synchronisation, the median of each).  Written: the bake time
 (density, colour and packing; wall clock), frames/s and rays/s of each mode beside its hit share, the grid's bytes, the marcher's
 own time per launch (HIP events), and the PSNR of the baked frames against the plain ones at this resolution, step and level.
-The weights are random: the hit share and the PSNR say nothing about a trained scene."""
+The weights are random: the hit share and the PSNR say nothing about a trained scene.
+
+--sh adds the baked scenes with spherical-harmonic colour, degree 1 and degree 2 baked at --dirs directions, as
+two more legs of the same alternating rounds -- so the degree-0 marcher of the same build runs beside them -- and writes
+--sh-out INSTEAD of --out: the rates, each scene's device bytes, the bake times (--dirs passes over the field each), the
+marchers' own times per launch, and the degree-0 rate beside the one recorded in --out's file where that exists."""
 import argparse
 import json
 import os
@@ -49,6 +55,9 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--bake-image", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "baked_render.json"))
+    ap.add_argument("--sh", action="store_true", help="also time the degree-1 and degree-2 spherical-harmonic scenes; writes --sh-out, not --out")
+    ap.add_argument("--dirs", type=int, default=48, help="directions of the spherical-harmonic bakes")
+    ap.add_argument("--sh-out", default=os.path.join(ROOT, "profiles", "baked_sh_render.json"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_baked.py measures on the GPU; none is visible")
@@ -82,6 +91,13 @@ def main():
     scene = bake()
     occ = OccupancyGrid.from_density(grid, BOUNDS, a.level, dilate=1)
     modes = {"plain": {}, "occupancy": {"occupancy": occ}, "baked": {"baked": scene, "baked_step": a.step}}
+    sh_scenes, sh_bake_s = {}, {}
+    if a.sh:
+        from upnerf_amd.baked import sphere_directions
+        for degree in (1, 2):  # (one timed bake each: K passes over the field)
+            bake_sh = lambda: BakedScene.build(sysm, BOUNDS, res, a.level, img_id=a.bake_image, sh_degree=degree, dirs=sphere_directions(a.dirs))
+            sh_bake_s[degree] = wall(lambda: sh_scenes.__setitem__(degree, bake_sh()))
+            modes[f"baked_sh{degree}"] = {"baked": sh_scenes[degree], "baked_step": a.step}
     share, frames = {}, {}
     for k, kw in modes.items():  # warm-up of every mode; the float frames for the PSNR
         frames[k] = render_path(sysm, path, outputs=("rgb_float",), **kw)["rgb_float"].clamp(0, 1)
@@ -93,10 +109,17 @@ def main():
     for _ in range(a.reps):
         for k, kw in modes.items():
             times[k].append(wall(lambda: render_path(sysm, path, outputs=("rgb",), **kw)))
+    summary = lambda v: {"ms_per_launch": v["avg_ms"], "launches": v["launches"], "rays_per_launch": v["units_per_launch"]}
+    sh_kern = {}
+    for degree in sh_scenes:  # (the two SH marchers share a timer name: one pass each)
+        TIMER.reset()
+        TIMER.enabled, TIMER.only = True, {"baked_sh_render"}
+        render_path(sysm, path, outputs=("rgb",), **modes[f"baked_sh{degree}"])
+        sh_kern[degree] = summary(TIMER.summary()["baked_sh_render"])
     TIMER.reset()
     TIMER.enabled, TIMER.only = True, {"baked_render"}
     render_path(sysm, path, outputs=("rgb",), **modes["baked"])
-    kern = {n: {"ms_per_launch": v["avg_ms"], "launches": v["launches"], "rays_per_launch": v["units_per_launch"]} for n, v in TIMER.summary().items()}
+    kern = {n: summary(v) for n, v in TIMER.summary().items()}
     TIMER.enabled, TIMER.only = False, None
     TIMER.reset()
     psnr = lambda x, y: float(-10 * torch.log10(((x - y) ** 2).mean().clamp_min(1e-20)))
@@ -112,6 +135,21 @@ def main():
            "psnr_baked_vs_plain_db": psnr(frames["baked"], frames["plain"]), "psnr_occupancy_vs_plain_db": psnr(frames["occupancy"], frames["plain"]),
            "baked_over_plain": runs["baked"]["rays_per_s"] / runs["plain"]["rays_per_s"],
            "baked_over_occupancy": runs["baked"]["rays_per_s"] / runs["occupancy"]["rays_per_s"]}
+    if a.sh:
+        recorded = None
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                recorded = json.load(f)["runs"]["baked"]["frames_per_s"]
+        out["metric"] = "camera-path frames from baked scenes: degree 0 (no view dependence) and spherical-harmonic degree 1 and 2, beside the two routes through the field (rgb output; random weights)"
+        out["dirs"] = a.dirs
+        out["degree0_frames_per_s_recorded"] = recorded  # (the figure of --out's file: the marcher before it was a template)
+        out["degree0_over_recorded"] = runs["baked"]["frames_per_s"] / recorded if recorded else None
+        for degree in (1, 2):
+            sc = sh_scenes[degree]
+            out[f"sh{degree}"] = {"grid_bytes": sc.nbytes, "bake_seconds": sh_bake_s[degree], "occupied_share": sc.fraction,
+                                  "kernel": sh_kern[degree], "psnr_vs_plain_db": psnr(frames[f"baked_sh{degree}"], frames["plain"]),
+                                  "over_degree0": runs[f"baked_sh{degree}"]["rays_per_s"] / runs["baked"]["rays_per_s"]}
+        a.out = a.sh_out
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)

@@ -4,7 +4,8 @@ appearance moving from photograph to photograph (upnerf_amd/novel_view.py; DESIG
     python tools/render_path.py --config scene.yaml --ckpt last.ckpt --images 3 17 42 --frames 120 --out DIR
                                 [--mode linear|catmull] [--downscale N] [--depth] [--normals] [--loop] [--chunk ROWS]
                                 [--occupancy NX NY NZ --level SIGMA [--dilate K] [--bounds X0 Y0 Z0 X1 Y1 Z1 | --margin M]]
-                                [--baked NX NY NZ --level SIGMA --step DT [--bake-image ID] [--save-baked F | --load-baked F]]
+                                [--baked NX NY NZ --level SIGMA --step DT [--bake-image ID] [--save-baked F | --load-baked F]
+                                 [--baked-sh {1,2} [--baked-dirs K]]]
 
 --occupancy skips empty space: the fine field's density is sampled on NX x NY x NZ grid points over the box (--bounds, or the
 box round the refined cameras and their far points grown by --margin), cells with a corner >= --level (grown by --dilate
@@ -16,7 +17,10 @@ tools/extract_mesh.py) and --dilate trade speed for that.
 the same box (points below --level are dropped), with the appearance of training image --bake-image (default: the first of
 --images) and for ONE viewing direction, the mean optical axis of the training cameras -- a baked scene has no view dependence
 and one appearance -- and every frame is marched from that grid with samples --step apart (upnerf_amd/baked.py).
---save-baked writes the grid to an .npz, --load-baked renders from one (then NX NY NZ and --level are those of the file).
+--baked-sh 1 | 2 gives the preview its view dependence back: the colour head is sampled for --baked-dirs directions (default 48,
+a Fibonacci lattice on the whole sphere: that many passes over the field), a spherical-harmonic expansion of that degree is
+fitted per grid point, and each ray evaluates it for its own direction (32 or 64 bytes a point instead of 16).
+--save-baked writes the grid to an .npz, --load-baked renders from one (then NX NY NZ, --level and the degree are those of the file).
 --depth works, --normals and --occupancy do not.
 
 Writes PNG files only -- DIR/path/step_<frame, 8 digits>/rgb.png (and depth.png with --depth, normal.png with
@@ -55,6 +59,8 @@ def parser():
     ap.add_argument("--baked", type=int, nargs=3, metavar=("NX", "NY", "NZ"), help="render from a colour-density grid of this many grid points instead of the field")
     ap.add_argument("--step", type=float, default=None, help="sample spacing of the baked render along a ray (required with --baked / --load-baked; no default)")
     ap.add_argument("--bake-image", type=int, default=None, help="training image whose appearance is baked (default: the first of --images)")
+    ap.add_argument("--baked-sh", type=int, choices=(1, 2), default=None, help="bake a spherical-harmonic expansion of this degree of the colour over the viewing direction (with --baked)")
+    ap.add_argument("--baked-dirs", type=int, default=None, help="directions the colour head is sampled for with --baked-sh (default 48)")
     ap.add_argument("--save-baked", default=None, help="write the baked grid to this .npz")
     ap.add_argument("--load-baked", default=None, help="render from the baked grid of this .npz instead of baking")
     return ap
@@ -74,6 +80,10 @@ def check_args(a):
         raise SystemExit("a baked render has no --normals and carries its own occupancy bits (no --occupancy)")
     if not baked and (a.step is not None or a.bake_image is not None or a.save_baked is not None):
         raise SystemExit("--step, --bake-image and --save-baked belong to --baked")
+    if a.baked is None and (a.baked_sh is not None or a.baked_dirs is not None):
+        raise SystemExit("--baked-sh and --baked-dirs belong to --baked (a file read with --load-baked carries its own degree)")
+    if a.baked_dirs is not None and a.baked_sh is None:
+        raise SystemExit("--baked-dirs counts the directions of --baked-sh")
     if a.load_baked is not None and (a.save_baked is not None or a.level is not None or a.bounds is not None):
         raise SystemExit("--load-baked takes the grid, its box and its level from the file")
     if a.occupancy is None and a.baked is None and (a.level is not None or a.bounds is not None):
@@ -109,18 +119,19 @@ def main(argv=None):
     scene = None
     if a.baked is not None or a.load_baked is not None:
         from upnerf_amd import geometry
-        from upnerf_amd.baked import BakedScene
+        from upnerf_amd.baked import BakedScene, sphere_directions
         tb = time.perf_counter()
         if a.load_baked is not None:
             scene = BakedScene.load(a.load_baked, next(system.parameters()).device)
         else:
             bounds = (tuple(a.bounds[:3]), tuple(a.bounds[3:])) if a.bounds else geometry.bounds_from_cameras(system, a.margin)
-            scene = BakedScene.build(system, bounds, a.baked, a.level, img_id=a.images[0] if a.bake_image is None else a.bake_image)
+            sh = {} if a.baked_sh is None else {"sh_degree": a.baked_sh, "dirs": sphere_directions(48 if a.baked_dirs is None else a.baked_dirs)}
+            scene = BakedScene.build(system, bounds, a.baked, a.level, img_id=a.images[0] if a.bake_image is None else a.bake_image, **sh)
             if a.save_baked is not None:
                 scene.save(a.save_baked)
         torch.cuda.synchronize()
         extra = {"baked_resolution": list(scene.resolution), "bounds": [list(scene.bounds[0]), list(scene.bounds[1])], "level": scene.level,
-                 "step": a.step, "occupied_share": scene.fraction, "baked_bytes": scene.nbytes, "bake_seconds": time.perf_counter() - tb}
+                 "sh_degree": scene.sh_degree, "step": a.step, "occupied_share": scene.fraction, "baked_bytes": scene.nbytes, "bake_seconds": time.perf_counter() - tb}
     t0 = time.perf_counter()
     render_path(system, path, chunk=a.chunk, outputs=("rgb",) + (("depth",) if a.depth else ()) + (("normal",) if a.normals else ()), sink=writer, occupancy=occ,
                 baked=scene, baked_step=a.step)

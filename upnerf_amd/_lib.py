@@ -381,6 +381,22 @@ class BakedPackArgs(C.Structure):
                 ("kept", _fp)]
 
 
+class BakedShRenderArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("R", C.c_int32), ("lo", C.c_float * 3),
+                ("hi", C.c_float * 3), ("step", C.c_float), ("background", C.c_float), ("stop", C.c_float), ("degree", C.c_int32),
+                ("records", _fp), ("words", _fp), ("rays", _fp), ("rgb", _fp), ("depth", _fp), ("opacity", _fp)]
+
+
+class ShAccumulateArgs(C.Structure):
+    _fields_ = [("n", C.c_int64), ("nb", C.c_int32), ("first", C.c_int32), ("w", C.c_float * 9), ("reserved_", C.c_int32),
+                ("rgb", _fp), ("acc", _fp)]
+
+
+class BakedShPackArgs(C.Structure):
+    _fields_ = [("n", C.c_int64), ("level", C.c_float), ("degree", C.c_int32), ("sigma", _fp), ("acc", _fp), ("records", _fp),
+                ("kept", _fp)]
+
+
 class DensityGradArgs(C.Structure):
     _fields_ = [("M", C.c_int32), ("reserved_", C.c_int32), ("points", _fp), ("P", _fp), ("PT", _fp), ("wk_xyz", C.c_float * 10),
                 ("sigma", _fp), ("grad", _fp)]
@@ -500,6 +516,9 @@ _SIGNATURES = {
     "upnerf_vit_patches16": [C.POINTER(VitPatches16Args), _p],
     "upnerf_baked_render": [C.POINTER(BakedRenderArgs), _p],
     "upnerf_baked_pack": [C.POINTER(BakedPackArgs), _p],
+    "upnerf_baked_sh_render": [C.POINTER(BakedShRenderArgs), _p],
+    "upnerf_sh_accumulate": [C.POINTER(ShAccumulateArgs), _p],
+    "upnerf_baked_sh_pack": [C.POINTER(BakedShPackArgs), _p],
 }
 _LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
              "upnerf_occ_compact_scratch", "upnerf_pca_fit_scratch")

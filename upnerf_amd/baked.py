@@ -10,8 +10,16 @@ The grid holds r, g, b, sigma at the Nx x Ny x Nz points of `density_grid`; a po
 is stored as (0, 0, 0, 0), and the occupancy bits are those of the kept sigmas (`OccupancyGrid.from_density` at the smallest
 positive fp32, no dilation): an unoccupied cell has eight exact zeros and contributes exactly nothing, so the bits only say where
 the integrand is zero and never change the picture.  Colour is the static colour head at sched_mult = 1 with ONE appearance row
-and for ONE viewing direction: a baked scene has NO view dependence.  The marcher is `upnerf_baked_render` (csrc/baked.hip;
-include/upnerf_hip.h states its arithmetic).  There is no CPU path."""
+and, at sh_degree = 0 (the default), for ONE viewing direction: such a scene has NO view dependence.  The marcher is
+`upnerf_baked_render` (csrc/baked.hip; include/upnerf_hip.h states its arithmetic).  There is no CPU path.
+
+    scene = BakedScene.build(system, bounds, (256, 256, 256), level=10.0, img_id=3, sh_degree=2)    # dirs=sphere_directions(48)
+
+With sh_degree = 1 or 2 a grid point holds instead the coefficients of a real spherical-harmonic expansion of its colour over
+the viewing direction -- the least-squares fit to the colour head at K directions, stored as fp16 beside the fp32 sigma in a
+record of 32 or 64 bytes -- and `upnerf_baked_sh_render` evaluates the expansion for each ray's own direction.
+`scene.rgbs` is None then and `scene.records` holds the grid; everything else (bits, skipping, save / load, render_path) is the
+same.  Still ONE appearance.  How close either kind comes to the field on a TRAINED scene is unchecked."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,7 +33,7 @@ from ._lib import check, lib, ptr, stream
 from .ops import TIMER
 from .static_scene import box, c_float3, field_of, refined_training_poses, require_cuda
 
-__all__ = ["BakedScene", "field_colour", "TINY"]
+__all__ = ["BakedScene", "field_colour", "sphere_directions", "sh_basis", "sh_weights", "TINY"]
 
 TINY = float(np.float32(2.0 ** -149))  # the smallest positive fp32: the level at which the kept sigmas are packed into bits
 
@@ -117,6 +125,63 @@ def field_colour(system, bounds, resolution: Sequence[int], view_dir, img_id=Non
     return out.view(Nz, Ny, Nx, 3)
 
 
+RECORD_BYTES = {1: 32, 2: 64}  # one grid point of an SH scene (include/upnerf_hip.h)
+SIGMA_BYTE = {1: 24, 2: 56}
+_Y = (0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396)
+
+
+def _degree(sh_degree) -> int:
+    if sh_degree not in (1, 2):
+        raise ValueError(f"sh_degree is 1 or 2 (0: a scene without view dependence), got {sh_degree!r}")
+    return int(sh_degree)
+
+
+def sphere_directions(K: int = 48) -> np.ndarray:
+    """[K, 3] fp64 unit vectors: a Fibonacci lattice on the WHOLE sphere (z evenly spaced, the longitude advancing by the golden
+    angle).  A field trained from one side of a scene has seen nothing of the other, and what its colour head says there is
+    extrapolation that the fit weighs like everything else; `dirs` restricted to the training cameras' hemisphere is the
+    alternative.  Which of the two is better on a trained scene is unchecked."""
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"K is a number of directions, got {K}")
+    i = np.arange(K, dtype=np.float64)
+    z = 1.0 - (2.0 * i + 1.0) / K
+    r = np.sqrt(1.0 - z * z)
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], 1)
+
+
+def sh_basis(dirs, sh_degree: int) -> np.ndarray:
+    """[K, nb] fp64: the real spherical-harmonic basis of include/upnerf_hip.h at the directions `dirs` [K, 3] (normalised
+    here)."""
+    nb = (_degree(sh_degree) + 1) ** 2
+    d = np.asarray(dirs, np.float64)
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise ValueError("dirs are [K, 3]")
+    n = np.linalg.norm(d, axis=1)
+    if not np.isfinite(d).all() or not (n > 0).all():
+        raise ValueError("dirs are directions: three finite numbers each, not all zero")
+    x, y, z = (d / n[:, None]).T
+    B = [np.full_like(x, _Y[0]), -_Y[1] * y, _Y[1] * z, -_Y[1] * x, _Y[2] * x * y, -_Y[2] * y * z,
+         _Y[3] * (2 * z * z - x * x - y * y), -_Y[2] * x * z, _Y[4] * (x * x - y * y)]
+    return np.stack(B[:nb], 1)
+
+
+def sh_weights(dirs, sh_degree: int) -> np.ndarray:
+    """[nb, K] fp32: the pseudo-inverse of the fp64 basis matrix of `dirs`, rounded once -- the weights with which the colours at
+    the K directions sum to the least-squares coefficients.  Refused: K < nb, and a basis matrix whose smallest singular value is
+    below 1e-6 of its largest (a rank test in fp64: directions that do not determine the expansion, e.g. coplanar ones at
+    degree 2)."""
+    B = sh_basis(dirs, sh_degree)
+    K, nb = B.shape
+    if K < nb:
+        raise ValueError(f"degree {sh_degree} has {nb} coefficients: {K} directions cannot determine them")
+    sv = np.linalg.svd(B, compute_uv=False)
+    if not sv[-1] >= 1e-6 * sv[0]:
+        raise ValueError(f"the directions do not determine a degree-{sh_degree} expansion (singular values {sv[0]:.3g} .. {sv[-1]:.3g})")
+    return np.ascontiguousarray(np.linalg.pinv(B).astype(np.float32))
+
+
 def _render_args(rays, step, background, stop):
     step, background, stop = float(step), float(background), float(stop)
     if not (step > 0 and np.isfinite(step)):
@@ -132,7 +197,11 @@ def _render_args(rays, step, background, stop):
 
 class BakedScene:
     """`rgbs` [Nz, Ny, Nx, 4] fp32 on the device (r, g, b, sigma at the grid points, pruned at `level`), the box it spans and
-    the OccupancyGrid of its kept sigmas."""
+    the OccupancyGrid of its kept sigmas.  An SH scene (from_records, from_direction_grids, build(sh_degree=1 | 2)) has
+    `rgbs` None, `sh_degree` 1 or 2 and `records` [Nz, Ny, Nx, 32 | 64] uint8 instead."""
+
+    sh_degree = 0
+    records = None
 
     def __init__(self, rgbs: torch.Tensor, bounds, level: float):
         from .occupancy import OccupancyGrid
@@ -143,6 +212,29 @@ class BakedScene:
         self.bounds = box(bounds, strict=True)
         self.level = float(level)
         self.occupancy = OccupancyGrid.from_density(rgbs[..., 3].contiguous(), self.bounds, level=TINY, dilate=0)
+
+    @classmethod
+    def from_records(cls, records: torch.Tensor, bounds, level: float, sh_degree: int) -> "BakedScene":
+        """An SH scene from its records, a contiguous uint8 device tensor [Nz, Ny, Nx, 32 (degree 1) | 64 (degree 2)] laid out as
+        include/upnerf_hip.h says; the occupancy bits are those of the records' sigmas."""
+        from .occupancy import OccupancyGrid
+        degree = _degree(sh_degree)
+        require_cuda("BakedScene.from_records", records)
+        size = RECORD_BYTES[degree]
+        if records.dtype != torch.uint8 or records.dim() != 4 or records.shape[3] != size or min(records.shape[:3]) < 2:
+            raise ValueError(f"records is a uint8 tensor [Nz, Ny, Nx, {size}] with two points per axis at least")
+        records = records.contiguous()
+        if records.data_ptr() % size:  # (a record is aligned to its own size)
+            spare = torch.empty(records.numel() + size, dtype=torch.uint8, device=records.device)
+            off = -spare.data_ptr() % size
+            records = spare[off:off + records.numel()].view(records.shape).copy_(records)
+        self = cls.__new__(cls)
+        self.rgbs, self.records, self.sh_degree = None, records, degree
+        self.bounds = box(bounds, strict=True)
+        self.level = float(level)
+        sigma = records[..., SIGMA_BYTE[degree]:SIGMA_BYTE[degree] + 4].contiguous().view(torch.float32).squeeze(-1)
+        self.occupancy = OccupancyGrid.from_density(sigma.contiguous(), self.bounds, level=TINY, dilate=0)
+        return self
 
     # ---- construction ------------------------------------------------------------------------------------------------------
 
@@ -169,15 +261,76 @@ class BakedScene:
 
     @classmethod
     @torch.no_grad()
+    def _project(cls, sigma: torch.Tensor, colour_of, dirs, bounds, level: float, sh_degree: int) -> "BakedScene":
+        """The SH scene of sigma [Nz, Ny, Nx] and colour_of(k) -> [Nz, Ny, Nx, 3], the colour grid for direction k of `dirs`:
+        upnerf_sh_accumulate for k = 0 .. K-1 in order (one direction's colours and the accumulator resident at a time), then
+        upnerf_baked_sh_pack."""
+        degree = _degree(sh_degree)
+        W = sh_weights(dirs, degree)
+        nb, K = W.shape
+        level = float(level)
+        if level != level:
+            raise ValueError("level is not a number")
+        sigma = sigma.detach().contiguous()
+        n, dev = sigma.numel(), sigma.device
+        acc = torch.empty(tuple(sigma.shape) + (3, nb), device=dev, dtype=torch.float32)
+        for k in range(K):
+            rgb = colour_of(k)
+            if rgb.dtype != torch.float32 or tuple(rgb.shape) != tuple(sigma.shape) + (3,) or rgb.device != dev:
+                raise ValueError("the colours of a direction are a fp32 tensor [Nz, Ny, Nx, 3] on sigma's device")
+            rgb = rgb.detach().contiguous()
+            a = _lib.ShAccumulateArgs(n=n, nb=nb, first=int(k == 0), w=(C.c_float * 9)(*W[:, k].tolist()), rgb=ptr(rgb), acc=ptr(acc))
+            check(TIMER.run("sh_accumulate", lambda: lib.upnerf_sh_accumulate(C.byref(a), stream()), units=n), "upnerf_sh_accumulate")
+        size = RECORD_BYTES[degree]
+        spare = torch.empty(n * size + size, dtype=torch.uint8, device=dev)
+        off = -spare.data_ptr() % size
+        records = spare[off:off + n * size].view(tuple(sigma.shape) + (size,))
+        a = _lib.BakedShPackArgs(n=n, level=level, degree=degree, sigma=ptr(sigma), acc=ptr(acc), records=ptr(records), kept=None)
+        check(TIMER.run("baked_sh_pack", lambda: lib.upnerf_baked_sh_pack(C.byref(a), stream()), units=n), "upnerf_baked_sh_pack")
+        return cls.from_records(records, bounds, level, degree)
+
+    @classmethod
+    @torch.no_grad()
+    def from_direction_grids(cls, sigma: torch.Tensor, rgb_dirs: torch.Tensor, dirs, bounds, level: float = 0.0,
+                             sh_degree: int = 1) -> "BakedScene":
+        """The SH sibling of from_grids: a density grid [Nz, Ny, Nx] and the colour grids rgb_dirs [K, Nz, Ny, Nx, 3] of the
+        caller's own for the K directions `dirs` [K, 3], fp32 on the device.  Each coefficient is the least-squares fit
+        sum_k W[j][k] rgb_k (sh_weights), summed in fp32 in the order of k.  A point is kept iff its sigma is finite, positive
+        and >= level and its coefficients are finite; every other point becomes a zero record (upnerf_baked_sh_pack)."""
+        require_cuda("BakedScene.from_direction_grids", sigma, rgb_dirs)
+        if sigma.dtype != torch.float32 or sigma.dim() != 3 or min(sigma.shape) < 2:
+            raise ValueError("sigma is a fp32 tensor [Nz, Ny, Nx] with two points per axis at least")
+        K = np.asarray(dirs).shape[0] if np.asarray(dirs).ndim == 2 else -1
+        if rgb_dirs.dtype != torch.float32 or tuple(rgb_dirs.shape) != (K,) + tuple(sigma.shape) + (3,):
+            raise ValueError("rgb_dirs is a fp32 tensor [K, Nz, Ny, Nx, 3], one colour grid per row of dirs [K, 3]")
+        return cls._project(sigma, lambda k: rgb_dirs[k], dirs, bounds, level, sh_degree)
+
+    @classmethod
+    @torch.no_grad()
     def build(cls, system, bounds, resolution: Sequence[int], level: float, img_id=None, rows=None, view_dir=None,
-              field: str = "fine", chunk: Optional[int] = None) -> "BakedScene":
+              field: str = "fine", chunk: Optional[int] = None, sh_degree: int = 0, dirs=None) -> "BakedScene":
         """Bake the static scene of `system`: sigma = geometry.density_grid, colour = field_colour with the appearance row of
         training image `img_id` (or `rows`, a row of the caller's own) for the viewing direction `view_dir` (default: the
         normalised mean optical axis of the refined training cameras).  `level` has no default: the useful threshold depends on
-        the scene's scale (see extract_surface).  `resolution` counts grid POINTS per axis, two at least."""
+        the scene's scale (see extract_surface).  `resolution` counts grid POINTS per axis, two at least.
+
+        sh_degree = 1 | 2: colour is instead the degree's spherical-harmonic fit to field_colour at the directions `dirs` [K, 3]
+        (default sphere_directions(48): the whole sphere -- see there), K passes over the field; view_dir has no meaning then and
+        is refused, as dirs is at degree 0."""
         from .geometry import density_grid
         if min(int(n) for n in resolution) < 2:
             raise ValueError(f"resolution is the number of grid points per axis (two at least), got {tuple(resolution)}")
+        if sh_degree != 0:
+            _degree(sh_degree)
+            if view_dir is not None:
+                raise ValueError("view_dir is the ONE direction of a scene without view dependence: with sh_degree > 0 pass dirs")
+            dirs = sphere_directions() if dirs is None else np.asarray(torch.as_tensor(dirs).detach().cpu().numpy(), np.float64)
+            sh_weights(dirs, sh_degree)  # (refused before any pass over the field)
+            sigma = density_grid(system, bounds, resolution, field=field, chunk=chunk)
+            colour = lambda k: field_colour(system, bounds, resolution, dirs[k], img_id=img_id, rows=rows, field=field, chunk=chunk)
+            return cls._project(sigma, colour, dirs, bounds, level, sh_degree)
+        if dirs is not None:
+            raise ValueError("dirs are the directions of a spherical-harmonic fit: pass sh_degree = 1 or 2 with them")
         if view_dir is None:
             view_dir = mean_optical_axis(system)
         sigma = density_grid(system, bounds, resolution, field=field, chunk=chunk)
@@ -187,9 +340,10 @@ class BakedScene:
     # ---- rendering ---------------------------------------------------------------------------------------------------------
 
     def render(self, rays: torch.Tensor, step: float, background: float = 0.0, stop: float = 0.0, out: Optional[dict] = None) -> dict:
-        """{"rgb" [R, 3], "depth" [R], "opacity" [R]} of [R, 8] device rays (upnerf_baked_render): samples every `step` of t
-        from near + step / 2, alpha-composited front to back; what the ray does not hit shows `background` at depth `far`.
-        stop > 0 ends a ray once its transmittance falls below it.  out: preallocated buffers of at least R rows."""
+        """{"rgb" [R, 3], "depth" [R], "opacity" [R]} of [R, 8] device rays (upnerf_baked_render; upnerf_baked_sh_render for an
+        SH scene, each sample's colour then being the expansion at the ray's own direction, clamped to [0, 1]): samples every
+        `step` of t from near + step / 2, alpha-composited front to back; what the ray does not hit shows `background` at depth
+        `far`.  stop > 0 ends a ray once its transmittance falls below it.  out: preallocated buffers of at least R rows."""
         require_cuda("BakedScene.render", rays)
         step, background, stop = _render_args(rays, step, background, stop)
         rays = rays.contiguous()
@@ -204,34 +358,54 @@ class BakedScene:
                 raise ValueError("the outputs are fp32 [>= R, 3], [>= R] and [>= R] on the rays' device")
         Cx, Cy, Cz = self.occupancy.dims
         lo, hi = self.bounds
-        a = _lib.BakedRenderArgs(Cx=Cx, Cy=Cy, Cz=Cz, R=R, lo=c_float3(lo), hi=c_float3(hi), step=step, background=background,
-                                 stop=stop, rgbs=ptr(self.rgbs), words=ptr(self.occupancy.words), rays=ptr(rays),
-                                 rgb=ptr(out["rgb"]), depth=ptr(out["depth"]), opacity=ptr(out["opacity"]))
-        check(TIMER.run("baked_render", lambda: lib.upnerf_baked_render(C.byref(a), stream()), units=R), "upnerf_baked_render")
+        common = dict(Cx=Cx, Cy=Cy, Cz=Cz, R=R, lo=c_float3(lo), hi=c_float3(hi), step=step, background=background, stop=stop,
+                      words=ptr(self.occupancy.words), rays=ptr(rays), rgb=ptr(out["rgb"]), depth=ptr(out["depth"]),
+                      opacity=ptr(out["opacity"]))
+        if self.sh_degree:
+            a = _lib.BakedShRenderArgs(degree=self.sh_degree, records=ptr(self.records), **common)
+            check(TIMER.run("baked_sh_render", lambda: lib.upnerf_baked_sh_render(C.byref(a), stream()), units=R), "upnerf_baked_sh_render")
+        else:
+            a = _lib.BakedRenderArgs(rgbs=ptr(self.rgbs), **common)
+            check(TIMER.run("baked_render", lambda: lib.upnerf_baked_render(C.byref(a), stream()), units=R), "upnerf_baked_render")
         return {k: out[k][:R] for k in ("rgb", "depth", "opacity")}
 
     # ---- files -------------------------------------------------------------------------------------------------------------
 
     def save(self, path: str) -> None:
-        """An .npz holding the grid, the bounds and the level; the bits are rebuilt on load."""
-        save_arrays(path, self.rgbs.detach().cpu().numpy(), self.bounds, self.level)
+        """An .npz holding the grid (`rgbs`, or `records` and `degree` of an SH scene), the bounds and the level; the bits are
+        rebuilt on load."""
+        if self.sh_degree:
+            save_arrays(path, self.records.detach().cpu().numpy(), self.bounds, self.level, sh_degree=self.sh_degree)
+        else:
+            save_arrays(path, self.rgbs.detach().cpu().numpy(), self.bounds, self.level)
 
     @classmethod
     def load(cls, path: str, device="cuda") -> "BakedScene":
-        rgbs, bounds, level = load_arrays(path)
-        return cls(torch.from_numpy(rgbs).to(device).contiguous(), bounds, level)
+        grid, bounds, level, *degree = load_arrays(path)
+        if degree:
+            return cls.from_records(torch.from_numpy(grid).to(device).contiguous(), bounds, level, degree[0])
+        return cls(torch.from_numpy(grid).to(device).contiguous(), bounds, level)
 
     # ---- accessors ---------------------------------------------------------------------------------------------------------
 
     @property
+    def grid(self) -> torch.Tensor:
+        """The tensor the marcher reads: `records` of an SH scene, else `rgbs`."""
+        return self.records if self.sh_degree else self.rgbs
+
+    @property
+    def device(self):
+        return self.grid.device
+
+    @property
     def resolution(self):
-        Nz, Ny, Nx, _ = self.rgbs.shape
+        Nz, Ny, Nx, _ = self.grid.shape
         return Nx, Ny, Nz
 
     @property
     def nbytes(self) -> int:
         """Device bytes of the grid and its bits."""
-        return self.rgbs.numel() * 4 + self.occupancy.words.numel() * 4
+        return self.grid.numel() * self.grid.element_size() + self.occupancy.words.numel() * 4
 
     @property
     def fraction(self) -> float:
@@ -239,7 +413,17 @@ class BakedScene:
         return self.occupancy.fraction
 
 
-def save_arrays(path: str, rgbs: np.ndarray, bounds, level: float) -> None:
+def save_arrays(path: str, rgbs: np.ndarray, bounds, level: float, sh_degree: int = 0) -> None:
+    """rgbs: the fp32 grid [Nz, Ny, Nx, 4]; with sh_degree = 1 | 2 the uint8 records [Nz, Ny, Nx, 32 | 64] instead, written as
+    the arrays records, degree, bounds, level."""
+    if sh_degree != 0:
+        records = np.asarray(rgbs)
+        if records.dtype != np.uint8 or records.ndim != 4 or records.shape[3] != RECORD_BYTES[_degree(sh_degree)]:
+            raise ValueError(f"the records of degree {sh_degree} are a uint8 array [Nz, Ny, Nx, {RECORD_BYTES[sh_degree]}]")
+        lo, hi = box(bounds, strict=True)
+        with open(path, "wb") as fh:
+            np.savez(fh, records=records, degree=np.int64(sh_degree), bounds=np.asarray([lo, hi], np.float64), level=np.float64(level))
+        return
     rgbs = np.asarray(rgbs)
     if rgbs.dtype != np.float32 or rgbs.ndim != 4 or rgbs.shape[3] != 4:
         raise ValueError("rgbs is a fp32 array [Nz, Ny, Nx, 4]")
@@ -249,8 +433,15 @@ def save_arrays(path: str, rgbs: np.ndarray, bounds, level: float) -> None:
 
 
 def load_arrays(path: str):
-    """(rgbs fp32 [Nz, Ny, Nx, 4], bounds, level) of a file BakedScene.save wrote; anything else raises ValueError."""
+    """(rgbs fp32 [Nz, Ny, Nx, 4], bounds, level) of a file BakedScene.save wrote, or (records uint8 [Nz, Ny, Nx, 32 | 64],
+    bounds, level, degree) of an SH scene's; anything else raises ValueError."""
     with np.load(path) as f:
+        if set(f.files) == {"records", "degree", "bounds", "level"}:
+            records, bounds, level, degree = f["records"], f["bounds"], float(f["level"]), f["degree"]
+            if degree.shape != () or int(degree) not in RECORD_BYTES or records.dtype != np.uint8 or records.ndim != 4 or \
+                    records.shape[3] != RECORD_BYTES[int(degree)] or bounds.shape != (2, 3) or min(records.shape[:3]) < 2:
+                raise ValueError(f"{path}: not a baked scene (records {records.dtype} {records.shape}, degree {degree}, bounds {bounds.shape})")
+            return np.ascontiguousarray(records), box(bounds.tolist(), strict=True), level, int(degree)
         if set(f.files) != {"rgbs", "bounds", "level"}:
             raise ValueError(f"{path}: not a baked scene (arrays {sorted(f.files)})")
         rgbs, bounds, level = f["rgbs"], f["bounds"], float(f["level"])

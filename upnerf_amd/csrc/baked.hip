@@ -14,6 +14,12 @@
 //                        picture is, bit for bit, the one that visits every sample (tests/test_hip_baked.py runs both).
 //                        A visited sample reads its eight corners as eight 16-byte loads; the rays of a wave are 64 neighbouring
 //                        pixels of an image row and read neighbouring corners.  All per-ray state is in registers; no LDS.
+//   upnerf_baked_sh_render  the same march (ONE template, baked_march<DEG>) through records that hold, per grid point, the fp16
+//                        coefficients of a spherical-harmonic expansion of the colour over direction and a fp32 sigma (32 bytes at
+//                        degree 1, 64 at degree 2).  The basis of the ray's direction is formed once per ray and
+//                        kept in registers; a corner is reduced to (r, g, b, sigma) as it is read -- nb fmas per channel -- so the
+//                        blend sees the four floats per corner it sees at degree 0.  Degree 0 is the instantiation that reads rgbs.
+//   upnerf_sh_accumulate, upnerf_baked_sh_pack  the projection's running sum over directions, and the records from it.
 // All stores are ordinary vector stores from plain C++.
 #include "common.cuh"
 #include "grid.cuh"
@@ -67,9 +73,62 @@ struct BakedOut {
   float rgb[3], depth, opacity;
 };
 
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// where the four channels of a corner come from: BakedCorner<0> reads rgbs, BakedCorner<1 | 2> evaluates a record's expansion
+// for the direction of the ray it was made for (include/upnerf_hip.h states the basis and the order of the sum)
+template <int DEG>
+struct BakedCorner {
+  typedef upnerf_baked_sh_render_args Args;
+  static constexpr int NB = (DEG + 1) * (DEG + 1), Q = DEG == 1 ? 2 : 4;  // basis functions; 16-byte loads per record
+  const u32x4* rec;
+  float Y[NB];
+  __host__ __device__ __forceinline__ BakedCorner(const Args& A, const float* d, float len) : rec((const u32x4*)A.records) {
+    const float x = d[0] / len, y = d[1] / len, z = d[2] / len;
+    Y[0] = 0.28209479177387814f;
+    Y[1] = -0.4886025119029199f * y, Y[2] = 0.4886025119029199f * z, Y[3] = -0.4886025119029199f * x;
+    if constexpr (DEG > 1) {
+      Y[4] = 1.0925484305920792f * (x * y), Y[5] = -1.0925484305920792f * (y * z);
+      Y[6] = 0.31539156525252005f * fmaf(2.0f * z, z, -fmaf(x, x, y * y));
+      Y[7] = -1.0925484305920792f * (x * z), Y[8] = 0.5462742152960396f * fmaf(x, x, -(y * y));
+    }
+  }
+  __host__ __device__ __forceinline__ f32x4 operator()(int64_t p) const {
+    uint32_t w[4 * Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const u32x4 v = rec[p * Q + q];
+      w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+    }
+    f32x4 out;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float acc = 0.0f;
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const int h = c * NB + j;
+        const float k = (float)__builtin_bit_cast(_Float16, (uint16_t)(w[h >> 1] >> ((h & 1) * 16)));
+        acc = fmaf(Y[j], k, acc);
+      }
+      out[c] = acc;
+    }
+    out[3] = __builtin_bit_cast(float, w[4 * Q - 2]);  // sigma: byte 24 of 32, byte 56 of 64
+    return out;
+  }
+};
+
+template <>
+struct BakedCorner<0> {
+  typedef upnerf_baked_render_args Args;
+  const f32x4* pts;
+  __host__ __device__ __forceinline__ BakedCorner(const Args& A, const float*, float) : pts((const f32x4*)A.rgbs) {}
+  __host__ __device__ __forceinline__ f32x4 operator()(int64_t p) const { return pts[p]; }
+};
+
 // the march of one ray row (host and device: the host build is what a CPU program checks against the fp64 restatement)
-__host__ __device__ __forceinline__ BakedOut baked_march(const upnerf_baked_render_args& A, const BakedGrid& G, const OccDims& dm,
-                                                         const float* row, bool use_bits) {
+template <int DEG>
+__host__ __device__ __forceinline__ BakedOut baked_march(const typename BakedCorner<DEG>::Args& A, const BakedGrid& G,
+                                                         const OccDims& dm, const float* row, bool use_bits) {
   const float o[3] = {row[0], row[1], row[2]}, d[3] = {row[3], row[4], row[5]};
   const float near = row[6], far = row[7];
   BakedOut out;
@@ -82,10 +141,11 @@ __host__ __device__ __forceinline__ BakedOut baked_march(const upnerf_baked_rend
   if (ok) {
     const float nk = ceilf((far - near) / A.step);
     const int K = nk < (float)UPNERF_BAKED_MAX_SAMPLES ? (int)nk : UPNERF_BAKED_MAX_SAMPLES;
-    const float delta = A.step * sqrtf(fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0])));
+    const float len = sqrtf(fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0])));
+    const float delta = A.step * len;
     const uint32_t* fine = A.words;
     const uint32_t* brick = A.words + dm.fine_words;
-    const f32x4* pts = (const f32x4*)A.rgbs;
+    const BakedCorner<DEG> pts(A, d, len);
     float T = 1.0f;
     int k = 0;
     while (k < K) {
@@ -146,10 +206,10 @@ __host__ __device__ __forceinline__ BakedOut baked_march(const upnerf_baked_rend
       // the sample counts: trilinear blend of the eight corners, x first, then y, then z
       const int64_t base = ((int64_t)s.i[2] * G.sz + (int64_t)s.i[1] * G.sy) + s.i[0];
       const float fx = s.g[0] - (float)s.i[0], fy = s.g[1] - (float)s.i[1], fz = s.g[2] - (float)s.i[2];
-      const f32x4 c000 = pts[base], c100 = pts[base + 1];
-      const f32x4 c010 = pts[base + G.sy], c110 = pts[base + G.sy + 1];
-      const f32x4 c001 = pts[base + G.sz], c101 = pts[base + G.sz + 1];
-      const f32x4 c011 = pts[base + G.sz + G.sy], c111 = pts[base + G.sz + G.sy + 1];
+      const f32x4 c000 = pts(base), c100 = pts(base + 1);
+      const f32x4 c010 = pts(base + G.sy), c110 = pts(base + G.sy + 1);
+      const f32x4 c001 = pts(base + G.sz), c101 = pts(base + G.sz + 1);
+      const f32x4 c011 = pts(base + G.sz + G.sy), c111 = pts(base + G.sz + G.sy + 1);
       float v[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -157,6 +217,10 @@ __host__ __device__ __forceinline__ BakedOut baked_march(const upnerf_baked_rend
         const float x01 = fmaf(fx, c101[c] - c001[c], c001[c]), x11 = fmaf(fx, c111[c] - c011[c], c011[c]);
         const float y0 = fmaf(fy, x10 - x00, x00), y1 = fmaf(fy, x11 - x01, x01);
         v[c] = fmaf(fz, y1 - y0, y0);
+      }
+      if (DEG > 0) {  // an expansion is not held to [0, 1] as the colour head's sigmoid is
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = fminf(fmaxf(v[c], 0.0f), 1.0f);
       }
       const float e = expf(-delta * v[3]);
       const float alpha = 1.0f - e;
@@ -177,13 +241,14 @@ __host__ __device__ __forceinline__ BakedOut baked_march(const upnerf_baked_rend
   return out;
 }
 
-__global__ __launch_bounds__(BAKED_THREADS) void baked_render_kernel(upnerf_baked_render_args a, BakedGrid G, OccDims dm) {
+template <int DEG>
+__global__ __launch_bounds__(BAKED_THREADS) void baked_render_kernel(typename BakedCorner<DEG>::Args a, BakedGrid G, OccDims dm) {
   const int r = blockIdx.x * BAKED_THREADS + threadIdx.x;
   if (r >= a.R) return;
   const f32x4* rp = (const f32x4*)(a.rays + (int64_t)r * 8);  // (rows of 32 bytes in a buffer the host found 16-byte aligned)
   const f32x4 r0 = rp[0], r1 = rp[1];
   const float row[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-  const BakedOut out = baked_march(a, G, dm, row, true);
+  const BakedOut out = baked_march<DEG>(a, G, dm, row, true);
   float* c = a.rgb + (int64_t)r * 3;
   c[0] = out.rgb[0], c[1] = out.rgb[1], c[2] = out.rgb[2];
   a.depth[r] = out.depth;
@@ -204,13 +269,51 @@ __global__ __launch_bounds__(NTHREADS) void baked_pack_kernel(upnerf_baked_pack_
   if (a.kept) a.kept[n] = keep ? 1 : 0;
 }
 
+__global__ __launch_bounds__(NTHREADS) void sh_accumulate_kernel(upnerf_sh_accumulate_args a) {
+  const int64_t n = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
+  if (n >= a.n) return;
+  const float* rgb = a.rgb + n * 3;
+  float* acc = a.acc + n * 3 * a.nb;
+  for (int c = 0; c < 3; ++c) {
+    const float v = rgb[c];
+    for (int j = 0; j < a.nb; ++j) acc[c * a.nb + j] = fmaf(a.w[j], v, a.first ? 0.0f : acc[c * a.nb + j]);
+  }
+}
+
+template <int DEG>
+__global__ __launch_bounds__(NTHREADS) void baked_sh_pack_kernel(upnerf_baked_sh_pack_args a) {
+  constexpr int NB = (DEG + 1) * (DEG + 1), Q = DEG == 1 ? 2 : 4;
+  const int64_t n = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
+  if (n >= a.n) return;
+  const float s = a.sigma[n];
+  bool keep = isfinite(s) && s > 0.0f && s >= a.level;
+  uint32_t w[4 * Q];
+#pragma unroll
+  for (int i = 0; i < 4 * Q; ++i) w[i] = 0u;
+  const float* acc = a.acc + n * 3 * NB;
+#pragma unroll
+  for (int h = 0; h < 3 * NB; ++h) {
+    const float k = acc[h];
+    keep = keep && isfinite(k);
+    const _Float16 half = (_Float16)fminf(fmaxf(k, -65504.0f), 65504.0f);  // (the conversion rounds to nearest even)
+    w[h >> 1] |= (uint32_t)__builtin_bit_cast(uint16_t, half) << ((h & 1) * 16);
+  }
+  w[4 * Q - 2] = __builtin_bit_cast(uint32_t, s);
+  u32x4* rec = (u32x4*)a.records + n * Q;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) rec[q] = keep ? u32x4{w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]} : u32x4{0u, 0u, 0u, 0u};
+  if (a.kept) a.kept[n] = keep ? 1 : 0;
+}
+
 bool baked_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // the arguments a launch may be given, and the grid as the kernel reads it
-bool baked_grid(const upnerf_baked_render_args* a, BakedGrid* G, OccDims* dm) {
+// (`points`: the rgbs or the records of `a`, aligned to `size`, the bytes of one point)
+template <class Args>
+bool baked_grid(const Args* a, const void* points, size_t size, BakedGrid* G, OccDims* dm) {
   if (!a || !occ_dims(a->Cx, a->Cy, a->Cz, dm) || a->R <= 0) return false;
-  if (!a->rgbs || !a->words || !a->rays || !a->rgb || !a->depth || !a->opacity) return false;
-  if (!baked_aligned16(a->rgbs) || !baked_aligned16(a->rays)) return false;
+  if (!points || !a->words || !a->rays || !a->rgb || !a->depth || !a->opacity) return false;
+  if (((uintptr_t)points & (size - 1)) != 0 || !baked_aligned16(a->rays)) return false;
   if (!(a->step > 0.0f) || !isfinite(a->step) || !isfinite(a->background) || !(a->stop >= 0.0f && a->stop < 1.0f)) return false;
   const int C[3] = {a->Cx, a->Cy, a->Cz};
   for (int k = 0; k < 3; ++k) {
@@ -231,8 +334,8 @@ bool baked_grid(const upnerf_baked_render_args* a, BakedGrid* G, OccDims* dm) {
 extern "C" int upnerf_baked_render(const upnerf_baked_render_args* a, void* stream) {
   BakedGrid G;
   OccDims dm;
-  if (!baked_grid(a, &G, &dm)) return UPNERF_EINVAL;
-  hipLaunchKernelGGL(baked_render_kernel, dim3((a->R + BAKED_THREADS - 1) / BAKED_THREADS), dim3(BAKED_THREADS), 0,
+  if (!baked_grid(a, a ? a->rgbs : nullptr, 16, &G, &dm)) return UPNERF_EINVAL;
+  hipLaunchKernelGGL(baked_render_kernel<0>, dim3((a->R + BAKED_THREADS - 1) / BAKED_THREADS), dim3(BAKED_THREADS), 0,
                      (hipStream_t)stream, *a, G, dm);
   return (int)hipGetLastError();
 }
@@ -242,5 +345,37 @@ extern "C" int upnerf_baked_pack(const upnerf_baked_pack_args* a, void* stream) 
   const int64_t blocks = (a->n + NTHREADS - 1) / NTHREADS;
   if (blocks > 0x7fffffff) return UPNERF_EUNSUP;
   hipLaunchKernelGGL(baked_pack_kernel, dim3((unsigned)blocks), dim3(NTHREADS), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int upnerf_baked_sh_render(const upnerf_baked_sh_render_args* a, void* stream) {
+  BakedGrid G;
+  OccDims dm;
+  if (!a || (a->degree != 1 && a->degree != 2)) return UPNERF_EINVAL;
+  if (!baked_grid(a, a->records, a->degree == 1 ? 32 : 64, &G, &dm)) return UPNERF_EINVAL;
+  const dim3 grid((a->R + BAKED_THREADS - 1) / BAKED_THREADS), block(BAKED_THREADS);
+  if (a->degree == 1) hipLaunchKernelGGL(baked_render_kernel<1>, grid, block, 0, (hipStream_t)stream, *a, G, dm);
+  else hipLaunchKernelGGL(baked_render_kernel<2>, grid, block, 0, (hipStream_t)stream, *a, G, dm);
+  return (int)hipGetLastError();
+}
+
+extern "C" int upnerf_sh_accumulate(const upnerf_sh_accumulate_args* a, void* stream) {
+  if (!a || a->n <= 0 || (a->nb != 4 && a->nb != 9) || !a->rgb || !a->acc) return UPNERF_EINVAL;
+  for (int j = 0; j < a->nb; ++j)
+    if (!isfinite(a->w[j])) return UPNERF_EINVAL;
+  const int64_t blocks = (a->n + NTHREADS - 1) / NTHREADS;
+  if (blocks > 0x7fffffff) return UPNERF_EUNSUP;
+  hipLaunchKernelGGL(sh_accumulate_kernel, dim3((unsigned)blocks), dim3(NTHREADS), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int upnerf_baked_sh_pack(const upnerf_baked_sh_pack_args* a, void* stream) {
+  if (!a || a->n <= 0 || (a->degree != 1 && a->degree != 2) || !a->sigma || !a->acc || !a->records || a->level != a->level)
+    return UPNERF_EINVAL;
+  if (((uintptr_t)a->records & (a->degree == 1 ? 31 : 63)) != 0) return UPNERF_EINVAL;
+  const int64_t blocks = (a->n + NTHREADS - 1) / NTHREADS;
+  if (blocks > 0x7fffffff) return UPNERF_EUNSUP;
+  if (a->degree == 1) hipLaunchKernelGGL(baked_sh_pack_kernel<1>, dim3((unsigned)blocks), dim3(NTHREADS), 0, (hipStream_t)stream, *a);
+  else hipLaunchKernelGGL(baked_sh_pack_kernel<2>, dim3((unsigned)blocks), dim3(NTHREADS), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }

@@ -224,7 +224,8 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
     One host read per chunk (the hit count); a chunk without hits launches no field kernel.  LAST_STATS holds the sequence's
     number of rays and hits.  None: nothing of this runs.
     baked: a `baked.BakedScene`, with `baked_step` (the sample spacing in units of t; no default).  The frames come from
-    `baked.render` on the rays upnerf_path_rays makes and the fields are never evaluated: no view dependence, ONE appearance (the
+    `baked.render` on the rays upnerf_path_rays makes and the fields are never evaluated: no view dependence unless the scene was
+    baked with sh_degree > 0 (its render then evaluates each ray's own direction: nothing to pass here), ONE appearance (the
     one the scene was baked with: the path's blend is not looked at), outputs "rgb", "depth" and "rgb_float" only.  Asking for a
     normal map, or passing `occupancy` as well (the scene carries its own bits), raises ValueError."""
     if baked is not None:
@@ -361,7 +362,8 @@ def render_path(system, path: CameraPath, chunk: Optional[int] = None, outputs: 
 
 
 def _render_path_baked(system, path: CameraPath, chunk, outputs, depth_range, sink, occupancy, baked, baked_step):
-    """render_path(..., baked=scene, baked_step=dt): the frames of `path` from the baked scene's grid alone."""
+    """render_path(..., baked=scene, baked_step=dt): the frames of `path` from the baked scene's grid alone (scene.render
+    dispatches on scene.sh_degree: view dependence is the scene's, not an argument here)."""
     from .baked import BakedScene
     from .visualization import depth_image, min_max_of, rgb_image
     if not isinstance(baked, BakedScene):
@@ -373,7 +375,7 @@ def _render_path_baked(system, path: CameraPath, chunk, outputs, depth_range, si
     unknown = set(outputs) - {"rgb", "depth", "rgb_float"}
     if unknown:
         raise ValueError(f"a baked scene renders rgb, depth and rgb_float only, not {sorted(unknown)}")
-    dev = baked.rgbs.device
+    dev = baked.device
     W, H = path.img_wh
     F, n = path.n_frames, W * H
     total = F * n
