@@ -657,7 +657,10 @@ int upnerf_frag_copy(const float* src, float* dst, const upnerf_frag_desc* descs
  * pack   (unpack = 0): P[dst_off + r*dst_ld + c] = ptr[r*src_ld + c] for c < cols (padding columns are left alone: start
  *                      from a zeroed P); with `accumulate` the value is added to what P holds (bias of the folded layer).
  * unpack (unpack = 1): ((float*)ptr)[r*src_ld + c] = P[dst_off + r*dst_ld + c]   -- the backward of pack on dP.
- * Descriptors are host memory, `ptr` are device pointers; at most UPNERF_MAX_PACK_DESC per call. */
+ * Descriptors are host memory, `ptr` are device pointers; at most UPNERF_MAX_PACK_DESC per call.
+ * The destinations of one call must be disjoint (pack: the P elements of all descriptors, unpack: the parameters): one thread
+ * moves one element, so two descriptors that write -- or accumulate into -- the same element in one call race.
+ * The elements of one call (sum of rows * cols) are indexed in int: more than 2^31 - 2048 of them are refused (UPNERF_EINVAL). */
 #define UPNERF_MAX_PACK_DESC 48
 typedef struct {
   const float* ptr;              /* device pointer of the parameter (pack: source, unpack: destination) */

@@ -9,6 +9,8 @@
 //   A second tiny kernel sums the slabs in a fixed order -> bitwise reproducible, no float atomics.
 //   MFMA orientation: lane (i, h) feeds A-operand A[m+h][n0+i] and B-operand B[m+h][k0+i]; both are plain
 //   ds_read_b32 of 32 consecutive floats per half-wave (bank-conflict free without padding).
+#include <limits.h>
+
 #include "common.cuh"
 #include "wgrad_host.h"
 
@@ -1077,16 +1079,25 @@ extern "C" int upnerf_linear(int M, int N, int K, const float* A, int lda, const
   return (int)hipGetLastError();
 }
 
+// The descriptor-driven kernels (frag_copy, pack / unpack, add_pairs, frag16) index their elements in int, and a thread's index
+// runs up to the launch's rounded-up extent (256 elements per workgroup, 2048 in frag16_amax_kernel).  The hosts below form
+// rows * cols and its running total in 64 bits and refuse (UPNERF_EINVAL, before any launch) a set whose total, rounded up so,
+// would pass INT_MAX -- in int the sum wrapped and the launch covered the wrong range.
+static const long long MAX_DESC_ELEMS = (long long)INT_MAX - 2047;
+
 extern "C" int upnerf_frag_copy(const float* src, float* dst, const upnerf_frag_desc* descs, int ndesc, void* stream) {
   if (!src || !dst || !descs || ndesc <= 0 || ndesc > UPNERF_MAX_FRAG_DESC) return UPNERF_EINVAL;
   FragDescs D;
   D.n = ndesc;
   D.start[0] = 0;
+  long long total64 = 0;  // (the kernels index in int: a descriptor set past INT_MAX elements is refused, not wrapped)
   for (int j = 0; j < ndesc; ++j) {
     const upnerf_frag_desc& q = descs[j];
     if (q.rows <= 0 || q.cols <= 0 || (q.rows & 31) || (q.dst_kp & 7) || q.dst_k0 + q.cols > q.dst_kp) return UPNERF_EINVAL;
+    total64 += (long long)q.rows * q.cols;
+    if (total64 > MAX_DESC_ELEMS) return UPNERF_EINVAL;
     D.d[j] = q;
-    D.start[j + 1] = D.start[j] + q.rows * q.cols;
+    D.start[j + 1] = (int)total64;
   }
   const int total = D.start[ndesc];
   hipLaunchKernelGGL(frag_copy_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, src, dst, D);
@@ -1098,11 +1109,14 @@ extern "C" int upnerf_pack(float* P, const upnerf_pack_desc* descs, int ndesc, i
   PackDescs D;
   D.n = ndesc;
   D.start[0] = 0;
+  long long total64 = 0;  // (int indices in the kernels: past INT_MAX elements the call is refused, not wrapped)
   for (int j = 0; j < ndesc; ++j) {
     const upnerf_pack_desc& q = descs[j];
     if (!q.ptr || q.rows <= 0 || q.cols <= 0 || q.src_ld < q.cols || q.dst_ld < q.cols || q.dst_off < 0) return UPNERF_EINVAL;
+    total64 += (long long)q.rows * q.cols;
+    if (total64 > MAX_DESC_ELEMS) return UPNERF_EINVAL;
     D.d[j] = q;
-    D.start[j + 1] = D.start[j] + q.rows * q.cols;
+    D.start[j + 1] = (int)total64;
   }
   const int total = D.start[ndesc];
   if (unpack)
@@ -1132,10 +1146,13 @@ extern "C" int upnerf_add_pairs(const upnerf_add_pair* pairs, int npairs, void* 
   AddPairs D;
   D.n = npairs;
   D.start[0] = 0;
+  long long total64 = 0;  // (int indices in the kernel: past INT_MAX elements the call is refused, not wrapped)
   for (int j = 0; j < npairs; ++j) {
     if (!pairs[j].a || !pairs[j].b || !pairs[j].out || pairs[j].n <= 0) return UPNERF_EINVAL;
+    total64 += pairs[j].n;
+    if (total64 > MAX_DESC_ELEMS) return UPNERF_EINVAL;
     D.d[j] = pairs[j];
-    D.start[j + 1] = D.start[j] + pairs[j].n;
+    D.start[j + 1] = (int)total64;
   }
   hipLaunchKernelGGL(add_pairs_kernel, dim3((D.start[npairs] + 255) / 256), dim3(256), 0, (hipStream_t)stream, D);
   return (int)hipGetLastError();
@@ -1145,13 +1162,16 @@ static int frag16_build(const upnerf_frag16_desc* descs, int n, Frag16Descs* D) 
   if (!descs || n <= 0 || n > UPNERF_MAX_FRAG_DESC) return UPNERF_EINVAL;
   D->n = n;
   D->start[0] = 0;
+  long long total64 = 0;  // (int indices in the kernels: past INT_MAX elements the call is refused, not wrapped)
   for (int j = 0; j < n; ++j) {
     const upnerf_frag16_desc& q = descs[j];
     if (q.rows <= 0 || q.cols <= 0 || (q.rows & 31) || (q.dst_kp & 15) || q.dst_k0 + q.cols > q.dst_kp || q.exp_id < 0 ||
         q.exp_id >= 16)
       return UPNERF_EINVAL;
+    total64 += (long long)q.rows * q.cols;
+    if (total64 > MAX_DESC_ELEMS) return UPNERF_EINVAL;
     D->d[j] = q;
-    D->start[j + 1] = D->start[j] + q.rows * q.cols;
+    D->start[j + 1] = (int)total64;
   }
   return 0;
 }

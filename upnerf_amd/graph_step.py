@@ -150,7 +150,8 @@ class GraphedTrainingStep:
             for k, t in static.items():
                 t.copy_(batch[k], non_blocking=True)
             return
-        descs = [PackDesc(batch[k].data_ptr(), 1, words[k], words[k], offs[k], words[k], 0) for k in static]
+        descs = [PackDesc(ptr=batch[k].data_ptr(), rows=1, cols=words[k], src_ld=words[k], dst_off=offs[k], dst_ld=words[k], accumulate=0)
+                 for k in static]
         arr = (PackDesc * len(descs))(*descs)
         check(lib.upnerf_pack(ptr(flat), arr, len(descs), 0, stream()), "upnerf_pack")
 

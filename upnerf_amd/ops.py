@@ -512,24 +512,28 @@ class _Fanout(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gs):
         n = len(gs) // 2
-        outs, pairs = [None] * n, []
+        outs, pairs, keep = [None] * n, [], []
         for j in range(n):
             a, b = gs[j], gs[n + j]
             if a is None or b is None:
                 outs[j] = a if b is None else b
                 continue
             a, b = a.contiguous(), b.contiguous()
-            if not (a.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32 and a.shape == b.shape):
+            if not (a.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32 and a.shape == b.shape
+                    and 0 < a.numel() < 2 ** 31):
                 outs[j] = a + b
                 continue
             out = torch.empty_like(a)
             outs[j] = out
             pairs.append(_lib.AddPair(a=a.data_ptr(), b=b.data_ptr(), out=out.data_ptr(), n=a.numel()))
-            ctx_keep = (a, b)  # noqa: F841  (alive until the launch below is enqueued; the caching allocator is stream-ordered)
+            # every pair's copies stay alive until the last launch below is enqueued: the caching allocator is stream-ordered, and a
+            # block freed before that would be handed to a later pair's .contiguous() copy, which is enqueued ahead of the add
+            keep.append((a, b, out))
         for lo in range(0, len(pairs), _lib.MAX_ADD_PAIRS):
             part = pairs[lo:lo + _lib.MAX_ADD_PAIRS]
             arr = (_lib.AddPair * len(part))(*part)
             check(lib.upnerf_add_pairs(arr, len(part), stream()), "upnerf_add_pairs")
+        del keep
         return tuple(outs)
 
 

@@ -47,30 +47,52 @@ def _gather(flat: torch.Tensor, views, tensors, scatter: bool = False) -> None:
     """views[i] <- tensors[i] (scatter: tensors[i] <- views[i]); `views` tile the start of `flat` in order.  On the GPU through
     upnerf_pack, 48 tensors per launch (three launches of ~8 us for the step's ~130 gradients): torch._foreach_copy_ spends two
     33 us multi-tensor launches on the same 9 MB, and pack + unpack were 0.14 of the 0.36 ms the exchange costs a replayed step
-    on one device (tools/rccl_probe.py).  CPU tensors (gloo tests) and anything that is not contiguous
-    fp32 keep the torch path."""
-    ok = os.environ.get("UPNERF_GATHER", "1") != "0" and flat.is_cuda and all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() < 2 ** 31 for t in tensors)
+    on one device (tools/rccl_probe.py).  A launch also ends where its floats would reach the library's
+    int index range (_pack_chunks).  CPU tensors (gloo tests), anything that is not contiguous fp32, a single tensor at that
+    size or a view that starts at or beyond float 2^31 of `flat` (dst_off is an int32) keep the torch path."""
+    ok = os.environ.get("UPNERF_GATHER", "1") != "0" and flat.is_cuda and all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() < _PACK_MAX_FLOATS for t in tensors)
     if ok:
         try:
             from ._lib import PackDesc, check, lib, ptr, stream
         except Exception:  # noqa: BLE001 -- the exchange does not depend on the extension
             ok = False
+    descs = []
+    if ok:
+        base = flat.data_ptr()
+        for v, t in zip(views, tensors):
+            n = t.numel()
+            if n:
+                off = (v.data_ptr() - base) // 4
+                ok = ok and 0 <= off < 2 ** 31
+                descs.append(PackDesc(ptr=t.data_ptr(), rows=1, cols=n, src_ld=n, dst_off=off if ok else 0, dst_ld=n, accumulate=0))
     if not ok:
         if scatter:
             torch._foreach_copy_(list(tensors), list(views))
         else:
             torch._foreach_copy_(list(views), list(tensors))
         return
-    base = flat.data_ptr()
-    descs = []
-    for v, t in zip(views, tensors):
-        n = t.numel()
-        if n:
-            descs.append(PackDesc(ptr=t.data_ptr(), rows=1, cols=n, src_ld=n, dst_off=(v.data_ptr() - base) // 4, dst_ld=n, accumulate=0))
-    for i in range(0, len(descs), 48):
-        chunk = descs[i:i + 48]
+    for lo, hi in _pack_chunks([d.cols for d in descs]):
+        chunk = descs[lo:hi]
         arr = (PackDesc * len(chunk))(*chunk)
         check(lib.upnerf_pack(ptr(flat), arr, len(chunk), 1 if scatter else 0, stream()), "upnerf_pack")
+
+
+_PACK_MAX_DESC = 48               # UPNERF_MAX_PACK_DESC
+_PACK_MAX_FLOATS = 2 ** 31 - 2048  # upnerf_pack indexes the elements of one call in int and refuses more than this
+
+
+def _pack_chunks(sizes):
+    """[lo, hi) ranges over `sizes` (floats per descriptor, each below _PACK_MAX_FLOATS), one per upnerf_pack launch: a range is
+    closed when it holds 48 descriptors or when the next descriptor would bring its floats to the library's limit."""
+    out, lo, total = [], 0, 0
+    for i, n in enumerate(sizes):
+        if i - lo == _PACK_MAX_DESC or total + n >= _PACK_MAX_FLOATS:
+            out.append((lo, i))
+            lo, total = i, 0
+        total += n
+    if len(sizes) > lo:
+        out.append((lo, len(sizes)))
+    return out
 
 
 class GradSync:
