@@ -1508,6 +1508,124 @@ typedef struct {
 } upnerf_baked_sh_pack_args;
 int upnerf_baked_sh_pack(const upnerf_baked_sh_pack_args* a, void* stream);
 
+/* ---- a sparse baked scene: only the occupied 8 x 8 x 8-cell bricks of the grid are stored (csrc/brick.hip, the marcher in
+ * csrc/baked.hip).  Added under ABI 11: new symbols only.  Every entry point: arguments refused on the host
+ * before anything is launched, nothing allocated, no host read-back, no atomics, all launches on `stream`; the same bits every
+ * run and however the work is cut into launches.
+ *
+ * Geometry and occupancy words are those of the occupancy grid above: cells C = N - 1 per axis, bricks B = ceil(C / 8), linear
+ * brick index (bz * By + by) * Bx + bx.  The layout, stated once:
+ *   slots  [Bz][By][Bx] int32: an occupied brick holds its rank among the occupied bricks in ascending linear brick index, an
+ *          empty brick holds -1;
+ *   bricks [n_bricks] int32: the inverse of slots, the linear brick index of each slot (ascending);
+ *   pool   [n_bricks][9][9][9][E] bytes, E = 16 (degree 0: r, g, b, sigma fp32), 32 (degree 1) or 64 (degree 2): the records
+ *          of the dense scene, unchanged, aligned to E.  (E = 4 is a plain fp32 grid, e.g. sigma alone: gather / scatter / occ.)
+ * Pool point (slot, lz, ly, lx) is grid point (8 bx + lx, 8 by + ly, 8 bz + lz); a pool point beyond the grid (a ragged last
+ * brick) is all zero bytes.  A brick stores its far faces as well -- UPNERF_BRICK_POINTS = 9 points per axis, not 8 -- so the
+ * eight corners of any of its cells are inside it; points on faces that bricks share are stored once per brick with identical
+ * bytes.  A kept point makes every cell that touches it occupied and every brick that contains such a cell occupied: no kept
+ * point is lost, and an empty brick holds only zero records.
+ *
+ * upnerf_brick_table: slots, bricks and count[0] = n_bricks (device) from the brick bits of `words` (block scan, scan of the block
+ *   sums, emit).  `bricks` has room for every brick, Bx By Bz entries; the entries from n_bricks on are not written.  `scratch`:
+ *   upnerf_brick_table_scratch(Cx, Cy, Cz) bytes, 16-byte aligned.
+ * upnerf_brick_gather: pool from a dense grid [Cz+1][Cy+1][Cx+1][E]; one thread per 4-byte (E = 4) or 16-byte word of the pool;
+ *   out-of-grid points become zero.
+ * upnerf_brick_scatter: the inverse, into a dense grid the caller has zeroed.  A grid point is written only by its owner brick,
+ *   the brick of cell min(i, C - 1) per axis: no two threads store to one address.
+ * upnerf_brick_occ: the upnerf_occ_words(Cx, Cy, Cz) words from the pool and its table; one thread per output word.  A cell bit
+ *   is set iff its brick has a slot and any of the cell's eight pool corners has a finite sigma >= the smallest positive fp32
+ *   (upnerf_occ_build at that level, no dilation); a brick bit is set iff any of its cells' bits is.  sigma is the fp32 at byte
+ *   sigma_offset of a record.  n_bricks = 0 (pool and bricks may be NULL then) gives all-zero words. */
+#define UPNERF_BRICK_POINTS 9
+typedef struct {
+  int32_t Cx, Cy, Cz, reserved_;
+  const uint32_t* words;     /* [upnerf_occ_words(Cx, Cy, Cz)] */
+  int32_t* slots;            /* [Bz][By][Bx] */
+  int32_t* bricks;           /* [Bx By Bz] capacity; [count] written */
+  int32_t* count;            /* [1] */
+  void* scratch;             /* [upnerf_brick_table_scratch] bytes, 16-byte aligned */
+} upnerf_brick_table_args;
+long long upnerf_brick_table_scratch(int Cx, int Cy, int Cz);
+int upnerf_brick_table(const upnerf_brick_table_args* a, void* stream);
+
+typedef struct {
+  int32_t Cx, Cy, Cz;
+  int32_t n_bricks;          /* >= 1, <= Bx By Bz */
+  int32_t E;                 /* bytes per point: 4, 16, 32 or 64 */
+  int32_t reserved_;
+  const int32_t* bricks;     /* [n_bricks] */
+  const uint8_t* grid;       /* [Cz+1][Cy+1][Cx+1][E], aligned to min(E, 16) */
+  uint8_t* pool;             /* [n_bricks][9][9][9][E], aligned to E */
+} upnerf_brick_gather_args;
+int upnerf_brick_gather(const upnerf_brick_gather_args* a, void* stream);
+
+typedef struct {
+  int32_t Cx, Cy, Cz;
+  int32_t n_bricks;          /* >= 1, <= Bx By Bz */
+  int32_t E;                 /* bytes per point: 4, 16, 32 or 64 */
+  int32_t reserved_;
+  const int32_t* bricks;     /* [n_bricks] */
+  const uint8_t* pool;       /* [n_bricks][9][9][9][E], aligned to E */
+  uint8_t* grid;             /* [Cz+1][Cy+1][Cx+1][E], aligned to min(E, 16), zeroed by the caller */
+} upnerf_brick_scatter_args;
+int upnerf_brick_scatter(const upnerf_brick_scatter_args* a, void* stream);
+
+typedef struct {
+  int32_t Cx, Cy, Cz;
+  int32_t n_bricks;          /* >= 0, <= Bx By Bz */
+  int32_t E;                 /* bytes per point: 4, 16, 32 or 64 */
+  int32_t sigma_offset;      /* byte of the fp32 sigma in a record: a multiple of 4, <= E - 4 */
+  const int32_t* slots;      /* [Bz][By][Bx] */
+  const uint8_t* pool;       /* [n_bricks][9][9][9][E], aligned to E */
+  uint32_t* words;           /* [upnerf_occ_words(Cx, Cy, Cz)] */
+} upnerf_brick_occ_args;
+int upnerf_brick_occ(const upnerf_brick_occ_args* a, void* stream);
+
+/* upnerf_brick_columns: rays that make the field kernels evaluate pool points, the sibling of upnerf_grid_columns.  Line
+ * l = (slot * 9 + ly) * 9 + lx of the pool; row r of the outputs is line line0 + r.  With (bx, by, bz) the brick of the slot:
+ *   o[r] = (coord_x(min(8 bx + lx, Nx - 1)), coord_y(min(8 by + ly, Ny - 1)), 0), d[r] = (0, 0, 1),
+ *   z[r][s] = coord_z(min(8 bz + min(s, 8), Nz - 1)) for s < S, S >= 32 (the field kernels' minimum),
+ * coordinates by the rule of upnerf_grid_columns (fp64, every operation rounded on its own, rounded to fp32 once): for a pool
+ * point inside the grid o + d z is the grid point the dense bake evaluates, in the same bits.  (A line beyond the grid in x or
+ * y, or a sample beyond it in z, repeats the last grid point: its pool point is zero whatever the field says there.)  A row
+ * depends on its line only: any split into calls gives the same bits. */
+typedef struct {
+  int32_t Nx, Ny, Nz, S;
+  float lo[3], hi[3];
+  int64_t line0;             /* >= 0 */
+  int32_t count;             /* rows R of this call, >= 1; line0 + count <= 81 n_bricks */
+  int32_t n_bricks;
+  const int32_t* bricks;     /* [n_bricks] */
+  float* o;                  /* [count][3] */
+  float* d;                  /* [count][3] */
+  float* z;                  /* [count][S] */
+} upnerf_brick_columns_args;
+int upnerf_brick_columns(const upnerf_brick_columns_args* a, void* stream);
+
+/* upnerf_baked_sparse_render: upnerf_baked_render (degree 0) / upnerf_baked_sh_render (degree 1, 2) through a brick pool: the
+ * same template with another layout -- lattice, skipping proposals, blend, clamp and compositing are one source.  Where the
+ * dense march tests the brick bit of a sample's brick, this one reads slot = slots[brick]: slot < 0 is the empty brick; else the
+ * eight corners of cell (ix, iy, iz) are pool points base, base + 1, + 9, + 81 with
+ * base = slot * 729 + ((iz & 7) * 9 + (iy & 7)) * 9 + (ix & 7).  `words` are read for their cell bits only.  On a pool gathered
+ * from a dense scene, with that scene's words, the result is bit for bit the dense marcher's. */
+typedef struct {
+  int32_t Cx, Cy, Cz, R;
+  float lo[3], hi[3];        /* hi > lo, finite */
+  float step;                /* > 0, finite */
+  float background;          /* finite */
+  float stop;                /* >= 0, < 1; 0 = never */
+  int32_t degree;            /* 0, 1 or 2 */
+  const uint8_t* pool;       /* [n_bricks][9][9][9][16 | 32 | 64], aligned to the record size */
+  const int32_t* slots;      /* [Bz][By][Bx]; every entry < n_bricks */
+  const uint32_t* words;     /* [upnerf_occ_words(Cx, Cy, Cz)] */
+  const float* rays;         /* [R][8], 16-byte aligned */
+  float* rgb;                /* [R][3] */
+  float* depth;              /* [R] */
+  float* opacity;            /* [R] */
+} upnerf_baked_sparse_render_args;
+int upnerf_baked_sparse_render(const upnerf_baked_sparse_render_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

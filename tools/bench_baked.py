@@ -16,7 +16,14 @@ The weights are random: the hit share and the PSNR say nothing about a trained s
 --sh adds the baked scenes with spherical-harmonic colour, degree 1 and degree 2 baked at --dirs directions, as
 two more legs of the same alternating rounds -- so the degree-0 marcher of the same build runs beside them -- and writes
 --sh-out INSTEAD of --out: the rates, each scene's device bytes, the bake times (--dirs passes over the field each), the
-marchers' own times per launch, and the degree-0 rate beside the one recorded in --out's file where that exists."""
+marchers' own times per launch, and the degree-0 rate beside the one recorded in --out's file where that exists.
+
+--sparse measures the sparse layout INSTEAD and writes --sparse-out: (1) the marcher, dense against sparse, on
+the same frames through an analytic shell volume (an ellipsoid's surface, four cells thick; from_grids / from_direction_grids at 12
+directions) at 128^3 and 256^3 points, degree 0 and 2, alternately in one process, medians of --reps: ms per launch, frames/s,
+bytes, the occupied share of the bricks f_b and the hit share; (2) the bake, dense against sparse=True, at degree 2 and --dirs
+directions on bench.py's system at --resolution, with f_b; (3) with --parent-lib PATH (the library built from the parent
+commit), the three DENSE marchers' times per launch on the scenes of --sh, this build and that one alternately."""
 import argparse
 import json
 import os
@@ -58,6 +65,9 @@ def main():
     ap.add_argument("--sh", action="store_true", help="also time the degree-1 and degree-2 spherical-harmonic scenes; writes --sh-out, not --out")
     ap.add_argument("--dirs", type=int, default=48, help="directions of the spherical-harmonic bakes")
     ap.add_argument("--sh-out", default=os.path.join(ROOT, "profiles", "baked_sh_render.json"))
+    ap.add_argument("--sparse", action="store_true", help="measure the sparse layout instead; writes --sparse-out")
+    ap.add_argument("--sparse-out", default=os.path.join(ROOT, "profiles", "baked_sparse_render.json"))
+    ap.add_argument("--parent-lib", default=None, help="with --sparse: the parent commit's libupnerf_hip.so, for the dense marchers' times beside this build's")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_baked.py measures on the GPU; none is visible")
@@ -81,6 +91,8 @@ def main():
     path = CameraPath.from_poses(c2w, (0.1, 5.0), F, appearance=(a.bake_image, a.bake_image), img_wh=(W, H), K=K)  # ONE appearance: the baked one
     rays = F * H * W
     res = tuple(a.resolution)
+    if a.sparse:
+        return sparse_main(a, sysm, path, dev)
     view = (0.0, 0.0, -1.0)  # the cameras of this path look down -z; the synthetic dataset has no poses to average
     grid = density_grid(sysm, BOUNDS, res)
     if a.level is None:  # a quarter of the points kept (a stated rule, not a tuned number: the field is random)
@@ -152,6 +164,114 @@ def main():
         a.out = a.sh_out
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+def shell_grids(n, dev, dirs=None):
+    """(sigma [n, n, n], rgb [n, n, n, 3] or rgb_dirs [K, n, n, n, 3]) of an ellipsoid's surface, four cells thick, in the middle of
+    BOUNDS: density 40, the colour a smooth function of the position (and, with dirs, of the direction)."""
+    t = torch.linspace(-1, 1, n, device=dev)
+    z, y, x = t[:, None, None], t[None, :, None], t[None, None, :]
+    r = (x * x + y * y + z * z).sqrt()
+    sigma = torch.where((r - 0.6).abs() <= 2.0 * 2 / (n - 1), torch.full((), 40.0, device=dev), torch.zeros((), device=dev))
+    base = torch.stack([(0.5 + 0.5 * x).expand(n, n, n), (0.5 + 0.5 * y).expand(n, n, n), (0.5 + 0.5 * z).expand(n, n, n)], -1)
+    if dirs is None:
+        return sigma, base.contiguous()
+    d = torch.as_tensor(dirs, dtype=torch.float32, device=dev)
+    return sigma, torch.stack([(base * (0.75 + 0.25 * (x * dk[0] + y * dk[1] + z * dk[2]))[..., None]).clamp(0, 1) for dk in d])
+
+
+def sparse_main(a, sysm, path, dev):
+    import ctypes as C
+    import statistics as st
+    from upnerf_amd import _lib, baked as bk, novel_view
+    from upnerf_amd.baked import BakedScene, sphere_directions
+    from upnerf_amd.geometry import density_grid
+    from upnerf_amd.novel_view import render_path
+    from upnerf_amd.ops import TIMER
+    F, W, H = a.frames, a.width, a.height
+    rays = F * H * W
+    frame0 = novel_view.path_rays(*novel_view.path_poses(path.key_c2w.to(dev), path.key_near_far.to(dev), path.u.to(dev), path.mode),
+                                  (W, H), path.K, 0, H * W)[0]
+
+    def kernel_ms(scene, name):
+        TIMER.reset()
+        TIMER.enabled, TIMER.only = True, {name}
+        render_path(sysm, path, outputs=("rgb",), baked=scene, baked_step=a.step)
+        v = TIMER.summary()[name]
+        TIMER.enabled, TIMER.only = False, None
+        TIMER.reset()
+        return v["avg_ms"]
+
+    marcher = []
+    for n in (128, 256):
+        for degree in (0, 2):
+            if degree == 0:
+                dense = BakedScene.from_grids(*shell_grids(n, dev), BOUNDS, 1.0)
+            else:
+                dirs = sphere_directions(12)
+                sigma, rgb_dirs = shell_grids(n, dev, dirs)
+                dense = BakedScene.from_direction_grids(sigma, rgb_dirs, dirs, BOUNDS, 1.0, sh_degree=2)
+                del sigma, rgb_dirs
+            sparse = dense.sparsify()
+            legs = {"dense": dense, "sparse": sparse}
+            frames = {k: render_path(sysm, path, outputs=("rgb_float",), baked=sc, baked_step=a.step)["rgb_float"] for k, sc in legs.items()}  # warm-up
+            times, ms = {k: [] for k in legs}, {k: [] for k in legs}
+            for _ in range(a.reps):
+                for k, sc in legs.items():
+                    times[k].append(wall(lambda: render_path(sysm, path, outputs=("rgb",), baked=sc, baked_step=a.step)))
+                for k, sc in legs.items():
+                    ms[k].append(kernel_ms(sc, "baked_sparse_render" if sc.sparse else ("baked_sh_render" if degree else "baked_render")))
+            row = {"resolution": n, "degree": degree, "occupied_bricks": sparse.n_bricks, "f_b": sparse.brick_fraction,
+                   "occupied_cells": sparse.fraction, "same_picture": bool(torch.equal(frames["dense"], frames["sparse"])),
+                   "hit_share": float((dense.render(frame0, a.step)["opacity"] > 0).float().mean())}
+            for k, sc in legs.items():
+                row[k] = {"bytes": sc.nbytes, "ms_per_launch": st.median(ms[k]), "frames_per_s": F / st.median(times[k]), "seconds": sorted(times[k])}
+            row["sparse_over_dense"] = row["sparse"]["frames_per_s"] / row["dense"]["frames_per_s"]
+            row["dense_ms_over_sparse_ms"] = row["dense"]["ms_per_launch"] / row["sparse"]["ms_per_launch"]
+            marcher.append(row)
+            del dense, sparse, legs, frames
+            torch.cuda.empty_cache()
+    # the bake, on bench.py's system (random weights: the density is nearly uniform, so f_b says what this number can show)
+    res = tuple(a.resolution)
+    grid = density_grid(sysm, BOUNDS, res)
+    if a.level is None:
+        a.level = float(torch.quantile(grid.reshape(-1)[::max(1, grid.numel() // 1_000_000)].float(), 0.75))
+    dirs = sphere_directions(a.dirs)
+    made = {}
+    bake = lambda sparse: made.__setitem__(sparse, BakedScene.build(sysm, BOUNDS, res, a.level, img_id=a.bake_image, sh_degree=2, dirs=dirs, sparse=sparse))
+    bake_s = {k: wall(lambda: bake(k)) for k in (False, True)}
+    f_b = made[True].brick_fraction
+    bake_out = {"resolution": list(res), "degree": 2, "dirs": a.dirs, "level": a.level, "dense_seconds": bake_s[False], "sparse_seconds": bake_s[True],
+                "f_b": f_b, "expected_colour_work_ratio": f_b * (729 / 512) * (32 / 9), "dense_bytes": made[False].nbytes, "sparse_bytes": made[True].nbytes,
+                "same_pool": bool(torch.equal(made[True].pool, made[False].sparsify().pool)),
+                "pool_records": made[True].pool[..., 0].numel(), "pool_records_that_differ": int((made[True].pool != made[False].sparsify().pool).any(-1).sum()),
+                "largest_coefficient_difference": float((made[True].pool[..., :54].contiguous().view(torch.float16).float() -
+                                                         made[False].sparsify().pool[..., :54].contiguous().view(torch.float16).float()).abs().max()),
+                "note": "random weights: above f_b = 0.20 this shows the cost side only; a trained scene is unchecked"}
+    parent = None
+    if a.parent_lib:  # the dense marchers of the parent commit's library beside this build's, on the scenes of --sh
+        old = C.CDLL(a.parent_lib)
+        for name, cls in (("upnerf_baked_render", _lib.BakedRenderArgs), ("upnerf_baked_sh_render", _lib.BakedShRenderArgs)):
+            getattr(old, name).argtypes, getattr(old, name).restype = [C.POINTER(cls), C.c_void_p], C.c_int
+        scenes = {0: BakedScene.build(sysm, BOUNDS, res, a.level, img_id=a.bake_image, view_dir=(0.0, 0.0, -1.0)),
+                  1: BakedScene.build(sysm, BOUNDS, res, a.level, img_id=a.bake_image, sh_degree=1, dirs=dirs), 2: made[False]}
+        new, ms = bk.lib, {(d, w): [] for d in scenes for w in ("parent", "this")}
+        for _ in range(a.reps + 1):  # (the first round warms up)
+            for d, sc in scenes.items():
+                for w, library in (("parent", old), ("this", new)):
+                    bk.lib = library
+                    ms[d, w].append(kernel_ms(sc, "baked_sh_render" if d else "baked_render"))
+        bk.lib = new
+        parent = {f"degree{d}": {"parent_ms_per_launch": st.median(ms[d, "parent"][1:]), "this_ms_per_launch": st.median(ms[d, "this"][1:]),
+                                 "parent_over_this": st.median(ms[d, "parent"][1:]) / st.median(ms[d, "this"][1:])} for d in scenes}
+    out = {"metric": "sparse baked scenes: the marcher dense against sparse on an analytic shell, the degree-2 bake dense against sparse, the dense marchers against the parent commit's",
+           "frames": F, "img_wh": [W, H], "chunk": a.chunk, "step": a.step, "reps": a.reps, "bounds": [list(b) for b in BOUNDS],
+           "marcher": marcher, "bake": bake_out, "dense_vs_parent": parent}
+    os.makedirs(os.path.dirname(os.path.abspath(a.sparse_out)), exist_ok=True)
+    with open(a.sparse_out, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
     print(json.dumps(out))

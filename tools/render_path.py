@@ -5,7 +5,7 @@ appearance moving from photograph to photograph (upnerf_amd/novel_view.py; DESIG
                                 [--mode linear|catmull] [--downscale N] [--depth] [--normals] [--loop] [--chunk ROWS]
                                 [--occupancy NX NY NZ --level SIGMA [--dilate K] [--bounds X0 Y0 Z0 X1 Y1 Z1 | --margin M]]
                                 [--baked NX NY NZ --level SIGMA --step DT [--bake-image ID] [--save-baked F | --load-baked F]
-                                 [--baked-sh {1,2} [--baked-dirs K]]]
+                                 [--baked-sh {1,2} [--baked-dirs K]] [--baked-sparse]]
 
 --occupancy skips empty space: the fine field's density is sampled on NX x NY x NZ grid points over the box (--bounds, or the
 box round the refined cameras and their far points grown by --margin), cells with a corner >= --level (grown by --dilate
@@ -20,7 +20,11 @@ and one appearance -- and every frame is marched from that grid with samples --s
 --baked-sh 1 | 2 gives the preview its view dependence back: the colour head is sampled for --baked-dirs directions (default 48,
 a Fibonacci lattice on the whole sphere: that many passes over the field), a spherical-harmonic expansion of that degree is
 fitted per grid point, and each ray evaluates it for its own direction (32 or 64 bytes a point instead of 16).
---save-baked writes the grid to an .npz, --load-baked renders from one (then NX NY NZ, --level and the degree are those of the file).
+--baked-sparse stores only the occupied 8 x 8 x 8-cell bricks of that grid and evaluates the colour only there (the picture is
+bit for bit the dense scene's; the colour passes cost about 5.06 times the occupied share of the bricks of the dense bake's, so
+it pays below a share of 0.20, which is what a fine grid of a real scene has).
+--save-baked writes the grid to an .npz, --load-baked renders from one (then NX NY NZ, --level, the degree and the layout are those
+of the file).
 --depth works, --normals and --occupancy do not.
 
 Writes PNG files only -- DIR/path/step_<frame, 8 digits>/rgb.png (and depth.png with --depth, normal.png with
@@ -61,6 +65,7 @@ def parser():
     ap.add_argument("--bake-image", type=int, default=None, help="training image whose appearance is baked (default: the first of --images)")
     ap.add_argument("--baked-sh", type=int, choices=(1, 2), default=None, help="bake a spherical-harmonic expansion of this degree of the colour over the viewing direction (with --baked)")
     ap.add_argument("--baked-dirs", type=int, default=None, help="directions the colour head is sampled for with --baked-sh (default 48)")
+    ap.add_argument("--baked-sparse", action="store_true", help="store and bake only the occupied bricks of the grid (with --baked)")
     ap.add_argument("--save-baked", default=None, help="write the baked grid to this .npz")
     ap.add_argument("--load-baked", default=None, help="render from the baked grid of this .npz instead of baking")
     return ap
@@ -82,6 +87,8 @@ def check_args(a):
         raise SystemExit("--step, --bake-image and --save-baked belong to --baked")
     if a.baked is None and (a.baked_sh is not None or a.baked_dirs is not None):
         raise SystemExit("--baked-sh and --baked-dirs belong to --baked (a file read with --load-baked carries its own degree)")
+    if a.baked is None and a.baked_sparse:
+        raise SystemExit("--baked-sparse belongs to --baked (a file read with --load-baked carries its own layout)")
     if a.baked_dirs is not None and a.baked_sh is None:
         raise SystemExit("--baked-dirs counts the directions of --baked-sh")
     if a.load_baked is not None and (a.save_baked is not None or a.level is not None or a.bounds is not None):
@@ -126,12 +133,12 @@ def main(argv=None):
         else:
             bounds = (tuple(a.bounds[:3]), tuple(a.bounds[3:])) if a.bounds else geometry.bounds_from_cameras(system, a.margin)
             sh = {} if a.baked_sh is None else {"sh_degree": a.baked_sh, "dirs": sphere_directions(48 if a.baked_dirs is None else a.baked_dirs)}
-            scene = BakedScene.build(system, bounds, a.baked, a.level, img_id=a.images[0] if a.bake_image is None else a.bake_image, **sh)
+            scene = BakedScene.build(system, bounds, a.baked, a.level, img_id=a.images[0] if a.bake_image is None else a.bake_image, sparse=a.baked_sparse, **sh)
             if a.save_baked is not None:
                 scene.save(a.save_baked)
         torch.cuda.synchronize()
         extra = {"baked_resolution": list(scene.resolution), "bounds": [list(scene.bounds[0]), list(scene.bounds[1])], "level": scene.level,
-                 "sh_degree": scene.sh_degree, "step": a.step, "occupied_share": scene.fraction, "baked_bytes": scene.nbytes, "bake_seconds": time.perf_counter() - tb}
+                 "sh_degree": scene.sh_degree, "sparse": scene.sparse, "occupied_bricks": scene.n_bricks, "brick_share": scene.brick_fraction, "step": a.step, "occupied_share": scene.fraction, "baked_bytes": scene.nbytes, "bake_seconds": time.perf_counter() - tb}
     t0 = time.perf_counter()
     render_path(system, path, chunk=a.chunk, outputs=("rgb",) + (("depth",) if a.depth else ()) + (("normal",) if a.normals else ()), sink=writer, occupancy=occ,
                 baked=scene, baked_step=a.step)

@@ -397,6 +397,41 @@ class BakedShPackArgs(C.Structure):
                 ("kept", _fp)]
 
 
+BRICK_POINTS = 9  # UPNERF_BRICK_POINTS: points per axis of a stored brick (its far faces included)
+
+
+class BrickTableArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("reserved_", C.c_int32), ("words", _fp), ("slots", _fp),
+                ("bricks", _fp), ("count", _fp), ("scratch", _fp)]
+
+
+class BrickGatherArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("n_bricks", C.c_int32), ("E", C.c_int32),
+                ("reserved_", C.c_int32), ("bricks", _fp), ("grid", _fp), ("pool", _fp)]
+
+
+class BrickScatterArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("n_bricks", C.c_int32), ("E", C.c_int32),
+                ("reserved_", C.c_int32), ("bricks", _fp), ("pool", _fp), ("grid", _fp)]
+
+
+class BrickOccArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("n_bricks", C.c_int32), ("E", C.c_int32),
+                ("sigma_offset", C.c_int32), ("slots", _fp), ("pool", _fp), ("words", _fp)]
+
+
+class BrickColumnsArgs(C.Structure):
+    _fields_ = [("Nx", C.c_int32), ("Ny", C.c_int32), ("Nz", C.c_int32), ("S", C.c_int32), ("lo", C.c_float * 3),
+                ("hi", C.c_float * 3), ("line0", C.c_int64), ("count", C.c_int32), ("n_bricks", C.c_int32), ("bricks", _fp),
+                ("o", _fp), ("d", _fp), ("z", _fp)]
+
+
+class BakedSparseRenderArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("R", C.c_int32), ("lo", C.c_float * 3),
+                ("hi", C.c_float * 3), ("step", C.c_float), ("background", C.c_float), ("stop", C.c_float), ("degree", C.c_int32),
+                ("pool", _fp), ("slots", _fp), ("words", _fp), ("rays", _fp), ("rgb", _fp), ("depth", _fp), ("opacity", _fp)]
+
+
 class DensityGradArgs(C.Structure):
     _fields_ = [("M", C.c_int32), ("reserved_", C.c_int32), ("points", _fp), ("P", _fp), ("PT", _fp), ("wk_xyz", C.c_float * 10),
                 ("sigma", _fp), ("grad", _fp)]
@@ -519,9 +554,16 @@ _SIGNATURES = {
     "upnerf_baked_sh_render": [C.POINTER(BakedShRenderArgs), _p],
     "upnerf_sh_accumulate": [C.POINTER(ShAccumulateArgs), _p],
     "upnerf_baked_sh_pack": [C.POINTER(BakedShPackArgs), _p],
+    "upnerf_brick_table_scratch": [_i, _i, _i],
+    "upnerf_brick_table": [C.POINTER(BrickTableArgs), _p],
+    "upnerf_brick_gather": [C.POINTER(BrickGatherArgs), _p],
+    "upnerf_brick_scatter": [C.POINTER(BrickScatterArgs), _p],
+    "upnerf_brick_occ": [C.POINTER(BrickOccArgs), _p],
+    "upnerf_brick_columns": [C.POINTER(BrickColumnsArgs), _p],
+    "upnerf_baked_sparse_render": [C.POINTER(BakedSparseRenderArgs), _p],
 }
 _LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
-             "upnerf_occ_compact_scratch", "upnerf_pca_fit_scratch")
+             "upnerf_occ_compact_scratch", "upnerf_pca_fit_scratch", "upnerf_brick_table_scratch")
 MAX_SCALARS = 96
 EXPORTS = tuple(_SIGNATURES)
 

@@ -19,7 +19,14 @@ With sh_degree = 1 or 2 a grid point holds instead the coefficients of a real sp
 the viewing direction -- the least-squares fit to the colour head at K directions, stored as fp16 beside the fp32 sigma in a
 record of 32 or 64 bytes -- and `upnerf_baked_sh_render` evaluates the expansion for each ray's own direction.
 `scene.rgbs` is None then and `scene.records` holds the grid; everything else (bits, skipping, save / load, render_path) is the
-same.  Still ONE appearance.  How close either kind comes to the field on a TRAINED scene is unchecked."""
+same.  Still ONE appearance.  How close either kind comes to the field on a TRAINED scene is unchecked.
+
+    sparse = scene.sparsify()                                           # or BakedScene.build(..., sparse=True)
+
+A sparse scene of any degree stores only the occupied 8 x 8 x 8-cell bricks of the grid, 9 x 9 x 9 points each, in `scene.pool`,
+found through `scene.slots` (include/upnerf_hip.h states the layout; csrc/brick.hip).  The marcher
+(`upnerf_baked_sparse_render`, the same march with another layout) never visits a sample outside an occupied brick, so the
+picture is bit for bit the dense scene's; `rgbs` and `records` are None then and `grid` is the pool."""
 from __future__ import annotations
 
 import ctypes as C
@@ -33,7 +40,7 @@ from ._lib import check, lib, ptr, stream
 from .ops import TIMER
 from .static_scene import box, c_float3, field_of, refined_training_poses, require_cuda
 
-__all__ = ["BakedScene", "field_colour", "sphere_directions", "sh_basis", "sh_weights", "TINY"]
+__all__ = ["BakedScene", "field_colour", "pool_colour", "sphere_directions", "sh_basis", "sh_weights", "save_bricks", "load_bricks", "TINY"]
 
 TINY = float(np.float32(2.0 ** -149))  # the smallest positive fp32: the level at which the kept sigmas are packed into bits
 
@@ -125,8 +132,123 @@ def field_colour(system, bounds, resolution: Sequence[int], view_dir, img_id=Non
     return out.view(Nz, Ny, Nx, 3)
 
 
+def _view_and_row(system, model, field, view_dir, img_id, rows, dev):
+    """(the normalised viewing direction [3] fp32 on the device, the one appearance row or None) of a colour pass."""
+    v = torch.as_tensor(view_dir, dtype=torch.float64).reshape(3)
+    n = float(v.norm())
+    if not n > 0 or not np.isfinite(n):
+        raise ValueError("view_dir is a direction: three finite numbers, not all zero")
+    return (v / n).to(torch.float32).to(dev), _appearance(system, model, field, img_id, rows, dev)
+
+
+@torch.no_grad()
+def pool_colour(system, bounds, resolution: Sequence[int], bricks: torch.Tensor, view_dir, img_id=None, rows=None,
+                field: str = "fine", chunk: Optional[int] = None) -> torch.Tensor:
+    """[n_bricks, 9, 9, 9, 3] fp32: field_colour at the pool points of the bricks `bricks` alone (upnerf_brick_columns: one ray per
+    line (slot, ly, lx) of a brick, its first nine samples the line's points), `chunk` lines at a time.  o + d z of a point
+    inside the grid is field_colour's, in the same bits, and so is the colour but for the field kernels' last bit: the f16
+    kernels scale every tile of samples by a power of two taken from the tile's own largest magnitude (csrc/common16.cuh), so
+    which samples share a tile can move a sample's colour by one unit in the last place (DESIGN.md 2.33 has the count)."""
+    from .geometry import MIN_SAMPLES
+    model, dev = field_of(system, field, "pool_colour")
+    lo, hi = box(bounds)
+    Nx, Ny, Nz = (int(n) for n in resolution)
+    v, a_row = _view_and_row(system, model, field, view_dir, img_id, rows, dev)
+    nb, S, P = bricks.numel(), MIN_SAMPLES, _lib.BRICK_POINTS
+    lines = nb * P * P
+    chunk = int(chunk) if chunk is not None else max(1, (1 << 20) // S)
+    if chunk < 1:
+        raise ValueError(f"chunk must be positive, got {chunk}")
+    chunk = min(chunk, lines)
+    col = torch.empty(lines, P, 3, device=dev, dtype=torch.float32)  # [line][s = lz]
+    view = v.expand(chunk, 3).contiguous()
+    a_rows = a_row.expand(chunk, -1).contiguous() if a_row is not None else None
+    o, d, z = (torch.empty(chunk, k, device=dev, dtype=torch.float32) for k in (3, 3, S))
+    for l0 in range(0, lines, chunk):
+        n = min(chunk, lines - l0)
+        a = _lib.BrickColumnsArgs(Nx=Nx, Ny=Ny, Nz=Nz, S=S, lo=c_float3(lo), hi=c_float3(hi), line0=l0, count=n, n_bricks=nb,
+                                  bricks=ptr(bricks), o=ptr(o), d=ptr(d), z=ptr(z))
+        check(TIMER.run("brick_columns", lambda: lib.upnerf_brick_columns(C.byref(a), stream()), units=n), "upnerf_brick_columns")
+        _, rgb = _field_rgb(model, o[:n], d[:n], z[:n], view[:n], a_rows[:n] if a_rows is not None else None)
+        col[l0:l0 + n].copy_(rgb[:, :P])
+    return col.view(nb, P * P, P, 3).permute(0, 2, 1, 3).contiguous().view(nb, P, P, P, 3)  # [slot][lz][ly][lx]
+
+
 RECORD_BYTES = {1: 32, 2: 64}  # one grid point of an SH scene (include/upnerf_hip.h)
 SIGMA_BYTE = {1: 24, 2: 56}
+POINT_BYTES = {0: 16, **RECORD_BYTES}  # one point of a scene of each degree: what a brick pool stores 729 of per brick
+SIGMA_AT = {0: 12, **SIGMA_BYTE}
+
+
+def _aligned(nbytes: int, size: int, dev) -> torch.Tensor:
+    """A uint8 device vector of `nbytes` (one at least) whose address is a multiple of `size`."""
+    spare = torch.empty(max(nbytes, size) + size, dtype=torch.uint8, device=dev)
+    off = -spare.data_ptr() % size
+    return spare[off:off + max(nbytes, size)]
+
+
+def _point_bytes(grid: torch.Tensor) -> torch.Tensor:
+    """A contiguous tensor [..., k] of fp32 or uint8 as uint8 [..., E]: the bytes of its points."""
+    return grid if grid.dtype == torch.uint8 else grid.view(torch.uint8)
+
+
+def brick_table(words: torch.Tensor, dims: Sequence[int]):
+    """(slots int32 [Bz, By, Bx], bricks int32 [n_bricks], n_bricks) of the brick bits of an occupancy grid's words
+    (upnerf_brick_table).  One host read: the count."""
+    Cx, Cy, Cz = (int(c) for c in dims)
+    B = tuple((c + 7) // 8 for c in (Cx, Cy, Cz))
+    dev = words.device
+    slots = torch.empty(B[2], B[1], B[0], device=dev, dtype=torch.int32)
+    bricks = torch.empty(slots.numel(), device=dev, dtype=torch.int32)
+    count = torch.empty(1, device=dev, dtype=torch.int32)
+    scratch = _aligned(int(lib.upnerf_brick_table_scratch(Cx, Cy, Cz)), 16, dev)
+    a = _lib.BrickTableArgs(Cx=Cx, Cy=Cy, Cz=Cz, words=ptr(words), slots=ptr(slots), bricks=ptr(bricks), count=ptr(count),
+                            scratch=ptr(scratch))
+    check(TIMER.run("brick_table", lambda: lib.upnerf_brick_table(C.byref(a), stream()), units=slots.numel()), "upnerf_brick_table")
+    n = int(count.cpu())  # the one host read of a build: it sizes the pool
+    return slots, bricks[:n].clone(), n
+
+
+def brick_gather(grid: torch.Tensor, bricks: torch.Tensor, out_dtype=None) -> torch.Tensor:
+    """The pool [n_bricks, 9, 9, 9, k] of a dense grid [Nz, Ny, Nx, k] (fp32 or uint8, 4, 16, 32 or 64 bytes per point) for the
+    bricks `bricks` (upnerf_brick_gather); points beyond the grid are zero.  With no brick nothing is launched."""
+    Nz, Ny, Nx, k = grid.shape
+    g = _point_bytes(grid.contiguous())
+    E, n, P = g.shape[3], bricks.numel(), _lib.BRICK_POINTS
+    if g.data_ptr() % min(E, 16):
+        g = _aligned(g.numel(), 16, g.device)[:g.numel()].view(g.shape).copy_(g)
+    store = _aligned(n * P ** 3 * E, E, grid.device)
+    if n:
+        a = _lib.BrickGatherArgs(Cx=Nx - 1, Cy=Ny - 1, Cz=Nz - 1, n_bricks=n, E=E, bricks=ptr(bricks), grid=ptr(g), pool=ptr(store))
+        check(TIMER.run("brick_gather", lambda: lib.upnerf_brick_gather(C.byref(a), stream()), units=n * P ** 3), "upnerf_brick_gather")
+    pool = store[:n * P ** 3 * E].view(n, P, P, P, E)
+    return pool if grid.dtype == torch.uint8 else pool.view(grid.dtype)
+
+
+def brick_scatter(pool: torch.Tensor, bricks: torch.Tensor, resolution: Sequence[int]) -> torch.Tensor:
+    """The dense grid [Nz, Ny, Nx, k] of a pool [n_bricks, 9, 9, 9, k] (upnerf_brick_scatter): zero outside the bricks."""
+    Nx, Ny, Nz = (int(n) for n in resolution)
+    p = _point_bytes(pool.contiguous())
+    E, n = p.shape[4], bricks.numel()
+    store = _aligned(Nz * Ny * Nx * E, max(E, 16), pool.device).zero_()
+    if n:
+        if p.data_ptr() % E:
+            p = _aligned(p.numel(), E, p.device)[:p.numel()].view(p.shape).copy_(p)
+        a = _lib.BrickScatterArgs(Cx=Nx - 1, Cy=Ny - 1, Cz=Nz - 1, n_bricks=n, E=E, bricks=ptr(bricks), pool=ptr(p), grid=ptr(store))
+        check(TIMER.run("brick_scatter", lambda: lib.upnerf_brick_scatter(C.byref(a), stream()), units=n * 729), "upnerf_brick_scatter")
+    grid = store[:Nz * Ny * Nx * E].view(Nz, Ny, Nx, E)
+    return grid if pool.dtype == torch.uint8 else grid.view(pool.dtype)
+
+
+def brick_words(pool_bytes: torch.Tensor, slots: torch.Tensor, n_bricks: int, resolution: Sequence[int], E: int, sigma_at: int) -> torch.Tensor:
+    """The occupancy words (cell bits, then brick bits) of a pool and its table (upnerf_brick_occ): a cell is occupied iff one of
+    its eight pool corners has a finite sigma >= the smallest positive fp32."""
+    Nx, Ny, Nz = (int(n) for n in resolution)
+    words = torch.empty(int(lib.upnerf_occ_words(Nx - 1, Ny - 1, Nz - 1)), device=slots.device, dtype=torch.int32)
+    a = _lib.BrickOccArgs(Cx=Nx - 1, Cy=Ny - 1, Cz=Nz - 1, n_bricks=n_bricks, E=E, sigma_offset=sigma_at, slots=ptr(slots),
+                          pool=ptr(pool_bytes) if n_bricks else None, words=ptr(words))
+    check(TIMER.run("brick_occ", lambda: lib.upnerf_brick_occ(C.byref(a), stream()), units=words.numel()), "upnerf_brick_occ")
+    return words
 _Y = (0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396)
 
 
@@ -202,6 +324,7 @@ class BakedScene:
 
     sh_degree = 0
     records = None
+    pool = slots = bricks = None  # a sparse scene's (sparsify, from_bricks, build(sparse=True)): see _sparse
 
     def __init__(self, rgbs: torch.Tensor, bounds, level: float):
         from .occupancy import OccupancyGrid
@@ -236,14 +359,90 @@ class BakedScene:
         self.occupancy = OccupancyGrid.from_density(sigma.contiguous(), self.bounds, level=TINY, dilate=0)
         return self
 
+    # ---- sparse scenes: a pool of the occupied bricks (include/upnerf_hip.h states the layout) -------------------
+
+    @classmethod
+    def _sparse(cls, pool: torch.Tensor, slots: torch.Tensor, bricks: torch.Tensor, resolution, bounds, level: float,
+                degree: int) -> "BakedScene":
+        """The sparse scene of a pool [n_bricks, 9, 9, 9, 4] fp32 (degree 0) or [n_bricks, 9, 9, 9, 32 | 64] uint8 aligned to its
+        point size, and its table.  Every sparse scene gets its bits here, from the pool alone (upnerf_brick_occ)."""
+        from .occupancy import OccupancyGrid
+        self = cls.__new__(cls)
+        self.rgbs, self.records, self.sh_degree = None, None, int(degree)
+        self.pool, self.slots, self.bricks = pool, slots, bricks
+        self._resolution = tuple(int(n) for n in resolution)
+        self.bounds = box(bounds, strict=True)
+        self.level = float(level)
+        E = POINT_BYTES[self.sh_degree]
+        # the address the marcher is given: the pool's, or with no brick at all one spare aligned point (never read)
+        self._pool_bytes = _point_bytes(pool).view(-1) if bricks.numel() else _aligned(E, E, slots.device)
+        Nx, Ny, Nz = self._resolution
+        words = brick_words(self._pool_bytes, slots, bricks.numel(), self._resolution, E, SIGMA_AT[self.sh_degree])
+        self.occupancy = OccupancyGrid(words, self.bounds, (Nx - 1, Ny - 1, Nz - 1))
+        return self
+
+    @torch.no_grad()
+    def sparsify(self) -> "BakedScene":
+        """The same scene with only its occupied bricks stored: upnerf_brick_table on the brick bits, upnerf_brick_gather, and the
+        bits again from the pool.  The marcher visits no sample outside an occupied brick, so the picture is bit for bit this
+        scene's."""
+        if self.sparse:
+            return self
+        slots, bricks, n = brick_table(self.occupancy.words, self.occupancy.dims)
+        return self._sparse(brick_gather(self.grid, bricks), slots, bricks, self.resolution, self.bounds, self.level, self.sh_degree)
+
+    @torch.no_grad()
+    def densify(self) -> "BakedScene":
+        """The dense scene of a sparse one (upnerf_brick_scatter into a zeroed grid)."""
+        if not self.sparse:
+            return self
+        grid = brick_scatter(self.pool, self.bricks, self._resolution)
+        if self.sh_degree:
+            return self.from_records(grid, self.bounds, self.level, self.sh_degree)
+        return type(self)(grid, self.bounds, self.level)
+
+    @classmethod
+    def from_bricks(cls, pool: torch.Tensor, bricks: torch.Tensor, resolution: Sequence[int], bounds, level: float,
+                    sh_degree: int = 0) -> "BakedScene":
+        """A sparse scene from volumes of the caller's own: `pool` [n_bricks, 9, 9, 9, 4] fp32 (degree 0) or
+        [n_bricks, 9, 9, 9, 32 | 64] uint8 (degree 1 | 2) on the device, contiguous and aligned to the bytes of one point;
+        `bricks` int32 [n_bricks], the linear brick indices (bz * By + by) * Bx + bx in strictly ascending order; `resolution`
+        the grid POINTS per axis.  Refused with ValueError: another dtype, shape or alignment, bricks unsorted, duplicated or out
+        of range, a degree outside {0, 1, 2}.  One host read: the bricks, to check them."""
+        if sh_degree not in (0, 1, 2):
+            raise ValueError(f"sh_degree is 0, 1 or 2, got {sh_degree!r}")
+        degree, P = int(sh_degree), _lib.BRICK_POINTS
+        E = POINT_BYTES[degree]
+        want = (torch.float32, 4) if degree == 0 else (torch.uint8, E)
+        if not torch.is_tensor(pool) or pool.dtype != want[0] or pool.dim() != 5 or tuple(pool.shape[1:]) != (P, P, P, want[1]) or \
+                not pool.is_contiguous():
+            raise ValueError(f"the pool of degree {degree} is a contiguous {want[0]} tensor [n_bricks, {P}, {P}, {P}, {want[1]}]")
+        if pool.numel() and pool.data_ptr() % E:
+            raise ValueError(f"the pool is aligned to the {E} bytes of one point")
+        res = tuple(int(n) for n in resolution)
+        if len(res) != 3 or min(res) < 2:
+            raise ValueError(f"resolution is the number of grid points per axis (two at least), got {tuple(resolution)}")
+        B = tuple((n - 1 + 7) // 8 for n in res)
+        if not torch.is_tensor(bricks) or bricks.dtype != torch.int32 or bricks.dim() != 1 or bricks.numel() != pool.shape[0]:
+            raise ValueError("bricks is an int32 tensor [n_bricks], one linear brick index per brick of the pool")
+        b = bricks.detach().cpu().numpy().astype(np.int64)
+        if b.size and (b.min() < 0 or b.max() >= B[0] * B[1] * B[2] or not (np.diff(b) > 0).all()):
+            raise ValueError(f"bricks are strictly ascending linear indices in [0, {B[0] * B[1] * B[2]})")
+        require_cuda("BakedScene.from_bricks", pool, bricks)
+        bricks = bricks.detach().contiguous()
+        slots = torch.full((B[2], B[1], B[0]), -1, device=pool.device, dtype=torch.int32)
+        slots.view(-1)[bricks.long()] = torch.arange(bricks.numel(), device=pool.device, dtype=torch.int32)
+        return cls._sparse(pool.detach(), slots, bricks, res, bounds, level, degree)
+
     # ---- construction ------------------------------------------------------------------------------------------------------
 
     @classmethod
     @torch.no_grad()
-    def from_grids(cls, sigma: torch.Tensor, rgb: Optional[torch.Tensor], bounds, level: float = 0.0) -> "BakedScene":
+    def from_grids(cls, sigma: torch.Tensor, rgb: Optional[torch.Tensor], bounds, level: float = 0.0, sparse: bool = False) -> "BakedScene":
         """From a density grid [Nz, Ny, Nx] and a colour grid [Nz, Ny, Nx, 3] (None: black) of the caller's own, fp32 on the
         device.  A point is kept iff its sigma is finite, positive and >= level; every other point becomes (0, 0, 0, 0)
-        (upnerf_baked_pack)."""
+        (upnerf_baked_pack).  sparse: the dense scene's sparsify() -- the caller's grids are dense already, so the dense records
+        exist for the length of this call."""
         require_cuda("BakedScene.from_grids", sigma, *([rgb] if rgb is not None else []))
         if sigma.dtype != torch.float32 or sigma.dim() != 3 or min(sigma.shape) < 2:
             raise ValueError("sigma is a fp32 tensor [Nz, Ny, Nx] with two points per axis at least")
@@ -257,14 +456,20 @@ class BakedScene:
         rgbs = torch.empty(tuple(sigma.shape) + (4,), device=sigma.device, dtype=torch.float32)
         a = _lib.BakedPackArgs(n=sigma.numel(), level=level, sigma=ptr(sigma), rgb=ptr(rgb), rgbs=ptr(rgbs), kept=None)
         check(TIMER.run("baked_pack", lambda: lib.upnerf_baked_pack(C.byref(a), stream()), units=sigma.numel()), "upnerf_baked_pack")
-        return cls(rgbs, bounds, level)
+        return cls(rgbs, bounds, level).sparsify() if sparse else cls(rgbs, bounds, level)
 
     @classmethod
     @torch.no_grad()
     def _project(cls, sigma: torch.Tensor, colour_of, dirs, bounds, level: float, sh_degree: int) -> "BakedScene":
-        """The SH scene of sigma [Nz, Ny, Nx] and colour_of(k) -> [Nz, Ny, Nx, 3], the colour grid for direction k of `dirs`:
-        upnerf_sh_accumulate for k = 0 .. K-1 in order (one direction's colours and the accumulator resident at a time), then
-        upnerf_baked_sh_pack."""
+        """The SH scene of sigma [Nz, Ny, Nx] and colour_of(k) -> [Nz, Ny, Nx, 3], the colour grid for direction k of `dirs`."""
+        return cls.from_records(cls._project_records(sigma, colour_of, dirs, level, sh_degree), bounds, level, _degree(sh_degree))
+
+    @staticmethod
+    @torch.no_grad()
+    def _project_records(sigma: torch.Tensor, colour_of, dirs, level: float, sh_degree: int) -> torch.Tensor:
+        """The records [shape of sigma, 32 | 64] uint8 of sigma (any shape: a grid [Nz, Ny, Nx] or a pool [n, 9, 9, 9]) and
+        colour_of(k) -> [shape of sigma, 3]: upnerf_sh_accumulate for k = 0 .. K-1 in order (one direction's colours and the
+        accumulator resident at a time), then upnerf_baked_sh_pack."""
         degree = _degree(sh_degree)
         W = sh_weights(dirs, degree)
         nb, K = W.shape
@@ -277,7 +482,7 @@ class BakedScene:
         for k in range(K):
             rgb = colour_of(k)
             if rgb.dtype != torch.float32 or tuple(rgb.shape) != tuple(sigma.shape) + (3,) or rgb.device != dev:
-                raise ValueError("the colours of a direction are a fp32 tensor [Nz, Ny, Nx, 3] on sigma's device")
+                raise ValueError("the colours of a direction are a fp32 tensor [shape of sigma, 3] on sigma's device")
             rgb = rgb.detach().contiguous()
             a = _lib.ShAccumulateArgs(n=n, nb=nb, first=int(k == 0), w=(C.c_float * 9)(*W[:, k].tolist()), rgb=ptr(rgb), acc=ptr(acc))
             check(TIMER.run("sh_accumulate", lambda: lib.upnerf_sh_accumulate(C.byref(a), stream()), units=n), "upnerf_sh_accumulate")
@@ -287,28 +492,30 @@ class BakedScene:
         records = spare[off:off + n * size].view(tuple(sigma.shape) + (size,))
         a = _lib.BakedShPackArgs(n=n, level=level, degree=degree, sigma=ptr(sigma), acc=ptr(acc), records=ptr(records), kept=None)
         check(TIMER.run("baked_sh_pack", lambda: lib.upnerf_baked_sh_pack(C.byref(a), stream()), units=n), "upnerf_baked_sh_pack")
-        return cls.from_records(records, bounds, level, degree)
+        return records
 
     @classmethod
     @torch.no_grad()
     def from_direction_grids(cls, sigma: torch.Tensor, rgb_dirs: torch.Tensor, dirs, bounds, level: float = 0.0,
-                             sh_degree: int = 1) -> "BakedScene":
+                             sh_degree: int = 1, sparse: bool = False) -> "BakedScene":
         """The SH sibling of from_grids: a density grid [Nz, Ny, Nx] and the colour grids rgb_dirs [K, Nz, Ny, Nx, 3] of the
         caller's own for the K directions `dirs` [K, 3], fp32 on the device.  Each coefficient is the least-squares fit
         sum_k W[j][k] rgb_k (sh_weights), summed in fp32 in the order of k.  A point is kept iff its sigma is finite, positive
-        and >= level and its coefficients are finite; every other point becomes a zero record (upnerf_baked_sh_pack)."""
+        and >= level and its coefficients are finite; every other point becomes a zero record (upnerf_baked_sh_pack).  sparse:
+        the dense scene's sparsify(), as in from_grids."""
         require_cuda("BakedScene.from_direction_grids", sigma, rgb_dirs)
         if sigma.dtype != torch.float32 or sigma.dim() != 3 or min(sigma.shape) < 2:
             raise ValueError("sigma is a fp32 tensor [Nz, Ny, Nx] with two points per axis at least")
         K = np.asarray(dirs).shape[0] if np.asarray(dirs).ndim == 2 else -1
         if rgb_dirs.dtype != torch.float32 or tuple(rgb_dirs.shape) != (K,) + tuple(sigma.shape) + (3,):
             raise ValueError("rgb_dirs is a fp32 tensor [K, Nz, Ny, Nx, 3], one colour grid per row of dirs [K, 3]")
-        return cls._project(sigma, lambda k: rgb_dirs[k], dirs, bounds, level, sh_degree)
+        scene = cls._project(sigma, lambda k: rgb_dirs[k], dirs, bounds, level, sh_degree)
+        return scene.sparsify() if sparse else scene
 
     @classmethod
     @torch.no_grad()
     def build(cls, system, bounds, resolution: Sequence[int], level: float, img_id=None, rows=None, view_dir=None,
-              field: str = "fine", chunk: Optional[int] = None, sh_degree: int = 0, dirs=None) -> "BakedScene":
+              field: str = "fine", chunk: Optional[int] = None, sh_degree: int = 0, dirs=None, sparse: bool = False) -> "BakedScene":
         """Bake the static scene of `system`: sigma = geometry.density_grid, colour = field_colour with the appearance row of
         training image `img_id` (or `rows`, a row of the caller's own) for the viewing direction `view_dir` (default: the
         normalised mean optical axis of the refined training cameras).  `level` has no default: the useful threshold depends on
@@ -316,7 +523,17 @@ class BakedScene:
 
         sh_degree = 1 | 2: colour is instead the degree's spherical-harmonic fit to field_colour at the directions `dirs` [K, 3]
         (default sphere_directions(48): the whole sphere -- see there), K passes over the field; view_dir has no meaning then and
-        is refused, as dirs is at degree 0."""
+        is refused, as dirs is at degree 0.
+
+        sparse = True: a sparse scene, with the bricks, the sigmas and the bits of build(...).sparsify() -- and its colours, to
+        the last bit of the field kernels' output (pool_colour says why not always bit for bit) -- but the colour passes, the
+        accumulator and the records only where the scene is occupied.  sigma is still evaluated on the whole grid (one pass, 4
+        bytes a point: the field has to be asked everywhere to know where it is empty); its occupied bricks are found
+        (upnerf_brick_table) and it is gathered to the pool; the colour is then evaluated on the pool's lines alone
+        (pool_colour), once or once per direction, and packed as above.  The cost: a line is one ray of the field kernels'
+        minimum of 32 samples for 9 stored points, and a brick stores 729 points for its 512 cells, so with f_b the share of
+        occupied bricks the colour work is f_b * (729 / 512) * (32 / 9) ~ 5.06 f_b of the dense bake's: a sparse bake is the
+        cheaper one only below f_b ~ 0.20 (`brick_fraction` reports f_b).  `chunk` counts lines in the colour passes then."""
         from .geometry import density_grid
         if min(int(n) for n in resolution) < 2:
             raise ValueError(f"resolution is the number of grid points per axis (two at least), got {tuple(resolution)}")
@@ -327,6 +544,8 @@ class BakedScene:
             dirs = sphere_directions() if dirs is None else np.asarray(torch.as_tensor(dirs).detach().cpu().numpy(), np.float64)
             sh_weights(dirs, sh_degree)  # (refused before any pass over the field)
             sigma = density_grid(system, bounds, resolution, field=field, chunk=chunk)
+            if sparse:
+                return cls._build_sparse(system, sigma, bounds, resolution, level, img_id, rows, None, field, chunk, sh_degree, dirs)
             colour = lambda k: field_colour(system, bounds, resolution, dirs[k], img_id=img_id, rows=rows, field=field, chunk=chunk)
             return cls._project(sigma, colour, dirs, bounds, level, sh_degree)
         if dirs is not None:
@@ -334,14 +553,44 @@ class BakedScene:
         if view_dir is None:
             view_dir = mean_optical_axis(system)
         sigma = density_grid(system, bounds, resolution, field=field, chunk=chunk)
+        if sparse:
+            return cls._build_sparse(system, sigma, bounds, resolution, level, img_id, rows, view_dir, field, chunk, 0, None)
         rgb = field_colour(system, bounds, resolution, view_dir, img_id=img_id, rows=rows, field=field, chunk=chunk)
         return cls.from_grids(sigma, rgb, bounds, level)
+
+    @classmethod
+    @torch.no_grad()
+    def _build_sparse(cls, system, sigma, bounds, resolution, level, img_id, rows, view_dir, field, chunk, degree, dirs) -> "BakedScene":
+        """build(sparse=True) from the dense sigma on: table, sigma to the pool, colour on the pool's lines, packing."""
+        from .occupancy import OccupancyGrid
+        level = float(level)
+        if level != level:
+            raise ValueError("level is not a number")
+        res = tuple(int(n) for n in resolution)
+        # the cells that touch a kept point: a corner finite and >= max(level, TINY) is a corner that is finite, > 0 and >= level
+        occ = OccupancyGrid.from_density(sigma, bounds, level=max(level, TINY), dilate=0)
+        slots, bricks, n = brick_table(occ.words, occ.dims)
+        pool_sigma = brick_gather(sigma.unsqueeze(-1), bricks).squeeze(-1)  # [n, 9, 9, 9]; zero beyond the grid: dropped below
+        del sigma, occ
+        P, dev = _lib.BRICK_POINTS, pool_sigma.device
+        E = POINT_BYTES[degree]
+        if n == 0:
+            pool = torch.empty((0, P, P, P, 4) if degree == 0 else (0, P, P, P, E), device=dev, dtype=torch.float32 if degree == 0 else torch.uint8)
+        elif degree == 0:
+            rgb = pool_colour(system, bounds, res, bricks, view_dir, img_id=img_id, rows=rows, field=field, chunk=chunk)
+            pool = _aligned(n * P ** 3 * E, E, dev)[:n * P ** 3 * E].view(n, P, P, P, E).view(torch.float32)
+            a = _lib.BakedPackArgs(n=pool_sigma.numel(), level=level, sigma=ptr(pool_sigma), rgb=ptr(rgb), rgbs=ptr(pool), kept=None)
+            check(TIMER.run("baked_pack", lambda: lib.upnerf_baked_pack(C.byref(a), stream()), units=pool_sigma.numel()), "upnerf_baked_pack")
+        else:
+            colour = lambda k: pool_colour(system, bounds, res, bricks, dirs[k], img_id=img_id, rows=rows, field=field, chunk=chunk)
+            pool = cls._project_records(pool_sigma, colour, dirs, level, degree)
+        return cls._sparse(pool, slots, bricks, res, bounds, level, degree)
 
     # ---- rendering ---------------------------------------------------------------------------------------------------------
 
     def render(self, rays: torch.Tensor, step: float, background: float = 0.0, stop: float = 0.0, out: Optional[dict] = None) -> dict:
         """{"rgb" [R, 3], "depth" [R], "opacity" [R]} of [R, 8] device rays (upnerf_baked_render; upnerf_baked_sh_render for an
-        SH scene, each sample's colour then being the expansion at the ray's own direction, clamped to [0, 1]): samples every
+        SH scene; upnerf_baked_sparse_render for a sparse scene of any degree, the same march and the same bits; each sample's colour then being the expansion at the ray's own direction, clamped to [0, 1]): samples every
         `step` of t from near + step / 2, alpha-composited front to back; what the ray does not hit shows `background` at depth
         `far`.  stop > 0 ends a ray once its transmittance falls below it.  out: preallocated buffers of at least R rows."""
         require_cuda("BakedScene.render", rays)
@@ -361,7 +610,11 @@ class BakedScene:
         common = dict(Cx=Cx, Cy=Cy, Cz=Cz, R=R, lo=c_float3(lo), hi=c_float3(hi), step=step, background=background, stop=stop,
                       words=ptr(self.occupancy.words), rays=ptr(rays), rgb=ptr(out["rgb"]), depth=ptr(out["depth"]),
                       opacity=ptr(out["opacity"]))
-        if self.sh_degree:
+        if self.sparse:
+            a = _lib.BakedSparseRenderArgs(degree=self.sh_degree, pool=ptr(self._pool_bytes), slots=ptr(self.slots), **common)
+            check(TIMER.run("baked_sparse_render", lambda: lib.upnerf_baked_sparse_render(C.byref(a), stream()), units=R),
+                  "upnerf_baked_sparse_render")
+        elif self.sh_degree:
             a = _lib.BakedShRenderArgs(degree=self.sh_degree, records=ptr(self.records), **common)
             check(TIMER.run("baked_sh_render", lambda: lib.upnerf_baked_sh_render(C.byref(a), stream()), units=R), "upnerf_baked_sh_render")
         else:
@@ -373,14 +626,26 @@ class BakedScene:
 
     def save(self, path: str) -> None:
         """An .npz holding the grid (`rgbs`, or `records` and `degree` of an SH scene), the bounds and the level; the bits are
-        rebuilt on load."""
-        if self.sh_degree:
+        rebuilt on load.  A sparse scene: pool, bricks, resolution, degree, bounds, level (save_bricks)."""
+        if self.sparse:
+            save_bricks(path, self.pool.detach().cpu().numpy(), self.bricks.cpu().numpy(), self._resolution, self.bounds, self.level,
+                        sh_degree=self.sh_degree)
+        elif self.sh_degree:
             save_arrays(path, self.records.detach().cpu().numpy(), self.bounds, self.level, sh_degree=self.sh_degree)
         else:
             save_arrays(path, self.rgbs.detach().cpu().numpy(), self.bounds, self.level)
 
     @classmethod
     def load(cls, path: str, device="cuda") -> "BakedScene":
+        with np.load(path) as f:
+            keys = set(f.files)
+        if keys == BRICK_KEYS:
+            pool, bricks, resolution, bounds, level, degree = load_bricks(path)
+            E = POINT_BYTES[degree]
+            store = _aligned(pool.nbytes, E, torch.device(device))[:pool.nbytes].view(pool.shape[:4] + (E,))
+            store.copy_(torch.from_numpy(pool.view(np.uint8).reshape(pool.shape[:4] + (E,))))
+            return cls.from_bricks(store if degree else store.view(torch.float32), torch.from_numpy(bricks).to(device), resolution,
+                                   bounds, level, degree)
         grid, bounds, level, *degree = load_arrays(path)
         if degree:
             return cls.from_records(torch.from_numpy(grid).to(device).contiguous(), bounds, level, degree[0])
@@ -390,21 +655,43 @@ class BakedScene:
 
     @property
     def grid(self) -> torch.Tensor:
-        """The tensor the marcher reads: `records` of an SH scene, else `rgbs`."""
+        """The tensor the marcher reads: `pool` of a sparse scene, `records` of an SH scene, else `rgbs`."""
+        if self.sparse:
+            return self.pool
         return self.records if self.sh_degree else self.rgbs
 
     @property
+    def sparse(self) -> bool:
+        """Whether only the occupied bricks are stored (`pool`, `slots`, `bricks`)."""
+        return self.pool is not None
+
+    @property
+    def n_bricks(self) -> int:
+        """Occupied bricks: the bricks of a sparse scene's pool; of a dense scene, the set brick bits (a device reduction)."""
+        return int(self.bricks.numel()) if self.sparse else int(self.occupancy.bricks().sum())
+
+    @property
+    def brick_fraction(self) -> float:
+        """f_b: the occupied share of the bricks."""
+        Bx, By, Bz = self.occupancy.brick_dims
+        return self.n_bricks / (Bx * By * Bz)
+
+    @property
     def device(self):
-        return self.grid.device
+        return self.occupancy.words.device
 
     @property
     def resolution(self):
+        if self.sparse:
+            return self._resolution
         Nz, Ny, Nx, _ = self.grid.shape
         return Nx, Ny, Nz
 
     @property
     def nbytes(self) -> int:
-        """Device bytes of the grid and its bits."""
+        """Device bytes of the grid and its bits; of a sparse scene, of the pool, its table (slots and bricks) and the bits."""
+        if self.sparse:
+            return self.pool.numel() * self.pool.element_size() + (self.slots.numel() + self.bricks.numel() + self.occupancy.words.numel()) * 4
         return self.grid.numel() * self.grid.element_size() + self.occupancy.words.numel() * 4
 
     @property
@@ -430,6 +717,54 @@ def save_arrays(path: str, rgbs: np.ndarray, bounds, level: float, sh_degree: in
     lo, hi = box(bounds, strict=True)
     with open(path, "wb") as fh:  # (a file object: numpy appends no .npz of its own to the name)
         np.savez(fh, rgbs=rgbs, bounds=np.asarray([lo, hi], np.float64), level=np.float64(level))
+
+
+BRICK_KEYS = {"pool", "bricks", "resolution", "degree", "bounds", "level"}
+
+
+def _brick_arrays(what: str, pool, bricks, resolution, degree):
+    """The arrays of a sparse scene, checked against each other; ValueError names `what`."""
+    pool, bricks, resolution, degree = np.asarray(pool), np.asarray(bricks), np.asarray(resolution), np.asarray(degree)
+    bad = ValueError(f"{what}: not a sparse baked scene (pool {pool.dtype} {pool.shape}, bricks {bricks.dtype} {bricks.shape}, "
+                     f"resolution {resolution.tolist() if resolution.size < 8 else resolution.shape}, degree {degree.tolist() if degree.size < 8 else degree.shape})")
+    if degree.shape != () or degree.dtype.kind not in "iu" or int(degree) not in POINT_BYTES:
+        raise bad
+    if resolution.shape != (3,) or resolution.dtype.kind not in "iu" or resolution.min() < 2:
+        raise bad
+    d, P = int(degree), _lib.BRICK_POINTS
+    want = (np.float32, 4) if d == 0 else (np.uint8, POINT_BYTES[d])
+    if pool.dtype != want[0] or pool.ndim != 5 or pool.shape[1:] != (P, P, P, want[1]):
+        raise bad
+    B = [(int(n) - 1 + 7) // 8 for n in resolution]
+    if bricks.dtype != np.int32 or bricks.shape != (pool.shape[0],):
+        raise bad
+    if bricks.size and (bricks.min() < 0 or bricks.max() >= B[0] * B[1] * B[2] or not (np.diff(bricks.astype(np.int64)) > 0).all()):
+        raise bad
+    return np.ascontiguousarray(pool), np.ascontiguousarray(bricks), tuple(int(n) for n in resolution), d
+
+
+def save_bricks(path: str, pool: np.ndarray, bricks: np.ndarray, resolution, bounds, level: float, sh_degree: int = 0) -> None:
+    """A sparse scene's file: the arrays pool ([n_bricks, 9, 9, 9, 4] fp32, or [n_bricks, 9, 9, 9, 32 | 64] uint8 at sh_degree
+    1 | 2), bricks (int32 [n_bricks], strictly ascending), resolution (Nx, Ny, Nz), degree, bounds, level.  Anything else raises
+    ValueError."""
+    pool, bricks, resolution, degree = _brick_arrays("save_bricks", pool, bricks, np.asarray(resolution, np.int64), np.int64(sh_degree) if sh_degree in (0, 1, 2) else np.float64(-1))
+    lo, hi = box(bounds, strict=True)
+    with open(path, "wb") as fh:
+        np.savez(fh, pool=pool, bricks=bricks, resolution=np.asarray(resolution, np.int64), degree=np.int64(degree),
+                 bounds=np.asarray([lo, hi], np.float64), level=np.float64(level))
+
+
+def load_bricks(path: str):
+    """(pool, bricks, resolution, bounds, level, degree) of a file save_bricks wrote; any other key set, and arrays that do not
+    fit each other, raise ValueError."""
+    with np.load(path) as f:
+        if set(f.files) != BRICK_KEYS:
+            raise ValueError(f"{path}: not a sparse baked scene (arrays {sorted(f.files)})")
+        pool, bricks, resolution, degree, bounds, level = (f[k] for k in ("pool", "bricks", "resolution", "degree", "bounds", "level"))
+    if bounds.shape != (2, 3) or level.shape != ():
+        raise ValueError(f"{path}: not a sparse baked scene (bounds {bounds.shape}, level {level.shape})")
+    pool, bricks, resolution, degree = _brick_arrays(path, pool, bricks, resolution, degree)
+    return pool, bricks, resolution, box(bounds.tolist(), strict=True), float(level), degree
 
 
 def load_arrays(path: str):

@@ -19,6 +19,9 @@
 //                        degree 1, 64 at degree 2).  The basis of the ray's direction is formed once per ray and
 //                        kept in registers; a corner is reduced to (r, g, b, sigma) as it is read -- nb fmas per channel -- so the
 //                        blend sees the four floats per corner it sees at degree 0.  Degree 0 is the instantiation that reads rgbs.
+//   upnerf_baked_sparse_render  the same march again through a brick pool (brick.hip): the template's second
+//                        parameter is the layout.  Where the dense march tests a sample's brick bit, the sparse one reads the
+//                        brick's slot (< 0: the empty brick), and the eight corners are base, + 1, + 9, + 81 inside that slot.
 //   upnerf_sh_accumulate, upnerf_baked_sh_pack  the projection's running sum over directions, and the records from it.
 // All stores are ordinary vector stores from plain C++.
 #include "common.cuh"
@@ -79,11 +82,10 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // for the direction of the ray it was made for (include/upnerf_hip.h states the basis and the order of the sum)
 template <int DEG>
 struct BakedCorner {
-  typedef upnerf_baked_sh_render_args Args;
   static constexpr int NB = (DEG + 1) * (DEG + 1), Q = DEG == 1 ? 2 : 4;  // basis functions; 16-byte loads per record
   const u32x4* rec;
   float Y[NB];
-  __host__ __device__ __forceinline__ BakedCorner(const Args& A, const float* d, float len) : rec((const u32x4*)A.records) {
+  __host__ __device__ __forceinline__ BakedCorner(const void* points, const float* d, float len) : rec((const u32x4*)points) {
     const float x = d[0] / len, y = d[1] / len, z = d[2] / len;
     Y[0] = 0.28209479177387814f;
     Y[1] = -0.4886025119029199f * y, Y[2] = 0.4886025119029199f * z, Y[3] = -0.4886025119029199f * x;
@@ -119,16 +121,37 @@ struct BakedCorner {
 
 template <>
 struct BakedCorner<0> {
-  typedef upnerf_baked_render_args Args;
   const f32x4* pts;
-  __host__ __device__ __forceinline__ BakedCorner(const Args& A, const float*, float) : pts((const f32x4*)A.rgbs) {}
+  __host__ __device__ __forceinline__ BakedCorner(const void* points, const float*, float) : pts((const f32x4*)points) {}
   __host__ __device__ __forceinline__ f32x4 operator()(int64_t p) const { return pts[p]; }
 };
 
+// where the points of a scene are: the dense layouts index the whole grid [Cz+1][Cy+1][Cx+1]; the sparse one (brick.hip;
+// include/upnerf_hip.h states it) finds a sample's brick in a slot table and its corners among the 9 x 9 x 9 points of that slot
+template <class Args>
+struct BakedLayout;
+template <>
+struct BakedLayout<upnerf_baked_render_args> {
+  static constexpr bool SPARSE = false;
+  static __host__ __device__ __forceinline__ const void* points(const upnerf_baked_render_args& A) { return A.rgbs; }
+};
+template <>
+struct BakedLayout<upnerf_baked_sh_render_args> {
+  static constexpr bool SPARSE = false;
+  static __host__ __device__ __forceinline__ const void* points(const upnerf_baked_sh_render_args& A) { return A.records; }
+};
+template <>
+struct BakedLayout<upnerf_baked_sparse_render_args> {
+  static constexpr bool SPARSE = true;
+  static __host__ __device__ __forceinline__ const void* points(const upnerf_baked_sparse_render_args& A) { return A.pool; }
+};
+#define BAKED_BRICK_P UPNERF_BRICK_POINTS
+
 // the march of one ray row (host and device: the host build is what a CPU program checks against the fp64 restatement)
-template <int DEG>
-__host__ __device__ __forceinline__ BakedOut baked_march(const typename BakedCorner<DEG>::Args& A, const BakedGrid& G,
-                                                         const OccDims& dm, const float* row, bool use_bits) {
+template <int DEG, class Args>
+__host__ __device__ __forceinline__ BakedOut baked_march(const Args& A, const BakedGrid& G, const OccDims& dm, const float* row,
+                                                         bool use_bits) {
+  constexpr bool SPARSE = BakedLayout<Args>::SPARSE;
   const float o[3] = {row[0], row[1], row[2]}, d[3] = {row[3], row[4], row[5]};
   const float near = row[6], far = row[7];
   BakedOut out;
@@ -145,7 +168,7 @@ __host__ __device__ __forceinline__ BakedOut baked_march(const typename BakedCor
     const float delta = A.step * len;
     const uint32_t* fine = A.words;
     const uint32_t* brick = A.words + dm.fine_words;
-    const BakedCorner<DEG> pts(A, d, len);
+    const BakedCorner<DEG> pts(BakedLayout<Args>::points(A), d, len);
     float T = 1.0f;
     int k = 0;
     while (k < K) {
@@ -177,11 +200,20 @@ __host__ __device__ __forceinline__ BakedOut baked_march(const typename BakedCor
         k = next;
         continue;
       }
-      if (use_bits) {
+      int64_t slot = 0;  // (sparse: the sample's brick in the pool; it is read with or without the bits, the points hang on it)
+      if (use_bits || SPARSE) {
         const int bx = s.i[0] / OCC_BRICK, by = s.i[1] / OCC_BRICK, bz = s.i[2] / OCC_BRICK;
+        const int64_t b = ((int64_t)bz * dm.By + by) * dm.Bx + bx;
         int shift = -1;  // the empty region the sample lies in: 3 = its brick, 0 = its cell, -1 = none
-        if (!occ_bit(brick, ((int64_t)bz * dm.By + by) * dm.Bx + bx)) shift = 3;
-        else if (!occ_bit(fine, ((int64_t)s.i[2] * dm.Cy + s.i[1]) * dm.Cx + s.i[0])) shift = 0;
+        bool empty_brick;
+        if constexpr (SPARSE) empty_brick = (slot = A.slots[b]) < 0;
+        else empty_brick = !occ_bit(brick, b);
+        if (empty_brick) shift = 3;
+        else if (use_bits && !occ_bit(fine, ((int64_t)s.i[2] * dm.Cy + s.i[1]) * dm.Cx + s.i[0])) shift = 0;
+        if (shift >= 0 && !use_bits) {  // (sparse, every sample visited: an empty brick holds nothing)
+          k = next;
+          continue;
+        }
         if (shift >= 0) {
           float t_out = INFINITY;
 #pragma unroll
@@ -204,12 +236,15 @@ __host__ __device__ __forceinline__ BakedOut baked_march(const typename BakedCor
         }
       }
       // the sample counts: trilinear blend of the eight corners, x first, then y, then z
-      const int64_t base = ((int64_t)s.i[2] * G.sz + (int64_t)s.i[1] * G.sy) + s.i[0];
+      const int64_t sy = SPARSE ? BAKED_BRICK_P : G.sy, sz = SPARSE ? BAKED_BRICK_P * BAKED_BRICK_P : G.sz;
+      const int64_t base = SPARSE ? slot * (BAKED_BRICK_P * BAKED_BRICK_P * BAKED_BRICK_P) +
+                                        (((s.i[2] % OCC_BRICK) * BAKED_BRICK_P + s.i[1] % OCC_BRICK) * BAKED_BRICK_P + s.i[0] % OCC_BRICK)
+                                  : ((int64_t)s.i[2] * G.sz + (int64_t)s.i[1] * G.sy) + s.i[0];
       const float fx = s.g[0] - (float)s.i[0], fy = s.g[1] - (float)s.i[1], fz = s.g[2] - (float)s.i[2];
       const f32x4 c000 = pts(base), c100 = pts(base + 1);
-      const f32x4 c010 = pts(base + G.sy), c110 = pts(base + G.sy + 1);
-      const f32x4 c001 = pts(base + G.sz), c101 = pts(base + G.sz + 1);
-      const f32x4 c011 = pts(base + G.sz + G.sy), c111 = pts(base + G.sz + G.sy + 1);
+      const f32x4 c010 = pts(base + sy), c110 = pts(base + sy + 1);
+      const f32x4 c001 = pts(base + sz), c101 = pts(base + sz + 1);
+      const f32x4 c011 = pts(base + sz + sy), c111 = pts(base + sz + sy + 1);
       float v[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -241,8 +276,8 @@ __host__ __device__ __forceinline__ BakedOut baked_march(const typename BakedCor
   return out;
 }
 
-template <int DEG>
-__global__ __launch_bounds__(BAKED_THREADS) void baked_render_kernel(typename BakedCorner<DEG>::Args a, BakedGrid G, OccDims dm) {
+template <int DEG, class Args>
+__global__ __launch_bounds__(BAKED_THREADS) void baked_render_kernel(Args a, BakedGrid G, OccDims dm) {
   const int r = blockIdx.x * BAKED_THREADS + threadIdx.x;
   if (r >= a.R) return;
   const f32x4* rp = (const f32x4*)(a.rays + (int64_t)r * 8);  // (rows of 32 bytes in a buffer the host found 16-byte aligned)
@@ -335,7 +370,7 @@ extern "C" int upnerf_baked_render(const upnerf_baked_render_args* a, void* stre
   BakedGrid G;
   OccDims dm;
   if (!baked_grid(a, a ? a->rgbs : nullptr, 16, &G, &dm)) return UPNERF_EINVAL;
-  hipLaunchKernelGGL(baked_render_kernel<0>, dim3((a->R + BAKED_THREADS - 1) / BAKED_THREADS), dim3(BAKED_THREADS), 0,
+  hipLaunchKernelGGL((baked_render_kernel<0, upnerf_baked_render_args>), dim3((a->R + BAKED_THREADS - 1) / BAKED_THREADS), dim3(BAKED_THREADS), 0,
                      (hipStream_t)stream, *a, G, dm);
   return (int)hipGetLastError();
 }
@@ -354,8 +389,21 @@ extern "C" int upnerf_baked_sh_render(const upnerf_baked_sh_render_args* a, void
   if (!a || (a->degree != 1 && a->degree != 2)) return UPNERF_EINVAL;
   if (!baked_grid(a, a->records, a->degree == 1 ? 32 : 64, &G, &dm)) return UPNERF_EINVAL;
   const dim3 grid((a->R + BAKED_THREADS - 1) / BAKED_THREADS), block(BAKED_THREADS);
-  if (a->degree == 1) hipLaunchKernelGGL(baked_render_kernel<1>, grid, block, 0, (hipStream_t)stream, *a, G, dm);
-  else hipLaunchKernelGGL(baked_render_kernel<2>, grid, block, 0, (hipStream_t)stream, *a, G, dm);
+  if (a->degree == 1) hipLaunchKernelGGL((baked_render_kernel<1, upnerf_baked_sh_render_args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
+  else hipLaunchKernelGGL((baked_render_kernel<2, upnerf_baked_sh_render_args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
+  return (int)hipGetLastError();
+}
+
+extern "C" int upnerf_baked_sparse_render(const upnerf_baked_sparse_render_args* a, void* stream) {
+  typedef upnerf_baked_sparse_render_args Args;
+  BakedGrid G;
+  OccDims dm;
+  if (!a || a->degree < 0 || a->degree > 2 || !a->slots) return UPNERF_EINVAL;
+  if (!baked_grid(a, a->pool, (size_t)16 << a->degree, &G, &dm)) return UPNERF_EINVAL;
+  const dim3 grid((a->R + BAKED_THREADS - 1) / BAKED_THREADS), block(BAKED_THREADS);
+  if (a->degree == 0) hipLaunchKernelGGL((baked_render_kernel<0, Args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
+  else if (a->degree == 1) hipLaunchKernelGGL((baked_render_kernel<1, Args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
+  else hipLaunchKernelGGL((baked_render_kernel<2, Args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
   return (int)hipGetLastError();
 }
 
