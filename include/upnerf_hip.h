@@ -1626,6 +1626,68 @@ typedef struct {
 } upnerf_baked_sparse_render_args;
 int upnerf_baked_sparse_render(const upnerf_baked_sparse_render_args* a, void* stream);
 
+/* ---- tuning a baked scene: the marcher's backward pass (csrc/baked.hip).  Added under ABI 11: new symbols only.
+ * upnerf_baked_render_bwd: the gradient of a loss over the outputs of upnerf_baked_render (degree 0, `points` = rgbs) or
+ * upnerf_baked_sh_render (degree 1, 2, `points` = records) with respect to the points of a DENSE scene, ADDED into outputs the
+ * caller has zeroed.  Lattice, skipping, step, background, stop, words, rays, misses and the refusals are the forward's; one
+ * thread per ray, one launch, nothing allocated, no host read-back.  The sums over rays are float atomic adds: their order is the
+ * order of arrival, so this entry point -- alone among the baked ones -- does NOT give the same bits every run.
+ *
+ * The definition.  The visited samples of a ray are exactly those the forward composites, in its order; the sample after which
+ * `stop` ends the ray is the last.  For visited sample k, with v the blended and (degree > 0) clamped channels and e, alpha,
+ * w_k = T_k alpha_k, T_{k+1} = T_k (1 - alpha_k) formed as the forward forms them (all fp32):
+ *   q_k = fmaf(g_rgb[0], v.r - background, fmaf(g_rgb[1], v.g - background, fmaf(g_rgb[2], v.b - background,
+ *         fmaf(g_depth, t_k - far, g_opacity))))            (a NULL g_depth or g_opacity is zero);
+ *   dL/dc_k[c] = w_k g_rgb[c] where the unclamped blend was in [0, 1] (always, at degree 0), else 0;
+ *   dL/dsigma_k = delta fmaf(T_{k+1}, q_k, -(Q - P_k)),  P_k = fmaf(w_k, q_k, P_{k-1}),  Q = P of the last visited sample
+ *   (a first march forms Q, a second the gradients: Q - P_k is the sum over the later samples, sum_{j > k} w_j q_j).
+ * These are the derivatives of rgb = sum w (c - background) + background, depth = sum w (t - far) + far, opacity = sum w.
+ * Corner j of the sample's cell (x = j & 1, y = j >> 1 & 1, z = j >> 2) receives its trilinear weight
+ *   ((z ? fz : 1 - fz) * (y ? fy : 1 - fy)) * (x ? fx : 1 - fx)
+ * times these four numbers; the shares of consecutive samples in one cell are summed first (fmaf, in sample order) and added to
+ * memory once.  Degree 0: grad[p] += (r, g, b, sigma shares).  Degree 1, 2: grad_coef[p][c][j] += Y_j * (the colour share of c),
+ * Y the basis of the ray's direction exactly as upnerf_baked_sh_render forms it, and grad_sigma[p] += the sigma share: the
+ * gradient with respect to the fp32 value of each stored half, in the layout upnerf_baked_sh_pack reads its `acc` in.
+ * A corner whose stored sigma is exactly zero is not a parameter and receives nothing (a cell with a clear bit keeps eight zero
+ * corners).  Nothing is added for a miss, nor for a ray whose g_rgb, g_depth and g_opacity are all zero.
+ * Refused: what the forward refuses (UPNERF_EINVAL), a NULL g_rgb or output, a degree outside {0, 1, 2}; `slots` not NULL, a
+ * brick pool, is UPNERF_EUNSUP: faces that bricks share are stored once per brick, so a gradient would have to be summed over the
+ * copies -- densify the scene, tune it, sparsify it again. */
+typedef struct {
+  int32_t Cx, Cy, Cz, R;
+  float lo[3], hi[3];        /* hi > lo, finite */
+  float step;                /* > 0, finite */
+  float background;          /* finite */
+  float stop;                /* >= 0, < 1; 0 = never */
+  int32_t degree;            /* 0, 1 or 2 */
+  const uint8_t* points;     /* rgbs [..][16] (degree 0) or records [..][32 | 64], aligned to the size of a point */
+  const uint32_t* words;     /* [upnerf_occ_words(Cx, Cy, Cz)] */
+  const float* rays;         /* [R][8], 16-byte aligned */
+  const int32_t* slots;      /* NULL (a sparse scene's slots: UPNERF_EUNSUP) */
+  const float* g_rgb;        /* [R][3] */
+  const float* g_depth;      /* [R] or NULL */
+  const float* g_opacity;    /* [R] or NULL */
+  float* grad;               /* [n][4], n = (Cx+1)(Cy+1)(Cz+1): degree 0 */
+  float* grad_coef;          /* [n][3][nb]: degree 1, 2 */
+  float* grad_sigma;         /* [n]: degree 1, 2 */
+} upnerf_baked_render_bwd_args;
+int upnerf_baked_render_bwd(const upnerf_baked_render_bwd_args* a, void* stream);
+
+/* upnerf_baked_project: after an optimiser step, the points back into the set the marcher is defined on.  One thread per point.
+ * A sigma that is finite and > 0 stays; every other sigma (negative, zero, NaN, an infinity) becomes +0.  Degree 0, `rgbs` [n][4]
+ * in place: where sigma stays, each colour c becomes c > 0 ? (c < 1 ? c : 1) : 0 (the degree-0 forward does not clamp; NaN -> 0);
+ * where it does not, the point becomes (0, 0, 0, 0), as upnerf_baked_pack leaves a dropped point.  Degree 1, 2: `sigma` [n] in
+ * place (upnerf_baked_sh_pack drops the point).  A sigma projected to zero is dead from then on: upnerf_baked_render_bwd gives a
+ * corner whose sigma is zero no gradient. */
+typedef struct {
+  int64_t n;
+  int32_t degree;            /* 0, 1 or 2 */
+  int32_t reserved_;
+  float* rgbs;               /* [n][4], 16-byte aligned: degree 0 */
+  float* sigma;              /* [n]: degree 1, 2 */
+} upnerf_baked_project_args;
+int upnerf_baked_project(const upnerf_baked_project_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

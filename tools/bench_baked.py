@@ -23,7 +23,15 @@ the same frames through an analytic shell volume (an ellipsoid's surface, four c
 directions) at 128^3 and 256^3 points, degree 0 and 2, alternately in one process, medians of --reps: ms per launch, frames/s,
 bytes, the occupied share of the bricks f_b and the hit share; (2) the bake, dense against sparse=True, at degree 2 and --dirs
 directions on bench.py's system at --resolution, with f_b; (3) with --parent-lib PATH (the library built from the parent
-commit), the three DENSE marchers' times per launch on the scenes of --sh, this build and that one alternately."""
+commit), the three DENSE marchers' times per launch on the scenes of --sh, this build and that one alternately.
+
+--tune measures the backward march INSTEAD and writes --tune-out: the scenes of --sh (degree 0, 1, 2 at --resolution),
+the --frames frames as rays in launches of --chunk, random upstream gradients, forward and backward alternately in one process,
+medians of --reps (HIP events round a pass over all rays): ms per backward and per forward launch; the atomic bytes a pass
+flushes -- counted here from the definition: cell changes along each ray's visited samples, times the cell's corners with a
+sigma, times the floats of a point -- over the time, beside the guide's 1.3 and 0.08 TB/s; and on the first chunk the same
+gradient from a restatement in torch's own ops (every sample, gather-based trilinear, autograd), its time and its distance.
+Then a distill() on this system: PSNR of the baked frames against the plain ones before and after.  The weights are random."""
 import argparse
 import json
 import os
@@ -67,6 +75,9 @@ def main():
     ap.add_argument("--sh-out", default=os.path.join(ROOT, "profiles", "baked_sh_render.json"))
     ap.add_argument("--sparse", action="store_true", help="measure the sparse layout instead; writes --sparse-out")
     ap.add_argument("--sparse-out", default=os.path.join(ROOT, "profiles", "baked_sparse_render.json"))
+    ap.add_argument("--tune", action="store_true", help="measure the backward march instead; writes --tune-out")
+    ap.add_argument("--tune-out", default=os.path.join(ROOT, "profiles", "baked_tune.json"))
+    ap.add_argument("--tune-iters", type=int, default=200, help="with --tune: iterations of the distill")
     ap.add_argument("--parent-lib", default=None, help="with --sparse: the parent commit's libupnerf_hip.so, for the dense marchers' times beside this build's")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -93,6 +104,8 @@ def main():
     res = tuple(a.resolution)
     if a.sparse:
         return sparse_main(a, sysm, path, dev)
+    if a.tune:
+        return tune_main(a, sysm, path, dev)
     view = (0.0, 0.0, -1.0)  # the cameras of this path look down -z; the synthetic dataset has no poses to average
     grid = density_grid(sysm, BOUNDS, res)
     if a.level is None:  # a quarter of the points kept (a stated rule, not a tuned number: the field is random)
@@ -181,6 +194,165 @@ def shell_grids(n, dev, dirs=None):
         return sigma, base.contiguous()
     d = torch.as_tensor(dirs, dtype=torch.float32, device=dev)
     return sigma, torch.stack([(base * (0.75 + 0.25 * (x * dk[0] + y * dk[1] + z * dk[2]))[..., None]).clamp(0, 1) for dk in d])
+
+
+def torch_march(scene, params, rays, step, cells):
+    """The definition in torch's own ops on `rays` [R, 8]: every lattice sample, the eight corners gathered, blended x, y, z,
+    (degree > 0: the expansion at the ray's direction, clamped), composited.  Returns (rgb, depth, opacity, flushed floats): the
+    last the atomic adds the backward kernel's register accumulator sends to memory for these rays, counted from the visited
+    samples' cells.  `params`: the fp32 tensors of baked_tune.SceneParams (leaves for autograd)."""
+    from upnerf_amd.baked import sh_basis
+    degree = scene.sh_degree
+    (lo, hi), (Nx, Ny, Nz) = scene.bounds, scene.resolution
+    dev = rays.device
+    lo_t, hi_t = torch.tensor(lo, device=dev), torch.tensor(hi, device=dev)
+    C = torch.tensor([Nx - 1, Ny - 1, Nz - 1], device=dev, dtype=torch.float32)
+    o, d, near, far = rays[:, :3], rays[:, 3:6], rays[:, 6], rays[:, 7]
+    K = int(torch.ceil((far - near) / step).max())
+    k = torch.arange(K, device=dev, dtype=torch.float32)
+    t = near[:, None] + (k[None] + 0.5) * step
+    live_k = k[None] < torch.ceil((far - near) / step)[:, None]
+    g = (o[:, None] + t[..., None] * d[:, None] - lo_t) * (C / (hi_t - lo_t))
+    inside = ((g >= 0) & (g <= C)).all(-1) & live_k
+    gi = torch.where(inside[..., None], g, torch.zeros_like(g))
+    i = torch.minimum(gi.floor(), C - 1)
+    f = gi - i
+    i = i.long()
+    base = (i[..., 2] * Ny + i[..., 1]) * Nx + i[..., 0]
+    if degree == 0:
+        flat = params[0].reshape(-1, 4)
+        corner = lambda off: flat[base + off]
+        sig_flat, per = flat[:, 3], 4
+    else:
+        nb = (degree + 1) ** 2
+        coef, sig_flat = params[0].reshape(-1, 3, nb), params[1].reshape(-1)
+        Y = torch.as_tensor(sh_basis(d.cpu().numpy(), degree), dtype=torch.float32, device=dev)
+        corner = lambda off: torch.cat([torch.einsum("rkcj,rj->rkc", coef[base + off], Y), sig_flat[base + off][..., None]], -1)
+        per = 3 * nb + 1
+    offs = [dx + dy * Nx + dz * Nx * Ny for dz in (0, 1) for dy in (0, 1) for dx in (0, 1)]
+    c = [corner(off) for off in offs]
+    fx, fy, fz = f[..., 0:1], f[..., 1:2], f[..., 2:3]
+    x00, x10, x01, x11 = c[0] + fx * (c[1] - c[0]), c[2] + fx * (c[3] - c[2]), c[4] + fx * (c[5] - c[4]), c[6] + fx * (c[7] - c[6])
+    y0, y1 = x00 + fy * (x10 - x00), x01 + fy * (x11 - x01)
+    v = (y0 + fz * (y1 - y0)) * inside[..., None]
+    col = v[..., :3].clamp(0, 1) if degree else v[..., :3]
+    delta = step * d.norm(dim=1, keepdim=True)
+    alpha = 1 - torch.exp(-delta * v[..., 3])
+    T = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), 1 - alpha[:, :-1]], 1), 1)
+    w = T * alpha
+    opacity = w.sum(1)
+    rgb = (w[..., None] * col).sum(1)
+    depth = (w * t).sum(1) + (1 - opacity) * far
+    with torch.no_grad():  # the flushes: a visited sample (inside, its cell's bit set) whose cell differs from the last visited one's
+        cell = (i[..., 2] * (Ny - 1) + i[..., 1]) * (Nx - 1) + i[..., 0]
+        visited = inside & cells.reshape(-1)[cell]
+        key = torch.where(visited, cell, torch.full_like(cell, -1))
+        last = torch.cummax(torch.where(visited, torch.arange(K, device=dev)[None].expand_as(cell), torch.full_like(cell, -1)), 1)[0]
+        prev = torch.cat([torch.full_like(last[:, :1], -1), last[:, :-1]], 1)
+        prev_cell = torch.where(prev >= 0, torch.gather(key, 1, prev.clamp(min=0)), torch.full_like(cell, -2))
+        flush = visited & (key != prev_cell)
+        n_live = sum((sig_flat[base + off] != 0).long() for off in offs)
+        floats = int((flush * n_live).sum()) * per
+    return rgb, depth, opacity, floats
+
+
+def tune_main(a, sysm, path, dev):
+    import statistics as st
+    from upnerf_amd import baked_tune, novel_view
+    from upnerf_amd.baked import BakedScene, sphere_directions
+    from upnerf_amd.geometry import density_grid
+    from upnerf_amd.novel_view import render_path
+    F, W, H = a.frames, a.width, a.height
+    res = tuple(a.resolution)
+    rays = novel_view.path_rays(*novel_view.path_poses(path.key_c2w.to(dev), path.key_near_far.to(dev), path.u.to(dev), path.mode),
+                                (W, H), path.K, 0, F * H * W)[0]
+    R = rays.shape[0]
+    grid = density_grid(sysm, BOUNDS, res)
+    if a.level is None:
+        a.level = float(torch.quantile(grid.reshape(-1)[::max(1, grid.numel() // 1_000_000)].float(), 0.75))
+    gen = torch.Generator(device="cpu").manual_seed(5)
+    g_rgb, g_depth, g_op = (torch.randn(*shape, generator=gen).to(dev) for shape in ((R, 3), (R,), (R,)))
+    chunks = [(r0, min(a.chunk, R - r0)) for r0 in range(0, R, a.chunk)]
+    out = {"metric": "the baked marcher's backward pass (upnerf_baked_render_bwd) beside its forward, per degree; random weights, random upstream gradients",
+           "resolution": list(res), "level": a.level, "step": a.step, "rays": R, "rays_per_launch": a.chunk, "launches": len(chunks),
+           "guide_atomic_TBps": {"shaped_and_spread": 1.3, "one_lane_per_row_or_one_row": 0.08}, "degrees": {}}
+    scenes = {}
+    for degree in (0, 1, 2):
+        kw = dict(sh_degree=degree, dirs=sphere_directions(a.dirs)) if degree else dict(view_dir=(0.0, 0.0, -1.0))
+        scenes[degree] = BakedScene.build(sysm, BOUNDS, res, a.level, img_id=a.bake_image, **kw)
+
+    def passes(degree):
+        scene = scenes[degree]
+        nb = (degree + 1) ** 2
+        shape = tuple(reversed(scene.resolution))
+        bufs = torch.zeros(shape + (4,), device=dev) if degree == 0 else (torch.zeros(shape + (3, nb), device=dev), torch.zeros(shape, device=dev))
+        fwd = lambda: [scene.render(rays[r0:r0 + n], a.step) for r0, n in chunks]
+        bwd = lambda: [baked_tune.backward(scene.grid, degree, scene.occupancy, scene.bounds, rays[r0:r0 + n], a.step, 0.0, 0.0, g_rgb[r0:r0 + n],
+                                           g_depth[r0:r0 + n], g_op[r0:r0 + n], out=bufs) for r0, n in chunks]
+        return fwd, bwd
+
+    def event_ms(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    fns = {d_: passes(d_) for d_ in scenes}
+    for fwd, bwd in fns.values():  # warm-up
+        fwd(), bwd()
+    ms = {d_: {"fwd": [], "bwd": []} for d_ in scenes}
+    for _ in range(a.reps):
+        for d_, (fwd, bwd) in fns.items():
+            ms[d_]["fwd"].append(event_ms(fwd))
+            ms[d_]["bwd"].append(event_ms(bwd))
+    for degree, scene in scenes.items():
+        cells = scene.occupancy.cells()
+        params = baked_tune.SceneParams.of(scene)
+        floats = 0
+        sub = max(1, 2048 if degree else 16384)  # (rows of the torch restatement at a time: it materialises every sample)
+        with torch.no_grad():
+            for r0 in range(0, R, sub):
+                floats += torch_march(scene, [p.detach() for p in params.tensors], rays[r0:r0 + sub], a.step, cells)[3]
+        # the same gradient from torch's autograd on the first rows
+        n = sub
+        torch_fn = lambda: torch.autograd.grad((lambda o: (o[0] * g_rgb[:n]).sum() + (o[1] * g_depth[:n]).sum() + (o[2] * g_op[:n]).sum())(
+            torch_march(scene, params.tensors, rays[:n], a.step, cells)), params.tensors)
+        torch_fn()
+        t_ms = st.median(event_ms(torch_fn) for _ in range(a.reps))
+        want = torch_fn()
+        ours_fn = lambda: baked_tune.backward(scene.grid, degree, scene.occupancy, scene.bounds, rays[:n], a.step, 0.0, 0.0, g_rgb[:n], g_depth[:n], g_op[:n])
+        ours_fn()
+        k_ms = st.median(event_ms(ours_fn) for _ in range(a.reps))
+        got = ours_fn()
+        got = (got,) if degree == 0 else got
+        live = (params.tensors[-1][..., 3] if degree == 0 else params.tensors[1]) != 0  # (autograd also fills the dead corners: not parameters here)
+        dist = max(float(((g_ - w_) * (live[..., None] if g_.dim() == 4 else live[..., None, None] if g_.dim() == 5 else live)).abs().max() / w_.abs().max())
+                   for g_, w_ in zip(got, want))
+        b_ms, f_ms = st.median(ms[degree]["bwd"]), st.median(ms[degree]["fwd"])
+        out["degrees"][str(degree)] = {
+            "bwd_ms_per_launch": b_ms / len(chunks), "fwd_ms_per_launch": f_ms / len(chunks), "bwd_over_fwd": b_ms / f_ms,
+            "bwd_rays_per_s": R / (b_ms * 1e-3), "atomic_bytes_per_pass": floats * 4, "atomic_TBps": floats * 4 / (b_ms * 1e-3) / 1e12,
+            "torch_autograd": {"rays": n, "torch_ms": t_ms, "kernel_ms": k_ms, "torch_over_kernel": t_ms / k_ms, "max_abs_diff_over_max": dist},
+            "hit_share_frame0": float((scene.render(rays[:H * W], a.step)["opacity"] > 0).float().mean())}
+    # distill on this system: the degree-0 scene against the field's own renders of the path's keyframe cameras
+    plain = render_path(sysm, path, outputs=("rgb_float",))["rgb_float"].clamp(0, 1)
+    psnr = lambda sc: float(-10 * torch.log10(((render_path(sysm, path, outputs=("rgb_float",), baked=sc, baked_step=a.step)["rgb_float"].clamp(0, 1) - plain) ** 2).mean()))
+    out["distill"] = {}
+    for degree in (0, 2):
+        before = psnr(scenes[degree])
+        t0 = time.perf_counter()
+        tuned, curve = baked_tune.distill(sysm, scenes[degree], path, iters=a.tune_iters, batch=a.chunk, baked_step=a.step, seed=0, lr=1e-2, img_id=a.bake_image)
+        torch.cuda.synchronize()
+        out["distill"][str(degree)] = {"iters": a.tune_iters, "batch": a.chunk, "lr": 1e-2, "seconds": time.perf_counter() - t0, "loss_first": curve[0],
+                                       "loss_last": curve[-1], "psnr_db_before": before, "psnr_db_after": psnr(tuned),
+                                       "note": "targets: the keyframe cameras; PSNR: all frames of the path; random weights, no trained scene"}
+    os.makedirs(os.path.dirname(os.path.abspath(a.tune_out)), exist_ok=True)
+    with open(a.tune_out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
 
 
 def sparse_main(a, sysm, path, dev):

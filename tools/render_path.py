@@ -5,7 +5,7 @@ appearance moving from photograph to photograph (upnerf_amd/novel_view.py; DESIG
                                 [--mode linear|catmull] [--downscale N] [--depth] [--normals] [--loop] [--chunk ROWS]
                                 [--occupancy NX NY NZ --level SIGMA [--dilate K] [--bounds X0 Y0 Z0 X1 Y1 Z1 | --margin M]]
                                 [--baked NX NY NZ --level SIGMA --step DT [--bake-image ID] [--save-baked F | --load-baked F]
-                                 [--baked-sh {1,2} [--baked-dirs K]] [--baked-sparse]]
+                                 [--baked-sh {1,2} [--baked-dirs K]] [--baked-sparse] [--baked-tune ITERS [--baked-tune-lr LR]]]
 
 --occupancy skips empty space: the fine field's density is sampled on NX x NY x NZ grid points over the box (--bounds, or the
 box round the refined cameras and their far points grown by --margin), cells with a corner >= --level (grown by --dilate
@@ -23,6 +23,8 @@ fitted per grid point, and each ray evaluates it for its own direction (32 or 64
 --baked-sparse stores only the occupied 8 x 8 x 8-cell bricks of that grid and evaluates the colour only there (the picture is
 bit for bit the dense scene's; the colour passes cost about 5.06 times the occupied share of the bricks of the dense bake's, so
 it pays below a share of 0.20, which is what a fine grid of a real scene has).
+--baked-tune ITERS fits the baked grid, before it is rendered or saved, to the field's own renders of the path's keyframe cameras
+under the baked appearance: ITERS iterations of Adam through the marcher's backward pass (upnerf_amd/baked_tune.py).
 --save-baked writes the grid to an .npz, --load-baked renders from one (then NX NY NZ, --level, the degree and the layout are those
 of the file).
 --depth works, --normals and --occupancy do not.
@@ -66,6 +68,8 @@ def parser():
     ap.add_argument("--baked-sh", type=int, choices=(1, 2), default=None, help="bake a spherical-harmonic expansion of this degree of the colour over the viewing direction (with --baked)")
     ap.add_argument("--baked-dirs", type=int, default=None, help="directions the colour head is sampled for with --baked-sh (default 48)")
     ap.add_argument("--baked-sparse", action="store_true", help="store and bake only the occupied bricks of the grid (with --baked)")
+    ap.add_argument("--baked-tune", type=int, default=None, metavar="ITERS", help="after baking, fit the grid to the field's own renders of the path's keyframe cameras for this many Adam iterations (with --baked)")
+    ap.add_argument("--baked-tune-lr", type=float, default=None, metavar="LR", help="learning rate of --baked-tune (default 0.01)")
     ap.add_argument("--save-baked", default=None, help="write the baked grid to this .npz")
     ap.add_argument("--load-baked", default=None, help="render from the baked grid of this .npz instead of baking")
     return ap
@@ -89,6 +93,12 @@ def check_args(a):
         raise SystemExit("--baked-sh and --baked-dirs belong to --baked (a file read with --load-baked carries its own degree)")
     if a.baked is None and a.baked_sparse:
         raise SystemExit("--baked-sparse belongs to --baked (a file read with --load-baked carries its own layout)")
+    if a.baked is None and (a.baked_tune is not None or a.baked_tune_lr is not None):
+        raise SystemExit("--baked-tune and --baked-tune-lr belong to --baked (the targets are rendered under the appearance the grid is baked with)")
+    if a.baked_tune_lr is not None and a.baked_tune is None:
+        raise SystemExit("--baked-tune-lr is the learning rate of --baked-tune")
+    if a.baked_tune is not None and a.baked_tune < 1:
+        raise SystemExit("--baked-tune counts iterations: one at least")
     if a.baked_dirs is not None and a.baked_sh is None:
         raise SystemExit("--baked-dirs counts the directions of --baked-sh")
     if a.load_baked is not None and (a.save_baked is not None or a.level is not None or a.bounds is not None):
@@ -134,11 +144,20 @@ def main(argv=None):
             bounds = (tuple(a.bounds[:3]), tuple(a.bounds[3:])) if a.bounds else geometry.bounds_from_cameras(system, a.margin)
             sh = {} if a.baked_sh is None else {"sh_degree": a.baked_sh, "dirs": sphere_directions(48 if a.baked_dirs is None else a.baked_dirs)}
             scene = BakedScene.build(system, bounds, a.baked, a.level, img_id=a.images[0] if a.bake_image is None else a.bake_image, sparse=a.baked_sparse, **sh)
+            if a.baked_tune is not None:  # distil on the path's own keyframe cameras; a sparse scene is tuned dense and stored sparse again
+                from upnerf_amd.baked_tune import distill
+                tt = time.perf_counter()
+                tuned, curve = distill(system, scene.densify(), path, iters=a.baked_tune, batch=a.chunk or system.hparams["val.chunk_size"], baked_step=a.step,
+                                       seed=0, lr=0.01 if a.baked_tune_lr is None else a.baked_tune_lr, img_id=a.images[0] if a.bake_image is None else a.bake_image)
+                scene = tuned.sparsify() if a.baked_sparse else tuned
+                tune_extra = {"tune_iters": a.baked_tune, "tune_loss_first": curve[0], "tune_loss_last": curve[-1], "tune_seconds": time.perf_counter() - tt}
             if a.save_baked is not None:
                 scene.save(a.save_baked)
         torch.cuda.synchronize()
         extra = {"baked_resolution": list(scene.resolution), "bounds": [list(scene.bounds[0]), list(scene.bounds[1])], "level": scene.level,
                  "sh_degree": scene.sh_degree, "sparse": scene.sparse, "occupied_bricks": scene.n_bricks, "brick_share": scene.brick_fraction, "step": a.step, "occupied_share": scene.fraction, "baked_bytes": scene.nbytes, "bake_seconds": time.perf_counter() - tb}
+        if a.baked_tune is not None:
+            extra.update(tune_extra)
     t0 = time.perf_counter()
     render_path(system, path, chunk=a.chunk, outputs=("rgb",) + (("depth",) if a.depth else ()) + (("normal",) if a.normals else ()), sink=writer, occupancy=occ,
                 baked=scene, baked_step=a.step)

@@ -622,6 +622,11 @@ class BakedScene:
             check(TIMER.run("baked_render", lambda: lib.upnerf_baked_render(C.byref(a), stream()), units=R), "upnerf_baked_render")
         return {k: out[k][:R] for k in ("rgb", "depth", "opacity")}
 
+    def tune(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8):
+        """A `baked_tune.BakedTuner` on this (dense) scene: Adam on its points against target pixels."""
+        from .baked_tune import BakedTuner
+        return BakedTuner(self, lr, betas=betas, eps=eps)
+
     # ---- files -------------------------------------------------------------------------------------------------------------
 
     def save(self, path: str) -> None:

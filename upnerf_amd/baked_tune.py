@@ -1,0 +1,304 @@
+"""Fine-tuning a baked scene against pixels: the marcher's backward pass (`upnerf_baked_render_bwd`, csrc/baked.hip;
+include/upnerf_hip.h states the gradient), an autograd function over it and a tuner round it.
+
+    params = SceneParams.of(scene)                                      # fp32 leaves: rgbs, or (coef, sigma) of an SH scene
+    out = render(params, rays, step=0.01)                               # {"rgb", "depth", "opacity"}: any torch loss works on them
+    tuner = scene.tune(lr=1e-2)                                         # = BakedTuner(scene, 1e-2)
+    loss = tuner.step(rays, target_rgb, step=0.01); tuned = tuner.scene()
+    tuned, curve = distill(system, scene, [0, 3, 5], iters=200, batch=4096, baked_step=0.01, seed=0, img_id=3)
+
+Dense scenes of degree 0, 1 and 2.  A sparse scene is refused: its pool stores the faces bricks share once per brick, so a
+gradient would have to be summed over the copies -- `scene.densify()`, tune, `.sparsify()`.  The occupancy is frozen while tuning:
+a grid point whose sigma is zero is no parameter (it receives no gradient), so a clear cell keeps its eight zero corners, and a
+sigma the optimiser drives to zero (`upnerf_baked_project`) is dead from then on.  The gradient's sums over rays are float atomic
+adds: two runs agree to rounding, not to the bit.  There is no CPU path."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, lib, ptr, stream
+from .baked import RECORD_BYTES, SIGMA_BYTE, BakedScene, _aligned, _render_args
+from .ops import TIMER
+from .static_scene import c_float3, require_cuda
+
+__all__ = ["SceneParams", "render", "backward", "project", "BakedTuner", "distill", "SPARSE_REFUSAL"]
+
+SPARSE_REFUSAL = ("a sparse baked scene cannot be tuned: its pool stores the faces that bricks share once per brick, so a gradient "
+                  "would have to be summed over the copies -- tune scene.densify() and sparsify() the result")
+
+
+def _dense(scene, what: str) -> None:
+    if not isinstance(scene, BakedScene):
+        raise ValueError(f"{what} takes a baked.BakedScene")
+    if scene.sparse:
+        raise ValueError(SPARSE_REFUSAL)
+
+
+def unpack_records(records: torch.Tensor, degree: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(coef fp32 [Nz, Ny, Nx, 3, nb], sigma fp32 [Nz, Ny, Nx]) of an SH scene's records: the stored halves converted exactly."""
+    nb = (degree + 1) ** 2
+    coef = records[..., :6 * nb].contiguous().view(torch.float16).to(torch.float32).view(records.shape[:3] + (3, nb))
+    at = SIGMA_BYTE[degree]
+    return coef.contiguous(), records[..., at:at + 4].contiguous().view(torch.float32).squeeze(-1).contiguous()
+
+
+def pack_records(coef: torch.Tensor, sigma: torch.Tensor, degree: int, level: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The records [shape of sigma, 32 | 64] of fp32 coefficients and sigmas (upnerf_baked_sh_pack at `level`)."""
+    size, n = RECORD_BYTES[degree], sigma.numel()
+    if out is None:
+        out = _aligned(n * size, size, sigma.device)[:n * size].view(tuple(sigma.shape) + (size,))
+    a = _lib.BakedShPackArgs(n=n, level=float(level), degree=degree, sigma=ptr(sigma), acc=ptr(coef), records=ptr(out), kept=None)
+    check(TIMER.run("baked_sh_pack", lambda: lib.upnerf_baked_sh_pack(C.byref(a), stream()), units=n), "upnerf_baked_sh_pack")
+    return out
+
+
+class SceneParams:
+    """The fp32 parameters of a dense scene with what the marcher needs beside them: `rgbs` [Nz, Ny, Nx, 4] at degree 0, else
+    `coef` [Nz, Ny, Nx, 3, nb] and `sigma` [Nz, Ny, Nx]; the (frozen) occupancy, the bounds, the degree.  The tensors are leaves a
+    caller may set requires_grad on; `tensors` lists them."""
+
+    def __init__(self, occupancy, bounds, degree: int, rgbs=None, coef=None, sigma=None):
+        self.occupancy, self.bounds, self.degree = occupancy, bounds, int(degree)
+        self.rgbs, self.coef, self.sigma = rgbs, coef, sigma
+        nb = (self.degree + 1) ** 2
+        Cx, Cy, Cz = occupancy.dims
+        shape = (Cz + 1, Cy + 1, Cx + 1)
+        if self.degree == 0:
+            ok = rgbs is not None and rgbs.dtype == torch.float32 and tuple(rgbs.shape) == shape + (4,)
+        else:
+            ok = self.degree in (1, 2) and coef is not None and sigma is not None and coef.dtype == sigma.dtype == torch.float32 and \
+                tuple(coef.shape) == shape + (3, nb) and tuple(sigma.shape) == shape
+        if not ok:
+            raise ValueError(f"a degree-{degree} scene of {shape} points has fp32 rgbs [.., 4] (degree 0) or coef [.., 3, nb] and sigma [..]")
+        require_cuda("SceneParams", *self.tensors)
+
+    @classmethod
+    def of(cls, scene: BakedScene, requires_grad: bool = True) -> "SceneParams":
+        _dense(scene, "SceneParams.of")
+        if scene.sh_degree == 0:
+            p = cls(scene.occupancy, scene.bounds, 0, rgbs=scene.rgbs.detach().clone())
+        else:
+            coef, sigma = unpack_records(scene.records, scene.sh_degree)
+            p = cls(scene.occupancy, scene.bounds, scene.sh_degree, coef=coef, sigma=sigma)
+        for t in p.tensors:
+            t.requires_grad_(requires_grad)
+        return p
+
+    @property
+    def tensors(self):
+        return (self.rgbs,) if self.degree == 0 else (self.coef, self.sigma)
+
+
+def _common(occupancy, bounds, rays, step, background, stop):
+    Cx, Cy, Cz = occupancy.dims
+    lo, hi = bounds
+    return dict(Cx=Cx, Cy=Cy, Cz=Cz, R=rays.shape[0], lo=c_float3(lo), hi=c_float3(hi), step=step, background=background, stop=stop,
+                words=ptr(occupancy.words), rays=ptr(rays))
+
+
+def _rays16(rays: torch.Tensor) -> torch.Tensor:
+    rays = rays.detach().contiguous()
+    return rays.clone() if rays.data_ptr() % 16 else rays
+
+
+def _forward(points: torch.Tensor, degree: int, occupancy, bounds, rays, step, background, stop):
+    R, dev = rays.shape[0], rays.device
+    rgb, depth, opacity = torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)
+    common = dict(_common(occupancy, bounds, rays, step, background, stop), rgb=ptr(rgb), depth=ptr(depth), opacity=ptr(opacity))
+    if degree == 0:
+        a = _lib.BakedRenderArgs(rgbs=ptr(points), **common)
+        check(TIMER.run("baked_render", lambda: lib.upnerf_baked_render(C.byref(a), stream()), units=R), "upnerf_baked_render")
+    else:
+        a = _lib.BakedShRenderArgs(degree=degree, records=ptr(points), **common)
+        check(TIMER.run("baked_sh_render", lambda: lib.upnerf_baked_sh_render(C.byref(a), stream()), units=R), "upnerf_baked_sh_render")
+    return rgb, depth, opacity
+
+
+def backward(points: torch.Tensor, degree: int, occupancy, bounds, rays: torch.Tensor, step: float, background: float, stop: float,
+             g_rgb: torch.Tensor, g_depth: Optional[torch.Tensor] = None, g_opacity: Optional[torch.Tensor] = None, out=None):
+    """upnerf_baked_render_bwd, called directly.  points: the grid the forward marched (`rgbs` [Nz, Ny, Nx, 4] fp32 at degree 0,
+    the uint8 records at degree 1 | 2).  Returns the gradient ADDED into `out` (zeroed here when None): one fp32 tensor
+    [Nz, Ny, Nx, 4] at degree 0, else the pair ([Nz, Ny, Nx, 3, nb], [Nz, Ny, Nx])."""
+    require_cuda("baked_tune.backward", points, rays, g_rgb)
+    step, background, stop = _render_args(rays, step, background, stop)
+    rays = _rays16(rays)
+    R, dev = rays.shape[0], rays.device
+    if g_rgb.dtype != torch.float32 or tuple(g_rgb.shape) != (R, 3):
+        raise ValueError("g_rgb is a fp32 tensor [R, 3]")
+    for g in (g_depth, g_opacity):
+        if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != (R,)):
+            raise ValueError("g_depth and g_opacity are fp32 tensors [R] or None")
+    Cx, Cy, Cz = occupancy.dims
+    shape, nb = (Cz + 1, Cy + 1, Cx + 1), (degree + 1) ** 2
+    if out is None:
+        out = torch.zeros(shape + (4,), device=dev) if degree == 0 else (torch.zeros(shape + (3, nb), device=dev), torch.zeros(shape, device=dev))
+    grads = dict(grad=ptr(out)) if degree == 0 else dict(grad_coef=ptr(out[0]), grad_sigma=ptr(out[1]))
+    a = _lib.BakedRenderBwdArgs(degree=degree, points=ptr(points), slots=None, g_rgb=ptr(g_rgb.contiguous()),
+                                g_depth=ptr(g_depth.contiguous()) if g_depth is not None else None,
+                                g_opacity=ptr(g_opacity.contiguous()) if g_opacity is not None else None, **grads,
+                                **_common(occupancy, bounds, rays, step, background, stop))
+    check(TIMER.run("baked_render_bwd", lambda: lib.upnerf_baked_render_bwd(C.byref(a), stream()), units=R), "upnerf_baked_render_bwd")
+    return out
+
+
+def project(degree: int, rgbs: Optional[torch.Tensor] = None, sigma: Optional[torch.Tensor] = None) -> None:
+    """upnerf_baked_project in place: `rgbs` [.., 4] at degree 0, `sigma` [..] at degree 1 | 2."""
+    t = rgbs if degree == 0 else sigma
+    n = t.numel() // 4 if degree == 0 else t.numel()
+    a = _lib.BakedProjectArgs(n=n, degree=degree, rgbs=ptr(rgbs) if degree == 0 else None, sigma=ptr(sigma) if degree else None)
+    check(TIMER.run("baked_project", lambda: lib.upnerf_baked_project(C.byref(a), stream()), units=n), "upnerf_baked_project")
+
+
+class _Render(torch.autograd.Function):
+    """The marcher with its backward: (rgb, depth, opacity) of the parameter tensors of a SceneParams."""
+
+    @staticmethod
+    def forward(ctx, params, rays, step, background, stop, *tensors):
+        if params.degree == 0:
+            points = tensors[0].detach().contiguous()
+        else:  # the records the marcher reads; the gradient passes straight through the fp16 rounding to the fp32 coefficients
+            points = pack_records(tensors[0].detach().contiguous(), tensors[1].detach().contiguous(), params.degree, 0.0)
+        ctx.points, ctx.params, ctx.rays, ctx.args = points, params, rays, (step, background, stop)
+        ctx.set_materialize_grads(False)
+        return _forward(points, params.degree, params.occupancy, params.bounds, rays, step, background, stop)
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_opacity):
+        p, R = ctx.params, ctx.rays.shape[0]
+        if g_rgb is None:
+            g_rgb = torch.zeros(R, 3, device=ctx.rays.device)
+        out = backward(ctx.points, p.degree, p.occupancy, p.bounds, ctx.rays, *ctx.args, g_rgb.contiguous(),
+                       g_depth, g_opacity)
+        return (None,) * 5 + ((out,) if p.degree == 0 else tuple(out))
+
+
+def render(scene_params: SceneParams, rays: torch.Tensor, step: float, background: float = 0.0, stop: float = 0.0) -> dict:
+    """{"rgb" [R, 3], "depth" [R], "opacity" [R]} of `rays` [R, 8] through the scene of `scene_params`, differentiable with
+    respect to scene_params.rgbs, or to scene_params.coef and .sigma: forward the existing marcher (at degree 1 | 2 on records
+    packed from the parameters by upnerf_baked_sh_pack at level 0), backward upnerf_baked_render_bwd.  No gradient for the rays."""
+    if not isinstance(scene_params, SceneParams):
+        raise ValueError("scene_params is a baked_tune.SceneParams (SceneParams.of(scene))")
+    require_cuda("baked_tune.render", rays)
+    step, background, stop = _render_args(rays, step, background, stop)
+    rgb, depth, opacity = _Render.apply(scene_params, _rays16(rays), step, background, stop, *scene_params.tensors)
+    return {"rgb": rgb, "depth": depth, "opacity": opacity}
+
+
+class BakedTuner:
+    """Adam on the points of a dense scene against target pixels.  Holds the fp32 masters (one flat buffer: rgbs, or the
+    coefficients followed by the sigmas), their gradient and the Adam moments; the occupancy is the scene's and is frozen."""
+
+    def __init__(self, scene: BakedScene, lr: float, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8):
+        _dense(scene, "BakedTuner")
+        lr, eps = float(lr), float(eps)
+        if not (lr > 0 and np.isfinite(lr)) or not (eps > 0) or not all(0 <= float(b) < 1 for b in betas):
+            raise ValueError("lr and eps are positive, the betas in [0, 1)")
+        self.lr, self.betas, self.eps, self.t = lr, (float(betas[0]), float(betas[1])), eps, 0
+        self.degree, self.bounds, self.level, self.occupancy = scene.sh_degree, scene.bounds, scene.level, scene.occupancy
+        dev = scene.device
+        Nx, Ny, Nz = scene.resolution
+        shape, nb = (Nz, Ny, Nx), (self.degree + 1) ** 2
+        n = Nx * Ny * Nz
+        per = 4 if self.degree == 0 else 3 * nb + 1
+        self.p = torch.empty(n * per, device=dev)
+        self.g, self.m, self.v = (torch.zeros_like(self.p) for _ in range(3))
+        view = lambda t: (t.view(shape + (4,)),) if self.degree == 0 else (t[:n * 3 * nb].view(shape + (3, nb)), t[n * 3 * nb:].view(shape))
+        self.masters, self.grads = view(self.p), view(self.g)
+        if self.degree == 0:
+            self.masters[0].copy_(scene.rgbs)
+            self.records = None
+        else:
+            coef, sigma = unpack_records(scene.records, self.degree)
+            self.masters[0].copy_(coef), self.masters[1].copy_(sigma)
+            self.records = pack_records(*self.masters, self.degree, 0.0)
+
+    @property
+    def points(self) -> torch.Tensor:
+        """The grid the marcher reads now: the master rgbs, or the records packed from the masters."""
+        return self.masters[0] if self.degree == 0 else self.records
+
+    @torch.no_grad()
+    def step(self, rays: torch.Tensor, target_rgb: torch.Tensor, step: float, background: float = 0.0, stop: float = 0.0) -> torch.Tensor:
+        """One iteration on `rays` [R, 8] against `target_rgb` [R, 3]: zero the gradient (upnerf_zero), forward, the gradient of
+        the mean squared error (plain torch), upnerf_baked_render_bwd, upnerf_adam, upnerf_baked_project, and at degree 1 | 2
+        upnerf_baked_sh_pack.  Returns the loss BEFORE the update, a 0-dim device tensor (no host read here)."""
+        require_cuda("BakedTuner.step", rays, target_rgb)
+        step, background, stop = _render_args(rays, step, background, stop)
+        rays = _rays16(rays)
+        R = rays.shape[0]
+        if target_rgb.dtype != torch.float32 or tuple(target_rgb.shape) != (R, 3):
+            raise ValueError("target_rgb is a fp32 tensor [R, 3]")
+        st = stream()
+        check(lib.upnerf_zero(ptr(self.g), self.g.numel(), st), "upnerf_zero")
+        rgb, _, _ = _forward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop)
+        diff = rgb - target_rgb
+        loss = (diff * diff).mean()
+        g_rgb = diff * (2.0 / (3 * R))
+        backward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop, g_rgb,
+                 out=self.grads[0] if self.degree == 0 else self.grads)
+        self.t += 1
+        b1, b2 = self.betas
+        step_size, bc2_sqrt = self.lr / (1.0 - b1 ** self.t), math.sqrt(1.0 - b2 ** self.t)
+        check(TIMER.run("adam", lambda: lib.upnerf_adam(self.p.numel(), ptr(self.p), ptr(self.g), ptr(self.m), ptr(self.v), b1, b2,
+                                                       self.eps, step_size, bc2_sqrt, None, st), units=self.p.numel()), "upnerf_adam")
+        if self.degree == 0:
+            project(0, rgbs=self.masters[0])
+        else:
+            project(self.degree, sigma=self.masters[1])
+            pack_records(*self.masters, self.degree, 0.0, out=self.records)
+        return loss
+
+    @torch.no_grad()
+    def scene(self) -> BakedScene:
+        """The tuned scene: the masters pruned again at the scene's level, the bits rebuilt (from_grids / from_records)."""
+        if self.degree == 0:
+            rgbs = self.masters[0]
+            return BakedScene.from_grids(rgbs[..., 3].contiguous(), rgbs[..., :3].contiguous(), self.bounds, self.level)
+        return BakedScene.from_records(pack_records(*self.masters, self.degree, self.level), self.bounds, self.level, self.degree)
+
+
+def keyframe_rays(path, device) -> torch.Tensor:
+    """[K * W * H, 8] the rays of a path's own keyframe cameras, keyframe by keyframe (upnerf_path_rays)."""
+    from .novel_view import path_poses, path_rays
+    W, H = path.img_wh
+    c2w, nf = path_poses(path.key_c2w.to(device), path.key_near_far.to(device), path.u.to(device), path.mode)  # (as render_path)
+    return path_rays(c2w, nf, (W, H), path.K, 0, path.n_frames * W * H)[0]
+
+
+def distill(system, scene: BakedScene, path_or_img_ids, iters: int, batch: int, baked_step: float, seed: int = 0, lr: float = 1e-2,
+            img_id: Optional[int] = None, chunk: Optional[int] = None):
+    """Fit a dense baked scene to the field's own renders.  Cameras: the keyframes of a `novel_view.CameraPath`, or the refined
+    training cameras `img_ids` (two at least).  The targets are rendered ONCE from the field by the static renderer
+    (static_scene.render_static, through render_path) for those cameras' rays, all under the appearance of training image
+    `img_id` -- the ONE appearance the scene was baked with.  Batches of `batch` rays are drawn with a generator seeded by `seed`;
+    `iters` steps of BakedTuner(scene, lr) at sample spacing `baked_step`.  Returns (the tuned scene, the loss curve as a list of
+    floats -- one host read, at the end)."""
+    from .novel_view import CameraPath, render_path
+    _dense(scene, "distill")
+    if img_id is None:
+        raise ValueError("img_id: the training image whose appearance the scene was baked with (the targets are rendered under it)")
+    iters, batch = int(iters), int(batch)
+    if iters < 1 or batch < 1:
+        raise ValueError("iters and batch are positive")
+    src = path_or_img_ids if isinstance(path_or_img_ids, CameraPath) else \
+        CameraPath.through_images(system, list(path_or_img_ids), n_frames=len(list(path_or_img_ids)))
+    K = src.key_c2w.shape[0]
+    ids = torch.full((K,), int(img_id), dtype=torch.int32)
+    keys = CameraPath(src.key_c2w, src.key_near_far, torch.arange(K, dtype=torch.float32), ids, ids, torch.zeros(K), src.img_wh, src.K, "linear")
+    dev = scene.device
+    target = render_path(system, keys, chunk=chunk, outputs=("rgb_float",))["rgb_float"].reshape(-1, 3).contiguous()
+    rays = keyframe_rays(keys, dev)
+    background = 1.0 if getattr(system.train_dataset, "white_back", False) else 0.0
+    tuner = BakedTuner(scene, lr)
+    gen = torch.Generator(device="cpu").manual_seed(int(seed))
+    curve = []
+    for _ in range(iters):
+        idx = torch.randint(0, rays.shape[0], (min(batch, rays.shape[0]),), generator=gen).to(dev)
+        curve.append(tuner.step(rays[idx], target[idx], baked_step, background=background))
+    return tuner.scene(), [float(x) for x in torch.stack(curve).cpu()]

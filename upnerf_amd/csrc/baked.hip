@@ -23,7 +23,12 @@
 //                        parameter is the layout.  Where the dense march tests a sample's brick bit, the sparse one reads the
 //                        brick's slot (< 0: the empty brick), and the eight corners are base, + 1, + 9, + 81 inside that slot.
 //   upnerf_sh_accumulate, upnerf_baked_sh_pack  the projection's running sum over directions, and the records from it.
-// All stores are ordinary vector stores from plain C++.
+//   upnerf_baked_render_bwd  the gradient of a dense scene's render with respect to its points: one thread per
+//                        ray again, two marches -- the first forms Q = sum w q, the second hands every sample's four gradients to
+//                        the eight corners of its cell, summed in registers while the ray stays in the cell and added to memory
+//                        with atomicAdd(float*) when it leaves it.  The one entry point here whose bits depend on the run.
+//   upnerf_baked_project the tuned points back into the marcher's domain (sigma >= 0 and finite; degree 0: colours in [0, 1]).
+// All stores are ordinary vector stores and vector float atomics from plain C++.
 #include "common.cuh"
 #include "grid.cuh"
 
@@ -290,6 +295,221 @@ __global__ __launch_bounds__(BAKED_THREADS) void baked_render_kernel(Args a, Bak
   a.opacity[r] = out.opacity;
 }
 
+// ---- the backward march: upnerf_baked_render_bwd (include/upnerf_hip.h states the gradient) ---------------------
+// The walk of baked_march over a dense layout, restated: the samples that count -- inside the box, in a cell with a set bit -- are
+// handed in sample order to visit(s, base), `base` the point index of the cell's corner (0, 0, 0); visit returns true to end the
+// ray (`stop`).  baked_locate, baked_propose and the acceptance tests are baked_march's, so the visited set is the forward's.
+// (Handing baked_march's own loop a visitor instead moved the degree-0 forward kernels from 78 / 74 to 80 / 76 registers: the
+// forward stays as it was and the walk is stated twice.)
+template <class Visit>
+__device__ __forceinline__ void baked_walk_dense(const uint32_t* words, float step, const BakedGrid& G, const OccDims& dm, const float* o,
+                                                 const float* d, float near, int K, Visit&& visit) {
+  const uint32_t* fine = words;
+  const uint32_t* brick = words + dm.fine_words;
+  int k = 0;
+  while (k < K) {
+    const BakedSample s = baked_locate(G, o, d, near, step, k);
+    int next = k + 1;
+    if (!s.inside) {
+      bool gone = false;
+      float t_in = -INFINITY;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        if (s.side[a] == 1 || s.side[a] == -1) {
+          const bool away = s.side[a] > 0 ? d[a] >= 0.0f : d[a] <= 0.0f;
+          if (away) gone = true;
+          else t_in = fmaxf(t_in, ((s.side[a] > 0 ? G.lo[a] + G.Cf[a] / G.inv[a] : G.lo[a]) - o[a]) / d[a]);
+        }
+      }
+      if (gone) break;
+      const int kp = baked_propose(t_in, near, step, K);
+      if (kp > k) {
+        const BakedSample q = baked_locate(G, o, d, near, step, kp);
+        bool same = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) same = same || ((s.side[a] == 1 || s.side[a] == -1) && q.side[a] == s.side[a]);
+        if (same) next = kp + 1;
+      }
+      k = next;
+      continue;
+    }
+    const int bx = s.i[0] / OCC_BRICK, by = s.i[1] / OCC_BRICK, bz = s.i[2] / OCC_BRICK;
+    int shift = -1;  // the empty region the sample lies in: 3 = its brick, 0 = its cell, -1 = none
+    if (!occ_bit(brick, ((int64_t)bz * dm.By + by) * dm.Bx + bx)) shift = 3;
+    else if (!occ_bit(fine, ((int64_t)s.i[2] * dm.Cy + s.i[1]) * dm.Cx + s.i[0])) shift = 0;
+    if (shift >= 0) {
+      float t_out = INFINITY;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        if (d[a] == 0.0f) continue;
+        const int r = s.i[a] >> shift;
+        int plane = d[a] > 0.0f ? (r + 1) << shift : r << shift;
+        plane = plane < G.C[a] ? plane : G.C[a];
+        t_out = fminf(t_out, ((G.lo[a] + (float)plane / G.inv[a]) - o[a]) / d[a]);
+      }
+      const int kp = baked_propose(t_out, near, step, K);
+      if (kp > k) {
+        const BakedSample q = baked_locate(G, o, d, near, step, kp);
+        if (q.inside && (q.i[0] >> shift) == (s.i[0] >> shift) && (q.i[1] >> shift) == (s.i[1] >> shift) &&
+            (q.i[2] >> shift) == (s.i[2] >> shift))
+          next = kp + 1;
+      }
+      k = next;
+      continue;
+    }
+    if (visit(s, ((int64_t)s.i[2] * G.sz + (int64_t)s.i[1] * G.sy) + s.i[0])) break;
+    k = next;
+  }
+}
+
+// one counted sample as both passes of the backward see it: the forward's blend, clamp and compositing weight, and q
+struct BakedBwdSample {
+  float f[3];   // the sample's position in its cell
+  float w, Tn;  // w_k and T_{k+1}
+  float q;
+  unsigned live;  // bit j: corner j (x = j & 1, y = j >> 1 & 1, z = j >> 2) stores a sigma that is not zero
+  unsigned open;  // bit c: colour channel c was not clamped
+};
+
+template <int DEG>
+__device__ __forceinline__ BakedBwdSample baked_bwd_sample(const BakedCorner<DEG>& pts, const BakedGrid& G, const BakedSample& s,
+                                                           int64_t base, float delta, float T, const float* g, float background,
+                                                           float far) {
+  BakedBwdSample b;
+  b.f[0] = s.g[0] - (float)s.i[0], b.f[1] = s.g[1] - (float)s.i[1], b.f[2] = s.g[2] - (float)s.i[2];
+  f32x4 c[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) c[j] = pts(base + (j & 1) + (j >> 1 & 1) * G.sy + (j >> 2) * G.sz);
+  float v[4];
+#pragma unroll
+  for (int ch = 0; ch < 4; ++ch) {  // (baked_march's blend: x first, then y, then z)
+    const float x00 = fmaf(b.f[0], c[1][ch] - c[0][ch], c[0][ch]), x10 = fmaf(b.f[0], c[3][ch] - c[2][ch], c[2][ch]);
+    const float x01 = fmaf(b.f[0], c[5][ch] - c[4][ch], c[4][ch]), x11 = fmaf(b.f[0], c[7][ch] - c[6][ch], c[6][ch]);
+    const float y0 = fmaf(b.f[1], x10 - x00, x00), y1 = fmaf(b.f[1], x11 - x01, x01);
+    v[ch] = fmaf(b.f[2], y1 - y0, y0);
+  }
+  b.live = 0u;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) b.live |= (c[j][3] != 0.0f ? 1u : 0u) << j;
+  b.open = 7u;
+  if (DEG > 0) {
+    b.open = 0u;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      b.open |= (v[ch] >= 0.0f && v[ch] <= 1.0f ? 1u : 0u) << ch;
+      v[ch] = fminf(fmaxf(v[ch], 0.0f), 1.0f);
+    }
+  }
+  const float e = expf(-delta * v[3]);
+  const float alpha = 1.0f - e;
+  b.w = T * alpha;
+  b.Tn = T * (1.0f - alpha);
+  b.q = fmaf(g[0], v[0] - background, fmaf(g[1], v[1] - background, fmaf(g[2], v[2] - background, fmaf(g[3], s.t - far, g[4]))));
+  return b;
+}
+
+template <int DEG>
+__global__ __launch_bounds__(BAKED_THREADS) void baked_render_bwd_kernel(upnerf_baked_render_bwd_args a, BakedGrid G, OccDims dm) {
+  constexpr int NB = (DEG + 1) * (DEG + 1);
+  const int r = blockIdx.x * BAKED_THREADS + threadIdx.x;
+  if (r >= a.R) return;
+  // upstream: g_rgb | g_depth | g_opacity; a ray none of whose gradients is set adds nothing
+  const float g[5] = {a.g_rgb[(int64_t)r * 3], a.g_rgb[(int64_t)r * 3 + 1], a.g_rgb[(int64_t)r * 3 + 2], a.g_depth ? a.g_depth[r] : 0.0f,
+                      a.g_opacity ? a.g_opacity[r] : 0.0f};
+  if (g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f && g[3] == 0.0f && g[4] == 0.0f) return;
+  const f32x4* rp = (const f32x4*)(a.rays + (int64_t)r * 8);
+  const f32x4 r0 = rp[0], r1 = rp[1];
+  const float row[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+  const float o[3] = {row[0], row[1], row[2]}, d[3] = {row[3], row[4], row[5]};
+  const float near = row[6], far = row[7];
+  bool ok = far > near;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ok = ok && isfinite(row[j]);
+  if (!ok) return;  // a miss
+  const float nk = ceilf((far - near) / a.step);
+  const int K = nk < (float)UPNERF_BAKED_MAX_SAMPLES ? (int)nk : UPNERF_BAKED_MAX_SAMPLES;
+  const float len = sqrtf(fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0])));
+  const float delta = a.step * len;
+  const BakedCorner<DEG> pts(a.points, d, len);
+
+  // first pass: the forward's recurrence, and Q = sum_k w_k q_k
+  float Q = 0.0f, T = 1.0f;
+  baked_walk_dense(a.words, a.step, G, dm, o, d, near, K, [&](const BakedSample& s, int64_t base) __attribute__((always_inline)) {
+    const BakedBwdSample b = baked_bwd_sample<DEG>(pts, G, s, base, delta, T, g, a.background, far);
+    Q = fmaf(b.w, b.q, Q);
+    T = b.Tn;
+    return a.stop > 0.0f && T < a.stop;
+  });
+
+  // second pass: the same samples with the same numbers; the suffix of sample k is Q less the prefix up to and including k.  The
+  // four gradients of a sample go to the eight corners of its cell with their trilinear weights: summed in registers while the
+  // ray stays in one cell, added to memory when it leaves it
+  float acc[8][4];
+  int64_t cell = -1;
+  unsigned live = 0u;
+  auto flush = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (!(live >> j & 1u)) continue;  // a corner whose stored sigma is zero is no parameter
+      const int64_t p = cell + (j & 1) + (j >> 1 & 1) * G.sy + (j >> 2) * G.sz;
+      if constexpr (DEG == 0) {
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) atomicAdd(a.grad + p * 4 + ch, acc[j][ch]);
+      } else {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+          for (int jb = 0; jb < NB; ++jb) atomicAdd(a.grad_coef + (p * 3 + ch) * NB + jb, pts.Y[jb] * acc[j][ch]);
+        atomicAdd(a.grad_sigma + p, acc[j][3]);
+      }
+    }
+  };
+  float P = 0.0f;
+  T = 1.0f;
+  baked_walk_dense(a.words, a.step, G, dm, o, d, near, K, [&](const BakedSample& s, int64_t base) __attribute__((always_inline)) {
+    const BakedBwdSample b = baked_bwd_sample<DEG>(pts, G, s, base, delta, T, g, a.background, far);
+    P = fmaf(b.w, b.q, P);
+    const float gs = delta * fmaf(b.Tn, b.q, -(Q - P));
+    if (base != cell) {
+      if (cell >= 0) flush();
+      cell = base;
+      live = b.live;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0.0f;
+    }
+    float gc[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) gc[ch] = (b.open >> ch & 1u) ? b.w * g[ch] : 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float wt = ((j & 4 ? b.f[2] : 1.0f - b.f[2]) * (j & 2 ? b.f[1] : 1.0f - b.f[1])) * (j & 1 ? b.f[0] : 1.0f - b.f[0]);
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) acc[j][ch] = fmaf(wt, gc[ch], acc[j][ch]);
+      acc[j][3] = fmaf(wt, gs, acc[j][3]);
+    }
+    T = b.Tn;
+    return a.stop > 0.0f && T < a.stop;
+  });
+  if (cell >= 0) flush();
+}
+
+// upnerf_baked_project: the point of a tuned scene back into the set the marcher is defined on
+__global__ __launch_bounds__(NTHREADS) void baked_project_kernel(upnerf_baked_project_args a) {
+  const int64_t n = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
+  if (n >= a.n) return;
+  if (a.degree == 0) {
+    f32x4 v = ((f32x4*)a.rgbs)[n];
+    const bool keep = isfinite(v.w) && v.w > 0.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = keep && v[c] > 0.0f ? (v[c] < 1.0f ? v[c] : 1.0f) : 0.0f;
+    v.w = keep ? v.w : 0.0f;
+    ((f32x4*)a.rgbs)[n] = v;
+  } else {
+    const float s = a.sigma[n];
+    a.sigma[n] = isfinite(s) && s > 0.0f ? s : 0.0f;
+  }
+}
+
 __global__ __launch_bounds__(NTHREADS) void baked_pack_kernel(upnerf_baked_pack_args a) {
   const int64_t n = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
   if (n >= a.n) return;
@@ -345,9 +565,18 @@ bool baked_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // the arguments a launch may be given, and the grid as the kernel reads it
 // (`points`: the rgbs or the records of `a`, aligned to `size`, the bytes of one point)
 template <class Args>
+bool baked_lattice(const Args* a, const void* points, size_t size, BakedGrid* G, OccDims* dm);
+template <class Args>
 bool baked_grid(const Args* a, const void* points, size_t size, BakedGrid* G, OccDims* dm) {
+  if (!a || !a->rgb || !a->depth || !a->opacity) return false;
+  return baked_lattice(a, points, size, G, dm);
+}
+
+// (everything of baked_grid but the forward's outputs: the backward march takes the same scene, rays and step)
+template <class Args>
+bool baked_lattice(const Args* a, const void* points, size_t size, BakedGrid* G, OccDims* dm) {
   if (!a || !occ_dims(a->Cx, a->Cy, a->Cz, dm) || a->R <= 0) return false;
-  if (!points || !a->words || !a->rays || !a->rgb || !a->depth || !a->opacity) return false;
+  if (!points || !a->words || !a->rays) return false;
   if (((uintptr_t)points & (size - 1)) != 0 || !baked_aligned16(a->rays)) return false;
   if (!(a->step > 0.0f) || !isfinite(a->step) || !isfinite(a->background) || !(a->stop >= 0.0f && a->stop < 1.0f)) return false;
   const int C[3] = {a->Cx, a->Cy, a->Cz};
@@ -404,6 +633,29 @@ extern "C" int upnerf_baked_sparse_render(const upnerf_baked_sparse_render_args*
   if (a->degree == 0) hipLaunchKernelGGL((baked_render_kernel<0, Args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
   else if (a->degree == 1) hipLaunchKernelGGL((baked_render_kernel<1, Args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
   else hipLaunchKernelGGL((baked_render_kernel<2, Args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
+  return (int)hipGetLastError();
+}
+
+extern "C" int upnerf_baked_render_bwd(const upnerf_baked_render_bwd_args* a, void* stream) {
+  BakedGrid G;
+  OccDims dm;
+  if (!a || a->degree < 0 || a->degree > 2 || !a->g_rgb) return UPNERF_EINVAL;
+  if (a->degree == 0 ? !a->grad : (!a->grad_coef || !a->grad_sigma)) return UPNERF_EINVAL;
+  if (!baked_lattice(a, a->points, (size_t)16 << a->degree, &G, &dm)) return UPNERF_EINVAL;
+  if (a->slots) return UPNERF_EUNSUP;  // a brick pool stores shared faces once per brick: densify(), tune, sparsify()
+  const dim3 grid((a->R + BAKED_THREADS - 1) / BAKED_THREADS), block(BAKED_THREADS);
+  if (a->degree == 0) hipLaunchKernelGGL(baked_render_bwd_kernel<0>, grid, block, 0, (hipStream_t)stream, *a, G, dm);
+  else if (a->degree == 1) hipLaunchKernelGGL(baked_render_bwd_kernel<1>, grid, block, 0, (hipStream_t)stream, *a, G, dm);
+  else hipLaunchKernelGGL(baked_render_bwd_kernel<2>, grid, block, 0, (hipStream_t)stream, *a, G, dm);
+  return (int)hipGetLastError();
+}
+
+extern "C" int upnerf_baked_project(const upnerf_baked_project_args* a, void* stream) {
+  if (!a || a->n <= 0 || a->degree < 0 || a->degree > 2) return UPNERF_EINVAL;
+  if (a->degree == 0 ? (!a->rgbs || !baked_aligned16(a->rgbs)) : !a->sigma) return UPNERF_EINVAL;
+  const int64_t blocks = (a->n + NTHREADS - 1) / NTHREADS;
+  if (blocks > 0x7fffffff) return UPNERF_EUNSUP;
+  hipLaunchKernelGGL(baked_project_kernel, dim3((unsigned)blocks), dim3(NTHREADS), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }
 
