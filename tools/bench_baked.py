@@ -23,7 +23,8 @@ the same frames through an analytic shell volume (an ellipsoid's surface, four c
 directions) at 128^3 and 256^3 points, degree 0 and 2, alternately in one process, medians of --reps: ms per launch, frames/s,
 bytes, the occupied share of the bricks f_b and the hit share; (2) the bake, dense against sparse=True, at degree 2 and --dirs
 directions on bench.py's system at --resolution, with f_b; (3) with --parent-lib PATH (the library built from the parent
-commit), the three DENSE marchers' times per launch on the scenes of --sh, this build and that one alternately.
+commit), the times per launch of the nine marchers -- dense and sparse forward and the backward, degree 0, 1, 2 -- on the scenes
+of --sh (the backward on the inputs of --tune), this build and that one alternately, the first round discarded.
 
 --tune measures the backward march INSTEAD and writes --tune-out: the scenes of --sh (degree 0, 1, 2 at --resolution),
 the --frames frames as rays in launches of --chunk, random upstream gradients, forward and backward alternately in one process,
@@ -78,7 +79,7 @@ def main():
     ap.add_argument("--tune", action="store_true", help="measure the backward march instead; writes --tune-out")
     ap.add_argument("--tune-out", default=os.path.join(ROOT, "profiles", "baked_tune.json"))
     ap.add_argument("--tune-iters", type=int, default=200, help="with --tune: iterations of the distill")
-    ap.add_argument("--parent-lib", default=None, help="with --sparse: the parent commit's libupnerf_hip.so, for the dense marchers' times beside this build's")
+    ap.add_argument("--parent-lib", default=None, help="with --sparse: the parent commit's libupnerf_hip.so, for the nine marchers' times beside this build's")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_baked.py measures on the GPU; none is visible")
@@ -424,24 +425,52 @@ def sparse_main(a, sysm, path, dev):
                                                          made[False].sparsify().pool[..., :54].contiguous().view(torch.float16).float()).abs().max()),
                 "note": "random weights: above f_b = 0.20 this shows the cost side only; a trained scene is unchecked"}
     parent = None
-    if a.parent_lib:  # the dense marchers of the parent commit's library beside this build's, on the scenes of --sh
+    if a.parent_lib:  # the marchers of the parent commit's library beside this build's, on the scenes of --sh: nine instantiations
+        from upnerf_amd import baked_tune
         old = C.CDLL(a.parent_lib)
-        for name, cls in (("upnerf_baked_render", _lib.BakedRenderArgs), ("upnerf_baked_sh_render", _lib.BakedShRenderArgs)):
+        for name, cls in (("upnerf_baked_render", _lib.BakedRenderArgs), ("upnerf_baked_sh_render", _lib.BakedShRenderArgs),
+                          ("upnerf_baked_sparse_render", _lib.BakedSparseRenderArgs), ("upnerf_baked_render_bwd", _lib.BakedRenderBwdArgs)):
             getattr(old, name).argtypes, getattr(old, name).restype = [C.POINTER(cls), C.c_void_p], C.c_int
         scenes = {0: BakedScene.build(sysm, BOUNDS, res, a.level, img_id=a.bake_image, view_dir=(0.0, 0.0, -1.0)),
                   1: BakedScene.build(sysm, BOUNDS, res, a.level, img_id=a.bake_image, sh_degree=1, dirs=dirs), 2: made[False]}
-        new, ms = bk.lib, {(d, w): [] for d in scenes for w in ("parent", "this")}
+        # the backward on the inputs of --tune: every ray of the path in launches of --chunk, random upstream gradients
+        all_rays = novel_view.path_rays(*novel_view.path_poses(path.key_c2w.to(dev), path.key_near_far.to(dev), path.u.to(dev), path.mode),
+                                        (W, H), path.K, 0, rays)[0]
+        gen = torch.Generator(device="cpu").manual_seed(5)
+        g_rgb, g_depth, g_op = (torch.randn(*shape, generator=gen).to(dev) for shape in ((rays, 3), (rays,), (rays,)))
+        chunks = [(r0, min(a.chunk, rays - r0)) for r0 in range(0, rays, a.chunk)]
+
+        def bwd_ms(d):
+            sc, nb = scenes[d], (d + 1) ** 2
+            shape = tuple(reversed(sc.resolution))
+            bufs = torch.zeros(shape + (4,), device=dev) if d == 0 else (torch.zeros(shape + (3, nb), device=dev), torch.zeros(shape, device=dev))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for r0, n in chunks:
+                baked_tune.backward(sc.grid, d, sc.occupancy, sc.bounds, all_rays[r0:r0 + n], a.step, 0.0, 0.0, g_rgb[r0:r0 + n], g_depth[r0:r0 + n],
+                                    g_op[r0:r0 + n], out=bufs)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / len(chunks)
+
+        legs = {}
+        for d, sc in scenes.items():
+            sp = sc.sparsify()
+            legs[f"dense{d}"] = lambda sc=sc, d=d: kernel_ms(sc, "baked_sh_render" if d else "baked_render")
+            legs[f"sparse{d}"] = lambda sp=sp: kernel_ms(sp, "baked_sparse_render")
+            legs[f"bwd{d}"] = lambda d=d: bwd_ms(d)
+        new, ms = bk.lib, {(k, w): [] for k in legs for w in ("parent", "this")}
         for _ in range(a.reps + 1):  # (the first round warms up)
-            for d, sc in scenes.items():
+            for k, leg in legs.items():
                 for w, library in (("parent", old), ("this", new)):
-                    bk.lib = library
-                    ms[d, w].append(kernel_ms(sc, "baked_sh_render" if d else "baked_render"))
-        bk.lib = new
-        parent = {f"degree{d}": {"parent_ms_per_launch": st.median(ms[d, "parent"][1:]), "this_ms_per_launch": st.median(ms[d, "this"][1:]),
-                                 "parent_over_this": st.median(ms[d, "parent"][1:]) / st.median(ms[d, "this"][1:])} for d in scenes}
-    out = {"metric": "sparse baked scenes: the marcher dense against sparse on an analytic shell, the degree-2 bake dense against sparse, the dense marchers against the parent commit's",
+                    bk.lib = baked_tune.lib = library
+                    ms[k, w].append(leg())
+        bk.lib = baked_tune.lib = new
+        parent = {k: {"parent_ms_per_launch": st.median(ms[k, "parent"][1:]), "this_ms_per_launch": st.median(ms[k, "this"][1:]),
+                      "parent_over_this": st.median(ms[k, "parent"][1:]) / st.median(ms[k, "this"][1:])} for k in legs}
+    out = {"metric": "sparse baked scenes: the marcher dense against sparse on an analytic shell, the degree-2 bake dense against sparse, the nine marchers against the parent commit's",
            "frames": F, "img_wh": [W, H], "chunk": a.chunk, "step": a.step, "reps": a.reps, "bounds": [list(b) for b in BOUNDS],
-           "marcher": marcher, "bake": bake_out, "dense_vs_parent": parent}
+           "marcher": marcher, "bake": bake_out, "marchers_vs_parent": parent}
     os.makedirs(os.path.dirname(os.path.abspath(a.sparse_out)), exist_ok=True)
     with open(a.sparse_out, "w") as f:
         json.dump(out, f, indent=1)

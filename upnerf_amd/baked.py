@@ -37,6 +37,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream
+from .occupancy import OccupancyGrid
 from .ops import TIMER
 from .static_scene import box, c_float3, field_of, refined_training_poses, require_cuda
 
@@ -109,12 +110,7 @@ def field_colour(system, bounds, resolution: Sequence[int], view_dir, img_id=Non
     Nx, Ny, Nz = (int(n) for n in resolution)
     if min(Nx, Ny, Nz) < 1:
         raise ValueError(f"resolution is the number of grid points per axis, got {tuple(resolution)}")
-    v = torch.as_tensor(view_dir, dtype=torch.float64).reshape(3)
-    n = float(v.norm())
-    if not n > 0 or not np.isfinite(n):
-        raise ValueError("view_dir is a direction: three finite numbers, not all zero")
-    v = (v / n).to(torch.float32).to(dev)
-    a_row = _appearance(system, model, field, img_id, rows, dev)
+    v, a_row = _view_and_row(system, model, field, view_dir, img_id, rows, dev)
     S = max(Nz, MIN_SAMPLES)
     cols = Nx * Ny
     chunk = int(chunk) if chunk is not None else max(1, (1 << 20) // S)
@@ -187,9 +183,10 @@ def _aligned(nbytes: int, size: int, dev) -> torch.Tensor:
     return spare[off:off + max(nbytes, size)]
 
 
-def _point_bytes(grid: torch.Tensor) -> torch.Tensor:
-    """A contiguous tensor [..., k] of fp32 or uint8 as uint8 [..., E]: the bytes of its points."""
-    return grid if grid.dtype == torch.uint8 else grid.view(torch.uint8)
+def _aligned_copy(t: torch.Tensor, size: int) -> torch.Tensor:
+    """The contiguous tensor `t` itself where its address is a multiple of `size`, else a copy of it at such an address."""
+    n = t.numel() * t.element_size()
+    return t if t.data_ptr() % size == 0 else _aligned(n, size, t.device)[:n].view(t.dtype).view(t.shape).copy_(t)
 
 
 def brick_table(words: torch.Tensor, dims: Sequence[int]):
@@ -213,31 +210,29 @@ def brick_gather(grid: torch.Tensor, bricks: torch.Tensor, out_dtype=None) -> to
     """The pool [n_bricks, 9, 9, 9, k] of a dense grid [Nz, Ny, Nx, k] (fp32 or uint8, 4, 16, 32 or 64 bytes per point) for the
     bricks `bricks` (upnerf_brick_gather); points beyond the grid are zero.  With no brick nothing is launched."""
     Nz, Ny, Nx, k = grid.shape
-    g = _point_bytes(grid.contiguous())
+    g = grid.contiguous().view(torch.uint8)
     E, n, P = g.shape[3], bricks.numel(), _lib.BRICK_POINTS
-    if g.data_ptr() % min(E, 16):
-        g = _aligned(g.numel(), 16, g.device)[:g.numel()].view(g.shape).copy_(g)
+    g = _aligned_copy(g, min(E, 16))
     store = _aligned(n * P ** 3 * E, E, grid.device)
     if n:
         a = _lib.BrickGatherArgs(Cx=Nx - 1, Cy=Ny - 1, Cz=Nz - 1, n_bricks=n, E=E, bricks=ptr(bricks), grid=ptr(g), pool=ptr(store))
         check(TIMER.run("brick_gather", lambda: lib.upnerf_brick_gather(C.byref(a), stream()), units=n * P ** 3), "upnerf_brick_gather")
     pool = store[:n * P ** 3 * E].view(n, P, P, P, E)
-    return pool if grid.dtype == torch.uint8 else pool.view(grid.dtype)
+    return pool.view(grid.dtype)
 
 
 def brick_scatter(pool: torch.Tensor, bricks: torch.Tensor, resolution: Sequence[int]) -> torch.Tensor:
     """The dense grid [Nz, Ny, Nx, k] of a pool [n_bricks, 9, 9, 9, k] (upnerf_brick_scatter): zero outside the bricks."""
     Nx, Ny, Nz = (int(n) for n in resolution)
-    p = _point_bytes(pool.contiguous())
+    p = pool.contiguous().view(torch.uint8)
     E, n = p.shape[4], bricks.numel()
     store = _aligned(Nz * Ny * Nx * E, max(E, 16), pool.device).zero_()
     if n:
-        if p.data_ptr() % E:
-            p = _aligned(p.numel(), E, p.device)[:p.numel()].view(p.shape).copy_(p)
+        p = _aligned_copy(p, E)
         a = _lib.BrickScatterArgs(Cx=Nx - 1, Cy=Ny - 1, Cz=Nz - 1, n_bricks=n, E=E, bricks=ptr(bricks), pool=ptr(p), grid=ptr(store))
         check(TIMER.run("brick_scatter", lambda: lib.upnerf_brick_scatter(C.byref(a), stream()), units=n * 729), "upnerf_brick_scatter")
     grid = store[:Nz * Ny * Nx * E].view(Nz, Ny, Nx, E)
-    return grid if pool.dtype == torch.uint8 else grid.view(pool.dtype)
+    return grid.view(pool.dtype)
 
 
 def brick_words(pool_bytes: torch.Tensor, slots: torch.Tensor, n_bricks: int, resolution: Sequence[int], E: int, sigma_at: int) -> torch.Tensor:
@@ -250,6 +245,13 @@ def brick_words(pool_bytes: torch.Tensor, slots: torch.Tensor, n_bricks: int, re
     check(TIMER.run("brick_occ", lambda: lib.upnerf_brick_occ(C.byref(a), stream()), units=words.numel()), "upnerf_brick_occ")
     return words
 _Y = (0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396)
+
+
+def _level(level) -> float:
+    level = float(level)
+    if level != level:
+        raise ValueError("level is not a number")
+    return level
 
 
 def _degree(sh_degree) -> int:
@@ -304,6 +306,16 @@ def sh_weights(dirs, sh_degree: int) -> np.ndarray:
     return np.ascontiguousarray(np.linalg.pinv(B).astype(np.float32))
 
 
+def pack_records(coef: torch.Tensor, sigma: torch.Tensor, degree: int, level: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The records [shape of sigma, 32 | 64] of fp32 coefficients and sigmas (upnerf_baked_sh_pack at `level`)."""
+    size, n = RECORD_BYTES[degree], sigma.numel()
+    if out is None:
+        out = _aligned(n * size, size, sigma.device)[:n * size].view(tuple(sigma.shape) + (size,))
+    a = _lib.BakedShPackArgs(n=n, level=float(level), degree=degree, sigma=ptr(sigma), acc=ptr(coef), records=ptr(out), kept=None)
+    check(TIMER.run("baked_sh_pack", lambda: lib.upnerf_baked_sh_pack(C.byref(a), stream()), units=n), "upnerf_baked_sh_pack")
+    return out
+
+
 def _render_args(rays, step, background, stop):
     step, background, stop = float(step), float(background), float(stop)
     if not (step > 0 and np.isfinite(step)):
@@ -317,6 +329,32 @@ def _render_args(rays, step, background, stop):
     return step, background, stop
 
 
+def _common(occupancy, bounds, rays, step, background, stop):
+    Cx, Cy, Cz = occupancy.dims
+    lo, hi = bounds
+    return dict(Cx=Cx, Cy=Cy, Cz=Cz, R=rays.shape[0], lo=c_float3(lo), hi=c_float3(hi), step=step, background=background, stop=stop,
+                words=ptr(occupancy.words), rays=ptr(rays))
+
+
+def _rays16(rays: torch.Tensor) -> torch.Tensor:
+    rays = rays.detach().contiguous()
+    return rays.clone() if rays.data_ptr() % 16 else rays
+
+
+def march(points: torch.Tensor, degree: int, slots: Optional[torch.Tensor], occupancy, bounds, rays, step, background, stop, rgb, depth, opacity) -> None:
+    """One launch of the marcher on checked arguments (_render_args, _rays16) into rgb [>= R, 3], depth and opacity [>= R]: through
+    the pool `points` where `slots` is given, else on the records `points` at degree 1 | 2 and on rgbs at degree 0."""
+    common = dict(_common(occupancy, bounds, rays, step, background, stop), rgb=ptr(rgb), depth=ptr(depth), opacity=ptr(opacity))
+    if slots is not None:
+        name, a = "baked_sparse_render", _lib.BakedSparseRenderArgs(degree=degree, pool=ptr(points), slots=ptr(slots), **common)
+    elif degree:
+        name, a = "baked_sh_render", _lib.BakedShRenderArgs(degree=degree, records=ptr(points), **common)
+    else:
+        name, a = "baked_render", _lib.BakedRenderArgs(rgbs=ptr(points), **common)
+    fn = getattr(lib, "upnerf_" + name)
+    check(TIMER.run(name, lambda: fn(C.byref(a), stream()), units=rays.shape[0]), "upnerf_" + name)
+
+
 class BakedScene:
     """`rgbs` [Nz, Ny, Nx, 4] fp32 on the device (r, g, b, sigma at the grid points, pruned at `level`), the box it spans and
     the OccupancyGrid of its kept sigmas.  An SH scene (from_records, from_direction_grids, build(sh_degree=1 | 2)) has
@@ -327,7 +365,6 @@ class BakedScene:
     pool = slots = bricks = None  # a sparse scene's (sparsify, from_bricks, build(sparse=True)): see _sparse
 
     def __init__(self, rgbs: torch.Tensor, bounds, level: float):
-        from .occupancy import OccupancyGrid
         require_cuda("BakedScene", rgbs)
         if rgbs.dtype != torch.float32 or rgbs.dim() != 4 or rgbs.shape[3] != 4 or not rgbs.is_contiguous():
             raise ValueError("rgbs is a contiguous fp32 tensor [Nz, Ny, Nx, 4]")
@@ -340,17 +377,12 @@ class BakedScene:
     def from_records(cls, records: torch.Tensor, bounds, level: float, sh_degree: int) -> "BakedScene":
         """An SH scene from its records, a contiguous uint8 device tensor [Nz, Ny, Nx, 32 (degree 1) | 64 (degree 2)] laid out as
         include/upnerf_hip.h says; the occupancy bits are those of the records' sigmas."""
-        from .occupancy import OccupancyGrid
         degree = _degree(sh_degree)
         require_cuda("BakedScene.from_records", records)
         size = RECORD_BYTES[degree]
         if records.dtype != torch.uint8 or records.dim() != 4 or records.shape[3] != size or min(records.shape[:3]) < 2:
             raise ValueError(f"records is a uint8 tensor [Nz, Ny, Nx, {size}] with two points per axis at least")
-        records = records.contiguous()
-        if records.data_ptr() % size:  # (a record is aligned to its own size)
-            spare = torch.empty(records.numel() + size, dtype=torch.uint8, device=records.device)
-            off = -spare.data_ptr() % size
-            records = spare[off:off + records.numel()].view(records.shape).copy_(records)
+        records = _aligned_copy(records.contiguous(), size)  # (a record is aligned to its own size)
         self = cls.__new__(cls)
         self.rgbs, self.records, self.sh_degree = None, records, degree
         self.bounds = box(bounds, strict=True)
@@ -366,7 +398,6 @@ class BakedScene:
                 degree: int) -> "BakedScene":
         """The sparse scene of a pool [n_bricks, 9, 9, 9, 4] fp32 (degree 0) or [n_bricks, 9, 9, 9, 32 | 64] uint8 aligned to its
         point size, and its table.  Every sparse scene gets its bits here, from the pool alone (upnerf_brick_occ)."""
-        from .occupancy import OccupancyGrid
         self = cls.__new__(cls)
         self.rgbs, self.records, self.sh_degree = None, None, int(degree)
         self.pool, self.slots, self.bricks = pool, slots, bricks
@@ -375,7 +406,7 @@ class BakedScene:
         self.level = float(level)
         E = POINT_BYTES[self.sh_degree]
         # the address the marcher is given: the pool's, or with no brick at all one spare aligned point (never read)
-        self._pool_bytes = _point_bytes(pool).view(-1) if bricks.numel() else _aligned(E, E, slots.device)
+        self._pool_bytes = pool.view(torch.uint8).view(-1) if bricks.numel() else _aligned(E, E, slots.device)
         Nx, Ny, Nz = self._resolution
         words = brick_words(self._pool_bytes, slots, bricks.numel(), self._resolution, E, SIGMA_AT[self.sh_degree])
         self.occupancy = OccupancyGrid(words, self.bounds, (Nx - 1, Ny - 1, Nz - 1))
@@ -448,9 +479,7 @@ class BakedScene:
             raise ValueError("sigma is a fp32 tensor [Nz, Ny, Nx] with two points per axis at least")
         if rgb is not None and (rgb.dtype != torch.float32 or tuple(rgb.shape) != tuple(sigma.shape) + (3,)):
             raise ValueError("rgb is a fp32 tensor [Nz, Ny, Nx, 3]")
-        level = float(level)
-        if level != level:
-            raise ValueError("level is not a number")
+        level = _level(level)
         sigma = sigma.detach().contiguous()
         rgb = rgb.detach().contiguous() if rgb is not None else None
         rgbs = torch.empty(tuple(sigma.shape) + (4,), device=sigma.device, dtype=torch.float32)
@@ -473,9 +502,7 @@ class BakedScene:
         degree = _degree(sh_degree)
         W = sh_weights(dirs, degree)
         nb, K = W.shape
-        level = float(level)
-        if level != level:
-            raise ValueError("level is not a number")
+        level = _level(level)
         sigma = sigma.detach().contiguous()
         n, dev = sigma.numel(), sigma.device
         acc = torch.empty(tuple(sigma.shape) + (3, nb), device=dev, dtype=torch.float32)
@@ -486,13 +513,7 @@ class BakedScene:
             rgb = rgb.detach().contiguous()
             a = _lib.ShAccumulateArgs(n=n, nb=nb, first=int(k == 0), w=(C.c_float * 9)(*W[:, k].tolist()), rgb=ptr(rgb), acc=ptr(acc))
             check(TIMER.run("sh_accumulate", lambda: lib.upnerf_sh_accumulate(C.byref(a), stream()), units=n), "upnerf_sh_accumulate")
-        size = RECORD_BYTES[degree]
-        spare = torch.empty(n * size + size, dtype=torch.uint8, device=dev)
-        off = -spare.data_ptr() % size
-        records = spare[off:off + n * size].view(tuple(sigma.shape) + (size,))
-        a = _lib.BakedShPackArgs(n=n, level=level, degree=degree, sigma=ptr(sigma), acc=ptr(acc), records=ptr(records), kept=None)
-        check(TIMER.run("baked_sh_pack", lambda: lib.upnerf_baked_sh_pack(C.byref(a), stream()), units=n), "upnerf_baked_sh_pack")
-        return records
+        return pack_records(acc, sigma, degree, level)
 
     @classmethod
     @torch.no_grad()
@@ -543,29 +564,23 @@ class BakedScene:
                 raise ValueError("view_dir is the ONE direction of a scene without view dependence: with sh_degree > 0 pass dirs")
             dirs = sphere_directions() if dirs is None else np.asarray(torch.as_tensor(dirs).detach().cpu().numpy(), np.float64)
             sh_weights(dirs, sh_degree)  # (refused before any pass over the field)
-            sigma = density_grid(system, bounds, resolution, field=field, chunk=chunk)
-            if sparse:
-                return cls._build_sparse(system, sigma, bounds, resolution, level, img_id, rows, None, field, chunk, sh_degree, dirs)
-            colour = lambda k: field_colour(system, bounds, resolution, dirs[k], img_id=img_id, rows=rows, field=field, chunk=chunk)
-            return cls._project(sigma, colour, dirs, bounds, level, sh_degree)
-        if dirs is not None:
+        elif dirs is not None:
             raise ValueError("dirs are the directions of a spherical-harmonic fit: pass sh_degree = 1 or 2 with them")
-        if view_dir is None:
+        elif view_dir is None:
             view_dir = mean_optical_axis(system)
         sigma = density_grid(system, bounds, resolution, field=field, chunk=chunk)
         if sparse:
-            return cls._build_sparse(system, sigma, bounds, resolution, level, img_id, rows, view_dir, field, chunk, 0, None)
-        rgb = field_colour(system, bounds, resolution, view_dir, img_id=img_id, rows=rows, field=field, chunk=chunk)
-        return cls.from_grids(sigma, rgb, bounds, level)
+            return cls._build_sparse(system, sigma, bounds, resolution, level, img_id, rows, view_dir, field, chunk, int(sh_degree), dirs)
+        colour = lambda d: field_colour(system, bounds, resolution, d, img_id=img_id, rows=rows, field=field, chunk=chunk)
+        if sh_degree != 0:
+            return cls._project(sigma, lambda k: colour(dirs[k]), dirs, bounds, level, sh_degree)
+        return cls.from_grids(sigma, colour(view_dir), bounds, level)
 
     @classmethod
     @torch.no_grad()
     def _build_sparse(cls, system, sigma, bounds, resolution, level, img_id, rows, view_dir, field, chunk, degree, dirs) -> "BakedScene":
         """build(sparse=True) from the dense sigma on: table, sigma to the pool, colour on the pool's lines, packing."""
-        from .occupancy import OccupancyGrid
-        level = float(level)
-        if level != level:
-            raise ValueError("level is not a number")
+        level = _level(level)
         res = tuple(int(n) for n in resolution)
         # the cells that touch a kept point: a corner finite and >= max(level, TINY) is a corner that is finite, > 0 and >= level
         occ = OccupancyGrid.from_density(sigma, bounds, level=max(level, TINY), dilate=0)
@@ -595,9 +610,7 @@ class BakedScene:
         `far`.  stop > 0 ends a ray once its transmittance falls below it.  out: preallocated buffers of at least R rows."""
         require_cuda("BakedScene.render", rays)
         step, background, stop = _render_args(rays, step, background, stop)
-        rays = rays.contiguous()
-        if rays.data_ptr() % 16:
-            rays = rays.clone()
+        rays = _rays16(rays)
         R, dev = rays.shape[0], rays.device
         if out is None:
             out = {"rgb": torch.empty(R, 3, device=dev), "depth": torch.empty(R, device=dev), "opacity": torch.empty(R, device=dev)}
@@ -605,21 +618,8 @@ class BakedScene:
             t = out[k]
             if t.dtype != torch.float32 or t.shape[0] < R or tuple(t.shape[1:]) != shape or t.device != dev:
                 raise ValueError("the outputs are fp32 [>= R, 3], [>= R] and [>= R] on the rays' device")
-        Cx, Cy, Cz = self.occupancy.dims
-        lo, hi = self.bounds
-        common = dict(Cx=Cx, Cy=Cy, Cz=Cz, R=R, lo=c_float3(lo), hi=c_float3(hi), step=step, background=background, stop=stop,
-                      words=ptr(self.occupancy.words), rays=ptr(rays), rgb=ptr(out["rgb"]), depth=ptr(out["depth"]),
-                      opacity=ptr(out["opacity"]))
-        if self.sparse:
-            a = _lib.BakedSparseRenderArgs(degree=self.sh_degree, pool=ptr(self._pool_bytes), slots=ptr(self.slots), **common)
-            check(TIMER.run("baked_sparse_render", lambda: lib.upnerf_baked_sparse_render(C.byref(a), stream()), units=R),
-                  "upnerf_baked_sparse_render")
-        elif self.sh_degree:
-            a = _lib.BakedShRenderArgs(degree=self.sh_degree, records=ptr(self.records), **common)
-            check(TIMER.run("baked_sh_render", lambda: lib.upnerf_baked_sh_render(C.byref(a), stream()), units=R), "upnerf_baked_sh_render")
-        else:
-            a = _lib.BakedRenderArgs(rgbs=ptr(self.rgbs), **common)
-            check(TIMER.run("baked_render", lambda: lib.upnerf_baked_render(C.byref(a), stream()), units=R), "upnerf_baked_render")
+        march(self._pool_bytes if self.sparse else self.grid, self.sh_degree, self.slots, self.occupancy, self.bounds, rays, step,
+              background, stop, out["rgb"], out["depth"], out["opacity"])
         return {k: out[k][:R] for k in ("rgb", "depth", "opacity")}
 
     def tune(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8):
@@ -708,20 +708,18 @@ class BakedScene:
 def save_arrays(path: str, rgbs: np.ndarray, bounds, level: float, sh_degree: int = 0) -> None:
     """rgbs: the fp32 grid [Nz, Ny, Nx, 4]; with sh_degree = 1 | 2 the uint8 records [Nz, Ny, Nx, 32 | 64] instead, written as
     the arrays records, degree, bounds, level."""
+    grid = np.asarray(rgbs)
     if sh_degree != 0:
-        records = np.asarray(rgbs)
-        if records.dtype != np.uint8 or records.ndim != 4 or records.shape[3] != RECORD_BYTES[_degree(sh_degree)]:
+        if grid.dtype != np.uint8 or grid.ndim != 4 or grid.shape[3] != RECORD_BYTES[_degree(sh_degree)]:
             raise ValueError(f"the records of degree {sh_degree} are a uint8 array [Nz, Ny, Nx, {RECORD_BYTES[sh_degree]}]")
-        lo, hi = box(bounds, strict=True)
-        with open(path, "wb") as fh:
-            np.savez(fh, records=records, degree=np.int64(sh_degree), bounds=np.asarray([lo, hi], np.float64), level=np.float64(level))
-        return
-    rgbs = np.asarray(rgbs)
-    if rgbs.dtype != np.float32 or rgbs.ndim != 4 or rgbs.shape[3] != 4:
-        raise ValueError("rgbs is a fp32 array [Nz, Ny, Nx, 4]")
+        arrays = dict(records=grid, degree=np.int64(sh_degree))
+    else:
+        if grid.dtype != np.float32 or grid.ndim != 4 or grid.shape[3] != 4:
+            raise ValueError("rgbs is a fp32 array [Nz, Ny, Nx, 4]")
+        arrays = dict(rgbs=grid)
     lo, hi = box(bounds, strict=True)
     with open(path, "wb") as fh:  # (a file object: numpy appends no .npz of its own to the name)
-        np.savez(fh, rgbs=rgbs, bounds=np.asarray([lo, hi], np.float64), level=np.float64(level))
+        np.savez(fh, **arrays, bounds=np.asarray([lo, hi], np.float64), level=np.float64(level))
 
 
 BRICK_KEYS = {"pool", "bricks", "resolution", "degree", "bounds", "level"}

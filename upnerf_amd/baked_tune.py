@@ -23,9 +23,9 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream
-from .baked import RECORD_BYTES, SIGMA_BYTE, BakedScene, _aligned, _render_args
+from .baked import SIGMA_BYTE, BakedScene, _common, _rays16, _render_args, march, pack_records
 from .ops import TIMER
-from .static_scene import c_float3, require_cuda
+from .static_scene import require_cuda
 
 __all__ = ["SceneParams", "render", "backward", "project", "BakedTuner", "distill", "SPARSE_REFUSAL"]
 
@@ -46,16 +46,6 @@ def unpack_records(records: torch.Tensor, degree: int) -> Tuple[torch.Tensor, to
     coef = records[..., :6 * nb].contiguous().view(torch.float16).to(torch.float32).view(records.shape[:3] + (3, nb))
     at = SIGMA_BYTE[degree]
     return coef.contiguous(), records[..., at:at + 4].contiguous().view(torch.float32).squeeze(-1).contiguous()
-
-
-def pack_records(coef: torch.Tensor, sigma: torch.Tensor, degree: int, level: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The records [shape of sigma, 32 | 64] of fp32 coefficients and sigmas (upnerf_baked_sh_pack at `level`)."""
-    size, n = RECORD_BYTES[degree], sigma.numel()
-    if out is None:
-        out = _aligned(n * size, size, sigma.device)[:n * size].view(tuple(sigma.shape) + (size,))
-    a = _lib.BakedShPackArgs(n=n, level=float(level), degree=degree, sigma=ptr(sigma), acc=ptr(coef), records=ptr(out), kept=None)
-    check(TIMER.run("baked_sh_pack", lambda: lib.upnerf_baked_sh_pack(C.byref(a), stream()), units=n), "upnerf_baked_sh_pack")
-    return out
 
 
 class SceneParams:
@@ -95,28 +85,10 @@ class SceneParams:
         return (self.rgbs,) if self.degree == 0 else (self.coef, self.sigma)
 
 
-def _common(occupancy, bounds, rays, step, background, stop):
-    Cx, Cy, Cz = occupancy.dims
-    lo, hi = bounds
-    return dict(Cx=Cx, Cy=Cy, Cz=Cz, R=rays.shape[0], lo=c_float3(lo), hi=c_float3(hi), step=step, background=background, stop=stop,
-                words=ptr(occupancy.words), rays=ptr(rays))
-
-
-def _rays16(rays: torch.Tensor) -> torch.Tensor:
-    rays = rays.detach().contiguous()
-    return rays.clone() if rays.data_ptr() % 16 else rays
-
-
 def _forward(points: torch.Tensor, degree: int, occupancy, bounds, rays, step, background, stop):
     R, dev = rays.shape[0], rays.device
     rgb, depth, opacity = torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)
-    common = dict(_common(occupancy, bounds, rays, step, background, stop), rgb=ptr(rgb), depth=ptr(depth), opacity=ptr(opacity))
-    if degree == 0:
-        a = _lib.BakedRenderArgs(rgbs=ptr(points), **common)
-        check(TIMER.run("baked_render", lambda: lib.upnerf_baked_render(C.byref(a), stream()), units=R), "upnerf_baked_render")
-    else:
-        a = _lib.BakedShRenderArgs(degree=degree, records=ptr(points), **common)
-        check(TIMER.run("baked_sh_render", lambda: lib.upnerf_baked_sh_render(C.byref(a), stream()), units=R), "upnerf_baked_sh_render")
+    march(points, degree, None, occupancy, bounds, rays, step, background, stop, rgb, depth, opacity)
     return rgb, depth, opacity
 
 

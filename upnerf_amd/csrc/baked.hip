@@ -14,17 +14,18 @@
 //                        picture is, bit for bit, the one that visits every sample (tests/test_hip_baked.py runs both).
 //                        A visited sample reads its eight corners as eight 16-byte loads; the rays of a wave are 64 neighbouring
 //                        pixels of an image row and read neighbouring corners.  All per-ray state is in registers; no LDS.
-//   upnerf_baked_sh_render  the same march (ONE template, baked_march<DEG>) through records that hold, per grid point, the fp16
+//   upnerf_baked_sh_render  the same march (ONE template, baked_march<DEG, SPARSE>) through records that hold, per grid point, the fp16
 //                        coefficients of a spherical-harmonic expansion of the colour over direction and a fp32 sigma (32 bytes at
 //                        degree 1, 64 at degree 2).  The basis of the ray's direction is formed once per ray and
 //                        kept in registers; a corner is reduced to (r, g, b, sigma) as it is read -- nb fmas per channel -- so the
 //                        blend sees the four floats per corner it sees at degree 0.  Degree 0 is the instantiation that reads rgbs.
 //   upnerf_baked_sparse_render  the same march again through a brick pool (brick.hip): the template's second
-//                        parameter is the layout.  Where the dense march tests a sample's brick bit, the sparse one reads the
+//                        parameter is the layout, and all three entry points fill one BakedArgs.  Where the dense march tests a sample's brick bit, the sparse one reads the
 //                        brick's slot (< 0: the empty brick), and the eight corners are base, + 1, + 9, + 81 inside that slot.
 //   upnerf_sh_accumulate, upnerf_baked_sh_pack  the projection's running sum over directions, and the records from it.
 //   upnerf_baked_render_bwd  the gradient of a dense scene's render with respect to its points: one thread per
-//                        ray again, two marches -- the first forms Q = sum w q, the second hands every sample's four gradients to
+//                        ray again, two marches with the forward's own walk, ray and blend (baked_walk, BakedRay, baked_blend:
+//                        each stated once) -- the first forms Q = sum w q, the second hands every sample's four gradients to
 //                        the eight corners of its cell, summed in registers while the ray stays in the cell and added to memory
 //                        with atomicAdd(float*) when it leaves it.  The one entry point here whose bits depend on the run.
 //   upnerf_baked_project the tuned points back into the marcher's domain (sigma >= 0 and finite; degree 0: colours in [0, 1]).
@@ -33,6 +34,8 @@
 #include "grid.cuh"
 
 #include <math.h>
+
+#include <type_traits>
 
 namespace {
 
@@ -131,179 +134,44 @@ struct BakedCorner<0> {
   __host__ __device__ __forceinline__ f32x4 operator()(int64_t p) const { return pts[p]; }
 };
 
-// where the points of a scene are: the dense layouts index the whole grid [Cz+1][Cy+1][Cx+1]; the sparse one (brick.hip;
-// include/upnerf_hip.h states it) finds a sample's brick in a slot table and its corners among the 9 x 9 x 9 points of that slot
-template <class Args>
-struct BakedLayout;
-template <>
-struct BakedLayout<upnerf_baked_render_args> {
-  static constexpr bool SPARSE = false;
-  static __host__ __device__ __forceinline__ const void* points(const upnerf_baked_render_args& A) { return A.rgbs; }
-};
-template <>
-struct BakedLayout<upnerf_baked_sh_render_args> {
-  static constexpr bool SPARSE = false;
-  static __host__ __device__ __forceinline__ const void* points(const upnerf_baked_sh_render_args& A) { return A.records; }
-};
-template <>
-struct BakedLayout<upnerf_baked_sparse_render_args> {
-  static constexpr bool SPARSE = true;
-  static __host__ __device__ __forceinline__ const void* points(const upnerf_baked_sparse_render_args& A) { return A.pool; }
-};
-#define BAKED_BRICK_P UPNERF_BRICK_POINTS
-
-// the march of one ray row (host and device: the host build is what a CPU program checks against the fp64 restatement)
-template <int DEG, class Args>
-__host__ __device__ __forceinline__ BakedOut baked_march(const Args& A, const BakedGrid& G, const OccDims& dm, const float* row,
-                                                         bool use_bits) {
-  constexpr bool SPARSE = BakedLayout<Args>::SPARSE;
-  const float o[3] = {row[0], row[1], row[2]}, d[3] = {row[3], row[4], row[5]};
-  const float near = row[6], far = row[7];
-  BakedOut out;
-  out.rgb[0] = out.rgb[1] = out.rgb[2] = 0.0f;
-  out.depth = 0.0f;
-  out.opacity = 0.0f;
-  bool ok = far > near;
+// a ray as both marches read it: the 32-byte row o | d | near | far (16-byte aligned), whether it can hit at all (eight finite
+// numbers, far > near), its sample count K, |d| and the optical length of one step
+struct BakedRay {
+  float o[3], d[3], near, far;
+  bool ok;
+  int K;
+  float len, delta;
+  __host__ __device__ __forceinline__ BakedRay(const float* row, float step) {
+    const f32x4 r0 = ((const f32x4*)row)[0], r1 = ((const f32x4*)row)[1];
+    o[0] = r0.x, o[1] = r0.y, o[2] = r0.z, d[0] = r0.w, d[1] = r1.x, d[2] = r1.y, near = r1.z, far = r1.w;
+    ok = far > near;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) ok = ok && isfinite(row[j]);
-  if (ok) {
-    const float nk = ceilf((far - near) / A.step);
-    const int K = nk < (float)UPNERF_BAKED_MAX_SAMPLES ? (int)nk : UPNERF_BAKED_MAX_SAMPLES;
-    const float len = sqrtf(fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0])));
-    const float delta = A.step * len;
-    const uint32_t* fine = A.words;
-    const uint32_t* brick = A.words + dm.fine_words;
-    const BakedCorner<DEG> pts(BakedLayout<Args>::points(A), d, len);
-    float T = 1.0f;
-    int k = 0;
-    while (k < K) {
-      const BakedSample s = baked_locate(G, o, d, near, A.step, k);
-      int next = k + 1;
-      if (!s.inside) {
-        // outside on an axis along which the ray does not come back: every later sample is outside too
-        bool gone = false;
-        float t_in = -INFINITY;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          if (s.side[a] == 1 || s.side[a] == -1) {
-            const bool away = s.side[a] > 0 ? d[a] >= 0.0f : d[a] <= 0.0f;
-            if (away) gone = true;
-            else t_in = fmaxf(t_in, ((s.side[a] > 0 ? G.lo[a] + G.Cf[a] / G.inv[a] : G.lo[a]) - o[a]) / d[a]);
-          }
-        }
-        if (gone) break;
-        if (use_bits) {
-          const int kp = baked_propose(t_in, near, A.step, K);
-          if (kp > k) {
-            const BakedSample q = baked_locate(G, o, d, near, A.step, kp);
-            bool same = false;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) same = same || ((s.side[a] == 1 || s.side[a] == -1) && q.side[a] == s.side[a]);
-            if (same) next = kp + 1;
-          }
-        }
-        k = next;
-        continue;
-      }
-      int64_t slot = 0;  // (sparse: the sample's brick in the pool; it is read with or without the bits, the points hang on it)
-      if (use_bits || SPARSE) {
-        const int bx = s.i[0] / OCC_BRICK, by = s.i[1] / OCC_BRICK, bz = s.i[2] / OCC_BRICK;
-        const int64_t b = ((int64_t)bz * dm.By + by) * dm.Bx + bx;
-        int shift = -1;  // the empty region the sample lies in: 3 = its brick, 0 = its cell, -1 = none
-        bool empty_brick;
-        if constexpr (SPARSE) empty_brick = (slot = A.slots[b]) < 0;
-        else empty_brick = !occ_bit(brick, b);
-        if (empty_brick) shift = 3;
-        else if (use_bits && !occ_bit(fine, ((int64_t)s.i[2] * dm.Cy + s.i[1]) * dm.Cx + s.i[0])) shift = 0;
-        if (shift >= 0 && !use_bits) {  // (sparse, every sample visited: an empty brick holds nothing)
-          k = next;
-          continue;
-        }
-        if (shift >= 0) {
-          float t_out = INFINITY;
-#pragma unroll
-          for (int a = 0; a < 3; ++a) {
-            if (d[a] == 0.0f) continue;
-            const int r = s.i[a] >> shift;
-            int plane = d[a] > 0.0f ? (r + 1) << shift : r << shift;
-            plane = plane < G.C[a] ? plane : G.C[a];
-            t_out = fminf(t_out, ((G.lo[a] + (float)plane / G.inv[a]) - o[a]) / d[a]);
-          }
-          const int kp = baked_propose(t_out, near, A.step, K);
-          if (kp > k) {
-            const BakedSample q = baked_locate(G, o, d, near, A.step, kp);
-            if (q.inside && (q.i[0] >> shift) == (s.i[0] >> shift) && (q.i[1] >> shift) == (s.i[1] >> shift) &&
-                (q.i[2] >> shift) == (s.i[2] >> shift))
-              next = kp + 1;
-          }
-          k = next;
-          continue;
-        }
-      }
-      // the sample counts: trilinear blend of the eight corners, x first, then y, then z
-      const int64_t sy = SPARSE ? BAKED_BRICK_P : G.sy, sz = SPARSE ? BAKED_BRICK_P * BAKED_BRICK_P : G.sz;
-      const int64_t base = SPARSE ? slot * (BAKED_BRICK_P * BAKED_BRICK_P * BAKED_BRICK_P) +
-                                        (((s.i[2] % OCC_BRICK) * BAKED_BRICK_P + s.i[1] % OCC_BRICK) * BAKED_BRICK_P + s.i[0] % OCC_BRICK)
-                                  : ((int64_t)s.i[2] * G.sz + (int64_t)s.i[1] * G.sy) + s.i[0];
-      const float fx = s.g[0] - (float)s.i[0], fy = s.g[1] - (float)s.i[1], fz = s.g[2] - (float)s.i[2];
-      const f32x4 c000 = pts(base), c100 = pts(base + 1);
-      const f32x4 c010 = pts(base + sy), c110 = pts(base + sy + 1);
-      const f32x4 c001 = pts(base + sz), c101 = pts(base + sz + 1);
-      const f32x4 c011 = pts(base + sz + sy), c111 = pts(base + sz + sy + 1);
-      float v[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float x00 = fmaf(fx, c100[c] - c000[c], c000[c]), x10 = fmaf(fx, c110[c] - c010[c], c010[c]);
-        const float x01 = fmaf(fx, c101[c] - c001[c], c001[c]), x11 = fmaf(fx, c111[c] - c011[c], c011[c]);
-        const float y0 = fmaf(fy, x10 - x00, x00), y1 = fmaf(fy, x11 - x01, x01);
-        v[c] = fmaf(fz, y1 - y0, y0);
-      }
-      if (DEG > 0) {  // an expansion is not held to [0, 1] as the colour head's sigmoid is
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = fminf(fmaxf(v[c], 0.0f), 1.0f);
-      }
-      const float e = expf(-delta * v[3]);
-      const float alpha = 1.0f - e;
-      const float w = T * alpha;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) out.rgb[c] = fmaf(w, v[c], out.rgb[c]);
-      out.depth = fmaf(w, s.t, out.depth);
-      out.opacity += w;
-      T *= 1.0f - alpha;
-      if (A.stop > 0.0f && T < A.stop) break;
-      k = next;
+    for (int j = 0; j < 4; ++j) ok = ok && isfinite(r0[j]) && isfinite(r1[j]);
+    K = 0;
+    len = delta = 0.0f;
+    if (ok) {
+      const float nk = ceilf((far - near) / step);
+      K = nk < (float)UPNERF_BAKED_MAX_SAMPLES ? (int)nk : UPNERF_BAKED_MAX_SAMPLES;
+      len = sqrtf(fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0])));
+      delta = step * len;
     }
   }
-  const float rest = 1.0f - out.opacity;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) out.rgb[c] = fmaf(rest, A.background, out.rgb[c]);
-  out.depth = fmaf(rest, far, out.depth);
-  return out;
-}
+};
 
-template <int DEG, class Args>
-__global__ __launch_bounds__(BAKED_THREADS) void baked_render_kernel(Args a, BakedGrid G, OccDims dm) {
-  const int r = blockIdx.x * BAKED_THREADS + threadIdx.x;
-  if (r >= a.R) return;
-  const f32x4* rp = (const f32x4*)(a.rays + (int64_t)r * 8);  // (rows of 32 bytes in a buffer the host found 16-byte aligned)
-  const f32x4 r0 = rp[0], r1 = rp[1];
-  const float row[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-  const BakedOut out = baked_march<DEG>(a, G, dm, row, true);
-  float* c = a.rgb + (int64_t)r * 3;
-  c[0] = out.rgb[0], c[1] = out.rgb[1], c[2] = out.rgb[2];
-  a.depth[r] = out.depth;
-  a.opacity[r] = out.opacity;
-}
-
-// ---- the backward march: upnerf_baked_render_bwd (include/upnerf_hip.h states the gradient; DESIGN.md 2.34) ---------------------
-// The walk of baked_march over a dense layout, restated: the samples that count -- inside the box, in a cell with a set bit -- are
-// handed in sample order to visit(s, base), `base` the point index of the cell's corner (0, 0, 0); visit returns true to end the
-// ray (`stop`).  baked_locate, baked_propose and the acceptance tests are baked_march's, so the visited set is the forward's.
-// (Handing baked_march's own loop a visitor instead moved the degree-0 forward kernels from 78 / 74 to 80 / 76 registers: the
-// forward stays as it was and the walk is stated twice.)
-template <class Visit>
-__device__ __forceinline__ void baked_walk_dense(const uint32_t* words, float step, const BakedGrid& G, const OccDims& dm, const float* o,
-                                                 const float* d, float near, int K, Visit&& visit) {
+// The walk of a ray, the ONLY statement of the skipping logic: the samples that count -- inside the box, in a cell with a set bit
+// (use_bits == false: every sample inside the box; a sparse march still passes over the empty bricks, which hold nothing) -- are
+// handed in sample order to visit(s, base, sy, sz): `base` the point index of the cell's corner (0, 0, 0), sy and sz the strides
+// to its y and z neighbours; visit returns true to end the ray (`stop`).  The forward and both passes of the backward march with
+// it, so the backward's visited set is the forward's by construction.  The dense layouts index the whole grid
+// [Cz+1][Cy+1][Cx+1]; the sparse one (brick.hip; include/upnerf_hip.h states it) finds a sample's brick in `slots` (< 0: the empty
+// brick) and its corners among the 9 x 9 x 9 points of that slot.
+template <bool SPARSE, class Visit>
+__host__ __device__ __forceinline__ void baked_walk(const uint32_t* words, const int32_t* slots, float step, const BakedGrid& G,
+                                                    const OccDims& dm, const BakedRay& ray, bool use_bits, Visit&& visit) {
+  constexpr int P = UPNERF_BRICK_POINTS;
+  const float *o = ray.o, *d = ray.d;
+  const float near = ray.near;
+  const int K = ray.K;
   const uint32_t* fine = words;
   const uint32_t* brick = words + dm.fine_words;
   int k = 0;
@@ -311,6 +179,7 @@ __device__ __forceinline__ void baked_walk_dense(const uint32_t* words, float st
     const BakedSample s = baked_locate(G, o, d, near, step, k);
     int next = k + 1;
     if (!s.inside) {
+      // outside on an axis along which the ray does not come back: every later sample is outside too
       bool gone = false;
       float t_in = -INFINITY;
 #pragma unroll
@@ -322,92 +191,161 @@ __device__ __forceinline__ void baked_walk_dense(const uint32_t* words, float st
         }
       }
       if (gone) break;
-      const int kp = baked_propose(t_in, near, step, K);
-      if (kp > k) {
-        const BakedSample q = baked_locate(G, o, d, near, step, kp);
-        bool same = false;
+      if (use_bits) {
+        const int kp = baked_propose(t_in, near, step, K);
+        if (kp > k) {
+          const BakedSample q = baked_locate(G, o, d, near, step, kp);
+          bool same = false;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) same = same || ((s.side[a] == 1 || s.side[a] == -1) && q.side[a] == s.side[a]);
-        if (same) next = kp + 1;
+          for (int a = 0; a < 3; ++a) same = same || ((s.side[a] == 1 || s.side[a] == -1) && q.side[a] == s.side[a]);
+          if (same) next = kp + 1;
+        }
       }
       k = next;
       continue;
     }
-    const int bx = s.i[0] / OCC_BRICK, by = s.i[1] / OCC_BRICK, bz = s.i[2] / OCC_BRICK;
-    int shift = -1;  // the empty region the sample lies in: 3 = its brick, 0 = its cell, -1 = none
-    if (!occ_bit(brick, ((int64_t)bz * dm.By + by) * dm.Bx + bx)) shift = 3;
-    else if (!occ_bit(fine, ((int64_t)s.i[2] * dm.Cy + s.i[1]) * dm.Cx + s.i[0])) shift = 0;
-    if (shift >= 0) {
-      float t_out = INFINITY;
+    int64_t slot = 0;  // (sparse: the sample's brick in the pool; it is read with or without the bits, the points hang on it)
+    if (use_bits || SPARSE) {
+      const int bx = s.i[0] / OCC_BRICK, by = s.i[1] / OCC_BRICK, bz = s.i[2] / OCC_BRICK;
+      const int64_t b = ((int64_t)bz * dm.By + by) * dm.Bx + bx;
+      int shift = -1;  // the empty region the sample lies in: 3 = its brick, 0 = its cell, -1 = none
+      bool empty_brick;
+      if constexpr (SPARSE) empty_brick = (slot = slots[b]) < 0;
+      else empty_brick = !occ_bit(brick, b);
+      if (empty_brick) shift = 3;
+      else if (use_bits && !occ_bit(fine, ((int64_t)s.i[2] * dm.Cy + s.i[1]) * dm.Cx + s.i[0])) shift = 0;
+      if (shift >= 0 && !use_bits) {  // (sparse, every sample visited: an empty brick holds nothing)
+        k = next;
+        continue;
+      }
+      if (shift >= 0) {
+        float t_out = INFINITY;
 #pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        if (d[a] == 0.0f) continue;
-        const int r = s.i[a] >> shift;
-        int plane = d[a] > 0.0f ? (r + 1) << shift : r << shift;
-        plane = plane < G.C[a] ? plane : G.C[a];
-        t_out = fminf(t_out, ((G.lo[a] + (float)plane / G.inv[a]) - o[a]) / d[a]);
+        for (int a = 0; a < 3; ++a) {
+          if (d[a] == 0.0f) continue;
+          const int r = s.i[a] >> shift;
+          int plane = d[a] > 0.0f ? (r + 1) << shift : r << shift;
+          plane = plane < G.C[a] ? plane : G.C[a];
+          t_out = fminf(t_out, ((G.lo[a] + (float)plane / G.inv[a]) - o[a]) / d[a]);
+        }
+        const int kp = baked_propose(t_out, near, step, K);
+        if (kp > k) {
+          const BakedSample q = baked_locate(G, o, d, near, step, kp);
+          if (q.inside && (q.i[0] >> shift) == (s.i[0] >> shift) && (q.i[1] >> shift) == (s.i[1] >> shift) &&
+              (q.i[2] >> shift) == (s.i[2] >> shift))
+            next = kp + 1;
+        }
+        k = next;
+        continue;
       }
-      const int kp = baked_propose(t_out, near, step, K);
-      if (kp > k) {
-        const BakedSample q = baked_locate(G, o, d, near, step, kp);
-        if (q.inside && (q.i[0] >> shift) == (s.i[0] >> shift) && (q.i[1] >> shift) == (s.i[1] >> shift) &&
-            (q.i[2] >> shift) == (s.i[2] >> shift))
-          next = kp + 1;
-      }
-      k = next;
-      continue;
     }
-    if (visit(s, ((int64_t)s.i[2] * G.sz + (int64_t)s.i[1] * G.sy) + s.i[0])) break;
+    const int64_t sy = SPARSE ? P : G.sy, sz = SPARSE ? P * P : G.sz;
+    const int64_t base = SPARSE ? slot * (P * P * P) + (((s.i[2] % OCC_BRICK) * P + s.i[1] % OCC_BRICK) * P + s.i[0] % OCC_BRICK)
+                                : ((int64_t)s.i[2] * G.sz + (int64_t)s.i[1] * G.sy) + s.i[0];
+    if (visit(s, base, sy, sz)) break;
     k = next;
   }
 }
 
-// one counted sample as both passes of the backward see it: the forward's blend, clamp and compositing weight, and q
-struct BakedBwdSample {
-  float f[3];   // the sample's position in its cell
-  float w, Tn;  // w_k and T_{k+1}
-  float q;
+// one counted sample as every march sees it: the trilinear blend of the eight corners (x first, then y, then z), the clamp of an
+// expansion's colours, and the compositing step from the transmittance T before the sample
+struct BakedBlend {
+  float f[3];     // the sample's position in its cell
+  float v[4];     // r, g, b (clamped at DEG > 0), sigma
+  float w, Tn;    // w_k and T_{k+1}
   unsigned live;  // bit j: corner j (x = j & 1, y = j >> 1 & 1, z = j >> 2) stores a sigma that is not zero
   unsigned open;  // bit c: colour channel c was not clamped
 };
 
 template <int DEG>
-__device__ __forceinline__ BakedBwdSample baked_bwd_sample(const BakedCorner<DEG>& pts, const BakedGrid& G, const BakedSample& s,
-                                                           int64_t base, float delta, float T, const float* g, float background,
-                                                           float far) {
-  BakedBwdSample b;
+__host__ __device__ __forceinline__ BakedBlend baked_blend(const BakedCorner<DEG>& pts, const BakedSample& s, int64_t base, int64_t sy,
+                                                           int64_t sz, float delta, float T) {
+  BakedBlend b;
   b.f[0] = s.g[0] - (float)s.i[0], b.f[1] = s.g[1] - (float)s.i[1], b.f[2] = s.g[2] - (float)s.i[2];
-  f32x4 c[8];
+  // (written out, not a loop over j: with the loop the dense degree-1 forward holds 129 registers instead of 104, a wave less)
+  const f32x4 c[8] = {pts(base),      pts(base + 1),      pts(base + sy),      pts(base + sy + 1),
+                      pts(base + sz), pts(base + sz + 1), pts(base + sz + sy), pts(base + sz + sy + 1)};
 #pragma unroll
-  for (int j = 0; j < 8; ++j) c[j] = pts(base + (j & 1) + (j >> 1 & 1) * G.sy + (j >> 2) * G.sz);
-  float v[4];
-#pragma unroll
-  for (int ch = 0; ch < 4; ++ch) {  // (baked_march's blend: x first, then y, then z)
+  for (int ch = 0; ch < 4; ++ch) {
     const float x00 = fmaf(b.f[0], c[1][ch] - c[0][ch], c[0][ch]), x10 = fmaf(b.f[0], c[3][ch] - c[2][ch], c[2][ch]);
     const float x01 = fmaf(b.f[0], c[5][ch] - c[4][ch], c[4][ch]), x11 = fmaf(b.f[0], c[7][ch] - c[6][ch], c[6][ch]);
     const float y0 = fmaf(b.f[1], x10 - x00, x00), y1 = fmaf(b.f[1], x11 - x01, x01);
-    v[ch] = fmaf(b.f[2], y1 - y0, y0);
+    b.v[ch] = fmaf(b.f[2], y1 - y0, y0);
   }
   b.live = 0u;
 #pragma unroll
   for (int j = 0; j < 8; ++j) b.live |= (c[j][3] != 0.0f ? 1u : 0u) << j;
   b.open = 7u;
-  if (DEG > 0) {
+  if (DEG > 0) {  // an expansion is not held to [0, 1] as the colour head's sigmoid is
     b.open = 0u;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-      b.open |= (v[ch] >= 0.0f && v[ch] <= 1.0f ? 1u : 0u) << ch;
-      v[ch] = fminf(fmaxf(v[ch], 0.0f), 1.0f);
+      b.open |= (b.v[ch] >= 0.0f && b.v[ch] <= 1.0f ? 1u : 0u) << ch;
+      b.v[ch] = fminf(fmaxf(b.v[ch], 0.0f), 1.0f);
     }
   }
-  const float e = expf(-delta * v[3]);
+  const float e = expf(-delta * b.v[3]);
   const float alpha = 1.0f - e;
   b.w = T * alpha;
   b.Tn = T * (1.0f - alpha);
-  b.q = fmaf(g[0], v[0] - background, fmaf(g[1], v[1] - background, fmaf(g[2], v[2] - background, fmaf(g[3], s.t - far, g[4]))));
   return b;
 }
 
+// what a forward launch reads: the scene's points (rgbs, records or a pool) with, for a pool, its slot table; the bits; the rays.
+// (The scalars come first as they do in the public structs: with the pointers first the dense degree-1 kernel compiles to 138
+// registers instead of 104 and loses a wave per SIMD)
+struct BakedArgs {
+  int R;
+  float step, background, stop;
+  const void* points;
+  const int32_t* slots;  // NULL: a dense layout
+  const uint32_t* words;
+  const float* rays;
+  float *rgb, *depth, *opacity;
+};
+
+// the march of one ray row (host and device: the host build is what a CPU program checks against the fp64 restatement)
+template <int DEG, bool SPARSE>
+__host__ __device__ __forceinline__ BakedOut baked_march(const BakedArgs& A, const BakedGrid& G, const OccDims& dm, const float* row,
+                                                         bool use_bits) {
+  const BakedRay ray(row, A.step);
+  BakedOut out;
+  out.rgb[0] = out.rgb[1] = out.rgb[2] = 0.0f;
+  out.depth = 0.0f;
+  out.opacity = 0.0f;
+  if (ray.ok) {
+    const BakedCorner<DEG> pts(A.points, ray.d, ray.len);
+    float T = 1.0f;
+    auto composite = [&](const BakedSample& s, int64_t base, int64_t sy, int64_t sz) __attribute__((always_inline)) {
+      const BakedBlend b = baked_blend<DEG>(pts, s, base, sy, sz, ray.delta, T);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) out.rgb[c] = fmaf(b.w, b.v[c], out.rgb[c]);
+      out.depth = fmaf(b.w, s.t, out.depth);
+      out.opacity += b.w;
+      T = b.Tn;
+      return A.stop > 0.0f && T < A.stop;
+    };
+    baked_walk<SPARSE>(A.words, A.slots, A.step, G, dm, ray, use_bits, composite);
+  }
+  const float rest = 1.0f - out.opacity;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out.rgb[c] = fmaf(rest, A.background, out.rgb[c]);
+  out.depth = fmaf(rest, ray.far, out.depth);
+  return out;
+}
+
+template <int DEG, bool SPARSE>
+__global__ __launch_bounds__(BAKED_THREADS) void baked_render_kernel(BakedArgs a, BakedGrid G, OccDims dm) {
+  const int r = blockIdx.x * BAKED_THREADS + threadIdx.x;
+  if (r >= a.R) return;
+  const BakedOut out = baked_march<DEG, SPARSE>(a, G, dm, a.rays + (int64_t)r * 8, true);
+  float* c = a.rgb + (int64_t)r * 3;
+  c[0] = out.rgb[0], c[1] = out.rgb[1], c[2] = out.rgb[2];
+  a.depth[r] = out.depth;
+  a.opacity[r] = out.opacity;
+}
+
+// ---- the backward march: upnerf_baked_render_bwd (include/upnerf_hip.h states the gradient; DESIGN.md 2.34) ---------------------
 template <int DEG>
 __global__ __launch_bounds__(BAKED_THREADS) void baked_render_bwd_kernel(upnerf_baked_render_bwd_args a, BakedGrid G, OccDims dm) {
   constexpr int NB = (DEG + 1) * (DEG + 1);
@@ -417,29 +355,23 @@ __global__ __launch_bounds__(BAKED_THREADS) void baked_render_bwd_kernel(upnerf_
   const float g[5] = {a.g_rgb[(int64_t)r * 3], a.g_rgb[(int64_t)r * 3 + 1], a.g_rgb[(int64_t)r * 3 + 2], a.g_depth ? a.g_depth[r] : 0.0f,
                       a.g_opacity ? a.g_opacity[r] : 0.0f};
   if (g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f && g[3] == 0.0f && g[4] == 0.0f) return;
-  const f32x4* rp = (const f32x4*)(a.rays + (int64_t)r * 8);
-  const f32x4 r0 = rp[0], r1 = rp[1];
-  const float row[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-  const float o[3] = {row[0], row[1], row[2]}, d[3] = {row[3], row[4], row[5]};
-  const float near = row[6], far = row[7];
-  bool ok = far > near;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) ok = ok && isfinite(row[j]);
-  if (!ok) return;  // a miss
-  const float nk = ceilf((far - near) / a.step);
-  const int K = nk < (float)UPNERF_BAKED_MAX_SAMPLES ? (int)nk : UPNERF_BAKED_MAX_SAMPLES;
-  const float len = sqrtf(fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0])));
-  const float delta = a.step * len;
-  const BakedCorner<DEG> pts(a.points, d, len);
+  const BakedRay ray(a.rays + (int64_t)r * 8, a.step);
+  if (!ray.ok) return;  // a miss
+  const BakedCorner<DEG> pts(a.points, ray.d, ray.len);
+  // q of a counted sample, from the forward's numbers for it
+  auto q_of = [&](const BakedBlend& b, float t) __attribute__((always_inline)) {
+    return fmaf(g[0], b.v[0] - a.background, fmaf(g[1], b.v[1] - a.background, fmaf(g[2], b.v[2] - a.background, fmaf(g[3], t - ray.far, g[4]))));
+  };
 
   // first pass: the forward's recurrence, and Q = sum_k w_k q_k
   float Q = 0.0f, T = 1.0f;
-  baked_walk_dense(a.words, a.step, G, dm, o, d, near, K, [&](const BakedSample& s, int64_t base) __attribute__((always_inline)) {
-    const BakedBwdSample b = baked_bwd_sample<DEG>(pts, G, s, base, delta, T, g, a.background, far);
-    Q = fmaf(b.w, b.q, Q);
+  auto first = [&](const BakedSample& s, int64_t base, int64_t sy, int64_t sz) __attribute__((always_inline)) {
+    const BakedBlend b = baked_blend<DEG>(pts, s, base, sy, sz, ray.delta, T);
+    Q = fmaf(b.w, q_of(b, s.t), Q);
     T = b.Tn;
     return a.stop > 0.0f && T < a.stop;
-  });
+  };
+  baked_walk<false>(a.words, nullptr, a.step, G, dm, ray, true, first);
 
   // second pass: the same samples with the same numbers; the suffix of sample k is Q less the prefix up to and including k.  The
   // four gradients of a sample go to the eight corners of its cell with their trilinear weights: summed in registers while the
@@ -466,10 +398,11 @@ __global__ __launch_bounds__(BAKED_THREADS) void baked_render_bwd_kernel(upnerf_
   };
   float P = 0.0f;
   T = 1.0f;
-  baked_walk_dense(a.words, a.step, G, dm, o, d, near, K, [&](const BakedSample& s, int64_t base) __attribute__((always_inline)) {
-    const BakedBwdSample b = baked_bwd_sample<DEG>(pts, G, s, base, delta, T, g, a.background, far);
-    P = fmaf(b.w, b.q, P);
-    const float gs = delta * fmaf(b.Tn, b.q, -(Q - P));
+  auto second = [&](const BakedSample& s, int64_t base, int64_t sy, int64_t sz) __attribute__((always_inline)) {
+    const BakedBlend b = baked_blend<DEG>(pts, s, base, sy, sz, ray.delta, T);
+    const float q = q_of(b, s.t);
+    P = fmaf(b.w, q, P);
+    const float gs = ray.delta * fmaf(b.Tn, q, -(Q - P));
     if (base != cell) {
       if (cell >= 0) flush();
       cell = base;
@@ -489,7 +422,8 @@ __global__ __launch_bounds__(BAKED_THREADS) void baked_render_bwd_kernel(upnerf_
     }
     T = b.Tn;
     return a.stop > 0.0f && T < a.stop;
-  });
+  };
+  baked_walk<false>(a.words, nullptr, a.step, G, dm, ray, true, second);
   if (cell >= 0) flush();
 }
 
@@ -565,15 +499,6 @@ bool baked_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // the arguments a launch may be given, and the grid as the kernel reads it
 // (`points`: the rgbs or the records of `a`, aligned to `size`, the bytes of one point)
 template <class Args>
-bool baked_lattice(const Args* a, const void* points, size_t size, BakedGrid* G, OccDims* dm);
-template <class Args>
-bool baked_grid(const Args* a, const void* points, size_t size, BakedGrid* G, OccDims* dm) {
-  if (!a || !a->rgb || !a->depth || !a->opacity) return false;
-  return baked_lattice(a, points, size, G, dm);
-}
-
-// (everything of baked_grid but the forward's outputs: the backward march takes the same scene, rays and step)
-template <class Args>
 bool baked_lattice(const Args* a, const void* points, size_t size, BakedGrid* G, OccDims* dm) {
   if (!a || !occ_dims(a->Cx, a->Cy, a->Cz, dm) || a->R <= 0) return false;
   if (!points || !a->words || !a->rays) return false;
@@ -593,15 +518,34 @@ bool baked_lattice(const Args* a, const void* points, size_t size, BakedGrid* G,
   return true;
 }
 
+// a run-time degree in MIN .. 2, checked by the caller, to the code of that degree: f(std::integral_constant<int, DEG>())
+template <int MIN, class F>
+void baked_by_degree(int degree, F&& f) {
+  if constexpr (MIN == 0)
+    if (degree == 0) return f(std::integral_constant<int, 0>());
+  if (degree == 1) return f(std::integral_constant<int, 1>());
+  return f(std::integral_constant<int, 2>());
+}
+
+dim3 baked_blocks(int R) { return dim3((R + BAKED_THREADS - 1) / BAKED_THREADS); }
+
+// a forward entry point after its own refusals: the outputs, the lattice, the kernel's arguments, the launch
+template <bool SPARSE, class Args>
+int baked_forward(const Args* a, int degree, const void* points, const int32_t* slots, void* stream) {
+  BakedGrid G;
+  OccDims dm;
+  if (!a || !a->rgb || !a->depth || !a->opacity || !baked_lattice(a, points, (size_t)16 << degree, &G, &dm)) return UPNERF_EINVAL;
+  const BakedArgs A = {a->R, a->step, a->background, a->stop, points, slots, a->words, a->rays, a->rgb, a->depth, a->opacity};
+  baked_by_degree<0>(degree, [&](auto deg) {
+    hipLaunchKernelGGL((baked_render_kernel<decltype(deg)::value, SPARSE>), baked_blocks(a->R), dim3(BAKED_THREADS), 0, (hipStream_t)stream, A, G, dm);
+  });
+  return (int)hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" int upnerf_baked_render(const upnerf_baked_render_args* a, void* stream) {
-  BakedGrid G;
-  OccDims dm;
-  if (!baked_grid(a, a ? a->rgbs : nullptr, 16, &G, &dm)) return UPNERF_EINVAL;
-  hipLaunchKernelGGL((baked_render_kernel<0, upnerf_baked_render_args>), dim3((a->R + BAKED_THREADS - 1) / BAKED_THREADS), dim3(BAKED_THREADS), 0,
-                     (hipStream_t)stream, *a, G, dm);
-  return (int)hipGetLastError();
+  return baked_forward<false>(a, 0, a ? a->rgbs : nullptr, nullptr, stream);
 }
 
 extern "C" int upnerf_baked_pack(const upnerf_baked_pack_args* a, void* stream) {
@@ -613,27 +557,13 @@ extern "C" int upnerf_baked_pack(const upnerf_baked_pack_args* a, void* stream) 
 }
 
 extern "C" int upnerf_baked_sh_render(const upnerf_baked_sh_render_args* a, void* stream) {
-  BakedGrid G;
-  OccDims dm;
   if (!a || (a->degree != 1 && a->degree != 2)) return UPNERF_EINVAL;
-  if (!baked_grid(a, a->records, a->degree == 1 ? 32 : 64, &G, &dm)) return UPNERF_EINVAL;
-  const dim3 grid((a->R + BAKED_THREADS - 1) / BAKED_THREADS), block(BAKED_THREADS);
-  if (a->degree == 1) hipLaunchKernelGGL((baked_render_kernel<1, upnerf_baked_sh_render_args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
-  else hipLaunchKernelGGL((baked_render_kernel<2, upnerf_baked_sh_render_args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
-  return (int)hipGetLastError();
+  return baked_forward<false>(a, a->degree, a->records, nullptr, stream);
 }
 
 extern "C" int upnerf_baked_sparse_render(const upnerf_baked_sparse_render_args* a, void* stream) {
-  typedef upnerf_baked_sparse_render_args Args;
-  BakedGrid G;
-  OccDims dm;
   if (!a || a->degree < 0 || a->degree > 2 || !a->slots) return UPNERF_EINVAL;
-  if (!baked_grid(a, a->pool, (size_t)16 << a->degree, &G, &dm)) return UPNERF_EINVAL;
-  const dim3 grid((a->R + BAKED_THREADS - 1) / BAKED_THREADS), block(BAKED_THREADS);
-  if (a->degree == 0) hipLaunchKernelGGL((baked_render_kernel<0, Args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
-  else if (a->degree == 1) hipLaunchKernelGGL((baked_render_kernel<1, Args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
-  else hipLaunchKernelGGL((baked_render_kernel<2, Args>), grid, block, 0, (hipStream_t)stream, *a, G, dm);
-  return (int)hipGetLastError();
+  return baked_forward<true>(a, a->degree, a->pool, a->slots, stream);
 }
 
 extern "C" int upnerf_baked_render_bwd(const upnerf_baked_render_bwd_args* a, void* stream) {
@@ -643,10 +573,9 @@ extern "C" int upnerf_baked_render_bwd(const upnerf_baked_render_bwd_args* a, vo
   if (a->degree == 0 ? !a->grad : (!a->grad_coef || !a->grad_sigma)) return UPNERF_EINVAL;
   if (!baked_lattice(a, a->points, (size_t)16 << a->degree, &G, &dm)) return UPNERF_EINVAL;
   if (a->slots) return UPNERF_EUNSUP;  // a brick pool stores shared faces once per brick: densify(), tune, sparsify()
-  const dim3 grid((a->R + BAKED_THREADS - 1) / BAKED_THREADS), block(BAKED_THREADS);
-  if (a->degree == 0) hipLaunchKernelGGL(baked_render_bwd_kernel<0>, grid, block, 0, (hipStream_t)stream, *a, G, dm);
-  else if (a->degree == 1) hipLaunchKernelGGL(baked_render_bwd_kernel<1>, grid, block, 0, (hipStream_t)stream, *a, G, dm);
-  else hipLaunchKernelGGL(baked_render_bwd_kernel<2>, grid, block, 0, (hipStream_t)stream, *a, G, dm);
+  baked_by_degree<0>(a->degree, [&](auto deg) {
+    hipLaunchKernelGGL(baked_render_bwd_kernel<decltype(deg)::value>, baked_blocks(a->R), dim3(BAKED_THREADS), 0, (hipStream_t)stream, *a, G, dm);
+  });
   return (int)hipGetLastError();
 }
 
@@ -675,7 +604,8 @@ extern "C" int upnerf_baked_sh_pack(const upnerf_baked_sh_pack_args* a, void* st
   if (((uintptr_t)a->records & (a->degree == 1 ? 31 : 63)) != 0) return UPNERF_EINVAL;
   const int64_t blocks = (a->n + NTHREADS - 1) / NTHREADS;
   if (blocks > 0x7fffffff) return UPNERF_EUNSUP;
-  if (a->degree == 1) hipLaunchKernelGGL(baked_sh_pack_kernel<1>, dim3((unsigned)blocks), dim3(NTHREADS), 0, (hipStream_t)stream, *a);
-  else hipLaunchKernelGGL(baked_sh_pack_kernel<2>, dim3((unsigned)blocks), dim3(NTHREADS), 0, (hipStream_t)stream, *a);
+  baked_by_degree<1>(a->degree, [&](auto deg) {
+    hipLaunchKernelGGL(baked_sh_pack_kernel<decltype(deg)::value>, dim3((unsigned)blocks), dim3(NTHREADS), 0, (hipStream_t)stream, *a);
+  });
   return (int)hipGetLastError();
 }
