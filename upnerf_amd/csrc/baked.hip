@@ -304,7 +304,8 @@ struct BakedArgs {
   float *rgb, *depth, *opacity;
 };
 
-// the march of one ray row (host and device: the host build is what a CPU program checks against the fp64 restatement)
+// the march of one ray row (host and device: the host build is what tests/host/baked_host.hip, run by
+// tests/test_walks_host_cpu.py, checks against brute force over every sample and against the fp64 restatement)
 template <int DEG, bool SPARSE>
 __host__ __device__ __forceinline__ BakedOut baked_march(const BakedArgs& A, const BakedGrid& G, const OccDims& dm, const float* row,
                                                          bool use_bits) {

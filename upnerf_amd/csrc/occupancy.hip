@@ -129,7 +129,8 @@ __host__ __device__ __forceinline__ int occ_cell_of(const OccAxis& a, double p, 
 
 __host__ __device__ __forceinline__ int occ_imin(int a, int b) { return a < b ? a : b; }
 
-// the walk of one ray row (host and device: the host build is what a CPU program checks against brute force)
+// the walk of one ray row (host and device: the host build is what tests/host/occ_host.hip, run by
+// tests/test_walks_host_cpu.py, checks against brute force over every occupied cell)
 __host__ __device__ __forceinline__ bool occ_walk(const upnerf_occ_spans_args& a, const OccDims& dm, const float* row, float* t0_out,
                                                   float* t1_out) {
   const float near = row[6], far = row[7];
