@@ -1652,7 +1652,8 @@ int upnerf_baked_sparse_render(const upnerf_baked_sparse_render_args* a, void* s
  * corners).  Nothing is added for a miss, nor for a ray whose g_rgb, g_depth and g_opacity are all zero.
  * Refused: what the forward refuses (UPNERF_EINVAL), a NULL g_rgb or output, a degree outside {0, 1, 2}; `slots` not NULL, a
  * brick pool, is UPNERF_EUNSUP: faces that bricks share are stored once per brick, so a gradient would have to be summed over the
- * copies -- densify the scene, tune it, sparsify it again. */
+ * copies -- densify the scene, tune it, sparsify it again, or use upnerf_baked_sparse_render_bwd and upnerf_brick_face_sum
+ * below, whose outputs are pool-shaped. */
 typedef struct {
   int32_t Cx, Cy, Cz, R;
   float lo[3], hi[3];        /* hi > lo, finite */
@@ -1687,6 +1688,67 @@ typedef struct {
   float* sigma;              /* [n]: degree 1, 2 */
 } upnerf_baked_project_args;
 int upnerf_baked_project(const upnerf_baked_project_args* a, void* stream);
+
+/* ---- tuning a sparse baked scene in place: the backward pass on the brick pool (csrc/baked.hip, csrc/brick.hip).
+ * Added under ABI 11: new symbols only.
+ *
+ * upnerf_baked_sparse_render_bwd: the gradient of a loss over the outputs of upnerf_baked_sparse_render with respect to the
+ * points of its pool.  The definition is upnerf_baked_render_bwd's, word for word -- q, P, Q, the suffix, the live corners (a
+ * stored sigma that is not zero), the open channels, the trilinear weights, the Y_j share at degree 1, 2, the sums over the
+ * consecutive samples of one cell -- on the samples the sparse forward composites, through the same walk.  The outputs are
+ * POOL-shaped, n = 729 n_bricks points: corner (x, y, z) of cell (ix, iy, iz) is pool point base + x + 9 y + 81 z with the
+ * forward's base = slot * 729 + ((iz & 7) * 9 + (iy & 7)) * 9 + (ix & 7).  Contributions are ADDED with float atomics into
+ * buffers the caller has zeroed: not the same bits every run.
+ * A grid point on a face that bricks share is stored once per brick, and EACH COPY RECEIVES ONLY WHAT THE SAMPLES INSIDE ITS OWN
+ * BRICK'S CELLS GIVE IT: the gradient of the point is the sum over its copies, which upnerf_brick_face_sum forms and writes to
+ * every copy.  (A copy in a brick no ray enters stays exactly zero.)  Pool points beyond the grid receive nothing.
+ * Refused (UPNERF_EINVAL): what upnerf_baked_sparse_render refuses (a NULL `slots` among it), a NULL g_rgb, a NULL output of the
+ * degree (grad at degree 0; grad_coef or grad_sigma at degree 1, 2).  The fields keep the order of the other baked structs,
+ * scalars first. */
+typedef struct {
+  int32_t Cx, Cy, Cz, R;
+  float lo[3], hi[3];        /* hi > lo, finite */
+  float step;                /* > 0, finite */
+  float background;          /* finite */
+  float stop;                /* >= 0, < 1; 0 = never */
+  int32_t degree;            /* 0, 1 or 2 */
+  const uint8_t* pool;       /* [n_bricks][9][9][9][16 | 32 | 64], aligned to the record size */
+  const int32_t* slots;      /* [Bz][By][Bx]; every entry < n_bricks */
+  const uint32_t* words;     /* [upnerf_occ_words(Cx, Cy, Cz)] */
+  const float* rays;         /* [R][8], 16-byte aligned */
+  const float* g_rgb;        /* [R][3] */
+  const float* g_depth;      /* [R] or NULL */
+  const float* g_opacity;    /* [R] or NULL */
+  float* grad;               /* [n_bricks][9][9][9][4]: degree 0 */
+  float* grad_coef;          /* [n_bricks][9][9][9][3][nb]: degree 1, 2 */
+  float* grad_sigma;         /* [n_bricks][9][9][9]: degree 1, 2 */
+} upnerf_baked_sparse_render_bwd_args;
+int upnerf_baked_sparse_render_bwd(const upnerf_baked_sparse_render_bwd_args* a, void* stream);
+
+/* upnerf_brick_face_sum: in place on a pool-shaped fp32 array `data` [n_bricks][729][F] (F floats per point: 4, 3 nb, 1, ...),
+ * every copy of a grid point becomes the sum over its copies.  Grid point i of an axis (0 <= i <= C) lies in brick i / 8 at
+ * l = i % 8 where that brick exists (i / 8 < B), and, if i % 8 == 0 and i > 0, in brick i / 8 - 1 at l = 8 as well: a point has
+ * up to 2 x 2 x 2 = 8 copies.  With b_1 < ... < b_m the OCCUPIED bricks (slot >= 0) that hold a copy, in ascending linear
+ * brick index, and x_b the copy of brick b, every copy becomes
+ *   ((x_b1 + x_b2) + ...) + x_bm,   fp32, in that order,
+ * per float.  Where m = 1 nothing is written; pool points beyond the grid are not touched.  Two launches: in the first the
+ * thread of the copy in b_1 reads the others and stores the sum to its own copy, in the second the others read it -- no two
+ * threads store to one address, no atomics, nothing allocated, the same bits every run.  One thread per (face point, float): the
+ * 386 points of a brick with an l of 0 or 8; its 343 interior points are never read.  After it the copies of a point hold
+ * identical bytes again, which is the layout's invariant: an optimiser that is given identical gradients, parameters and
+ * moments on every copy keeps them identical.
+ * Refused (UPNERF_EINVAL): NULL arguments, cells outside upnerf_occ_words' range, n_bricks < 1 or > Bx By Bz, F < 1, `data`
+ * not 4-byte aligned; UPNERF_EUNSUP: more threads than a launch has. */
+typedef struct {
+  int32_t Cx, Cy, Cz;
+  int32_t n_bricks;          /* >= 1, <= Bx By Bz */
+  int32_t F;                 /* floats per point, >= 1 */
+  int32_t reserved_;
+  const int32_t* slots;      /* [Bz][By][Bx]; every entry < n_bricks */
+  const int32_t* bricks;     /* [n_bricks] */
+  float* data;               /* [n_bricks][9][9][9][F] */
+} upnerf_brick_face_sum_args;
+int upnerf_brick_face_sum(const upnerf_brick_face_sum_args* a, void* stream);
 
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase

@@ -32,7 +32,14 @@ medians of --reps (HIP events round a pass over all rays): ms per backward and p
 flushes -- counted here from the definition: cell changes along each ray's visited samples, times the cell's corners with a
 sigma, times the floats of a point -- over the time, beside the guide's 1.3 and 0.08 TB/s; and on the first chunk the same
 gradient from a restatement in torch's own ops (every sample, gather-based trilinear, autograd), its time and its distance.
-Then a distill() on this system: PSNR of the baked frames against the plain ones before and after.  The weights are random."""
+Then a distill() on this system: PSNR of the baked frames against the plain ones before and after.  The weights are random.
+
+--tune --sparse measures tuning a sparse scene in place INSTEAD and writes --pool-tune-out: on the analytic shell
+of --sparse at 128^3 and 256^3 points, degree 0 and 2, one step of the dense tuner (on the dense scene: what the densify / tune /
+sparsify detour runs) and one of the pool tuner (on its sparsify()), on the same --chunk rays and targets, alternately in one
+process, medians of --reps (HIP events round 5 steps); beside every time the occupied share of the bricks f_b and the bytes each
+tuner holds; and the new launches alone: the sparse backward, the face sum (collect and spread, over every gradient array), with
+the dense backward on the same rays beside them."""
 import argparse
 import json
 import os
@@ -79,6 +86,7 @@ def main():
     ap.add_argument("--tune", action="store_true", help="measure the backward march instead; writes --tune-out")
     ap.add_argument("--tune-out", default=os.path.join(ROOT, "profiles", "baked_tune.json"))
     ap.add_argument("--tune-iters", type=int, default=200, help="with --tune: iterations of the distill")
+    ap.add_argument("--pool-tune-out", default=os.path.join(ROOT, "profiles", "baked_sparse_tune.json"))
     ap.add_argument("--parent-lib", default=None, help="with --sparse: the parent commit's libupnerf_hip.so, for the nine marchers' times beside this build's")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -103,6 +111,8 @@ def main():
     path = CameraPath.from_poses(c2w, (0.1, 5.0), F, appearance=(a.bake_image, a.bake_image), img_wh=(W, H), K=K)  # ONE appearance: the baked one
     rays = F * H * W
     res = tuple(a.resolution)
+    if a.sparse and a.tune:
+        return pool_tune_main(a, path, dev)
     if a.sparse:
         return sparse_main(a, sysm, path, dev)
     if a.tune:
@@ -351,6 +361,76 @@ def tune_main(a, sysm, path, dev):
                                        "note": "targets: the keyframe cameras; PSNR: all frames of the path; random weights, no trained scene"}
     os.makedirs(os.path.dirname(os.path.abspath(a.tune_out)), exist_ok=True)
     with open(a.tune_out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+def pool_tune_main(a, path, dev):
+    import statistics as st
+    from upnerf_amd import baked_sparse_tune, baked_tune, novel_view
+    from upnerf_amd.baked import BakedScene, sphere_directions
+    W, H = a.width, a.height
+    rays = novel_view.path_rays(*novel_view.path_poses(path.key_c2w.to(dev), path.key_near_far.to(dev), path.u.to(dev), path.mode),
+                                (W, H), path.K, 0, H * W)[0][:a.chunk].contiguous()
+    R = rays.shape[0]
+    gen = torch.Generator(device="cpu").manual_seed(5)
+    g_rgb = torch.randn(R, 3, generator=gen).to(dev)
+    STEPS = 5
+
+    def event_ms(fn, n=1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    rows = []
+    for n in (128, 256):
+        for degree in (0, 2):
+            if degree == 0:
+                dense = BakedScene.from_grids(*shell_grids(n, dev), BOUNDS, 1.0)
+            else:
+                dirs = sphere_directions(12)
+                sigma, rgb_dirs = shell_grids(n, dev, dirs)
+                dense = BakedScene.from_direction_grids(sigma, rgb_dirs, dirs, BOUNDS, 1.0, sh_degree=2)
+                del sigma, rgb_dirs
+            sparse = dense.sparsify()
+            target = (dense.render(rays, a.step)["rgb"] + 0.05 * torch.randn(R, 3, generator=gen).to(dev)).clamp(0, 1)
+            tuners = {"dense": dense.tune(1e-2), "pool": sparse.tune_pool(1e-2)}
+            params = baked_sparse_tune.PoolParams.of(sparse, requires_grad=False)
+            grads = tuners["pool"].grads
+            legs = {f"{k}_step": (lambda t=t: t.step(rays, target, a.step)) for k, t in tuners.items()}
+            legs["sparse_bwd"] = lambda: baked_sparse_tune.backward(sparse.pool, params, rays, a.step, 0.0, 0.0, g_rgb, out=grads[0] if degree == 0 else grads,
+                                                                    face_sum=False)
+            legs["face_sum"] = lambda: [baked_sparse_tune.face_sum(t, sparse) for t in grads]
+            dgrads = tuners["dense"].grads
+            legs["dense_bwd"] = lambda: baked_tune.backward(dense.grid, degree, dense.occupancy, dense.bounds, rays, a.step, 0.0, 0.0, g_rgb,
+                                                            out=dgrads[0] if degree == 0 else dgrads)
+            for fn in legs.values():  # warm-up
+                fn()
+            ms = {k: [] for k in legs}
+            for _ in range(a.reps):
+                for k, fn in legs.items():
+                    ms[k].append(event_ms(fn, STEPS))
+            med = {k: st.median(v) for k, v in ms.items()}
+            rows.append({"resolution": n, "degree": degree, "occupied_bricks": sparse.n_bricks, "f_b": sparse.brick_fraction,
+                         "hit_share": float((dense.render(rays, a.step)["opacity"] > 0).float().mean()),
+                         "dense": {"step_ms": med["dense_step"], "tuner_bytes": tuners["dense"].nbytes, "scene_bytes": dense.nbytes, "step_ms_all": sorted(ms["dense_step"])},
+                         "pool": {"step_ms": med["pool_step"], "tuner_bytes": tuners["pool"].nbytes, "scene_bytes": sparse.nbytes, "step_ms_all": sorted(ms["pool_step"])},
+                         "dense_step_over_pool_step": med["dense_step"] / med["pool_step"],
+                         "dense_bytes_over_pool_bytes": tuners["dense"].nbytes / tuners["pool"].nbytes,
+                         "launches_ms": {"baked_sparse_render_bwd": med["sparse_bwd"], "brick_face_sum_collect_and_spread": med["face_sum"],
+                                         "baked_render_bwd_dense": med["dense_bwd"]}})
+            del dense, sparse, tuners, params, grads, dgrads, legs
+            torch.cuda.empty_cache()
+    out = {"metric": "one tuner step, dense (BakedTuner on the dense scene) against in place on the brick pool (PoolTuner), and the new launches alone; analytic shell, random targets",
+           "rays": R, "step": a.step, "reps": a.reps, "steps_per_timing": STEPS, "bounds": [list(b) for b in BOUNDS], "rows": rows,
+           "note": "an analytic shell, not a trained scene: f_b and the hit share are the shell's"}
+    os.makedirs(os.path.dirname(os.path.abspath(a.pool_tune_out)), exist_ok=True)
+    with open(a.pool_tune_out, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
     print(json.dumps(out))

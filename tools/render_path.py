@@ -5,7 +5,7 @@ appearance moving from photograph to photograph (upnerf_amd/novel_view.py; DESIG
                                 [--mode linear|catmull] [--downscale N] [--depth] [--normals] [--loop] [--chunk ROWS]
                                 [--occupancy NX NY NZ --level SIGMA [--dilate K] [--bounds X0 Y0 Z0 X1 Y1 Z1 | --margin M]]
                                 [--baked NX NY NZ --level SIGMA --step DT [--bake-image ID] [--save-baked F | --load-baked F]
-                                 [--baked-sh {1,2} [--baked-dirs K]] [--baked-sparse] [--baked-tune ITERS [--baked-tune-lr LR]]]
+                                 [--baked-sh {1,2} [--baked-dirs K]] [--baked-sparse] [--baked-tune ITERS [--baked-tune-lr LR] [--baked-tune-pool]]]
 
 --occupancy skips empty space: the fine field's density is sampled on NX x NY x NZ grid points over the box (--bounds, or the
 box round the refined cameras and their far points grown by --margin), cells with a corner >= --level (grown by --dilate
@@ -25,6 +25,8 @@ bit for bit the dense scene's; the colour passes cost about 5.06 times the occup
 it pays below a share of 0.20, which is what a fine grid of a real scene has).
 --baked-tune ITERS fits the baked grid, before it is rendered or saved, to the field's own renders of the path's keyframe cameras
 under the baked appearance: ITERS iterations of Adam through the marcher's backward pass (upnerf_amd/baked_tune.py).
+A --baked-sparse scene is made dense for that and stored sparse again, unless --baked-tune-pool is given: then the pool is tuned in
+place, with no buffer the size of the grid (upnerf_amd/baked_sparse_tune.py; the bricks stay the bake's).
 --save-baked writes the grid to an .npz, --load-baked renders from one (then NX NY NZ, --level, the degree and the layout are those
 of the file).
 --depth works, --normals and --occupancy do not.
@@ -70,6 +72,7 @@ def parser():
     ap.add_argument("--baked-sparse", action="store_true", help="store and bake only the occupied bricks of the grid (with --baked)")
     ap.add_argument("--baked-tune", type=int, default=None, metavar="ITERS", help="after baking, fit the grid to the field's own renders of the path's keyframe cameras for this many Adam iterations (with --baked)")
     ap.add_argument("--baked-tune-lr", type=float, default=None, metavar="LR", help="learning rate of --baked-tune (default 0.01)")
+    ap.add_argument("--baked-tune-pool", action="store_true", help="tune a --baked-sparse scene in place on its brick pool instead of through the dense layout (with --baked-sparse and --baked-tune)")
     ap.add_argument("--save-baked", default=None, help="write the baked grid to this .npz")
     ap.add_argument("--load-baked", default=None, help="render from the baked grid of this .npz instead of baking")
     return ap
@@ -97,6 +100,8 @@ def check_args(a):
         raise SystemExit("--baked-tune and --baked-tune-lr belong to --baked (the targets are rendered under the appearance the grid is baked with)")
     if a.baked_tune_lr is not None and a.baked_tune is None:
         raise SystemExit("--baked-tune-lr is the learning rate of --baked-tune")
+    if a.baked_tune_pool and (a.baked is None or not a.baked_sparse or a.baked_tune is None):
+        raise SystemExit("--baked-tune-pool tunes the brick pool of a sparse bake in place: it needs --baked-sparse and --baked-tune")
     if a.baked_tune is not None and a.baked_tune < 1:
         raise SystemExit("--baked-tune counts iterations: one at least")
     if a.baked_dirs is not None and a.baked_sh is None:
@@ -145,11 +150,14 @@ def main(argv=None):
             sh = {} if a.baked_sh is None else {"sh_degree": a.baked_sh, "dirs": sphere_directions(48 if a.baked_dirs is None else a.baked_dirs)}
             scene = BakedScene.build(system, bounds, a.baked, a.level, img_id=a.images[0] if a.bake_image is None else a.bake_image, sparse=a.baked_sparse, **sh)
             if a.baked_tune is not None:  # distil on the path's own keyframe cameras; a sparse scene is tuned dense and stored sparse again
-                from upnerf_amd.baked_tune import distill
+                if a.baked_tune_pool:  # ... unless the pool itself is tuned, in place
+                    from upnerf_amd.baked_sparse_tune import distill
+                else:
+                    from upnerf_amd.baked_tune import distill
                 tt = time.perf_counter()
-                tuned, curve = distill(system, scene.densify(), path, iters=a.baked_tune, batch=a.chunk or system.hparams["val.chunk_size"], baked_step=a.step,
+                tuned, curve = distill(system, scene if a.baked_tune_pool else scene.densify(), path, iters=a.baked_tune, batch=a.chunk or system.hparams["val.chunk_size"], baked_step=a.step,
                                        seed=0, lr=0.01 if a.baked_tune_lr is None else a.baked_tune_lr, img_id=a.images[0] if a.bake_image is None else a.bake_image)
-                scene = tuned.sparsify() if a.baked_sparse else tuned
+                scene = tuned.sparsify() if a.baked_sparse else tuned  # (a tuned pool is sparse already: sparsify() returns it)
                 tune_extra = {"tune_iters": a.baked_tune, "tune_loss_first": curve[0], "tune_loss_last": curve[-1], "tune_seconds": time.perf_counter() - tt}
             if a.save_baked is not None:
                 scene.save(a.save_baked)

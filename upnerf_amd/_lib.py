@@ -443,6 +443,18 @@ class BakedProjectArgs(C.Structure):
     _fields_ = [("n", C.c_int64), ("degree", C.c_int32), ("reserved_", C.c_int32), ("rgbs", _fp), ("sigma", _fp)]
 
 
+class BakedSparseRenderBwdArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("R", C.c_int32), ("lo", C.c_float * 3),
+                ("hi", C.c_float * 3), ("step", C.c_float), ("background", C.c_float), ("stop", C.c_float), ("degree", C.c_int32),
+                ("pool", _fp), ("slots", _fp), ("words", _fp), ("rays", _fp), ("g_rgb", _fp), ("g_depth", _fp), ("g_opacity", _fp),
+                ("grad", _fp), ("grad_coef", _fp), ("grad_sigma", _fp)]
+
+
+class BrickFaceSumArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("n_bricks", C.c_int32), ("F", C.c_int32),
+                ("reserved_", C.c_int32), ("slots", _fp), ("bricks", _fp), ("data", _fp)]
+
+
 class DensityGradArgs(C.Structure):
     _fields_ = [("M", C.c_int32), ("reserved_", C.c_int32), ("points", _fp), ("P", _fp), ("PT", _fp), ("wk_xyz", C.c_float * 10),
                 ("sigma", _fp), ("grad", _fp)]
@@ -574,6 +586,8 @@ _SIGNATURES = {
     "upnerf_baked_sparse_render": [C.POINTER(BakedSparseRenderArgs), _p],
     "upnerf_baked_render_bwd": [C.POINTER(BakedRenderBwdArgs), _p],
     "upnerf_baked_project": [C.POINTER(BakedProjectArgs), _p],
+    "upnerf_baked_sparse_render_bwd": [C.POINTER(BakedSparseRenderBwdArgs), _p],
+    "upnerf_brick_face_sum": [C.POINTER(BrickFaceSumArgs), _p],
 }
 _LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
              "upnerf_occ_compact_scratch", "upnerf_pca_fit_scratch", "upnerf_brick_table_scratch")

@@ -627,6 +627,11 @@ class BakedScene:
         from .baked_tune import BakedTuner
         return BakedTuner(self, lr, betas=betas, eps=eps)
 
+    def tune_pool(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8):
+        """A `baked_sparse_tune.PoolTuner` on this (sparse) scene: Adam on the points of its pool, in place."""
+        from .baked_sparse_tune import PoolTuner
+        return PoolTuner(self, lr, betas=betas, eps=eps)
+
     # ---- files -------------------------------------------------------------------------------------------------------------
 
     def save(self, path: str) -> None:

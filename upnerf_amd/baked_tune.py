@@ -8,7 +8,8 @@ include/upnerf_hip.h states the gradient), an autograd function 
     tuned, curve = distill(system, scene, [0, 3, 5], iters=200, batch=4096, baked_step=0.01, seed=0, img_id=3)
 
 Dense scenes of degree 0, 1 and 2.  A sparse scene is refused: its pool stores the faces bricks share once per brick, so a
-gradient would have to be summed over the copies -- `scene.densify()`, tune, `.sparsify()`.  The occupancy is frozen while tuning:
+gradient would have to be summed over the copies -- `scene.densify()`, tune, `.sparsify()`, or baked_sparse_tune.py, which tunes
+the pool in place and does that sum.  The occupancy is frozen while tuning:
 a grid point whose sigma is zero is no parameter (it receives no gradient), so a clear cell keeps its eight zero corners, and a
 sigma the optimiser drives to zero (`upnerf_baked_project`) is dead from then on.  The gradient's sums over rays are float atomic
 adds: two runs agree to rounding, not to the bit.  There is no CPU path."""
@@ -41,9 +42,10 @@ def _dense(scene, what: str) -> None:
 
 
 def unpack_records(records: torch.Tensor, degree: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(coef fp32 [Nz, Ny, Nx, 3, nb], sigma fp32 [Nz, Ny, Nx]) of an SH scene's records: the stored halves converted exactly."""
+    """(coef fp32 [Nz, Ny, Nx, 3, nb], sigma fp32 [Nz, Ny, Nx]) of an SH scene's records: the stored halves converted exactly.
+    (Any leading shape: the records of a pool [n_bricks, 9, 9, 9, 32 | 64] give [n_bricks, 9, 9, 9, 3, nb] and [n_bricks, 9, 9, 9].)"""
     nb = (degree + 1) ** 2
-    coef = records[..., :6 * nb].contiguous().view(torch.float16).to(torch.float32).view(records.shape[:3] + (3, nb))
+    coef = records[..., :6 * nb].contiguous().view(torch.float16).to(torch.float32).view(records.shape[:-1] + (3, nb))
     at = SIGMA_BYTE[degree]
     return coef.contiguous(), records[..., at:at + 4].contiguous().view(torch.float32).squeeze(-1).contiguous()
 
@@ -164,36 +166,58 @@ def render(scene_params: SceneParams, rays: torch.Tensor, step: float, backgroun
 
 class BakedTuner:
     """Adam on the points of a dense scene against target pixels.  Holds the fp32 masters (one flat buffer: rgbs, or the
-    coefficients followed by the sigmas), their gradient and the Adam moments; the occupancy is the scene's and is frozen."""
+    coefficients followed by the sigmas), their gradient and the Adam moments; the occupancy is the scene's and is frozen.
+    (The layout -- which scenes are taken, the shape of the point array, the forward and the gradient launches -- is in the four
+    methods after __init__; baked_sparse_tune.PoolTuner states them for a brick pool and shares the rest.)"""
 
     def __init__(self, scene: BakedScene, lr: float, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8):
-        _dense(scene, "BakedTuner")
+        self._accept(scene)
         lr, eps = float(lr), float(eps)
         if not (lr > 0 and np.isfinite(lr)) or not (eps > 0) or not all(0 <= float(b) < 1 for b in betas):
             raise ValueError("lr and eps are positive, the betas in [0, 1)")
         self.lr, self.betas, self.eps, self.t = lr, (float(betas[0]), float(betas[1])), eps, 0
         self.degree, self.bounds, self.level, self.occupancy = scene.sh_degree, scene.bounds, scene.level, scene.occupancy
         dev = scene.device
-        Nx, Ny, Nz = scene.resolution
-        shape, nb = (Nz, Ny, Nx), (self.degree + 1) ** 2
-        n = Nx * Ny * Nz
+        shape, grid = self._points(scene)
+        nb, n = (self.degree + 1) ** 2, math.prod(shape)
         per = 4 if self.degree == 0 else 3 * nb + 1
         self.p = torch.empty(n * per, device=dev)
         self.g, self.m, self.v = (torch.zeros_like(self.p) for _ in range(3))
         view = lambda t: (t.view(shape + (4,)),) if self.degree == 0 else (t[:n * 3 * nb].view(shape + (3, nb)), t[n * 3 * nb:].view(shape))
         self.masters, self.grads = view(self.p), view(self.g)
         if self.degree == 0:
-            self.masters[0].copy_(scene.rgbs)
+            self.masters[0].copy_(grid)
             self.records = None
         else:
-            coef, sigma = unpack_records(scene.records, self.degree)
+            coef, sigma = unpack_records(grid, self.degree)
             self.masters[0].copy_(coef), self.masters[1].copy_(sigma)
             self.records = pack_records(*self.masters, self.degree, 0.0)
+
+    def _accept(self, scene) -> None:
+        _dense(scene, "BakedTuner")
+
+    def _points(self, scene):
+        """(the shape of the scene's point array, the array: rgbs or records)."""
+        Nx, Ny, Nz = scene.resolution
+        return (Nz, Ny, Nx), scene.grid
+
+    def _march(self, rays, step, background, stop):
+        return _forward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop)
+
+    def _gradient(self, rays, step, background, stop, g_rgb) -> None:
+        """The gradient of the points, added into self.grads (zeroed by the caller)."""
+        backward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop, g_rgb,
+                 out=self.grads[0] if self.degree == 0 else self.grads)
 
     @property
     def points(self) -> torch.Tensor:
         """The grid the marcher reads now: the master rgbs, or the records packed from the masters."""
         return self.masters[0] if self.degree == 0 else self.records
+
+    @property
+    def nbytes(self) -> int:
+        """Device bytes the tuner holds: masters, gradient, two moments, and at degree 1 | 2 the records."""
+        return 4 * self.p.numel() * 4 + (self.records.numel() if self.records is not None else 0)
 
     @torch.no_grad()
     def step(self, rays: torch.Tensor, target_rgb: torch.Tensor, step: float, background: float = 0.0, stop: float = 0.0) -> torch.Tensor:
@@ -208,12 +232,11 @@ class BakedTuner:
             raise ValueError("target_rgb is a fp32 tensor [R, 3]")
         st = stream()
         check(lib.upnerf_zero(ptr(self.g), self.g.numel(), st), "upnerf_zero")
-        rgb, _, _ = _forward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop)
+        rgb, _, _ = self._march(rays, step, background, stop)
         diff = rgb - target_rgb
         loss = (diff * diff).mean()
         g_rgb = diff * (2.0 / (3 * R))
-        backward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop, g_rgb,
-                 out=self.grads[0] if self.degree == 0 else self.grads)
+        self._gradient(rays, step, background, stop, g_rgb)
         self.t += 1
         b1, b2 = self.betas
         step_size, bc2_sqrt = self.lr / (1.0 - b1 ** self.t), math.sqrt(1.0 - b2 ** self.t)
@@ -251,8 +274,13 @@ def distill(system, scene: BakedScene, path_or_img_ids, iters: int, batch: int, 
     `img_id` -- the ONE appearance the scene was baked with.  Batches of `batch` rays are drawn with a generator seeded by `seed`;
     `iters` steps of BakedTuner(scene, lr) at sample spacing `baked_step`.  Returns (the tuned scene, the loss curve as a list of
     floats -- one host read, at the end)."""
-    from .novel_view import CameraPath, render_path
     _dense(scene, "distill")
+    return _distill(BakedTuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk)
+
+
+def _distill(make_tuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk):
+    """distill on a scene its caller has accepted, with the tuner make_tuner(scene, lr)."""
+    from .novel_view import CameraPath, render_path
     if img_id is None:
         raise ValueError("img_id: the training image whose appearance the scene was baked with (the targets are rendered under it)")
     iters, batch = int(iters), int(batch)
@@ -267,7 +295,7 @@ def distill(system, scene: BakedScene, path_or_img_ids, iters: int, batch: int, 
     target = render_path(system, keys, chunk=chunk, outputs=("rgb_float",))["rgb_float"].reshape(-1, 3).contiguous()
     rays = keyframe_rays(keys, dev)
     background = 1.0 if getattr(system.train_dataset, "white_back", False) else 0.0
-    tuner = BakedTuner(scene, lr)
+    tuner = make_tuner(scene, lr)
     gen = torch.Generator(device="cpu").manual_seed(int(seed))
     curve = []
     for _ in range(iters):

@@ -28,6 +28,9 @@
 //                        each stated once) -- the first forms Q = sum w q, the second hands every sample's four gradients to
 //                        the eight corners of its cell, summed in registers while the ray stays in the cell and added to memory
 //                        with atomicAdd(float*) when it leaves it.  The one entry point here whose bits depend on the run.
+//   upnerf_baked_sparse_render_bwd  the same kernel's other layout (the template's second parameter again): the
+//                        gradient is pool-shaped, and a copy of a point on a face that bricks share receives the part that the
+//                        samples inside its own brick give it -- upnerf_brick_face_sum (brick.hip) makes the copies whole.
 //   upnerf_baked_project the tuned points back into the marcher's domain (sigma >= 0 and finite; degree 0: colours in [0, 1]).
 // All stores are ordinary vector stores and vector float atomics from plain C++.
 #include "common.cuh"
@@ -346,10 +349,19 @@ __global__ __launch_bounds__(BAKED_THREADS) void baked_render_kernel(BakedArgs a
   a.opacity[r] = out.opacity;
 }
 
-// ---- the backward march: upnerf_baked_render_bwd (include/upnerf_hip.h states the gradient) ---------------------
-template <int DEG>
-__global__ __launch_bounds__(BAKED_THREADS) void baked_render_bwd_kernel(upnerf_baked_render_bwd_args a, BakedGrid G, OccDims dm) {
+// ---- the backward march: upnerf_baked_render_bwd and, through a brick pool, upnerf_baked_sparse_render_bwd (include/upnerf_hip.h
+// states the gradient).  The kernel takes the public struct of its layout by value, scalars first (BakedArgs
+// says why); the two structs name the scene's points differently.
+template <bool SPARSE>
+using BakedBwdArgs = std::conditional_t<SPARSE, upnerf_baked_sparse_render_bwd_args, upnerf_baked_render_bwd_args>;
+__device__ __forceinline__ const void* baked_bwd_points(const upnerf_baked_render_bwd_args& a) { return a.points; }
+__device__ __forceinline__ const void* baked_bwd_points(const upnerf_baked_sparse_render_bwd_args& a) { return a.pool; }
+
+template <int DEG, bool SPARSE>
+__global__ __launch_bounds__(BAKED_THREADS) void baked_render_bwd_kernel(BakedBwdArgs<SPARSE> a, BakedGrid G, OccDims dm) {
   constexpr int NB = (DEG + 1) * (DEG + 1);
+  const int32_t* slots = nullptr;
+  if constexpr (SPARSE) slots = a.slots;
   const int r = blockIdx.x * BAKED_THREADS + threadIdx.x;
   if (r >= a.R) return;
   // upstream: g_rgb | g_depth | g_opacity; a ray none of whose gradients is set adds nothing
@@ -358,7 +370,7 @@ __global__ __launch_bounds__(BAKED_THREADS) void baked_render_bwd_kernel(upnerf_
   if (g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f && g[3] == 0.0f && g[4] == 0.0f) return;
   const BakedRay ray(a.rays + (int64_t)r * 8, a.step);
   if (!ray.ok) return;  // a miss
-  const BakedCorner<DEG> pts(a.points, ray.d, ray.len);
+  const BakedCorner<DEG> pts(baked_bwd_points(a), ray.d, ray.len);
   // q of a counted sample, from the forward's numbers for it
   auto q_of = [&](const BakedBlend& b, float t) __attribute__((always_inline)) {
     return fmaf(g[0], b.v[0] - a.background, fmaf(g[1], b.v[1] - a.background, fmaf(g[2], b.v[2] - a.background, fmaf(g[3], t - ray.far, g[4]))));
@@ -372,19 +384,23 @@ __global__ __launch_bounds__(BAKED_THREADS) void baked_render_bwd_kernel(upnerf_
     T = b.Tn;
     return a.stop > 0.0f && T < a.stop;
   };
-  baked_walk<false>(a.words, nullptr, a.step, G, dm, ray, true, first);
+  baked_walk<SPARSE>(a.words, slots, a.step, G, dm, ray, true, first);
 
   // second pass: the same samples with the same numbers; the suffix of sample k is Q less the prefix up to and including k.  The
   // four gradients of a sample go to the eight corners of its cell with their trilinear weights: summed in registers while the
   // ray stays in one cell, added to memory when it leaves it
+  // (`cell` is the visit's `base`, which names a cell uniquely in both layouts; the strides to its corners are the visit's too:
+  // the grid's in a dense scene, 9 and 81 inside a slot of a pool -- so a pool's copy of a shared point receives what the samples
+  // in its own brick's cells give it and nothing else)
   float acc[8][4];
   int64_t cell = -1;
   unsigned live = 0u;
   auto flush = [&]() __attribute__((always_inline)) {
+    const int64_t sy = SPARSE ? UPNERF_BRICK_POINTS : G.sy, sz = SPARSE ? UPNERF_BRICK_POINTS * UPNERF_BRICK_POINTS : G.sz;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       if (!(live >> j & 1u)) continue;  // a corner whose stored sigma is zero is no parameter
-      const int64_t p = cell + (j & 1) + (j >> 1 & 1) * G.sy + (j >> 2) * G.sz;
+      const int64_t p = cell + (j & 1) + (j >> 1 & 1) * sy + (j >> 2) * sz;
       if constexpr (DEG == 0) {
 #pragma unroll
         for (int ch = 0; ch < 4; ++ch) atomicAdd(a.grad + p * 4 + ch, acc[j][ch]);
@@ -424,7 +440,7 @@ __global__ __launch_bounds__(BAKED_THREADS) void baked_render_bwd_kernel(upnerf_
     T = b.Tn;
     return a.stop > 0.0f && T < a.stop;
   };
-  baked_walk<false>(a.words, nullptr, a.step, G, dm, ray, true, second);
+  baked_walk<SPARSE>(a.words, slots, a.step, G, dm, ray, true, second);
   if (cell >= 0) flush();
 }
 
@@ -567,17 +583,36 @@ extern "C" int upnerf_baked_sparse_render(const upnerf_baked_sparse_render_args*
   return baked_forward<true>(a, a->degree, a->pool, a->slots, stream);
 }
 
+// a backward entry point after its own refusals: the upstream gradient and the outputs of the degree, the lattice, the launch
+template <class Args>
+int baked_backward(const Args* a, const void* points, BakedGrid* G, OccDims* dm) {
+  if (!a || a->degree < 0 || a->degree > 2 || !a->g_rgb) return UPNERF_EINVAL;
+  if (a->degree == 0 ? !a->grad : (!a->grad_coef || !a->grad_sigma)) return UPNERF_EINVAL;
+  return baked_lattice(a, points, (size_t)16 << a->degree, G, dm) ? 0 : UPNERF_EINVAL;
+}
+
+template <bool SPARSE, class Args>
+int baked_backward_launch(const Args* a, const BakedGrid& G, const OccDims& dm, void* stream) {
+  baked_by_degree<0>(a->degree, [&](auto deg) {
+    hipLaunchKernelGGL((baked_render_bwd_kernel<decltype(deg)::value, SPARSE>), baked_blocks(a->R), dim3(BAKED_THREADS), 0, (hipStream_t)stream, *a, G, dm);
+  });
+  return (int)hipGetLastError();
+}
+
 extern "C" int upnerf_baked_render_bwd(const upnerf_baked_render_bwd_args* a, void* stream) {
   BakedGrid G;
   OccDims dm;
-  if (!a || a->degree < 0 || a->degree > 2 || !a->g_rgb) return UPNERF_EINVAL;
-  if (a->degree == 0 ? !a->grad : (!a->grad_coef || !a->grad_sigma)) return UPNERF_EINVAL;
-  if (!baked_lattice(a, a->points, (size_t)16 << a->degree, &G, &dm)) return UPNERF_EINVAL;
-  if (a->slots) return UPNERF_EUNSUP;  // a brick pool stores shared faces once per brick: densify(), tune, sparsify()
-  baked_by_degree<0>(a->degree, [&](auto deg) {
-    hipLaunchKernelGGL(baked_render_bwd_kernel<decltype(deg)::value>, baked_blocks(a->R), dim3(BAKED_THREADS), 0, (hipStream_t)stream, *a, G, dm);
-  });
-  return (int)hipGetLastError();
+  if (const int rc = baked_backward(a, a ? a->points : nullptr, &G, &dm)) return rc;
+  if (a->slots) return UPNERF_EUNSUP;  // a brick pool is upnerf_baked_sparse_render_bwd's: its output is pool-shaped
+  return baked_backward_launch<false>(a, G, dm, stream);
+}
+
+extern "C" int upnerf_baked_sparse_render_bwd(const upnerf_baked_sparse_render_bwd_args* a, void* stream) {
+  BakedGrid G;
+  OccDims dm;
+  if (!a || !a->slots) return UPNERF_EINVAL;
+  if (const int rc = baked_backward(a, a->pool, &G, &dm)) return rc;
+  return baked_backward_launch<true>(a, G, dm, stream);
 }
 
 extern "C" int upnerf_baked_project(const upnerf_baked_project_args* a, void* stream) {

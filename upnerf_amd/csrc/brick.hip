@@ -7,6 +7,8 @@
 //   upnerf_brick_scatter  pool -> dense grid (zeroed by the caller); a grid point is stored by its owner brick alone.
 //   upnerf_brick_occ      cell and brick bits from the pool: one thread per output word, every word written by one thread.
 //   upnerf_brick_columns  the rays that make the field kernels evaluate the pool's lines (upnerf_grid_columns for a brick pool).
+//   upnerf_brick_face_sum in place on a pool-shaped fp32 array, every copy of a point on a face that bricks share becomes the sum over
+//                         the copies, in ascending brick index: one launch collects into the first copy, one spreads it.
 // Everything is streaming and memory-bound; no LDS beyond the scan, no atomics.  All stores are ordinary vector stores from plain C++.
 #include "common.cuh"
 #include "grid.cuh"
@@ -19,6 +21,7 @@ namespace {
 
 #define BRICK_P UPNERF_BRICK_POINTS
 #define BRICK_N (BRICK_P * BRICK_P * BRICK_P)  // 729 points of a stored brick
+#define BRICK_FACE (BRICK_N - 7 * 7 * 7)       // 386 of them have an l of 0 or 8: the points a neighbouring brick can share
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -160,6 +163,76 @@ __global__ __launch_bounds__(NTHREADS) void brick_columns_kernel(upnerf_brick_co
   dd[2] = 1.f;
 }
 
+// face point f < 386 of a brick: the two z faces (81 points each), then the rim of the seven planes between them (32 each)
+__device__ __forceinline__ void brick_face_point(int f, int* lx, int* ly, int* lz) {
+  if (f < 2 * BRICK_P * BRICK_P) {
+    *lz = (f / (BRICK_P * BRICK_P)) * OCC_BRICK, *ly = (f % (BRICK_P * BRICK_P)) / BRICK_P, *lx = f % BRICK_P;
+    return;
+  }
+  f -= 2 * BRICK_P * BRICK_P;
+  const int r = f % 32;
+  *lz = 1 + f / 32;
+  if (r < 2 * BRICK_P) *ly = (r / BRICK_P) * OCC_BRICK, *lx = r % BRICK_P;
+  else *ly = 1 + (r - 2 * BRICK_P) / 2, *lx = ((r - 2 * BRICK_P) & 1) * OCC_BRICK;
+}
+
+// the bricks that hold grid point 8 b + l of an axis with B bricks, in ascending order, and where: one, or two on a shared plane
+struct BrickHolders {
+  int n, b0, l0, b1, l1;
+  __device__ __forceinline__ int b(int i) const { return i ? b1 : b0; }  // (selects, not an indexed array: the state stays in registers)
+  __device__ __forceinline__ int l(int i) const { return i ? l1 : l0; }
+};
+
+__device__ __forceinline__ BrickHolders brick_holders(int b, int l, int B) {
+  BrickHolders h = {1, b, l, b, l};
+  if (l == 0 && b > 0) h.n = 2, h.b0 = b - 1, h.l0 = OCC_BRICK;
+  else if (l == OCC_BRICK && b + 1 < B) h.n = 2, h.b1 = b + 1, h.l1 = 0;
+  return h;
+}
+
+// COLLECT: the copy in the first occupied holder becomes the sum over the occupied holders, in ascending brick index; the other
+// copies are read and not written.  !COLLECT (the launch after it): the other copies become the first.  One thread per float of a
+// face point of a slot; a point with one copy, or beyond the grid, is left alone.
+template <bool COLLECT>
+__global__ __launch_bounds__(NTHREADS) void brick_face_sum_kernel(upnerf_brick_face_sum_args a, OccDims d, int64_t n_threads) {
+  const int64_t id = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
+  if (id >= n_threads) return;
+  const int64_t fp = id / a.F;
+  const int q = (int)(id - fp * a.F);
+  const int64_t slot = fp / BRICK_FACE;
+  int lx, ly, lz;
+  brick_face_point((int)(fp - slot * BRICK_FACE), &lx, &ly, &lz);
+  const int b = a.bricks[slot];
+  if (b < 0 || b >= d.bricks) return;
+  const int bx = b % d.Bx, by = (b / d.Bx) % d.By, bz = b / (d.Bx * d.By);
+  if (bx * OCC_BRICK + lx > d.Cx || by * OCC_BRICK + ly > d.Cy || bz * OCC_BRICK + lz > d.Cz) return;
+  const BrickHolders hx = brick_holders(bx, lx, d.Bx), hy = brick_holders(by, ly, d.By), hz = brick_holders(bz, lz, d.Bz);
+  const int64_t self = (slot * BRICK_N + (lz * BRICK_P + ly) * BRICK_P + lx) * a.F + q;
+  int64_t first = -1;
+  int m = 0;  // occupied holders met
+  float sum = 0.0f;
+  for (int iz = 0; iz < hz.n; ++iz)
+    for (int iy = 0; iy < hy.n; ++iy)
+      for (int ix = 0; ix < hx.n; ++ix) {
+        const int s = a.slots[((int64_t)hz.b(iz) * d.By + hy.b(iy)) * d.Bx + hx.b(ix)];
+        if (s < 0 || s >= a.n_bricks) continue;
+        const int64_t at = ((int64_t)s * BRICK_N + (hz.l(iz) * BRICK_P + hy.l(iy)) * BRICK_P + hx.l(ix)) * a.F + q;
+        if (first < 0) {
+          if (COLLECT ? at != self : at == self) return;  // (collect: the first copy's thread alone works; spread: all but it)
+          first = at;
+          if (COLLECT) sum = a.data[at];
+          else {
+            a.data[self] = a.data[first];
+            return;
+          }
+        } else {
+          sum += a.data[at];
+        }
+        ++m;
+      }
+  if (COLLECT && m > 1) a.data[self] = sum;  // (with one copy nothing is written)
+}
+
 // the arguments gather and scatter share, and the words of the pool
 template <class Args>
 int brick_copy_check(const Args* a, const void* grid, const void* pool, OccDims* d, int* wpp, int64_t* n_words) {
@@ -240,5 +313,17 @@ extern "C" int upnerf_brick_columns(const upnerf_brick_columns_args* a, void* st
   const int64_t blocks = ceil_div64((int64_t)a->count * a->S + a->count, NTHREADS);
   if (blocks > INT_MAX) return UPNERF_EUNSUP;
   hipLaunchKernelGGL(brick_columns_kernel, dim3((unsigned)blocks), dim3(NTHREADS), 0, (hipStream_t)stream, *a, d.Bx, d.By);
+  return (int)hipGetLastError();
+}
+
+extern "C" int upnerf_brick_face_sum(const upnerf_brick_face_sum_args* a, void* stream) {
+  OccDims d;
+  if (!a || !occ_dims(a->Cx, a->Cy, a->Cz, &d) || a->F < 1) return UPNERF_EINVAL;
+  if (a->n_bricks < 1 || a->n_bricks > d.bricks || !a->slots || !a->bricks || !a->data || ((uintptr_t)a->data & 3) != 0) return UPNERF_EINVAL;
+  const int64_t n = (int64_t)a->n_bricks * BRICK_FACE * a->F;
+  if (ceil_div64(n, NTHREADS) > INT_MAX) return UPNERF_EUNSUP;
+  const dim3 grid((unsigned)ceil_div64(n, NTHREADS)), block(NTHREADS);
+  hipLaunchKernelGGL(brick_face_sum_kernel<true>, grid, block, 0, (hipStream_t)stream, *a, d, n);
+  hipLaunchKernelGGL(brick_face_sum_kernel<false>, grid, block, 0, (hipStream_t)stream, *a, d, n);
   return (int)hipGetLastError();
 }
