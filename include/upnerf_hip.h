@@ -1750,6 +1750,62 @@ typedef struct {
 } upnerf_brick_face_sum_args;
 int upnerf_brick_face_sum(const upnerf_brick_face_sum_args* a, void* stream);
 
+/* ---- posing a photograph against a baked scene: the marcher's ray gradients (csrc/baked.hip).  Added under
+ * ABI 11: new symbols only.
+ *
+ * upnerf_baked_ray_bwd: the gradient of a loss over (rgb, depth, opacity) of the baked forward with respect to each ray's own
+ * row o | d | near | far, WRITTEN (not added) to g_rays [R][8].  One entry point for both layouts: `slots` NULL is a dense grid
+ * (`points` = rgbs at degree 0, records at degree 1, 2), else `points` is the pool of upnerf_baked_sparse_render.  One thread per
+ * ray, one wave per workgroup, one launch, nothing allocated, no host read-back; a ray's sums stay in its thread's registers: no
+ * LDS, no atomics, the same bits every run and however the rays are cut into launches.  upnerf_pose_rays_bwd maps the rows' o and
+ * d parts on to se(3).
+ *
+ * The definition.  The visited samples of a ray, their cells i, positions f in the cell, corners c_0..7 (x = j & 1, y = j >> 1 & 1,
+ * z = j >> 2; at degree > 0 each colour already reduced with the ray's Y, as the forward reads it), blended channels v, the clamp
+ * with its `open` mask, w_k, T_{k+1} and the `stop` sample are the forward's, formed by the same code; q_k, P_k and Q are
+ * upnerf_baked_render_bwd's.  The set of visited samples and the cell of each are HELD FIXED: this is the derivative of the
+ * piecewise-smooth function the forward computes (K's dependence on near and far is a step function and contributes nothing).
+ * All fp32; lerp(f, a, b) = fmaf(f, b - a, a).  Per visited sample k, in sample order:
+ *   I_k = fmaf(T_{k+1}, q_k, -(Q - P_k));   a_k[c] = open_c ? w_k * g_rgb[c] : 0 (c = r, g, b);   a_k[sigma] = delta * I_k
+ *   per channel ch = r, g, b, sigma, the slopes of the blend
+ *     s_x = lerp(fz, lerp(fy, c1 - c0, c3 - c2), lerp(fy, c5 - c4, c7 - c6))
+ *     s_y = lerp(fz, lerp(fx, c2 - c0, c3 - c1), lerp(fx, c6 - c4, c7 - c5))
+ *     s_z = lerp(fy, lerp(fx, c4 - c0, c5 - c1), lerp(fx, c6 - c2, c7 - c3))
+ *   S_k[a] = the fmaf chain over ch in that order, from zero: S = fmaf(a_k[ch], s_a[ch], S)
+ *   So[a] += S_k[a];  St[a] = fmaf(t_k, S_k[a], St[a]);  E = fmaf(v_k.sigma, I_k, E);  O += w_k
+ *   degree > 0: for corner j = 0..7, with wt_j = ((z ? fz : 1 - fz) * (y ? fy : 1 - fy)) * (x ? fx : 1 - fx), for c = r, g, b and
+ *   basis function i ascending:  Z_i = fmaf(k_j[c][i], wt_j * a_k[c], Z_i),  k_j the corner's stored halves, converted exactly.
+ * The gradient with respect to the sample's position is G_k[a] = inv[a] S_k[a], inv[a] = C[a] / (hi[a] - lo[a]) as the forward
+ * holds it; the factor is applied once to the sums.  Per ray, with u = d / len as the forward forms it:
+ *   d_o[a]  = inv[a] * So[a]
+ *   d_d[a]  = fmaf(E * step, u[a], inv[a] * St[a])     (sum_k t_k G_k, and E, the gradient of delta = step len, through len)
+ *             + fmaf(-u[a], u . gu, gu[a]) / len  at degree > 0:  gu[a] = sum_i Z_i dY_i/du[a] for the basis as stated at
+ *             upnerf_baked_sh_render (a fmaf chain over i ascending, the constants folded into the factor of Z_i), u . gu =
+ *             fmaf(u_z, gu_z, fmaf(u_y, gu_y, u_x * gu_x)): dY/dd = (dY/du)(I - u u^T) / len
+ *   d_near  = fmaf(g_depth, O, fmaf(d_z, d_o[z], fmaf(d_y, d_o[y], d_x * d_o[x])))     (= sum_k (d . G_k + g_depth w_k))
+ *   d_far   = g_depth * (1 - O)
+ * A row of eight zeros is written for a miss (a number that is not finite, far <= near), for a ray with len == 0, and for a ray
+ * whose g_rgb, g_depth and g_opacity are all zero.
+ * Refused (UPNERF_EINVAL): what the forward of the same layout refuses, a NULL g_rgb or g_rays, g_rays not 16-byte aligned, a
+ * degree outside {0, 1, 2}. */
+typedef struct {
+  int32_t Cx, Cy, Cz, R;
+  float lo[3], hi[3];        /* hi > lo, finite */
+  float step;                /* > 0, finite */
+  float background;          /* finite */
+  float stop;                /* >= 0, < 1; 0 = never */
+  int32_t degree;            /* 0, 1 or 2 */
+  const uint8_t* points;     /* rgbs, records, or a pool [n_bricks][9][9][9][16 | 32 | 64]; aligned to the size of a point */
+  const int32_t* slots;      /* NULL: a dense grid; else [Bz][By][Bx], every entry < n_bricks */
+  const uint32_t* words;     /* [upnerf_occ_words(Cx, Cy, Cz)] */
+  const float* rays;         /* [R][8], 16-byte aligned */
+  const float* g_rgb;        /* [R][3] */
+  const float* g_depth;      /* [R] or NULL */
+  const float* g_opacity;    /* [R] or NULL */
+  float* g_rays;             /* [R][8], 16-byte aligned */
+} upnerf_baked_ray_bwd_args;
+int upnerf_baked_ray_bwd(const upnerf_baked_ray_bwd_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

@@ -39,7 +39,12 @@ of --sparse at 128^3 and 256^3 points, degree 0 and 2, one step of the dense tun
 sparsify detour runs) and one of the pool tuner (on its sparsify()), on the same --chunk rays and targets, alternately in one
 process, medians of --reps (HIP events round 5 steps); beside every time the occupied share of the bricks f_b and the bytes each
 tuner holds; and the new launches alone: the sparse backward, the face sum (collect and spread, over every gradient array), with
-the dense backward on the same rays beside them."""
+the dense backward on the same rays beside them.
+
+--pose measures the ray gradient INSTEAD and writes --pose-out: on the analytic shell of --sparse at 128^3 points,
+degree 0, 1 and 2, dense and sparse, ms per launch of upnerf_baked_ray_bwd on the --chunk rays beside the forward and the points
+backward of the same scene, alternately in one process, medians of --reps (HIP events round 5 launches), the ratios, and
+iterations per second of BakedLocaliser.step on two 64 x 64 photographs."""
 import argparse
 import json
 import os
@@ -87,6 +92,8 @@ def main():
     ap.add_argument("--tune-out", default=os.path.join(ROOT, "profiles", "baked_tune.json"))
     ap.add_argument("--tune-iters", type=int, default=200, help="with --tune: iterations of the distill")
     ap.add_argument("--pool-tune-out", default=os.path.join(ROOT, "profiles", "baked_sparse_tune.json"))
+    ap.add_argument("--pose", action="store_true", help="measure the ray gradient (upnerf_baked_ray_bwd) and the localiser instead; writes --pose-out")
+    ap.add_argument("--pose-out", default=os.path.join(ROOT, "profiles", "baked_pose.json"))
     ap.add_argument("--parent-lib", default=None, help="with --sparse: the parent commit's libupnerf_hip.so, for the nine marchers' times beside this build's")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -111,6 +118,8 @@ def main():
     path = CameraPath.from_poses(c2w, (0.1, 5.0), F, appearance=(a.bake_image, a.bake_image), img_wh=(W, H), K=K)  # ONE appearance: the baked one
     rays = F * H * W
     res = tuple(a.resolution)
+    if a.pose:
+        return pose_main(a, path, dev)
     if a.sparse and a.tune:
         return pool_tune_main(a, path, dev)
     if a.sparse:
@@ -431,6 +440,93 @@ def pool_tune_main(a, path, dev):
            "note": "an analytic shell, not a trained scene: f_b and the hit share are the shell's"}
     os.makedirs(os.path.dirname(os.path.abspath(a.pool_tune_out)), exist_ok=True)
     with open(a.pool_tune_out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+def pose_main(a, path, dev):
+    """--pose: ms per launch of upnerf_baked_ray_bwd on one chunk of rays beside the forward and the points backward of the same
+    scene (128^3 analytic shell, degree 0, 1, 2, dense and sparse), alternately in one process, medians of --reps; and
+    iterations per second of BakedLocaliser.step on two 64 x 64 photographs of the degree-0 scene."""
+    import statistics as st
+    from upnerf_amd import baked_pose, baked_sparse_tune, baked_tune, novel_view
+    from upnerf_amd.baked import BakedScene, sphere_directions
+    W, H = a.width, a.height
+    c2w, nf = novel_view.path_poses(path.key_c2w.to(dev), path.key_near_far.to(dev), path.u.to(dev), path.mode)
+    rays = novel_view.path_rays(c2w, nf, (W, H), path.K, 0, H * W)[0][:a.chunk].contiguous()
+    R = rays.shape[0]
+    gen = torch.Generator(device="cpu").manual_seed(5)
+    g_rgb = torch.randn(R, 3, generator=gen).to(dev)
+    STEPS = 5
+
+    def event_ms(fn, n=1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    rows, n = [], 128
+    for degree in (0, 1, 2):
+        if degree == 0:
+            dense = BakedScene.from_grids(*shell_grids(n, dev), BOUNDS, 1.0)
+        else:
+            dirs = sphere_directions(12)
+            sigma, rgb_dirs = shell_grids(n, dev, dirs)
+            dense = BakedScene.from_direction_grids(sigma, rgb_dirs, dirs, BOUNDS, 1.0, sh_degree=degree)
+            del sigma, rgb_dirs
+        sparse = dense.sparsify()
+        for layout, scene in (("dense", dense), ("sparse", sparse)):
+            out = torch.empty(R, 8, device=dev)
+            legs = {"forward": lambda: scene.render(rays, a.step),
+                    "ray_bwd": lambda: baked_pose.ray_backward(scene, rays, a.step, 0.0, 0.0, g_rgb, out=out)}
+            if layout == "dense":
+                grads = baked_tune.backward(dense.grid, degree, dense.occupancy, dense.bounds, rays, a.step, 0.0, 0.0, g_rgb)
+                legs["points_bwd"] = lambda: baked_tune.backward(dense.grid, degree, dense.occupancy, dense.bounds, rays, a.step, 0.0, 0.0, g_rgb, out=grads)
+            else:
+                params = baked_sparse_tune.PoolParams.of(sparse, requires_grad=False)
+                grads = baked_sparse_tune.backward(sparse.pool, params, rays, a.step, 0.0, 0.0, g_rgb, face_sum=False)
+                legs["points_bwd"] = lambda: baked_sparse_tune.backward(sparse.pool, params, rays, a.step, 0.0, 0.0, g_rgb, out=grads, face_sum=False)
+            for fn in legs.values():  # warm-up
+                fn()
+            ms = {k: [] for k in legs}
+            for _ in range(a.reps):
+                for k, fn in legs.items():
+                    ms[k].append(event_ms(fn, STEPS))
+            med = {k: st.median(v) for k, v in ms.items()}
+            rows.append({"resolution": n, "degree": degree, "layout": layout, "ms_per_launch": med, "ms_all": {k: sorted(v) for k, v in ms.items()},
+                         "ray_bwd_over_points_bwd": med["ray_bwd"] / med["points_bwd"], "ray_bwd_over_forward": med["ray_bwd"] / med["forward"],
+                         "hit_share": float((scene.render(rays, a.step)["opacity"] > 0).float().mean())})
+            del legs, grads
+        if degree == 0:  # the localiser: two photographs rendered by the marcher itself, poses a little off
+            w = 64
+            Kc = (0.8 * w, 0.8 * w, w / 2, w / 2)
+            yy, xx = torch.meshgrid(torch.arange(w, device=dev), torch.arange(w, device=dev), indexing="ij")
+            dirs_c = baked_pose.pixel_directions(xx.reshape(-1), yy.reshape(-1), Kc)
+            from upnerf_amd.camera import get_rays
+            poses = c2w[[0, c2w.shape[0] - 1]].contiguous()
+            targets = []
+            for p in poses:
+                o, d = get_rays(dirs_c, p)
+                targets.append(dense.render(torch.cat([o, d, nf[:1].expand(w * w, 2)], 1).contiguous(), a.step)["rgb"].view(w, w, 3))
+            init = poses.clone()
+            init[:, :, 3] += 0.01
+            loc = baked_pose.BakedLocaliser(dense, torch.stack(targets), Kc, init, nf[0].tolist(), lr=1e-3)
+            lgen = torch.Generator(device="cpu").manual_seed(7)
+            one = lambda: loc.step(4096, a.step, lgen)
+            one()
+            its = [1e3 / event_ms(one, 20) for _ in range(a.reps)]
+            localiser = {"images": 2, "pixels_per_image": w * w, "batch": 4096, "iterations_per_s": st.median(its), "all": sorted(its)}
+        del dense, sparse
+        torch.cuda.empty_cache()
+    out = {"metric": "the baked marcher's ray gradient (upnerf_baked_ray_bwd) beside the forward and the points backward of the same scene, and one localiser step; analytic shell, random upstream gradients",
+           "rays": R, "step": a.step, "reps": a.reps, "launches_per_timing": STEPS, "bounds": [list(b) for b in BOUNDS], "rows": rows, "localiser": localiser,
+           "note": "an analytic shell, not a trained scene: the hit share is the shell's"}
+    os.makedirs(os.path.dirname(os.path.abspath(a.pose_out)), exist_ok=True)
+    with open(a.pose_out, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
     print(json.dumps(out))

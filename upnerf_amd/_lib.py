@@ -455,6 +455,13 @@ class BrickFaceSumArgs(C.Structure):
                 ("reserved_", C.c_int32), ("slots", _fp), ("bricks", _fp), ("data", _fp)]
 
 
+class BakedRayBwdArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("R", C.c_int32), ("lo", C.c_float * 3),
+                ("hi", C.c_float * 3), ("step", C.c_float), ("background", C.c_float), ("stop", C.c_float), ("degree", C.c_int32),
+                ("points", _fp), ("slots", _fp), ("words", _fp), ("rays", _fp), ("g_rgb", _fp), ("g_depth", _fp), ("g_opacity", _fp),
+                ("g_rays", _fp)]
+
+
 class DensityGradArgs(C.Structure):
     _fields_ = [("M", C.c_int32), ("reserved_", C.c_int32), ("points", _fp), ("P", _fp), ("PT", _fp), ("wk_xyz", C.c_float * 10),
                 ("sigma", _fp), ("grad", _fp)]
@@ -588,6 +595,7 @@ _SIGNATURES = {
     "upnerf_baked_project": [C.POINTER(BakedProjectArgs), _p],
     "upnerf_baked_sparse_render_bwd": [C.POINTER(BakedSparseRenderBwdArgs), _p],
     "upnerf_brick_face_sum": [C.POINTER(BrickFaceSumArgs), _p],
+    "upnerf_baked_ray_bwd": [C.POINTER(BakedRayBwdArgs), _p],
 }
 _LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
              "upnerf_occ_compact_scratch", "upnerf_pca_fit_scratch", "upnerf_brick_table_scratch")

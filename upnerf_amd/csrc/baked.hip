@@ -31,6 +31,9 @@
 //   upnerf_baked_sparse_render_bwd  the same kernel's other layout (the template's second parameter again): the
 //                        gradient is pool-shaped, and a copy of a point on a face that bricks share receives the part that the
 //                        samples inside its own brick give it -- upnerf_brick_face_sum (brick.hip) makes the copies whole.
+//   upnerf_baked_ray_bwd  the gradient of a render with respect to each ray's own row o | d | near | far, both
+//                        layouts: two marches again, the second one meets every sample's four gradients with the slopes of
+//                        the blend in its cell; all sums in the ray's registers, the row written once: the same bits every run.
 //   upnerf_baked_project the tuned points back into the marcher's domain (sigma >= 0 and finite; degree 0: colours in [0, 1]).
 // All stores are ordinary vector stores and vector float atomics from plain C++.
 #include "common.cuh"
@@ -444,6 +447,156 @@ __global__ __launch_bounds__(BAKED_THREADS) void baked_render_bwd_kernel(BakedBw
   if (cell >= 0) flush();
 }
 
+// ---- the gradient of a ray's own row: upnerf_baked_ray_bwd (include/upnerf_hip.h states the gradient and the order of every sum;
+// DESIGN.md 2.36).  What a launch reads and writes, scalars first (BakedArgs says why); both layouts and the three degrees.
+struct BakedRayArgs {
+  int R;
+  float step, background, stop;
+  const void* points;
+  const int32_t* slots;  // NULL: a dense layout
+  const uint32_t* words;
+  const float* rays;
+  const float *g_rgb, *g_depth, *g_opacity;
+  float* g_rays;
+};
+
+struct BakedRayGrad {
+  float v[8];  // the gradient of o | d | near | far
+};
+
+__host__ __device__ __forceinline__ float baked_lerp(float f, float a, float b) { return fmaf(f, b - a, a); }
+
+// Z_j += sum_c s[c] k[c][j] over the stored halves of record p, channel by channel and j ascending (s: a corner's trilinear
+// weight times the colour gradients of the sample): the blend of the coefficients is never formed
+template <int DEG>
+__host__ __device__ __forceinline__ void baked_coef_sum(const BakedCorner<DEG>& pts, int64_t p, const float* s, float* Z) {
+  if constexpr (DEG > 0) {
+    constexpr int NB = BakedCorner<DEG>::NB, Q = BakedCorner<DEG>::Q;
+    uint32_t w[4 * Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const u32x4 v = pts.rec[p * Q + q];
+      w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const int h = c * NB + j;
+        const float k = (float)__builtin_bit_cast(_Float16, (uint16_t)(w[h >> 1] >> ((h & 1) * 16)));
+        Z[j] = fmaf(k, s[c], Z[j]);
+      }
+  }
+}
+
+// the gradient of one ray row for the upstream gradients g = g_rgb | g_depth | g_opacity (host and device: the host build is
+// what tests/host/baked_ray_host.hip holds to the fp64 restatement).  Two marches with the forward's walk, ray and blend: the
+// first forms Q, the second the sums; the visited samples and their cells are the forward's and are held fixed.
+template <int DEG, bool SPARSE>
+__host__ __device__ __forceinline__ BakedRayGrad baked_ray_grad(const BakedRayArgs& A, const BakedGrid& G, const OccDims& dm,
+                                                                const float* row, const float* g, bool use_bits) {
+  constexpr int NB = (DEG + 1) * (DEG + 1);
+  BakedRayGrad out;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) out.v[i] = 0.0f;
+  if (g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f && g[3] == 0.0f && g[4] == 0.0f) return out;
+  const BakedRay ray(row, A.step);
+  if (!ray.ok || ray.len == 0.0f) return out;  // a miss; a direction of length zero
+  const BakedCorner<DEG> pts(A.points, ray.d, ray.len);
+  auto q_of = [&](const BakedBlend& b, float t) __attribute__((always_inline)) {
+    return fmaf(g[0], b.v[0] - A.background, fmaf(g[1], b.v[1] - A.background, fmaf(g[2], b.v[2] - A.background, fmaf(g[3], t - ray.far, g[4]))));
+  };
+
+  float Q = 0.0f, T = 1.0f;
+  auto first = [&](const BakedSample& s, int64_t base, int64_t sy, int64_t sz) __attribute__((always_inline)) {
+    const BakedBlend b = baked_blend<DEG>(pts, s, base, sy, sz, ray.delta, T);
+    Q = fmaf(b.w, q_of(b, s.t), Q);
+    T = b.Tn;
+    return A.stop > 0.0f && T < A.stop;
+  };
+  baked_walk<SPARSE>(A.words, A.slots, A.step, G, dm, ray, use_bits, first);
+
+  // So[a] = sum_k S_k[a] and St[a] = sum_k t_k S_k[a], S_k[a] = sum_ch a_k[ch] s_a[ch]: the grid's 1 / cell is applied once, after
+  float P = 0.0f, O = 0.0f, E = 0.0f, So[3] = {0.0f, 0.0f, 0.0f}, St[3] = {0.0f, 0.0f, 0.0f}, Z[NB];
+#pragma unroll
+  for (int j = 0; j < NB; ++j) Z[j] = 0.0f;
+  T = 1.0f;
+  auto second = [&](const BakedSample& s, int64_t base, int64_t sy, int64_t sz) __attribute__((always_inline)) {
+    const BakedBlend b = baked_blend<DEG>(pts, s, base, sy, sz, ray.delta, T);
+    const float q = q_of(b, s.t);
+    P = fmaf(b.w, q, P);
+    const float I = fmaf(b.Tn, q, -(Q - P));
+    float a[4];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) a[ch] = (b.open >> ch & 1u) ? b.w * g[ch] : 0.0f;
+    a[3] = ray.delta * I;
+    E = fmaf(b.v[3], I, E);
+    O += b.w;
+    // the slopes of the blend in its cell, from the corners as the blend read them
+    const f32x4 c[8] = {pts(base),      pts(base + 1),      pts(base + sy),      pts(base + sy + 1),
+                        pts(base + sz), pts(base + sz + 1), pts(base + sz + sy), pts(base + sz + sy + 1)};
+    float S[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) {
+      const float sx = baked_lerp(b.f[2], baked_lerp(b.f[1], c[1][ch] - c[0][ch], c[3][ch] - c[2][ch]),
+                                  baked_lerp(b.f[1], c[5][ch] - c[4][ch], c[7][ch] - c[6][ch]));
+      const float sy_ = baked_lerp(b.f[2], baked_lerp(b.f[0], c[2][ch] - c[0][ch], c[3][ch] - c[1][ch]),
+                                   baked_lerp(b.f[0], c[6][ch] - c[4][ch], c[7][ch] - c[5][ch]));
+      const float sz_ = baked_lerp(b.f[1], baked_lerp(b.f[0], c[4][ch] - c[0][ch], c[5][ch] - c[1][ch]),
+                                   baked_lerp(b.f[0], c[6][ch] - c[2][ch], c[7][ch] - c[3][ch]));
+      S[0] = fmaf(a[ch], sx, S[0]), S[1] = fmaf(a[ch], sy_, S[1]), S[2] = fmaf(a[ch], sz_, S[2]);
+    }
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) So[ax] += S[ax], St[ax] = fmaf(s.t, S[ax], St[ax]);
+    if constexpr (DEG > 0) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float wt = ((j & 4 ? b.f[2] : 1.0f - b.f[2]) * (j & 2 ? b.f[1] : 1.0f - b.f[1])) * (j & 1 ? b.f[0] : 1.0f - b.f[0]);
+        const float sc[3] = {wt * a[0], wt * a[1], wt * a[2]};
+        baked_coef_sum<DEG>(pts, base + (j & 1) + (j >> 1 & 1) * sy + (j >> 2) * sz, sc, Z);
+      }
+    }
+    T = b.Tn;
+    return A.stop > 0.0f && T < A.stop;
+  };
+  baked_walk<SPARSE>(A.words, A.slots, A.step, G, dm, ray, use_bits, second);
+
+  const float u[3] = {ray.d[0] / ray.len, ray.d[1] / ray.len, ray.d[2] / ray.len};
+  const float Es = E * A.step;
+#pragma unroll
+  for (int ax = 0; ax < 3; ++ax) {
+    out.v[ax] = G.inv[ax] * So[ax];
+    out.v[3 + ax] = fmaf(Es, u[ax], G.inv[ax] * St[ax]);
+  }
+  if constexpr (DEG > 0) {  // sum_j Z_j dY_j/du, then through du/dd = (I - u u^T) / len
+    const float c1 = 0.4886025119029199f, c2 = 1.0925484305920792f, c3 = 0.31539156525252005f, c4 = 0.5462742152960396f;
+    float gu[3] = {-c1 * Z[3], -c1 * Z[1], c1 * Z[2]};
+    if constexpr (DEG > 1) {
+      gu[0] = fmaf(2.0f * c4 * u[0], Z[8], fmaf(-c2 * u[2], Z[7], fmaf(-2.0f * c3 * u[0], Z[6], fmaf(c2 * u[1], Z[4], gu[0]))));
+      gu[1] = fmaf(-2.0f * c4 * u[1], Z[8], fmaf(-2.0f * c3 * u[1], Z[6], fmaf(-c2 * u[2], Z[5], fmaf(c2 * u[0], Z[4], gu[1]))));
+      gu[2] = fmaf(-c2 * u[0], Z[7], fmaf(4.0f * c3 * u[2], Z[6], fmaf(-c2 * u[1], Z[5], gu[2])));
+    }
+    const float along = fmaf(u[2], gu[2], fmaf(u[1], gu[1], u[0] * gu[0]));
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) out.v[3 + ax] += fmaf(-u[ax], along, gu[ax]) / ray.len;
+  }
+  out.v[6] = fmaf(g[3], O, fmaf(ray.d[2], out.v[2], fmaf(ray.d[1], out.v[1], ray.d[0] * out.v[0])));
+  out.v[7] = g[3] * (1.0f - O);
+  return out;
+}
+
+template <int DEG, bool SPARSE>
+__global__ __launch_bounds__(BAKED_THREADS) void baked_ray_bwd_kernel(BakedRayArgs a, BakedGrid G, OccDims dm) {
+  const int r = blockIdx.x * BAKED_THREADS + threadIdx.x;
+  if (r >= a.R) return;
+  const float g[5] = {a.g_rgb[(int64_t)r * 3], a.g_rgb[(int64_t)r * 3 + 1], a.g_rgb[(int64_t)r * 3 + 2], a.g_depth ? a.g_depth[r] : 0.0f,
+                      a.g_opacity ? a.g_opacity[r] : 0.0f};
+  const BakedRayGrad out = baked_ray_grad<DEG, SPARSE>(a, G, dm, a.rays + (int64_t)r * 8, g, true);
+  f32x4* dst = (f32x4*)(a.g_rays + (int64_t)r * 8);
+  dst[0] = f32x4{out.v[0], out.v[1], out.v[2], out.v[3]};
+  dst[1] = f32x4{out.v[4], out.v[5], out.v[6], out.v[7]};
+}
+
 // upnerf_baked_project: the point of a tuned scene back into the set the marcher is defined on
 __global__ __launch_bounds__(NTHREADS) void baked_project_kernel(upnerf_baked_project_args a) {
   const int64_t n = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
@@ -613,6 +766,22 @@ extern "C" int upnerf_baked_sparse_render_bwd(const upnerf_baked_sparse_render_b
   if (!a || !a->slots) return UPNERF_EINVAL;
   if (const int rc = baked_backward(a, a->pool, &G, &dm)) return rc;
   return baked_backward_launch<true>(a, G, dm, stream);
+}
+
+extern "C" int upnerf_baked_ray_bwd(const upnerf_baked_ray_bwd_args* a, void* stream) {
+  BakedGrid G;
+  OccDims dm;
+  if (!a || a->degree < 0 || a->degree > 2 || !a->g_rgb || !a->g_rays || !baked_aligned16(a->g_rays)) return UPNERF_EINVAL;
+  if (!baked_lattice(a, a->points, (size_t)16 << a->degree, &G, &dm)) return UPNERF_EINVAL;
+  const BakedRayArgs A = {a->R,    a->step,  a->background, a->stop,      a->points, a->slots,
+                          a->words, a->rays, a->g_rgb,      a->g_depth,   a->g_opacity, a->g_rays};
+  baked_by_degree<0>(a->degree, [&](auto deg) {
+    if (a->slots)
+      hipLaunchKernelGGL((baked_ray_bwd_kernel<decltype(deg)::value, true>), baked_blocks(a->R), dim3(BAKED_THREADS), 0, (hipStream_t)stream, A, G, dm);
+    else
+      hipLaunchKernelGGL((baked_ray_bwd_kernel<decltype(deg)::value, false>), baked_blocks(a->R), dim3(BAKED_THREADS), 0, (hipStream_t)stream, A, G, dm);
+  });
+  return (int)hipGetLastError();
 }
 
 extern "C" int upnerf_baked_project(const upnerf_baked_project_args* a, void* stream) {
