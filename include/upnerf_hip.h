@@ -1806,6 +1806,107 @@ typedef struct {
 } upnerf_baked_ray_bwd_args;
 int upnerf_baked_ray_bwd(const upnerf_baked_ray_bwd_args* a, void* stream);
 
+/* ---- coarse-to-fine baked scenes: total variation and the doubling of the resolution (csrc/baked_reg.hip).  Added
+ * under ABI 11: new symbols only.  Arguments refused on the host before anything is launched, nothing allocated, no host read-back,
+ * no atomics, every output address has one writer: the same bits every run.
+ *
+ * upnerf_baked_tv: the total variation of a fp32 point array `data` [n][F] (F floats per point: rgbs with F = 4; coef with
+ * F = 3 nb; sigma with F = 1) over the OCCUPIED cells, and its gradient.  Geometry and `words` are the occupancy grid's.  Cell
+ * (i, j, k) has base point p = (i, j, k) and forward neighbours px = p + ex, py = p + ey, pz = p + ez (corners of the cell: they
+ * exist).  All fp32.  For every cell c whose cell bit is set and every float f with w[f] != 0:
+ *   dx = data[px][f] - data[p][f], dy and dz likewise;   tv_f(c) = sqrtf(fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps)))).
+ * The value is sum_f w[f] sum_c tv_f(c).  It is written as one partial sum per workgroup to partial[0 .. upnerf_baked_tv_blocks)
+ * (a thread adds its terms by fmaf(w[f], tv, .) in the order it meets them, the workgroup sums its 256 threads by a fixed tree);
+ * the caller adds the partials.  `partial` NULL: no value.
+ * The gradient, in gather form: point p receives up to four terms in this order -- the sum g IS the own term where that is
+ * present and 0.0f where it is not, and each later term present is added to it (g += term):
+ *   -((dx + dy) + dz) / tv_f(c)   of its own cell c = p, if that cell exists and is occupied,
+ *   + dx' / tv_f(c')              of cell c' = p - ex, if it exists and is occupied (dx' = data[p][f] - data[p - ex][f]: p is its px),
+ *   + dy' / tv_f(c')              of cell p - ey likewise,   + dz' / tv_f(c') of cell p - ez likewise,
+ * and grad[p][f] = fmaf(w[f], that sum, grad[p][f]): ADDED, as every baked gradient is.  A point none of whose four cells is
+ * occupied, and a float with w[f] == 0, are not touched.  A point whose sigma -- sigma[p * sigma_stride], an element stride so
+ * that rgbs' fourth float serves -- is exactly zero is not a parameter and receives nothing (upnerf_baked_render_bwd's rule); its
+ * own cell still counts in the value and in its neighbours' gradients: the field is zero there.
+ * Dense (n_bricks = 0, slots = bricks = NULL): n = (Cx+1)(Cy+1)(Cz+1).  One workgroup per tile of 8 x 8 x 8 points, staged in LDS
+ * with a one-point halo on either side, 8 floats of a point at a time.
+ * Pool (n_bricks >= 1, slots and bricks given): n = 729 n_bricks, the layout of the sparse scene above.  One workgroup per brick;
+ * only the 8 x 8 x 8 cells of the brick itself count for its points: EACH COPY of a point on a face that bricks share RECEIVES
+ * ONLY WHAT THE CELLS INSIDE ITS OWN BRICK GIVE IT (the contract of upnerf_baked_sparse_render_bwd), and upnerf_brick_face_sum
+ * forms the point's gradient on every copy.  Pool points beyond the grid receive nothing.  Every occupied cell lies in one brick:
+ * the value is the dense one's up to the order of the sum.
+ * Refused (UPNERF_EINVAL): NULL words, data, sigma or grad; cells outside upnerf_occ_words' range; n_bricks < 0 or > Bx By Bz;
+ * slots or bricks given without the other or without n_bricks >= 1; F < 1 or > 28; sigma_stride < 1; eps <= 0 or not finite; a
+ * weight among w[0 .. F-1] that is not finite.  UPNERF_EUNSUP: more workgroups than a launch has. */
+typedef struct {
+  int32_t Cx, Cy, Cz;
+  int32_t n_bricks;          /* 0: a dense grid; else the bricks of the pool */
+  int32_t F;                 /* floats per point, 1 .. 28 */
+  int32_t sigma_stride;      /* floats from one point's sigma to the next's, >= 1 */
+  float eps;                 /* > 0, finite */
+  float w[28];               /* w[0 .. F-1], finite */
+  int32_t reserved_;
+  const uint32_t* words;     /* [upnerf_occ_words(Cx, Cy, Cz)] */
+  const int32_t* slots;      /* NULL, or [Bz][By][Bx] */
+  const int32_t* bricks;     /* NULL, or [n_bricks] */
+  const float* data;         /* [n][F] */
+  const float* sigma;        /* sigma of point p at sigma[p * sigma_stride] */
+  float* grad;               /* [n][F], added into */
+  float* partial;            /* [upnerf_baked_tv_blocks(Cx, Cy, Cz, n_bricks)] or NULL */
+} upnerf_baked_tv_args;
+long long upnerf_baked_tv_blocks(int Cx, int Cy, int Cz, int n_bricks);
+int upnerf_baked_tv(const upnerf_baked_tv_args* a, void* stream);
+
+/* upnerf_baked_upsample: the dense scene of twice the cells per axis, 2 C cells and 2 N - 1 points, from the points of a dense
+ * scene (`points`: rgbs at degree 0, records at degree 1, 2).  One thread per child point.  Child point (i', j', k') is the
+ * trilinear value of the parent grid at (i' / 2, j' / 2, k' / 2), formed per stored number -- r, g, b, sigma at degree 0; the
+ * 3 nb halves, converted exactly to fp32, and the fp32 sigma at degree 1, 2 -- per axis in a fixed order: along x an even i'
+ * copies parent i' / 2 and an odd one is 0.5f * (a + b) of parents (i' - 1) / 2 and (i' + 1) / 2, for each of the up to 2 x 2
+ * (y, z) parents; then the same along y on those results, then along z.  The halving is exact (but for a subnormal), only the
+ * additions round; a dropped parent is the zero record it is stored as.  The child is then packed at `level` by the rule of
+ * upnerf_baked_pack (degree 0) or upnerf_baked_sh_pack (degree 1, 2: kept iff sigma is finite, > 0 and >= level and every
+ * coefficient is finite; the coefficients held to +-65504 and rounded to nearest even to fp16).
+ * Refused (UPNERF_EINVAL): NULL or misaligned points / out, a degree outside {0, 1, 2}, a NaN level, parent or child cells outside
+ * upnerf_occ_words' range.  UPNERF_EUNSUP: more threads than a launch has. */
+typedef struct {
+  int32_t Cx, Cy, Cz;        /* the PARENT's cells */
+  int32_t degree;            /* 0, 1 or 2 */
+  float level;               /* not NaN */
+  int32_t reserved_;
+  const uint8_t* points;     /* [Cz+1][Cy+1][Cx+1][16 | 32 | 64], aligned to the size of a point */
+  uint8_t* out;              /* [2Cz+1][2Cy+1][2Cx+1][16 | 32 | 64], aligned to the size of a point */
+} upnerf_baked_upsample_args;
+int upnerf_baked_upsample(const upnerf_baked_upsample_args* a, void* stream);
+
+/* The same from pool to pool, nothing the size of either grid.  The child grid has B' = ceil(2 C / 8) bricks per axis (2 B or
+ * 2 B - 1); child brick (bx', by', bz') holds child points 8 bx' .. 8 bx' + 8, whose parents are points 4 (bx' & 1) ..
+ * 4 (bx' & 1) + 4 of parent brick (bx' >> 1, by' >> 1, bz' >> 1): a 5 x 5 x 5 block of ONE parent brick.  PRECONDITION: the
+ * parent pool keeps the layout's invariant (a kept point makes every brick that contains a cell touching it occupied); then every
+ * child brick with a kept point is the child of an occupied parent, and children of empty parents are empty.
+ * upnerf_brick_upsample_mark: the brick bits of the CHILD grid into words[fine_words' ..] (words: the child's
+ *   upnerf_occ_words(2 Cx, 2 Cy, 2 Cz) words; only the brick words are written, all of them).  A child brick's bit is set iff its
+ *   parent has a slot and one of its child points inside the child grid is kept by upnerf_baked_upsample's rule at `level`: iff
+ *   one of its cells touches a kept child point.  One workgroup per word.  upnerf_brick_table then makes the child's table.
+ * upnerf_brick_upsample_fill: the child pool `out` [n_child][9][9][9][E] for the child bricks `child_bricks`: the records of
+ *   upnerf_baked_upsample, far faces included; zero records beyond the child grid (and for a child of an empty parent).  One
+ *   thread per child pool point.  upnerf_brick_occ then makes the child's cell bits.
+ * Refused (UPNERF_EINVAL): what upnerf_baked_upsample refuses, n_bricks < 1 or > Bx By Bz, NULL slots or pool; mark: NULL words;
+ * fill: n_child < 1 or > B'x B'y B'z, NULL or misaligned out, NULL child_bricks.  UPNERF_EUNSUP: more threads than a launch has. */
+typedef struct {
+  int32_t Cx, Cy, Cz;        /* the PARENT's cells */
+  int32_t degree;            /* 0, 1 or 2 */
+  float level;               /* not NaN */
+  int32_t n_bricks;          /* the parent's, >= 1 */
+  int32_t n_child;           /* fill: the child's bricks */
+  int32_t reserved_;
+  const int32_t* slots;      /* the parent's [Bz][By][Bx] */
+  const uint8_t* pool;       /* the parent's [n_bricks][9][9][9][16 | 32 | 64] */
+  const int32_t* child_bricks; /* fill: [n_child] */
+  uint32_t* words;           /* mark: the child's [upnerf_occ_words(2 Cx, 2 Cy, 2 Cz)] */
+  uint8_t* out;              /* fill: the child's pool */
+} upnerf_brick_upsample_args;
+int upnerf_brick_upsample_mark(const upnerf_brick_upsample_args* a, void* stream);
+int upnerf_brick_upsample_fill(const upnerf_brick_upsample_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

@@ -44,7 +44,14 @@ the dense backward on the same rays beside them.
 --pose measures the ray gradient INSTEAD and writes --pose-out: on the analytic shell of --sparse at 128^3 points,
 degree 0, 1 and 2, dense and sparse, ms per launch of upnerf_baked_ray_bwd on the --chunk rays beside the forward and the points
 backward of the same scene, alternately in one process, medians of --reps (HIP events round 5 launches), the ratios, and
-iterations per second of BakedLocaliser.step on two 64 x 64 photographs."""
+iterations per second of BakedLocaliser.step on two 64 x 64 photographs.
+
+--tv measures the total variation launch INSTEAD and writes --tv-out: on the analytic shell at 128^3 and 256^3
+points, degree 0 and 2, ms per upnerf_baked_tv launch on the dense grid and on the pool (the widest point array: rgbs, or the
+degree-2 coefficients) beside (a) the same definition in torch ops on the dense tensors, (b) a device copy of one read of data and
+one read-modify-write of grad and (c) the marcher's backward launch, alternately, medians of --reps; and the peak device bytes of
+a tuner step.  --upsample measures scene.upsample() INSTEAD and writes --upsample-out: 128^3 -> 255^3 and 256^3 -> 511^3, dense
+and pool to pool, seconds and peak bytes, and BakedScene.build(..., sparse=True) at 255^3, degree 2, on bench.py's weights."""
 import argparse
 import json
 import os
@@ -94,6 +101,10 @@ def main():
     ap.add_argument("--pool-tune-out", default=os.path.join(ROOT, "profiles", "baked_sparse_tune.json"))
     ap.add_argument("--pose", action="store_true", help="measure the ray gradient (upnerf_baked_ray_bwd) and the localiser instead; writes --pose-out")
     ap.add_argument("--pose-out", default=os.path.join(ROOT, "profiles", "baked_pose.json"))
+    ap.add_argument("--tv", action="store_true", help="measure the total variation launch (upnerf_baked_tv) instead; writes --tv-out")
+    ap.add_argument("--tv-out", default=os.path.join(ROOT, "profiles", "baked_tv.json"))
+    ap.add_argument("--upsample", action="store_true", help="measure the doubling of the resolution, dense and pool to pool, instead; writes --upsample-out")
+    ap.add_argument("--upsample-out", default=os.path.join(ROOT, "profiles", "baked_upsample.json"))
     ap.add_argument("--parent-lib", default=None, help="with --sparse: the parent commit's libupnerf_hip.so, for the nine marchers' times beside this build's")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -120,6 +131,10 @@ def main():
     res = tuple(a.resolution)
     if a.pose:
         return pose_main(a, path, dev)
+    if a.tv:
+        return tv_main(a, path, dev)
+    if a.upsample:
+        return upsample_main(a, sysm, path, dev)
     if a.sparse and a.tune:
         return pool_tune_main(a, path, dev)
     if a.sparse:
@@ -440,6 +455,178 @@ def pool_tune_main(a, path, dev):
            "note": "an analytic shell, not a trained scene: f_b and the hit share are the shell's"}
     os.makedirs(os.path.dirname(os.path.abspath(a.pool_tune_out)), exist_ok=True)
     with open(a.pool_tune_out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+def _event_ms(fn, n=1):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def _shell_scene(n, degree, dev):
+    from upnerf_amd.baked import BakedScene, sphere_directions
+    if degree == 0:
+        return BakedScene.from_grids(*shell_grids(n, dev), BOUNDS, 1.0)
+    dirs = sphere_directions(12)
+    sigma, rgb_dirs = shell_grids(n, dev, dirs)
+    return BakedScene.from_direction_grids(sigma, rgb_dirs, dirs, BOUNDS, 1.0, sh_degree=2)
+
+
+def torch_tv(data, sigma, cells, w, eps, out):
+    """The definition of upnerf_baked_tv in torch ops on the same dense tensors: value, and the gradient added into `out`."""
+    a = data[:-1, :-1, :-1]
+    dx, dy, dz = data[:-1, :-1, 1:] - a, data[:-1, 1:, :-1] - a, data[1:, :-1, :-1] - a
+    t = (eps + dx * dx + dy * dy + dz * dz).sqrt()
+    on = cells[..., None].to(data.dtype) * w
+    live = (sigma != 0)[..., None].to(data.dtype)
+    r = on / t
+    g = torch.zeros_like(data)
+    g[:-1, :-1, :-1] -= (dx + dy + dz) * r
+    g[:-1, :-1, 1:] += dx * r
+    g[:-1, 1:, :-1] += dy * r
+    g[1:, :-1, :-1] += dz * r
+    out += g * live
+    return (t * on).sum()
+
+
+def tv_main(a, path, dev):
+    """upnerf_baked_tv on the pool and on the dense grid of the analytic shell, beside (a) the same definition in torch ops on the
+    dense tensors, (b) a device copy of the bytes the launch must move at least and (c) the marcher's backward launch of the same
+    tuner step; alternately in one process, medians of --reps."""
+    import statistics as st
+    from upnerf_amd import baked_reg, baked_sparse_tune, baked_tune, novel_view
+    W, H = a.width, a.height
+    rays = novel_view.path_rays(*novel_view.path_poses(path.key_c2w.to(dev), path.key_near_far.to(dev), path.u.to(dev), path.mode),
+                                (W, H), path.K, 0, H * W)[0][:a.chunk].contiguous()
+    R = rays.shape[0]
+    g_rgb = torch.randn(R, 3, generator=torch.Generator(device="cpu").manual_seed(5)).to(dev)
+    STEPS, rows = 5, []
+    for n in (128, 256):
+        for degree in (0, 2):
+            dense = _shell_scene(n, degree, dev)
+            sparse = dense.sparsify()
+            target = dense.render(rays, a.step)["rgb"].clone()
+            tuners, peak = {}, {}
+            for k, make in (("dense", lambda: dense.tune(1e-2, tv_sigma=1e-3, tv_colour=1e-3)),
+                            ("pool", lambda: sparse.tune_pool(1e-2, tv_sigma=1e-3, tv_colour=1e-3))):
+                # each tuner alone: its construction and one step, above what was allocated before it (the scenes, the other tuner)
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                tuners[k] = make()
+                tuners[k].step(rays, target, a.step)
+                torch.cuda.synchronize()
+                peak[k] = torch.cuda.max_memory_allocated() - base
+            td, tp = tuners["dense"], tuners["pool"]
+            data = {"dense": td.masters[0], "pool": tp.masters[0]}  # rgbs [.., 4], or the coefficients [.., 3, 9]
+            sig = {k: (t.masters[0][..., 3] if degree == 0 else t.masters[1]) for k, t in tuners.items()}
+            F = data["dense"].numel() // sig["dense"].numel()
+            w = [1e-6] * F
+            cells = dense.occupancy.cells()
+            wt = torch.tensor(w, device=dev)
+            flat = data["dense"].reshape(tuple(sig["dense"].shape) + (F,))
+            gflat = td.grads[0].reshape(flat.shape)
+            legs = {"tv_dense": lambda: baked_reg.tv_backward(data["dense"], sig["dense"], td.occupancy, w, 1e-8, out=td.grads[0]),
+                    "tv_pool": lambda: baked_reg.tv_backward(data["pool"], sig["pool"], tp.occupancy, w, 1e-8, layout=tp.params, out=tp.grads[0], face_sum=False),
+                    "torch_dense": lambda: torch_tv(flat, sig["dense"], cells, wt, 1e-8, gflat),
+                    # one read of data, one read-modify-write of grad, in one launch: grad += data
+                    "copy_dense": lambda: td.grads[0].add_(data["dense"]),
+                    "copy_pool": lambda: tp.grads[0].add_(data["pool"]),
+                    "bwd_dense": lambda: baked_tune.backward(td.points, degree, td.occupancy, td.bounds, rays, a.step, 0.0, 0.0, g_rgb,
+                                                             out=td.grads[0] if degree == 0 else td.grads),
+                    "bwd_pool": lambda: baked_sparse_tune.backward(tp.points, tp.params, rays, a.step, 0.0, 0.0, g_rgb,
+                                                                   out=tp.grads[0] if degree == 0 else tp.grads, face_sum=False)}
+            for fn in legs.values():
+                fn()
+            ms = {k: [] for k in legs}
+            for _ in range(a.reps):
+                for k, fn in legs.items():
+                    ms[k].append(_event_ms(fn, STEPS))
+            med = {k: st.median(v) for k, v in ms.items()}
+            rows.append({"resolution": n, "degree": degree, "floats_per_point": F, "occupied_bricks": sparse.n_bricks, "f_b": sparse.brick_fraction,
+                         "ms": med, "ms_all": {k: sorted(v) for k, v in ms.items()}, "torch_over_hip_dense": med["torch_dense"] / med["tv_dense"],
+                         "hip_over_copy_dense": med["tv_dense"] / med["copy_dense"], "hip_over_copy_pool": med["tv_pool"] / med["copy_pool"],
+                         "tuner_peak_bytes_construction_and_step": peak, "tuner_bytes": {k: t.nbytes for k, t in tuners.items()}})
+            del dense, sparse, tuners, td, tp, data, sig, cells, flat, gflat, legs
+            torch.cuda.empty_cache()
+    out = {"metric": "one upnerf_baked_tv launch on the point array of widest F (rgbs, or the degree-2 coefficients) beside the same definition in torch ops, "
+                     "a device copy of one read of data and one read-modify-write of grad, and the marcher's backward launch; analytic shell",
+           "rays": R, "step": a.step, "reps": a.reps, "launches_per_timing": STEPS, "bounds": [list(b) for b in BOUNDS], "rows": rows,
+           "note": "an analytic shell, not a trained scene; torch_dense runs on the dense tensors only (the torch form of the pool would need the dense round trip)"}
+    os.makedirs(os.path.dirname(os.path.abspath(a.tv_out)), exist_ok=True)
+    with open(a.tv_out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+def upsample_main(a, sysm, path, dev):
+    """scene.upsample() 128^3 -> 255^3 and 256^3 -> 511^3 on the analytic shell, dense and pool to pool: time and peak device bytes;
+    for degree 2 at 128^3 -> 255^3, BakedScene.build(..., sparse=True) at the target size on bench.py's seeded weights beside them."""
+    import statistics as st
+    from upnerf_amd.baked import BakedScene, sphere_directions
+    rows = []
+
+    def measure(fn):
+        fn()  # warm-up
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        ts = []
+        for _ in range(a.reps):
+            ts.append(wall(fn))
+        return {"seconds": st.median(ts), "seconds_all": sorted(ts), "peak_bytes": torch.cuda.max_memory_allocated() - base}
+
+    for n in (128, 256):
+        for degree in (0, 2):
+            if n == 256 and degree == 2:
+                dense = None  # 511^3 records of 64 bytes are 8.5 GB beside their parents: the pool route alone
+                sparse = _shell_scene(n, degree, dev).sparsify()
+            else:
+                dense = _shell_scene(n, degree, dev)
+                sparse = dense.sparsify()
+            row = {"resolution": n, "target": 2 * n - 1, "degree": degree, "parent_bricks": sparse.n_bricks, "parent_f_b": sparse.brick_fraction,
+                   "parent_bytes": {"dense": dense.nbytes if dense is not None else None, "sparse": sparse.nbytes}}
+            if dense is not None:
+                row["dense"] = measure(lambda: dense.upsample())
+            row["sparse"] = measure(lambda: sparse.upsample())
+            child = sparse.upsample()
+            row["child_bricks"], row["child_f_b"], row["child_bytes_sparse"] = child.n_bricks, child.brick_fraction, child.nbytes
+            del child, dense, sparse
+            torch.cuda.empty_cache()
+            rows.append(row)
+    level = None
+    n = 255
+    from upnerf_amd.geometry import density_grid
+    grid = density_grid(sysm, BOUNDS, (64, 64, 64))
+    level = float(torch.quantile(grid.reshape(-1).float(), 0.95))  # a twentieth of the points kept: a stated rule, the field is random
+    del grid
+    dirs = sphere_directions(12)
+    bake = measure(lambda: BakedScene.build(sysm, BOUNDS, (n, n, n), level, img_id=a.bake_image, sh_degree=2, dirs=dirs, sparse=True))
+    # the loop working, not a fidelity figure: the weights are random.  A fixed-resolution distill against one with TV and one upsampling
+    from upnerf_amd import baked_tune
+    coarse = BakedScene.build(sysm, BOUNDS, (64, 64, 64), level, img_id=a.bake_image, view_dir=(0.0, 0.0, -1.0))
+    kw = dict(iters=60, batch=4096, baked_step=a.step, seed=0, lr=0.01, img_id=a.bake_image)
+    fixed = baked_tune.distill(sysm, coarse, path, **kw)
+    c2f = baked_tune.distill(sysm, coarse, path, tv=(1e-3, 1e-3), upsample_at=(30,), **kw)
+    curves = {"resolution": [64, 64, 64], "iters": 60, "batch": 4096, "lr": 0.01, "tv": [1e-3, 1e-3], "upsample_at": [30],
+              "fixed_resolution": {"final_resolution": list(fixed[0].resolution), "loss_every_5": fixed[1][::5] + fixed[1][-1:]},
+              "tv_and_one_upsampling": {"final_resolution": list(c2f[0].resolution), "loss_every_5": c2f[1][::5] + c2f[1][-1:]},
+              "note": "random weights: the loop working, not a fidelity figure; the loss is the batch's MSE before each update, without the penalty"}
+    out = {"metric": "scene.upsample(): wall seconds round a device synchronisation (median of --reps) and peak device bytes above the parent's",
+           "reps": a.reps, "bounds": [list(b) for b in BOUNDS], "rows": rows, "distill_curves": curves,
+           "bake_sparse_degree2_at_255": dict(bake, level=level, dirs=12, note="BakedScene.build(sparse=True) on bench.py's seeded (random) weights at the target size"),
+           "note": "an analytic shell, not a trained scene"}
+    os.makedirs(os.path.dirname(os.path.abspath(a.upsample_out)), exist_ok=True)
+    with open(a.upsample_out, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
     print(json.dumps(out))

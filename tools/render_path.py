@@ -5,7 +5,8 @@ appearance moving from photograph to photograph (upnerf_amd/novel_view.py; DESIG
                                 [--mode linear|catmull] [--downscale N] [--depth] [--normals] [--loop] [--chunk ROWS]
                                 [--occupancy NX NY NZ --level SIGMA [--dilate K] [--bounds X0 Y0 Z0 X1 Y1 Z1 | --margin M]]
                                 [--baked NX NY NZ --level SIGMA --step DT [--bake-image ID] [--save-baked F | --load-baked F]
-                                 [--baked-sh {1,2} [--baked-dirs K]] [--baked-sparse] [--baked-tune ITERS [--baked-tune-lr LR] [--baked-tune-pool]]]
+                                 [--baked-sh {1,2} [--baked-dirs K]] [--baked-sparse] [--baked-tune ITERS [--baked-tune-lr LR] [--baked-tune-pool]
+                                  [--baked-tv LS LC] [--baked-upsample-at I [I ...]]]]
 
 --occupancy skips empty space: the fine field's density is sampled on NX x NY x NZ grid points over the box (--bounds, or the
 box round the refined cameras and their far points grown by --margin), cells with a corner >= --level (grown by --dilate
@@ -27,6 +28,9 @@ it pays below a share of 0.20, which is what a fine grid of a real scene has; DE
 under the baked appearance: ITERS iterations of Adam through the marcher's backward pass (upnerf_amd/baked_tune.py).
 A --baked-sparse scene is made dense for that and stored sparse again, unless --baked-tune-pool is given: then the pool is tuned in
 place, with no buffer the size of the grid (upnerf_amd/baked_sparse_tune.py; the bricks stay the bake's).
+--baked-tv LS LC adds a total variation penalty to --baked-tune (weights of sigma and of the colour, per occupied cell), and
+--baked-upsample-at I [I ...] doubles the grid's resolution before each listed iteration, dense to dense or pool to pool
+(upnerf_amd/baked_reg.py): the rendered and saved scene has the final resolution.
 --save-baked writes the grid to an .npz, --load-baked renders from one (then NX NY NZ, --level, the degree and the layout are those
 of the file).
 --depth works, --normals and --occupancy do not.
@@ -73,6 +77,8 @@ def parser():
     ap.add_argument("--baked-tune", type=int, default=None, metavar="ITERS", help="after baking, fit the grid to the field's own renders of the path's keyframe cameras for this many Adam iterations (with --baked)")
     ap.add_argument("--baked-tune-lr", type=float, default=None, metavar="LR", help="learning rate of --baked-tune (default 0.01)")
     ap.add_argument("--baked-tune-pool", action="store_true", help="tune a --baked-sparse scene in place on its brick pool instead of through the dense layout (with --baked-sparse and --baked-tune)")
+    ap.add_argument("--baked-tv", type=float, nargs=2, default=None, metavar=("LS", "LC"), help="total variation weights of sigma and of the colour in --baked-tune")
+    ap.add_argument("--baked-upsample-at", type=int, nargs="+", default=None, metavar="I", help="double the grid's resolution before these iterations of --baked-tune")
     ap.add_argument("--save-baked", default=None, help="write the baked grid to this .npz")
     ap.add_argument("--load-baked", default=None, help="render from the baked grid of this .npz instead of baking")
     return ap
@@ -102,6 +108,10 @@ def check_args(a):
         raise SystemExit("--baked-tune-lr is the learning rate of --baked-tune")
     if a.baked_tune_pool and (a.baked is None or not a.baked_sparse or a.baked_tune is None):
         raise SystemExit("--baked-tune-pool tunes the brick pool of a sparse bake in place: it needs --baked-sparse and --baked-tune")
+    if (a.baked_tv is not None or a.baked_upsample_at is not None) and a.baked_tune is None:
+        raise SystemExit("--baked-tv and --baked-upsample-at belong to --baked-tune")
+    if a.baked_upsample_at is not None and any(not 0 <= i < a.baked_tune for i in a.baked_upsample_at):
+        raise SystemExit("--baked-upsample-at lists iterations of --baked-tune: 0 .. ITERS - 1")
     if a.baked_tune is not None and a.baked_tune < 1:
         raise SystemExit("--baked-tune counts iterations: one at least")
     if a.baked_dirs is not None and a.baked_sh is None:
@@ -156,7 +166,8 @@ def main(argv=None):
                     from upnerf_amd.baked_tune import distill
                 tt = time.perf_counter()
                 tuned, curve = distill(system, scene if a.baked_tune_pool else scene.densify(), path, iters=a.baked_tune, batch=a.chunk or system.hparams["val.chunk_size"], baked_step=a.step,
-                                       seed=0, lr=0.01 if a.baked_tune_lr is None else a.baked_tune_lr, img_id=a.images[0] if a.bake_image is None else a.bake_image)
+                                       seed=0, lr=0.01 if a.baked_tune_lr is None else a.baked_tune_lr, img_id=a.images[0] if a.bake_image is None else a.bake_image,
+                                       tv=tuple(a.baked_tv or (0.0, 0.0)), upsample_at=tuple(a.baked_upsample_at or ()))
                 scene = tuned.sparsify() if a.baked_sparse else tuned  # (a tuned pool is sparse already: sparsify() returns it)
                 tune_extra = {"tune_iters": a.baked_tune, "tune_loss_first": curve[0], "tune_loss_last": curve[-1], "tune_seconds": time.perf_counter() - tt}
             if a.save_baked is not None:

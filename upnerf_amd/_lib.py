@@ -462,6 +462,23 @@ class BakedRayBwdArgs(C.Structure):
                 ("g_rays", _fp)]
 
 
+class BakedTvArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("n_bricks", C.c_int32), ("F", C.c_int32),
+                ("sigma_stride", C.c_int32), ("eps", C.c_float), ("w", C.c_float * 28), ("reserved_", C.c_int32), ("words", _fp),
+                ("slots", _fp), ("bricks", _fp), ("data", _fp), ("sigma", _fp), ("grad", _fp), ("partial", _fp)]
+
+
+class BakedUpsampleArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("degree", C.c_int32), ("level", C.c_float),
+                ("reserved_", C.c_int32), ("points", _fp), ("out", _fp)]
+
+
+class BrickUpsampleArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("degree", C.c_int32), ("level", C.c_float),
+                ("n_bricks", C.c_int32), ("n_child", C.c_int32), ("reserved_", C.c_int32), ("slots", _fp), ("pool", _fp),
+                ("child_bricks", _fp), ("words", _fp), ("out", _fp)]
+
+
 class DensityGradArgs(C.Structure):
     _fields_ = [("M", C.c_int32), ("reserved_", C.c_int32), ("points", _fp), ("P", _fp), ("PT", _fp), ("wk_xyz", C.c_float * 10),
                 ("sigma", _fp), ("grad", _fp)]
@@ -596,9 +613,14 @@ _SIGNATURES = {
     "upnerf_baked_sparse_render_bwd": [C.POINTER(BakedSparseRenderBwdArgs), _p],
     "upnerf_brick_face_sum": [C.POINTER(BrickFaceSumArgs), _p],
     "upnerf_baked_ray_bwd": [C.POINTER(BakedRayBwdArgs), _p],
+    "upnerf_baked_tv_blocks": [_i, _i, _i, _i],
+    "upnerf_baked_tv": [C.POINTER(BakedTvArgs), _p],
+    "upnerf_baked_upsample": [C.POINTER(BakedUpsampleArgs), _p],
+    "upnerf_brick_upsample_mark": [C.POINTER(BrickUpsampleArgs), _p],
+    "upnerf_brick_upsample_fill": [C.POINTER(BrickUpsampleArgs), _p],
 }
 _LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
-             "upnerf_occ_compact_scratch", "upnerf_pca_fit_scratch", "upnerf_brick_table_scratch")
+             "upnerf_occ_compact_scratch", "upnerf_pca_fit_scratch", "upnerf_brick_table_scratch", "upnerf_baked_tv_blocks")
 MAX_SCALARS = 96
 EXPORTS = tuple(_SIGNATURES)
 

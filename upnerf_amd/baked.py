@@ -622,15 +622,24 @@ class BakedScene:
               background, stop, out["rgb"], out["depth"], out["opacity"])
         return {k: out[k][:R] for k in ("rgb", "depth", "opacity")}
 
-    def tune(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8):
-        """A `baked_tune.BakedTuner` on this (dense) scene: Adam on its points against target pixels."""
+    def tune(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, tv_sigma: float = 0.0, tv_colour: float = 0.0, tv_eps: float = 1e-8):
+        """A `baked_tune.BakedTuner` on this (dense) scene: Adam on its points against target pixels, with a total
+        variation penalty where tv_sigma or tv_colour is not zero."""
         from .baked_tune import BakedTuner
-        return BakedTuner(self, lr, betas=betas, eps=eps)
+        return BakedTuner(self, lr, betas=betas, eps=eps, tv_sigma=tv_sigma, tv_colour=tv_colour, tv_eps=tv_eps)
 
-    def tune_pool(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8):
-        """A `baked_sparse_tune.PoolTuner` on this (sparse) scene: Adam on the points of its pool, in place."""
+    def tune_pool(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, tv_sigma: float = 0.0, tv_colour: float = 0.0, tv_eps: float = 1e-8):
+        """A `baked_sparse_tune.PoolTuner` on this (sparse) scene: Adam on the points of its pool, in place, with
+        the same optional total variation penalty."""
         from .baked_sparse_tune import PoolTuner
-        return PoolTuner(self, lr, betas=betas, eps=eps)
+        return PoolTuner(self, lr, betas=betas, eps=eps, tv_sigma=tv_sigma, tv_colour=tv_colour, tv_eps=tv_eps)
+
+    def upsample(self, level: Optional[float] = None) -> "BakedScene":
+        """The scene of twice the cells per axis (2 N - 1 points): the same bounds, degree and layout -- dense stays dense, sparse
+        stays sparse, pool to pool -- every child point the trilinear value of this grid, pruned at `level` (default: this scene's).
+        `baked_reg.upsample`; DESIGN.md 2.37."""
+        from .baked_reg import upsample
+        return upsample(self, level)
 
     # ---- files -------------------------------------------------------------------------------------------------------------
 

@@ -219,7 +219,15 @@ class PoolTuner(BakedTuner):
         return _forward(self.points, self.params, rays, step, background, stop)
 
     def _gradient(self, rays, step, background, stop, g_rgb) -> None:
-        backward(self.points, self.params, rays, step, background, stop, g_rgb, out=self.grads[0] if self.degree == 0 else self.grads)
+        """The marcher's gradient with the face sum; with the penalty on, the per-copy gradients of the marcher and of
+        upnerf_baked_tv first and ONE face sum over both."""
+        backward(self.points, self.params, rays, step, background, stop, g_rgb, out=self.grads[0] if self.degree == 0 else self.grads,
+                 face_sum=not self.tv_on)
+        if self.tv_on:
+            from .baked_reg import tuner_tv
+            self.last_tv = tuner_tv(self, layout=self.params)
+            for t in self.grads:
+                face_sum(t, self.params)
 
     @torch.no_grad()
     def scene(self) -> BakedScene:
@@ -237,8 +245,9 @@ class PoolTuner(BakedTuner):
 
 
 def distill(system, scene: BakedScene, path_or_img_ids, iters: int, batch: int, baked_step: float, seed: int = 0, lr: float = 1e-2,
-            img_id: Optional[int] = None, chunk: Optional[int] = None):
+            img_id: Optional[int] = None, chunk: Optional[int] = None, tv: Tuple[float, float] = (0.0, 0.0), upsample_at=()):
     """baked_tune.distill for a sparse scene, tuned in place on its pool (PoolTuner): the same cameras, targets, batches and
-    return value (the tuned SPARSE scene with the same bricks, the loss curve)."""
+    return value (the tuned SPARSE scene -- with the same bricks unless upsample_at refines it pool to pool -- and the loss curve);
+    tv and upsample_at as there."""
     _sparse(scene, "distill")
-    return _distill(PoolTuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk)
+    return _distill(PoolTuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk, tv, upsample_at)

@@ -170,13 +170,20 @@ class BakedTuner:
     (The layout -- which scenes are taken, the shape of the point array, the forward and the gradient launches -- is in the four
     methods after __init__; baked_sparse_tune.PoolTuner states them for a brick pool and shares the rest.)"""
 
-    def __init__(self, scene: BakedScene, lr: float, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8):
+    def __init__(self, scene: BakedScene, lr: float, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 tv_sigma: float = 0.0, tv_colour: float = 0.0, tv_eps: float = 1e-8):
         self._accept(scene)
         lr, eps = float(lr), float(eps)
         if not (lr > 0 and np.isfinite(lr)) or not (eps > 0) or not all(0 <= float(b) < 1 for b in betas):
             raise ValueError("lr and eps are positive, the betas in [0, 1)")
+        self.tv_sigma, self.tv_colour, self.tv_eps = float(tv_sigma), float(tv_colour), float(tv_eps)
+        if not (np.isfinite(self.tv_sigma) and np.isfinite(self.tv_colour) and self.tv_eps > 0 and np.isfinite(self.tv_eps)):
+            raise ValueError("tv_sigma and tv_colour are finite weights, tv_eps is positive and finite")
         self.lr, self.betas, self.eps, self.t = lr, (float(betas[0]), float(betas[1])), eps, 0
         self.degree, self.bounds, self.level, self.occupancy = scene.sh_degree, scene.bounds, scene.level, scene.occupancy
+        # the total variation penalty (baked_reg; DESIGN.md 2.37): off at the defaults, and then nothing is launched for it
+        self.last_tv = None
+        self.tv_cells = max(1, self.occupancy.n_occupied()) if self.tv_on else None
         dev = scene.device
         shape, grid = self._points(scene)
         nb, n = (self.degree + 1) ** 2, math.prod(shape)
@@ -205,9 +212,26 @@ class BakedTuner:
         return _forward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop)
 
     def _gradient(self, rays, step, background, stop, g_rgb) -> None:
-        """The gradient of the points, added into self.grads (zeroed by the caller)."""
+        """The gradient of the points, added into self.grads (zeroed by the caller); with the penalty on, its gradient after the
+        marcher's (upnerf_baked_tv), the value left in self.last_tv."""
         backward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop, g_rgb,
                  out=self.grads[0] if self.degree == 0 else self.grads)
+        if self.tv_on:
+            from .baked_reg import tuner_tv
+            self.last_tv = tuner_tv(self)
+
+    @property
+    def tv_on(self) -> bool:
+        return self.tv_sigma != 0.0 or self.tv_colour != 0.0
+
+    def _settings(self) -> dict:
+        return dict(betas=self.betas, eps=self.eps, tv_sigma=self.tv_sigma, tv_colour=self.tv_colour, tv_eps=self.tv_eps)
+
+    @torch.no_grad()
+    def upsampled(self) -> "BakedTuner":
+        """A fresh tuner of the same kind and settings on self.scene().upsample(): twice the cells per axis, the Adam state
+        reset (t = 0, zero moments)."""
+        return type(self)(self.scene().upsample(), self.lr, **self._settings())
 
     @property
     def points(self) -> torch.Tensor:
@@ -222,8 +246,8 @@ class BakedTuner:
     @torch.no_grad()
     def step(self, rays: torch.Tensor, target_rgb: torch.Tensor, step: float, background: float = 0.0, stop: float = 0.0) -> torch.Tensor:
         """One iteration on `rays` [R, 8] against `target_rgb` [R, 3]: zero the gradient (upnerf_zero), forward, the gradient of
-        the mean squared error (plain torch), upnerf_baked_render_bwd, upnerf_adam, upnerf_baked_project, and at degree 1 | 2
-        upnerf_baked_sh_pack.  Returns the loss BEFORE the update, a 0-dim device tensor (no host read here)."""
+        the mean squared error (plain torch), upnerf_baked_render_bwd, with tv_sigma or tv_colour not zero upnerf_baked_tv,
+        upnerf_adam, upnerf_baked_project, and at degree 1 | 2 upnerf_baked_sh_pack.  Returns the loss BEFORE the update, a 0-dim device tensor (no host read here)."""
         require_cuda("BakedTuner.step", rays, target_rgb)
         step, background, stop = _render_args(rays, step, background, stop)
         rays = _rays16(rays)
@@ -267,18 +291,20 @@ def keyframe_rays(path, device) -> torch.Tensor:
 
 
 def distill(system, scene: BakedScene, path_or_img_ids, iters: int, batch: int, baked_step: float, seed: int = 0, lr: float = 1e-2,
-            img_id: Optional[int] = None, chunk: Optional[int] = None):
+            img_id: Optional[int] = None, chunk: Optional[int] = None, tv: Tuple[float, float] = (0.0, 0.0), upsample_at: Sequence[int] = ()):
     """Fit a dense baked scene to the field's own renders.  Cameras: the keyframes of a `novel_view.CameraPath`, or the refined
     training cameras `img_ids` (two at least).  The targets are rendered ONCE from the field by the static renderer
     (static_scene.render_static, through render_path) for those cameras' rays, all under the appearance of training image
     `img_id` -- the ONE appearance the scene was baked with.  Batches of `batch` rays are drawn with a generator seeded by `seed`;
     `iters` steps of BakedTuner(scene, lr) at sample spacing `baked_step`.  Returns (the tuned scene, the loss curve as a list of
-    floats -- one host read, at the end)."""
+    floats -- one host read, at the end).  tv = (tv_sigma, tv_colour): the tuner's total variation weights.  upsample_at: before
+    each listed iteration (0-based) the tuner is replaced by tuner.upsampled() -- the returned scene has the final resolution; the
+    sample spacing stays `baked_step`."""
     _dense(scene, "distill")
-    return _distill(BakedTuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk)
+    return _distill(BakedTuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk, tv, upsample_at)
 
 
-def _distill(make_tuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk):
+def _distill(make_tuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk, tv=(0.0, 0.0), upsample_at=()):
     """distill on a scene its caller has accepted, with the tuner make_tuner(scene, lr)."""
     from .novel_view import CameraPath, render_path
     if img_id is None:
@@ -286,6 +312,10 @@ def _distill(make_tuner, system, scene, path_or_img_ids, iters, batch, baked_ste
     iters, batch = int(iters), int(batch)
     if iters < 1 or batch < 1:
         raise ValueError("iters and batch are positive")
+    tv_sigma, tv_colour = (float(x) for x in tv)
+    upsample_at = sorted(int(i) for i in upsample_at)
+    if any(not 0 <= i < iters for i in upsample_at) or len(set(upsample_at)) != len(upsample_at):
+        raise ValueError(f"upsample_at lists distinct iterations in [0, {iters})")
     src = path_or_img_ids if isinstance(path_or_img_ids, CameraPath) else \
         CameraPath.through_images(system, list(path_or_img_ids), n_frames=len(list(path_or_img_ids)))
     K = src.key_c2w.shape[0]
@@ -295,10 +325,12 @@ def _distill(make_tuner, system, scene, path_or_img_ids, iters, batch, baked_ste
     target = render_path(system, keys, chunk=chunk, outputs=("rgb_float",))["rgb_float"].reshape(-1, 3).contiguous()
     rays = keyframe_rays(keys, dev)
     background = 1.0 if getattr(system.train_dataset, "white_back", False) else 0.0
-    tuner = make_tuner(scene, lr)
+    tuner = make_tuner(scene, lr, tv_sigma=tv_sigma, tv_colour=tv_colour) if tv_sigma or tv_colour else make_tuner(scene, lr)
     gen = torch.Generator(device="cpu").manual_seed(int(seed))
     curve = []
-    for _ in range(iters):
+    for it in range(iters):
+        if it in upsample_at:
+            tuner = tuner.upsampled()
         idx = torch.randint(0, rays.shape[0], (min(batch, rays.shape[0]),), generator=gen).to(dev)
         curve.append(tuner.step(rays[idx], target[idx], baked_step, background=background))
     return tuner.scene(), [float(x) for x in torch.stack(curve).cpu()]

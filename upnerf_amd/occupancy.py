@@ -116,6 +116,18 @@ class OccupancyGrid:
         Bx, By, Bz = self.brick_dims
         return _unpack(self.words[self.fine_words:], Bx * By * Bz).reshape(Bz, By, Bx)
 
+    def n_occupied(self) -> int:
+        """The number of occupied cells, counted from the packed words themselves: a population count per word in a few
+        word-sized integer passes (8 bytes a word, a quarter of a byte a cell -- nothing per cell, unlike cells()), the last word
+        masked to the grid's cells.  One host read."""
+        w = self.words[:self.fine_words].to(torch.int64) & 0xFFFFFFFF
+        tail = self.n_cells - 32 * (self.fine_words - 1)
+        w[-1] &= (1 << tail) - 1
+        w = w - ((w >> 1) & 0x55555555)
+        w = (w & 0x33333333) + ((w >> 2) & 0x33333333)
+        w = (w + (w >> 4)) & 0x0F0F0F0F
+        return int(((w * 0x01010101 >> 24) & 0xFF).sum())
+
     @property
     def fraction(self) -> float:
         """Occupied share of the cells."""
