@@ -1907,6 +1907,100 @@ typedef struct {
 int upnerf_brick_upsample_mark(const upnerf_brick_upsample_args* a, void* stream);
 int upnerf_brick_upsample_fill(const upnerf_brick_upsample_args* a, void* stream);
 
+/* ---- what lies outside the box of a baked scene: a cube-map environment behind the march (csrc/env.hip).  Added
+ * under ABI 11: new symbols only.  Arguments refused on the host before anything is launched, nothing allocated, no host read-back,
+ * one thread per item, no LDS, no atomics, every output address has one writer: the same bits every run and however the items are
+ * cut into launches.
+ *
+ * The map.  env is fp32 [6][E+1][E+1][4], E >= 1 cells per face side (E <= UPNERF_ENV_MAX_E: 2 iu - E and g stay exact fp32
+ * integers): node (face, iu, iv) is at env[((face (E+1) + iv) (E+1) + iu) 4 ..], its floats r, g, b and one padding float that is
+ * stored as 0 and never read (a node is one 16-byte load).  The nodes sit on the CORNERS of the cells, the edges of the faces
+ * included: a node on a face edge is stored once per face that contains it (2 copies; 3 at a cube corner), and with the copies
+ * equal the bilinear lookup is continuous over the whole sphere with no seam handling in it.
+ *
+ * The lookup env(d) of a direction d = (d_0, d_1, d_2), all fp32 (env_lookup, a __host__ __device__ function of csrc/env.hip):
+ *   m = the axis of the largest |d_a|, ties to the lowest axis;  face = 2 m + (d_m < 0);  (a, b) = the two other axes ascending;
+ *   u = d_a / |d_m|, v = d_b / |d_m| (one division each, in [-1, 1]);  g_u = (u + 1) * (E / 2) (an addition and a product; E / 2 is
+ *   exact), i_u = min((int)floorf(g_u), E - 1), f_u = g_u - i_u (exact, in [0, 1]);  v likewise.
+ *   With n00 = node (face, i_u, i_v), n10 = (face, i_u + 1, i_v), n01 = (face, i_u, i_v + 1), n11 = (face, i_u + 1, i_v + 1) and
+ *   lerp(f, p, q) = fmaf(f, q - p, p), per channel:  env(d) = lerp(f_v, lerp(f_u, n00, n10), lerp(f_u, n01, n11)).
+ * d is never normalised: env(s d) = env(d) for s > 0 up to the rounding of the divisions.  A direction with a component that is
+ * not finite, or with three zero components, is DEAD: colour (0, 0, 0), every gradient 0.
+ * Node (face, iu, iv) has the direction d_m = +-1, d_a = (2 iu - E) / E, d_b = (2 iv - E) / E: one fp32 division of exact integers
+ * each, so the copies of a shared node have bit-identical directions.
+ *
+ * upnerf_env_rays: the ray rows o | d | near | far [count][8] of nodes n0 .. n0 + count (n = (face (E+1) + iv) (E+1) + iu) that make
+ * render_static bake the map -- the sibling of upnerf_grid_columns and upnerf_brick_columns.  In fp64, every operation rounded
+ * on its own, rounded to fp32 once: o = (lo + hi) / 2, the box centre; d = the node direction x / sqrt(x_0^2 + x_1^2 + x_2^2) (the
+ * sum in the order of the AXES, not of the face: a shared node's copies get the same bits).  In fp32, from the o and d just
+ * written: near = fminf over the axes with d_a != 0 of ((d_a > 0 ? hi_a : lo_a) - o_a) / d_a, the t at which the ray leaves the
+ * box (the slab test from the inside);  far as given.  A row depends on its node only.
+ * Refused (UPNERF_EINVAL): NULL rays, rays not 16-byte aligned, E < 1 or > UPNERF_ENV_MAX_E, n0 < 0, count < 1,
+ * n0 + count > 6 (E+1)^2, a box that is not finite or has hi <= lo on an axis, far not finite or <= 0. */
+#define UPNERF_ENV_MAX_E 8192
+typedef struct {
+  int32_t E;
+  int32_t count;             /* rows of this call, >= 1 */
+  int64_t n0;                /* first node, >= 0; n0 + count <= 6 (E+1)^2 */
+  float lo[3], hi[3];        /* hi > lo, finite */
+  float far;                 /* > 0, finite */
+  int32_t reserved_;
+  float* rays;               /* [count][8], 16-byte aligned */
+} upnerf_env_rays_args;
+int upnerf_env_rays(const upnerf_env_rays_args* a, void* stream);
+
+/* upnerf_env_seam: makes the copies of every shared node byte-identical, in place: every copy takes the 16 bytes of the copy on
+ * the LOWEST face index (the owner).  The field kernels' last bit depends on which samples share a tile (upnerf_brick_columns),
+ * so a bake gives the copies of a node colours one ulp apart; after this pass the lookup is continuous to the bit.  One thread
+ * per edge node of every face (24 E per map).  A node's copies are the nodes of other faces with the SAME direction; the owner
+ * of a set of copies is never written (it has no lower copy) and every other copy is written by its own thread alone: no two
+ * threads store to one address, no thread reads what another writes.  Interior nodes are not touched.
+ * Refused (UPNERF_EINVAL): NULL env, env not 16-byte aligned, E < 1 or > UPNERF_ENV_MAX_E. */
+typedef struct {
+  int32_t E;
+  int32_t reserved_;
+  float* env;                /* [6][E+1][E+1][4], 16-byte aligned */
+} upnerf_env_seam_args;
+int upnerf_env_seam(const upnerf_env_seam_args* a, void* stream);
+
+/* upnerf_env_composite: the environment behind a march that was made with background 0.  For ray r with direction d_r =
+ * rays[r][3..5], per channel:  rgb_out[r] = fmaf(1 - opacity[r], env(d_r), rgb_in[r]).  rgb_out may be rgb_in.  With a map that
+ * holds the constant c this is the marcher's own fmaf(rest, background, rgb) at background = c, in the same bits (a dead
+ * direction shows 0 where the marcher shows c).
+ * upnerf_env_composite_bwd, from g_out [R][3] (the gradient of rgb_out; the gradient of rgb_in is g_out itself and is not written):
+ *   g_opacity[r] = -fmaf(g_out[2], e[2], fmaf(g_out[1], e[1], g_out[0] * e[0])),  e = env(d_r)
+ *   g_rays[r] = the gradient of the row o | d | near | far: zero but for d.  Face and cell are HELD FIXED (upnerf_baked_ray_bwd's
+ *   convention).  With x0 = lerp(f_u, n00, n10), x1 = lerp(f_u, n01, n11) per channel, the slopes of the blend are
+ *     s_u = lerp(f_v, n10 - n00, n11 - n01),  s_v = x1 - x0;   a[c] = (1 - opacity[r]) * g_out[c];
+ *     G_u = the fmaf chain over c = r, g, b from zero, G = fmaf(a[c], s_u[c], G);  G_v likewise;
+ *     p_u = G_u * (E / 2), p_v = G_v * (E / 2);   g_d[a] = p_u / |d_m|,  g_d[b] = p_v / |d_m|,  g_d[m] = -fmaf(u, p_u, v * p_v) / d_m.
+ *   A dead direction writes g_opacity = 0 and eight zeros.  There is no gradient with respect to the map: it is baked from the
+ *   field and stays frozen.
+ * Refused (UPNERF_EINVAL): R < 0, E < 1 or > UPNERF_ENV_MAX_E, a NULL pointer, env, rays or g_rays not 16-byte aligned, any other
+ * pointer not 4-byte aligned.  R == 0 launches nothing. */
+typedef struct {
+  int32_t E;
+  int32_t R;                 /* >= 0 */
+  const float* env;          /* [6][E+1][E+1][4], 16-byte aligned */
+  const float* rays;         /* [R][8], 16-byte aligned */
+  const float* opacity;      /* [R] */
+  const float* rgb_in;       /* [R][3] */
+  float* rgb_out;            /* [R][3]; may be rgb_in */
+} upnerf_env_composite_args;
+int upnerf_env_composite(const upnerf_env_composite_args* a, void* stream);
+
+typedef struct {
+  int32_t E;
+  int32_t R;                 /* >= 0 */
+  const float* env;          /* [6][E+1][E+1][4], 16-byte aligned */
+  const float* rays;         /* [R][8], 16-byte aligned */
+  const float* opacity;      /* [R] */
+  const float* g_out;        /* [R][3] */
+  float* g_opacity;          /* [R], written */
+  float* g_rays;             /* [R][8], 16-byte aligned, written */
+} upnerf_env_composite_bwd_args;
+int upnerf_env_composite_bwd(const upnerf_env_composite_bwd_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

@@ -105,6 +105,9 @@ def main():
     ap.add_argument("--tv-out", default=os.path.join(ROOT, "profiles", "baked_tv.json"))
     ap.add_argument("--upsample", action="store_true", help="measure the doubling of the resolution, dense and pool to pool, instead; writes --upsample-out")
     ap.add_argument("--upsample-out", default=os.path.join(ROOT, "profiles", "baked_upsample.json"))
+    ap.add_argument("--env", action="store_true", help="measure the environment map (upnerf_env_composite, its backward, the bake) instead; writes --env-out")
+    ap.add_argument("--env-out", default=os.path.join(ROOT, "profiles", "baked_env.json"))
+    ap.add_argument("--env-ratios", default=None, help="with --env: a JSON file of the tests' worst error / gate ratios to record beside the times")
     ap.add_argument("--parent-lib", default=None, help="with --sparse: the parent commit's libupnerf_hip.so, for the nine marchers' times beside this build's")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -129,6 +132,8 @@ def main():
     path = CameraPath.from_poses(c2w, (0.1, 5.0), F, appearance=(a.bake_image, a.bake_image), img_wh=(W, H), K=K)  # ONE appearance: the baked one
     rays = F * H * W
     res = tuple(a.resolution)
+    if a.env:
+        return env_main(a, sysm, path, dev)
     if a.pose:
         return pose_main(a, path, dev)
     if a.tv:
@@ -630,6 +635,85 @@ def upsample_main(a, sysm, path, dev):
         json.dump(out, f, indent=1)
         f.write("\n")
     print(json.dumps(out))
+
+
+def torch_env(env, rays, opacity, rgb):
+    """The definition of upnerf_env_composite in torch ops (tools/torch_ops.py style: the same arithmetic on the same tensors, one
+    op per step): face, cell, bilinear blend, composite.  Differentiable in rays, opacity and rgb through autograd."""
+    E = env.shape[1] - 1
+    d = rays[:, 3:6]
+    mag = d.abs()
+    m = torch.zeros(d.shape[0], dtype=torch.long, device=d.device)
+    m = torch.where(mag[:, 1] > mag.gather(1, m[:, None])[:, 0], torch.ones_like(m), m)
+    m = torch.where(mag[:, 2] > mag.gather(1, m[:, None])[:, 0], torch.full_like(m, 2), m)
+    a_, b_ = torch.where(m == 0, 1, 0), torch.where(m == 2, 1, 2)
+    pick = lambda i: d.gather(1, i[:, None])[:, 0]
+    dm = pick(m)
+    face = 2 * m + (dm < 0).long()
+    u, v = pick(a_) / dm.abs(), pick(b_) / dm.abs()
+    gu, gv = (u + 1) * (E / 2), (v + 1) * (E / 2)
+    iu, iv = gu.detach().floor().clamp(max=E - 1).long(), gv.detach().floor().clamp(max=E - 1).long()
+    fu, fv = (gu - iu)[:, None], (gv - iv)[:, None]
+    n00, n10, n01, n11 = env[face, iv, iu, :3], env[face, iv, iu + 1, :3], env[face, iv + 1, iu, :3], env[face, iv + 1, iu + 1, :3]
+    x0, x1 = torch.addcmul(n00, fu, n10 - n00), torch.addcmul(n01, fu, n11 - n01)
+    return torch.addcmul(rgb, (1 - opacity)[:, None], torch.addcmul(x0, fv, x1 - x0))
+
+
+def env_main(a, sysm, path, dev):
+    """--env: ms per launch of upnerf_env_composite and upnerf_env_composite_bwd on one chunk of rays (E = 64) beside the forward
+    march of the same rays through a 128^3 analytic shell and beside the same definition in torch ops (forward, and forward +
+    autograd backward), alternately in one process, medians of --reps; and the seconds of Environment.build at E = 64 and 256."""
+    import datetime
+    import statistics as st
+    from upnerf_amd import baked_env, novel_view
+    W, H = a.width, a.height
+    c2w, nf = novel_view.path_poses(path.key_c2w.to(dev), path.key_near_far.to(dev), path.u.to(dev), path.mode)
+    rays = novel_view.path_rays(c2w, nf, (W, H), path.K, 0, H * W)[0][:a.chunk].contiguous()
+    R = rays.shape[0]
+    gen = torch.Generator(device="cpu").manual_seed(5)
+    g_out = torch.randn(R, 3, generator=gen).to(dev)
+    scene = _shell_scene(128, 0, dev)
+    bake_s = {}
+    for E in (64, 256):
+        baked_env.Environment.build(sysm, BOUNDS, E, img_id=a.bake_image)  # warm-up
+        bake_s[E] = st.median(wall(lambda: baked_env.Environment.build(sysm, BOUNDS, E, img_id=a.bake_image)) for _ in range(a.reps))
+    env = baked_env.Environment.build(sysm, BOUNDS, 64, img_id=a.bake_image)
+    march = scene.render(rays, a.step)
+    rgb, opacity = march["rgb"].clone(), march["opacity"].clone()
+    out = torch.empty_like(rgb)
+
+    def torch_both():
+        r, o, c = rays.clone().requires_grad_(True), opacity.clone().requires_grad_(True), rgb.clone().requires_grad_(True)
+        torch_env(env.env, r, o, c).backward(g_out)
+
+    legs = {"march_forward": lambda: scene.render(rays, a.step),
+            "composite": lambda: baked_env._composite(env.env, rays, opacity, rgb, out),
+            "composite_bwd": lambda: baked_env.composite_backward(env.env, rays, opacity, g_out),
+            "torch_composite": lambda: torch_env(env.env, rays, opacity, rgb),
+            "torch_composite_and_bwd": torch_both}
+    STEPS = 5
+    for fn in legs.values():
+        fn()
+    ms = {k: [] for k in legs}
+    for _ in range(a.reps):  # alternately: every leg sees the same clocks
+        for k, fn in legs.items():
+            ms[k].append(_event_ms(fn, STEPS))
+    got = baked_env._composite(env.env, rays, opacity, rgb, torch.empty_like(rgb))
+    ratios = None
+    if a.env_ratios:
+        with open(a.env_ratios) as f:
+            ratios = json.load(f)
+    res = {"date": datetime.date.today().isoformat(), "device": torch.cuda.get_device_name(0), "rays": R, "E": 64, "step": a.step, "reps": a.reps,
+           "launches_per_sample": STEPS, "ms": {k: st.median(v) for k, v in ms.items()}, "ms_all": ms,
+           "max_abs_difference_to_torch_ops": float((got - torch_env(env.env, rays, opacity, rgb)).abs().max()),
+           "opacity_mean": float(opacity.mean()), "bake_seconds": {str(E): s for E, s in bake_s.items()},
+           "bake_node_rays": {str(E): 6 * (E + 1) ** 2 for E in bake_s}, "test_worst_err_over_gate": ratios,
+           "note": "random synthetic field and an analytic shell, not a trained scene: fidelity is unchecked; the map has no parallax"}
+    os.makedirs(os.path.dirname(os.path.abspath(a.env_out)), exist_ok=True)
+    with open(a.env_out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
 
 
 def pose_main(a, path, dev):

@@ -41,7 +41,7 @@ def parser():
     ap.add_argument("--lr", type=float, default=1e-2)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--downscale", type=int, default=1, help="work at 1/N of the photographs' size")
-    ap.add_argument("--background", type=float, default=0.0, help="grey level of what the scene does not cover")
+    ap.add_argument("--background", type=float, default=0.0, help="grey level of what the scene does not cover (not looked at where the loaded scene carries an environment map: that is shown instead)")
     ap.add_argument("--out", required=True, help=".npy [N, 3, 4]: the refined poses")
     return ap
 
@@ -83,7 +83,7 @@ def main(argv=None):
     dt = time.perf_counter() - t0
     np.save(a.out, poses.cpu().numpy())
     print(json.dumps({"photographs": len(files), "img_wh": [int(targets.shape[2]), int(targets.shape[1])], "iters": a.iters, "batch": a.batch,
-                      "loss_first": curve[0], "loss_last": curve[-1], "seconds": dt, "iterations_per_s": a.iters / dt, "out": a.out}))
+                      "env_size": scene.env.E if scene.env is not None else None, "loss_first": curve[0], "loss_last": curve[-1], "seconds": dt, "iterations_per_s": a.iters / dt, "out": a.out}))
 
 
 if __name__ == "__main__":

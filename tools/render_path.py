@@ -6,7 +6,7 @@ appearance moving from photograph to photograph (upnerf_amd/novel_view.py; DESIG
                                 [--occupancy NX NY NZ --level SIGMA [--dilate K] [--bounds X0 Y0 Z0 X1 Y1 Z1 | --margin M]]
                                 [--baked NX NY NZ --level SIGMA --step DT [--bake-image ID] [--save-baked F | --load-baked F]
                                  [--baked-sh {1,2} [--baked-dirs K]] [--baked-sparse] [--baked-tune ITERS [--baked-tune-lr LR] [--baked-tune-pool]
-                                  [--baked-tv LS LC] [--baked-upsample-at I [I ...]]]]
+                                  [--baked-tv LS LC] [--baked-upsample-at I [I ...]]] [--baked-env E [--baked-env-far T]]]
 
 --occupancy skips empty space: the fine field's density is sampled on NX x NY x NZ grid points over the box (--bounds, or the
 box round the refined cameras and their far points grown by --margin), cells with a corner >= --level (grown by --dilate
@@ -31,6 +31,9 @@ place, with no buffer the size of the grid (upnerf_amd/baked_sparse_tune.py; DES
 --baked-tv LS LC adds a total variation penalty to --baked-tune (weights of sigma and of the colour, per occupied cell), and
 --baked-upsample-at I [I ...] doubles the grid's resolution before each listed iteration, dense to dense or pool to pool
 (upnerf_amd/baked_reg.py): the rendered and saved scene has the final resolution.
+--baked-env E also bakes an environment: a cube map of E cells per face side of what the field shows from the box centre outwards
+(to --baked-env-far, default the training images' largest far plane), composited behind the march instead of the flat backdrop
+(upnerf_amd/baked_env.py); it has no parallax.  The tuners keep it frozen and it is saved with the grid.
 --save-baked writes the grid to an .npz, --load-baked renders from one (then NX NY NZ, --level, the degree and the layout are those
 of the file).
 --depth works, --normals and --occupancy do not.
@@ -79,6 +82,8 @@ def parser():
     ap.add_argument("--baked-tune-pool", action="store_true", help="tune a --baked-sparse scene in place on its brick pool instead of through the dense layout (with --baked-sparse and --baked-tune)")
     ap.add_argument("--baked-tv", type=float, nargs=2, default=None, metavar=("LS", "LC"), help="total variation weights of sigma and of the colour in --baked-tune")
     ap.add_argument("--baked-upsample-at", type=int, nargs="+", default=None, metavar="I", help="double the grid's resolution before these iterations of --baked-tune")
+    ap.add_argument("--baked-env", type=int, default=None, metavar="E", help="also bake an environment map of E cells per cube face side and show it behind the grid (with --baked)")
+    ap.add_argument("--baked-env-far", type=float, default=None, metavar="T", help="far end of the environment's rays (default: the largest far plane of the training images)")
     ap.add_argument("--save-baked", default=None, help="write the baked grid to this .npz")
     ap.add_argument("--load-baked", default=None, help="render from the baked grid of this .npz instead of baking")
     return ap
@@ -114,6 +119,10 @@ def check_args(a):
         raise SystemExit("--baked-upsample-at lists iterations of --baked-tune: 0 .. ITERS - 1")
     if a.baked_tune is not None and a.baked_tune < 1:
         raise SystemExit("--baked-tune counts iterations: one at least")
+    if a.baked is None and (a.baked_env is not None or a.baked_env_far is not None):
+        raise SystemExit("--baked-env and --baked-env-far belong to --baked (a file read with --load-baked carries its own environment)")
+    if a.baked_env_far is not None and a.baked_env is None:
+        raise SystemExit("--baked-env-far is the far end of --baked-env's rays")
     if a.baked_dirs is not None and a.baked_sh is None:
         raise SystemExit("--baked-dirs counts the directions of --baked-sh")
     if a.load_baked is not None and (a.save_baked is not None or a.level is not None or a.bounds is not None):
@@ -158,7 +167,8 @@ def main(argv=None):
         else:
             bounds = (tuple(a.bounds[:3]), tuple(a.bounds[3:])) if a.bounds else geometry.bounds_from_cameras(system, a.margin)
             sh = {} if a.baked_sh is None else {"sh_degree": a.baked_sh, "dirs": sphere_directions(48 if a.baked_dirs is None else a.baked_dirs)}
-            scene = BakedScene.build(system, bounds, a.baked, a.level, img_id=a.images[0] if a.bake_image is None else a.bake_image, sparse=a.baked_sparse, **sh)
+            scene = BakedScene.build(system, bounds, a.baked, a.level, img_id=a.images[0] if a.bake_image is None else a.bake_image, sparse=a.baked_sparse,
+                                     env_size=a.baked_env, env_far=a.baked_env_far, **sh)
             if a.baked_tune is not None:  # distil on the path's own keyframe cameras; a sparse scene is tuned dense and stored sparse again
                 if a.baked_tune_pool:  # ... unless the pool itself is tuned, in place
                     from upnerf_amd.baked_sparse_tune import distill
@@ -174,7 +184,8 @@ def main(argv=None):
                 scene.save(a.save_baked)
         torch.cuda.synchronize()
         extra = {"baked_resolution": list(scene.resolution), "bounds": [list(scene.bounds[0]), list(scene.bounds[1])], "level": scene.level,
-                 "sh_degree": scene.sh_degree, "sparse": scene.sparse, "occupied_bricks": scene.n_bricks, "brick_share": scene.brick_fraction, "step": a.step, "occupied_share": scene.fraction, "baked_bytes": scene.nbytes, "bake_seconds": time.perf_counter() - tb}
+                 "sh_degree": scene.sh_degree, "sparse": scene.sparse, "occupied_bricks": scene.n_bricks, "brick_share": scene.brick_fraction, "step": a.step, "occupied_share": scene.fraction, "baked_bytes": scene.nbytes,
+                 "env_size": scene.env.E if scene.env is not None else None, "env_bytes": scene.env.nbytes if scene.env is not None else 0, "bake_seconds": time.perf_counter() - tb}
         if a.baked_tune is not None:
             extra.update(tune_extra)
     t0 = time.perf_counter()

@@ -479,6 +479,27 @@ class BrickUpsampleArgs(C.Structure):
                 ("child_bricks", _fp), ("words", _fp), ("out", _fp)]
 
 
+ENV_MAX_E = 8192  # UPNERF_ENV_MAX_E: cells per face side of an environment map at the most
+
+
+class EnvRaysArgs(C.Structure):
+    _fields_ = [("E", C.c_int32), ("count", C.c_int32), ("n0", C.c_int64), ("lo", C.c_float * 3), ("hi", C.c_float * 3),
+                ("far", C.c_float), ("reserved_", C.c_int32), ("rays", _fp)]
+
+
+class EnvSeamArgs(C.Structure):
+    _fields_ = [("E", C.c_int32), ("reserved_", C.c_int32), ("env", _fp)]
+
+
+class EnvCompositeArgs(C.Structure):
+    _fields_ = [("E", C.c_int32), ("R", C.c_int32), ("env", _fp), ("rays", _fp), ("opacity", _fp), ("rgb_in", _fp), ("rgb_out", _fp)]
+
+
+class EnvCompositeBwdArgs(C.Structure):
+    _fields_ = [("E", C.c_int32), ("R", C.c_int32), ("env", _fp), ("rays", _fp), ("opacity", _fp), ("g_out", _fp), ("g_opacity", _fp),
+                ("g_rays", _fp)]
+
+
 class DensityGradArgs(C.Structure):
     _fields_ = [("M", C.c_int32), ("reserved_", C.c_int32), ("points", _fp), ("P", _fp), ("PT", _fp), ("wk_xyz", C.c_float * 10),
                 ("sigma", _fp), ("grad", _fp)]
@@ -618,6 +639,10 @@ _SIGNATURES = {
     "upnerf_baked_upsample": [C.POINTER(BakedUpsampleArgs), _p],
     "upnerf_brick_upsample_mark": [C.POINTER(BrickUpsampleArgs), _p],
     "upnerf_brick_upsample_fill": [C.POINTER(BrickUpsampleArgs), _p],
+    "upnerf_env_rays": [C.POINTER(EnvRaysArgs), _p],
+    "upnerf_env_seam": [C.POINTER(EnvSeamArgs), _p],
+    "upnerf_env_composite": [C.POINTER(EnvCompositeArgs), _p],
+    "upnerf_env_composite_bwd": [C.POINTER(EnvCompositeBwdArgs), _p],
 }
 _LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
              "upnerf_occ_compact_scratch", "upnerf_pca_fit_scratch", "upnerf_brick_table_scratch", "upnerf_baked_tv_blocks")

@@ -26,9 +26,16 @@ same.  Still ONE appearance.  How close either kind comes to the field on a TRAI
 A sparse scene of any degree stores only the occupied 8 x 8 x 8-cell bricks of the grid, 9 x 9 x 9 points each, in `scene.pool`,
 found through `scene.slots` (include/upnerf_hip.h states the layout; csrc/brick.hip).  The marcher
 (`upnerf_baked_sparse_render`, the same march with another layout) never visits a sample outside an occupied brick, so the
-picture is bit for bit the dense scene's; `rgbs` and `records` are None then and `grid` is the pool."""
+picture is bit for bit the dense scene's; `rgbs` and `records` are None then and `grid` is the pool.
+
+    scene = BakedScene.build(system, bounds, (256, 256, 256), level=10.0, img_id=3, env_size=64)    # or scene.with_environment(env)
+
+A scene of any kind may carry an environment (`scene.env`, a `baked_env.Environment`: a cube map of what the field shows from the
+box outwards).  Its render then marches with background 0 and composites the map behind the march; sparsify,
+densify, upsample, the tuners and save / load carry it along unchanged.  The map has no parallax."""
 from __future__ import annotations
 
+import copy
 import ctypes as C
 from typing import Optional, Sequence
 
@@ -363,6 +370,17 @@ class BakedScene:
     sh_degree = 0
     records = None
     pool = slots = bricks = None  # a sparse scene's (sparsify, from_bricks, build(sparse=True)): see _sparse
+    env = None  # a baked_env.Environment behind the march (with_environment, build(env_size=...)), or None: the flat `background`
+
+    def with_environment(self, env) -> "BakedScene":
+        """This scene (the same tensors, nothing copied) with the environment `env` behind it, a `baked_env.Environment` on the
+        scene's device, or None to remove it."""
+        from .baked_env import Environment
+        if env is not None and (not isinstance(env, Environment) or env.device != self.device):
+            raise ValueError("env is a baked_env.Environment on the scene's device, or None")
+        other = copy.copy(self)
+        other.env = env
+        return other
 
     def __init__(self, rgbs: torch.Tensor, bounds, level: float):
         require_cuda("BakedScene", rgbs)
@@ -420,7 +438,8 @@ class BakedScene:
         if self.sparse:
             return self
         slots, bricks, n = brick_table(self.occupancy.words, self.occupancy.dims)
-        return self._sparse(brick_gather(self.grid, bricks), slots, bricks, self.resolution, self.bounds, self.level, self.sh_degree)
+        sparse = self._sparse(brick_gather(self.grid, bricks), slots, bricks, self.resolution, self.bounds, self.level, self.sh_degree)
+        return sparse.with_environment(self.env)
 
     @torch.no_grad()
     def densify(self) -> "BakedScene":
@@ -429,8 +448,8 @@ class BakedScene:
             return self
         grid = brick_scatter(self.pool, self.bricks, self._resolution)
         if self.sh_degree:
-            return self.from_records(grid, self.bounds, self.level, self.sh_degree)
-        return type(self)(grid, self.bounds, self.level)
+            return self.from_records(grid, self.bounds, self.level, self.sh_degree).with_environment(self.env)
+        return type(self)(grid, self.bounds, self.level).with_environment(self.env)
 
     @classmethod
     def from_bricks(cls, pool: torch.Tensor, bricks: torch.Tensor, resolution: Sequence[int], bounds, level: float,
@@ -536,7 +555,8 @@ class BakedScene:
     @classmethod
     @torch.no_grad()
     def build(cls, system, bounds, resolution: Sequence[int], level: float, img_id=None, rows=None, view_dir=None,
-              field: str = "fine", chunk: Optional[int] = None, sh_degree: int = 0, dirs=None, sparse: bool = False) -> "BakedScene":
+              field: str = "fine", chunk: Optional[int] = None, sh_degree: int = 0, dirs=None, sparse: bool = False,
+              env_size: Optional[int] = None, env_far: Optional[float] = None) -> "BakedScene":
         """Bake the static scene of `system`: sigma = geometry.density_grid, colour = field_colour with the appearance row of
         training image `img_id` (or `rows`, a row of the caller's own) for the viewing direction `view_dir` (default: the
         normalised mean optical axis of the refined training cameras).  `level` has no default: the useful threshold depends on
@@ -554,7 +574,23 @@ class BakedScene:
         (pool_colour), once or once per direction, and packed as above.  The cost: a line is one ray of the field kernels'
         minimum of 32 samples for 9 stored points, and a brick stores 729 points for its 512 cells, so with f_b the share of
         occupied bricks the colour work is f_b * (729 / 512) * (32 / 9) ~ 5.06 f_b of the dense bake's: a sparse bake is the
-        cheaper one only below f_b ~ 0.20 (`brick_fraction` reports f_b).  `chunk` counts lines in the colour passes then."""
+        cheaper one only below f_b ~ 0.20 (`brick_fraction` reports f_b).  `chunk` counts lines in the colour passes then.
+
+        env_size = E: the scene also carries baked_env.Environment.build(system, bounds, E, far=env_far, ...) with the scene's
+        own appearance (img_id / rows) and field; env_far defaults to the largest far plane of the training images."""
+        if env_size is None:
+            if env_far is not None:
+                raise ValueError("env_far belongs to env_size=")
+            return cls._build(system, bounds, resolution, level, img_id, rows, view_dir, field, chunk, sh_degree, dirs, sparse)
+        from .baked_env import Environment, _size
+        _size(env_size)  # (refused before any pass over the field)
+        scene = cls._build(system, bounds, resolution, level, img_id, rows, view_dir, field, chunk, sh_degree, dirs, sparse)
+        return scene.with_environment(Environment.build(system, bounds, env_size, far=env_far, img_id=img_id, rows=rows, field=field))
+
+    @classmethod
+    @torch.no_grad()
+    def _build(cls, system, bounds, resolution, level, img_id, rows, view_dir, field, chunk, sh_degree, dirs, sparse) -> "BakedScene":
+        """build without the environment."""
         from .geometry import density_grid
         if min(int(n) for n in resolution) < 2:
             raise ValueError(f"resolution is the number of grid points per axis (two at least), got {tuple(resolution)}")
@@ -604,7 +640,11 @@ class BakedScene:
     # ---- rendering ---------------------------------------------------------------------------------------------------------
 
     def render(self, rays: torch.Tensor, step: float, background: float = 0.0, stop: float = 0.0, out: Optional[dict] = None) -> dict:
-        """{"rgb" [R, 3], "depth" [R], "opacity" [R]} of [R, 8] device rays (upnerf_baked_render; upnerf_baked_sh_render for an
+        """With an environment (`self.env` not None): the march below at background 0, then upnerf_env_composite in place on its
+        rgb -- rgb + (1 - opacity) env(d); `background` is NOT LOOKED AT then (it is still checked to be finite); depth and opacity
+        are the march's own (depth still gets (1 - opacity) far).  Without one, no launch is added and every bit is as it was:
+
+        {"rgb" [R, 3], "depth" [R], "opacity" [R]} of [R, 8] device rays (upnerf_baked_render; upnerf_baked_sh_render for an
         SH scene; upnerf_baked_sparse_render for a sparse scene of any degree, the same march and the same bits; each sample's colour then being the expansion at the ray's own direction, clamped to [0, 1]): samples every
         `step` of t from near + step / 2, alpha-composited front to back; what the ray does not hit shows `background` at depth
         `far`.  stop > 0 ends a ray once its transmittance falls below it.  out: preallocated buffers of at least R rows."""
@@ -619,7 +659,9 @@ class BakedScene:
             if t.dtype != torch.float32 or t.shape[0] < R or tuple(t.shape[1:]) != shape or t.device != dev:
                 raise ValueError("the outputs are fp32 [>= R, 3], [>= R] and [>= R] on the rays' device")
         march(self._pool_bytes if self.sparse else self.grid, self.sh_degree, self.slots, self.occupancy, self.bounds, rays, step,
-              background, stop, out["rgb"], out["depth"], out["opacity"])
+              background if self.env is None else 0.0, stop, out["rgb"], out["depth"], out["opacity"])
+        if self.env is not None:
+            self.env.composite_(rays, out["rgb"], out["opacity"])
         return {k: out[k][:R] for k in ("rgb", "depth", "opacity")}
 
     def tune(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, tv_sigma: float = 0.0, tv_colour: float = 0.0, tv_eps: float = 1e-8):
@@ -646,18 +688,31 @@ class BakedScene:
     def save(self, path: str) -> None:
         """An .npz holding the grid (`rgbs`, or `records` and `degree` of an SH scene), the bounds and the level; the bits are
         rebuilt on load.  A sparse scene: pool, bricks, resolution, degree, bounds, level (save_bricks)."""
+        env = self.env.env.cpu().numpy() if self.env is not None else None  # (a scene without one writes the file it always wrote)
         if self.sparse:
             save_bricks(path, self.pool.detach().cpu().numpy(), self.bricks.cpu().numpy(), self._resolution, self.bounds, self.level,
-                        sh_degree=self.sh_degree)
+                        sh_degree=self.sh_degree, env=env)
         elif self.sh_degree:
-            save_arrays(path, self.records.detach().cpu().numpy(), self.bounds, self.level, sh_degree=self.sh_degree)
+            save_arrays(path, self.records.detach().cpu().numpy(), self.bounds, self.level, sh_degree=self.sh_degree, env=env)
         else:
-            save_arrays(path, self.rgbs.detach().cpu().numpy(), self.bounds, self.level)
+            save_arrays(path, self.rgbs.detach().cpu().numpy(), self.bounds, self.level, env=env)
 
     @classmethod
     def load(cls, path: str, device="cuda") -> "BakedScene":
+        """The scene of a file `save` wrote; with the array `env` in it (ENV_KEY: a file of a scene with an environment) the
+        environment too, else `env` None."""
         with np.load(path) as f:
-            keys = set(f.files)
+            env = _env_array(path, f[ENV_KEY]) if ENV_KEY in f.files else None
+        scene = cls._load(path, device)
+        if env is None:
+            return scene
+        from .baked_env import Environment
+        return scene.with_environment(Environment.from_array(env, device))
+
+    @classmethod
+    def _load(cls, path: str, device) -> "BakedScene":
+        with np.load(path) as f:
+            keys = set(f.files) - {ENV_KEY}
         if keys == BRICK_KEYS:
             pool, bricks, resolution, bounds, level, degree = load_bricks(path)
             E = POINT_BYTES[degree]
@@ -719,9 +774,23 @@ class BakedScene:
         return self.occupancy.fraction
 
 
-def save_arrays(path: str, rgbs: np.ndarray, bounds, level: float, sh_degree: int = 0) -> None:
+ENV_KEY = "env"  # the one optional array of a scene's file: the environment map [6, E+1, E+1, 4] fp32
+
+
+def _env_array(what: str, env) -> np.ndarray:
+    env = np.asarray(env)
+    if env.dtype != np.float32 or env.ndim != 4 or env.shape[0] != 6 or env.shape[1] != env.shape[2] or env.shape[1] < 2 or env.shape[3] != 4:
+        raise ValueError(f"{what}: the environment is a fp32 array [6, E+1, E+1, 4], got {env.dtype} {env.shape}")
+    return np.ascontiguousarray(env)
+
+
+def _env_entry(what: str, env) -> dict:
+    return {} if env is None else {ENV_KEY: _env_array(what, env)}
+
+
+def save_arrays(path: str, rgbs: np.ndarray, bounds, level: float, sh_degree: int = 0, env=None) -> None:
     """rgbs: the fp32 grid [Nz, Ny, Nx, 4]; with sh_degree = 1 | 2 the uint8 records [Nz, Ny, Nx, 32 | 64] instead, written as
-    the arrays records, degree, bounds, level."""
+    the arrays records, degree, bounds, level.  env: the environment map [6, E+1, E+1, 4] fp32 or None (no array `env` then)."""
     grid = np.asarray(rgbs)
     if sh_degree != 0:
         if grid.dtype != np.uint8 or grid.ndim != 4 or grid.shape[3] != RECORD_BYTES[_degree(sh_degree)]:
@@ -733,7 +802,7 @@ def save_arrays(path: str, rgbs: np.ndarray, bounds, level: float, sh_degree: in
         arrays = dict(rgbs=grid)
     lo, hi = box(bounds, strict=True)
     with open(path, "wb") as fh:  # (a file object: numpy appends no .npz of its own to the name)
-        np.savez(fh, **arrays, bounds=np.asarray([lo, hi], np.float64), level=np.float64(level))
+        np.savez(fh, **arrays, **_env_entry("save_arrays", env), bounds=np.asarray([lo, hi], np.float64), level=np.float64(level))
 
 
 BRICK_KEYS = {"pool", "bricks", "resolution", "degree", "bounds", "level"}
@@ -760,22 +829,22 @@ def _brick_arrays(what: str, pool, bricks, resolution, degree):
     return np.ascontiguousarray(pool), np.ascontiguousarray(bricks), tuple(int(n) for n in resolution), d
 
 
-def save_bricks(path: str, pool: np.ndarray, bricks: np.ndarray, resolution, bounds, level: float, sh_degree: int = 0) -> None:
+def save_bricks(path: str, pool: np.ndarray, bricks: np.ndarray, resolution, bounds, level: float, sh_degree: int = 0, env=None) -> None:
     """A sparse scene's file: the arrays pool ([n_bricks, 9, 9, 9, 4] fp32, or [n_bricks, 9, 9, 9, 32 | 64] uint8 at sh_degree
-    1 | 2), bricks (int32 [n_bricks], strictly ascending), resolution (Nx, Ny, Nz), degree, bounds, level.  Anything else raises
-    ValueError."""
+    1 | 2), bricks (int32 [n_bricks], strictly ascending), resolution (Nx, Ny, Nz), degree, bounds, level, and with `env` given the
+    environment map `env`.  Anything else raises ValueError."""
     pool, bricks, resolution, degree = _brick_arrays("save_bricks", pool, bricks, np.asarray(resolution, np.int64), np.int64(sh_degree) if sh_degree in (0, 1, 2) else np.float64(-1))
     lo, hi = box(bounds, strict=True)
     with open(path, "wb") as fh:
         np.savez(fh, pool=pool, bricks=bricks, resolution=np.asarray(resolution, np.int64), degree=np.int64(degree),
-                 bounds=np.asarray([lo, hi], np.float64), level=np.float64(level))
+                 bounds=np.asarray([lo, hi], np.float64), level=np.float64(level), **_env_entry("save_bricks", env))
 
 
 def load_bricks(path: str):
     """(pool, bricks, resolution, bounds, level, degree) of a file save_bricks wrote; any other key set, and arrays that do not
     fit each other, raise ValueError."""
     with np.load(path) as f:
-        if set(f.files) != BRICK_KEYS:
+        if set(f.files) - {ENV_KEY} != BRICK_KEYS:
             raise ValueError(f"{path}: not a sparse baked scene (arrays {sorted(f.files)})")
         pool, bricks, resolution, degree, bounds, level = (f[k] for k in ("pool", "bricks", "resolution", "degree", "bounds", "level"))
     if bounds.shape != (2, 3) or level.shape != ():
@@ -788,13 +857,14 @@ def load_arrays(path: str):
     """(rgbs fp32 [Nz, Ny, Nx, 4], bounds, level) of a file BakedScene.save wrote, or (records uint8 [Nz, Ny, Nx, 32 | 64],
     bounds, level, degree) of an SH scene's; anything else raises ValueError."""
     with np.load(path) as f:
-        if set(f.files) == {"records", "degree", "bounds", "level"}:
+        files = set(f.files) - {ENV_KEY}  # (the environment, where there is one, is BakedScene.load's to read)
+        if files == {"records", "degree", "bounds", "level"}:
             records, bounds, level, degree = f["records"], f["bounds"], float(f["level"]), f["degree"]
             if degree.shape != () or int(degree) not in RECORD_BYTES or records.dtype != np.uint8 or records.ndim != 4 or \
                     records.shape[3] != RECORD_BYTES[int(degree)] or bounds.shape != (2, 3) or min(records.shape[:3]) < 2:
                 raise ValueError(f"{path}: not a baked scene (records {records.dtype} {records.shape}, degree {degree}, bounds {bounds.shape})")
             return np.ascontiguousarray(records), box(bounds.tolist(), strict=True), level, int(degree)
-        if set(f.files) != {"rgbs", "bounds", "level"}:
+        if files != {"rgbs", "bounds", "level"}:
             raise ValueError(f"{path}: not a baked scene (arrays {sorted(f.files)})")
         rgbs, bounds, level = f["rgbs"], f["bounds"], float(f["level"])
     if rgbs.dtype != np.float32 or rgbs.ndim != 4 or rgbs.shape[3] != 4 or bounds.shape != (2, 3) or min(rgbs.shape[:3]) < 2:

@@ -83,11 +83,17 @@ class _Render(torch.autograd.Function):
 
 def render(scene: BakedScene, rays: torch.Tensor, step: float, background: float = 0.0, stop: float = 0.0) -> dict:
     """{"rgb" [R, 3], "depth" [R], "opacity" [R]} of `rays` [R, 8] through `scene`, differentiable with respect to `rays` only:
-    forward the marcher of the scene's layout and degree (BakedScene.render, the same bits), backward upnerf_baked_ray_bwd."""
+    forward the marcher of the scene's layout and degree (BakedScene.render, the same bits), backward upnerf_baked_ray_bwd.
+    With scene.env set: the march at background 0 (`background` is not looked at), then the environment's composite through its
+    own autograd function (upnerf_env_composite / _bwd) -- the rays receive the gradient of both, the sky's included."""
     _scene(scene, "baked_pose.render")
     require_cuda("baked_pose.render", rays)
     step, background, stop = _render_args(rays, step, background, stop)
-    rgb, depth, opacity = _Render.apply(scene, rays, step, background, stop)
+    if scene.env is None:
+        rgb, depth, opacity = _Render.apply(scene, rays, step, background, stop)
+    else:
+        rgb, depth, opacity = _Render.apply(scene.with_environment(None), rays, step, 0.0, stop)
+        rgb = scene.env.composite(rays, rgb, opacity)
     return {"rgb": rgb, "depth": depth, "opacity": opacity}
 
 

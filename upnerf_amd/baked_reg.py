@@ -125,6 +125,10 @@ def upsample(scene: BakedScene, level: Optional[float] = None) -> BakedScene:
     brick count), upnerf_brick_upsample_fill, upnerf_brick_occ."""
     if not isinstance(scene, BakedScene):
         raise ValueError("upsample takes a baked.BakedScene")
+    return _upsample(scene, level).with_environment(scene.env)  # (the environment is no function of the grid: carried along)
+
+
+def _upsample(scene: BakedScene, level: Optional[float]) -> BakedScene:
     level = scene.level if level is None else _level(level)
     degree, dev = scene.sh_degree, scene.device
     Nx, Ny, Nz = scene.resolution

@@ -49,9 +49,9 @@ class PoolParams:
     [n_bricks, 9, 9, 9, 4] at degree 0, else `coef` [n_bricks, 9, 9, 9, 3, nb] and `sigma` [n_bricks, 9, 9, 9]; the (frozen) table
     `slots` and `bricks`, the (frozen) occupancy, the bounds, the degree.  The tensors are leaves; `tensors` lists them."""
 
-    def __init__(self, slots, bricks, occupancy, bounds, degree: int, rgbs=None, coef=None, sigma=None):
+    def __init__(self, slots, bricks, occupancy, bounds, degree: int, rgbs=None, coef=None, sigma=None, env=None):
         self.slots, self.bricks, self.occupancy, self.bounds, self.degree = slots, bricks, occupancy, bounds, int(degree)
-        self.rgbs, self.coef, self.sigma = rgbs, coef, sigma
+        self.rgbs, self.coef, self.sigma, self.env = rgbs, coef, sigma, env
         P, nb = _lib.BRICK_POINTS, (self.degree + 1) ** 2
         shape = (bricks.numel(), P, P, P)
         if self.degree == 0:
@@ -67,10 +67,10 @@ class PoolParams:
     def of(cls, scene: BakedScene, requires_grad: bool = True) -> "PoolParams":
         _sparse(scene, "PoolParams.of")
         if scene.sh_degree == 0:
-            p = cls(scene.slots, scene.bricks, scene.occupancy, scene.bounds, 0, rgbs=scene.pool.detach().clone())
+            p = cls(scene.slots, scene.bricks, scene.occupancy, scene.bounds, 0, rgbs=scene.pool.detach().clone(), env=scene.env)
         else:
             coef, sigma = unpack_records(scene.pool, scene.sh_degree)
-            p = cls(scene.slots, scene.bricks, scene.occupancy, scene.bounds, scene.sh_degree, coef=coef, sigma=sigma)
+            p = cls(scene.slots, scene.bricks, scene.occupancy, scene.bounds, scene.sh_degree, coef=coef, sigma=sigma, env=scene.env)
         for t in p.tensors:
             t.requires_grad_(requires_grad)
         return p
@@ -183,12 +183,16 @@ def render(pool_params: PoolParams, rays: torch.Tensor, step: float, background:
     """{"rgb" [R, 3], "depth" [R], "opacity" [R]} of `rays` [R, 8] through the pool of `pool_params`, differentiable with respect
     to pool_params.rgbs, or to pool_params.coef and .sigma: forward upnerf_baked_sparse_render (at degree 1 | 2 on records packed
     from the parameters at level 0), backward upnerf_baked_sparse_render_bwd followed by upnerf_brick_face_sum -- every copy of a
-    shared point receives the point's whole gradient.  No gradient for the rays."""
+    shared point receives the point's whole gradient.  No gradient for the rays.  With pool_params.env set: the march at background
+    0 and the environment's composite after it, as in baked_tune.render."""
     if not isinstance(pool_params, PoolParams):
         raise ValueError("pool_params is a baked_sparse_tune.PoolParams (PoolParams.of(scene))")
     require_cuda("baked_sparse_tune.render", rays)
     step, background, stop = _render_args(rays, step, background, stop)
-    rgb, depth, opacity = _Render.apply(pool_params, _rays16(rays), step, background, stop, *pool_params.tensors)
+    rays = _rays16(rays)
+    rgb, depth, opacity = _Render.apply(pool_params, rays, step, background if pool_params.env is None else 0.0, stop, *pool_params.tensors)
+    if pool_params.env is not None:
+        rgb = pool_params.env.composite(rays, rgb, opacity)
     return {"rgb": rgb, "depth": depth, "opacity": opacity}
 
 
@@ -218,11 +222,11 @@ class PoolTuner(BakedTuner):
     def _march(self, rays, step, background, stop):
         return _forward(self.points, self.params, rays, step, background, stop)
 
-    def _gradient(self, rays, step, background, stop, g_rgb) -> None:
+    def _gradient(self, rays, step, background, stop, g_rgb, g_opacity=None) -> None:
         """The marcher's gradient with the face sum; with the penalty on, the per-copy gradients of the marcher and of
         upnerf_baked_tv first and ONE face sum over both."""
-        backward(self.points, self.params, rays, step, background, stop, g_rgb, out=self.grads[0] if self.degree == 0 else self.grads,
-                 face_sum=not self.tv_on)
+        backward(self.points, self.params, rays, step, background, stop, g_rgb, g_opacity=g_opacity,
+                 out=self.grads[0] if self.degree == 0 else self.grads, face_sum=not self.tv_on)
         if self.tv_on:
             from .baked_reg import tuner_tv
             self.last_tv = tuner_tv(self, layout=self.params)
@@ -241,7 +245,7 @@ class PoolTuner(BakedTuner):
             check(TIMER.run("baked_pack", lambda: lib.upnerf_baked_pack(C.byref(a), stream()), units=sigma.numel()), "upnerf_baked_pack")
         else:
             pool = pack_records(*self.masters, self.degree, self.level)
-        return BakedScene._sparse(pool, self.slots, self.bricks, self.resolution, self.bounds, self.level, self.degree)
+        return BakedScene._sparse(pool, self.slots, self.bricks, self.resolution, self.bounds, self.level, self.degree).with_environment(self.env)
 
 
 def distill(system, scene: BakedScene, path_or_img_ids, iters: int, batch: int, baked_step: float, seed: int = 0, lr: float = 1e-2,

@@ -11,7 +11,9 @@ Dense scenes of degree 0, 1 and 2.  A sparse scene is refused: its pool stores t
 gradient would have to be summed over the copies -- `scene.densify()`, tune, `.sparsify()`, or baked_sparse_tune.py, which tunes
 the pool in place and does that sum.  The occupancy is frozen while tuning:
 a grid point whose sigma is zero is no parameter (it receives no gradient), so a clear cell keeps its eight zero corners, and a
-sigma the optimiser drives to zero (`upnerf_baked_project`) is dead from then on.  The gradient's sums over rays are float atomic
+sigma the optimiser drives to zero (`upnerf_baked_project`) is dead from then on.  A scene's environment (`scene.env`,
+baked_env.py) is frozen too: the render composites it behind the march, the points see its gradient through the opacity
+(g_opacity - g_rgb . env(d)), the map itself gets none.  The gradient's sums over rays are float atomic
 adds: two runs agree to rounding, not to the bit.  There is no CPU path."""
 from __future__ import annotations
 
@@ -55,9 +57,9 @@ class SceneParams:
     `coef` [Nz, Ny, Nx, 3, nb] and `sigma` [Nz, Ny, Nx]; the (frozen) occupancy, the bounds, the degree.  The tensors are leaves a
     caller may set requires_grad on; `tensors` lists them."""
 
-    def __init__(self, occupancy, bounds, degree: int, rgbs=None, coef=None, sigma=None):
+    def __init__(self, occupancy, bounds, degree: int, rgbs=None, coef=None, sigma=None, env=None):
         self.occupancy, self.bounds, self.degree = occupancy, bounds, int(degree)
-        self.rgbs, self.coef, self.sigma = rgbs, coef, sigma
+        self.rgbs, self.coef, self.sigma, self.env = rgbs, coef, sigma, env
         nb = (self.degree + 1) ** 2
         Cx, Cy, Cz = occupancy.dims
         shape = (Cz + 1, Cy + 1, Cx + 1)
@@ -74,10 +76,10 @@ class SceneParams:
     def of(cls, scene: BakedScene, requires_grad: bool = True) -> "SceneParams":
         _dense(scene, "SceneParams.of")
         if scene.sh_degree == 0:
-            p = cls(scene.occupancy, scene.bounds, 0, rgbs=scene.rgbs.detach().clone())
+            p = cls(scene.occupancy, scene.bounds, 0, rgbs=scene.rgbs.detach().clone(), env=scene.env)
         else:
             coef, sigma = unpack_records(scene.records, scene.sh_degree)
-            p = cls(scene.occupancy, scene.bounds, scene.sh_degree, coef=coef, sigma=sigma)
+            p = cls(scene.occupancy, scene.bounds, scene.sh_degree, coef=coef, sigma=sigma, env=scene.env)
         for t in p.tensors:
             t.requires_grad_(requires_grad)
         return p
@@ -155,12 +157,17 @@ class _Render(torch.autograd.Function):
 def render(scene_params: SceneParams, rays: torch.Tensor, step: float, background: float = 0.0, stop: float = 0.0) -> dict:
     """{"rgb" [R, 3], "depth" [R], "opacity" [R]} of `rays` [R, 8] through the scene of `scene_params`, differentiable with
     respect to scene_params.rgbs, or to scene_params.coef and .sigma: forward the existing marcher (at degree 1 | 2 on records
-    packed from the parameters by upnerf_baked_sh_pack at level 0), backward upnerf_baked_render_bwd.  No gradient for the rays."""
+    packed from the parameters by upnerf_baked_sh_pack at level 0), backward upnerf_baked_render_bwd.  No gradient for the rays.
+    With scene_params.env set: the march at background 0 (`background` is not looked at), then the environment's composite through
+    its own autograd function -- the points receive g_opacity - g_rgb . env(d) through the opacity."""
     if not isinstance(scene_params, SceneParams):
         raise ValueError("scene_params is a baked_tune.SceneParams (SceneParams.of(scene))")
     require_cuda("baked_tune.render", rays)
     step, background, stop = _render_args(rays, step, background, stop)
-    rgb, depth, opacity = _Render.apply(scene_params, _rays16(rays), step, background, stop, *scene_params.tensors)
+    rays = _rays16(rays)
+    rgb, depth, opacity = _Render.apply(scene_params, rays, step, background if scene_params.env is None else 0.0, stop, *scene_params.tensors)
+    if scene_params.env is not None:
+        rgb = scene_params.env.composite(rays, rgb, opacity)
     return {"rgb": rgb, "depth": depth, "opacity": opacity}
 
 
@@ -181,6 +188,7 @@ class BakedTuner:
             raise ValueError("tv_sigma and tv_colour are finite weights, tv_eps is positive and finite")
         self.lr, self.betas, self.eps, self.t = lr, (float(betas[0]), float(betas[1])), eps, 0
         self.degree, self.bounds, self.level, self.occupancy = scene.sh_degree, scene.bounds, scene.level, scene.occupancy
+        self.env = scene.env  # frozen: composited behind the march in step(), carried to scene()
         # the total variation penalty (baked_reg): off at the defaults, and then nothing is launched for it
         self.last_tv = None
         self.tv_cells = max(1, self.occupancy.n_occupied()) if self.tv_on else None
@@ -211,10 +219,10 @@ class BakedTuner:
     def _march(self, rays, step, background, stop):
         return _forward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop)
 
-    def _gradient(self, rays, step, background, stop, g_rgb) -> None:
+    def _gradient(self, rays, step, background, stop, g_rgb, g_opacity=None) -> None:
         """The gradient of the points, added into self.grads (zeroed by the caller); with the penalty on, its gradient after the
         marcher's (upnerf_baked_tv), the value left in self.last_tv."""
-        backward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop, g_rgb,
+        backward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop, g_rgb, g_opacity=g_opacity,
                  out=self.grads[0] if self.degree == 0 else self.grads)
         if self.tv_on:
             from .baked_reg import tuner_tv
@@ -247,7 +255,9 @@ class BakedTuner:
     def step(self, rays: torch.Tensor, target_rgb: torch.Tensor, step: float, background: float = 0.0, stop: float = 0.0) -> torch.Tensor:
         """One iteration on `rays` [R, 8] against `target_rgb` [R, 3]: zero the gradient (upnerf_zero), forward, the gradient of
         the mean squared error (plain torch), upnerf_baked_render_bwd, with tv_sigma or tv_colour not zero upnerf_baked_tv,
-        upnerf_adam, upnerf_baked_project, and at degree 1 | 2 upnerf_baked_sh_pack.  Returns the loss BEFORE the update, a 0-dim device tensor (no host read here)."""
+        upnerf_adam, upnerf_baked_project, and at degree 1 | 2 upnerf_baked_sh_pack.  Returns the loss BEFORE the update, a 0-dim device tensor (no host read here).
+        With an environment the march runs at background 0 (`background` is not looked at), upnerf_env_composite follows it, and
+        upnerf_env_composite_bwd gives the marcher's backward its g_opacity = -(g_rgb . env(d))."""
         require_cuda("BakedTuner.step", rays, target_rgb)
         step, background, stop = _render_args(rays, step, background, stop)
         rays = _rays16(rays)
@@ -256,11 +266,19 @@ class BakedTuner:
             raise ValueError("target_rgb is a fp32 tensor [R, 3]")
         st = stream()
         check(lib.upnerf_zero(ptr(self.g), self.g.numel(), st), "upnerf_zero")
-        rgb, _, _ = self._march(rays, step, background, stop)
+        if self.env is not None:
+            background = 0.0
+        rgb, _, opacity = self._march(rays, step, background, stop)
+        if self.env is not None:
+            self.env.composite_(rays, rgb, opacity)
         diff = rgb - target_rgb
         loss = (diff * diff).mean()
         g_rgb = diff * (2.0 / (3 * R))
-        self._gradient(rays, step, background, stop, g_rgb)
+        g_opacity = None
+        if self.env is not None:
+            from .baked_env import composite_backward
+            g_opacity = composite_backward(self.env.env, rays, opacity, g_rgb)[0]
+        self._gradient(rays, step, background, stop, g_rgb, g_opacity)
         self.t += 1
         b1, b2 = self.betas
         step_size, bc2_sqrt = self.lr / (1.0 - b1 ** self.t), math.sqrt(1.0 - b2 ** self.t)
@@ -278,8 +296,8 @@ class BakedTuner:
         """The tuned scene: the masters pruned again at the scene's level, the bits rebuilt (from_grids / from_records)."""
         if self.degree == 0:
             rgbs = self.masters[0]
-            return BakedScene.from_grids(rgbs[..., 3].contiguous(), rgbs[..., :3].contiguous(), self.bounds, self.level)
-        return BakedScene.from_records(pack_records(*self.masters, self.degree, self.level), self.bounds, self.level, self.degree)
+            return BakedScene.from_grids(rgbs[..., 3].contiguous(), rgbs[..., :3].contiguous(), self.bounds, self.level).with_environment(self.env)
+        return BakedScene.from_records(pack_records(*self.masters, self.degree, self.level), self.bounds, self.level, self.degree).with_environment(self.env)
 
 
 def keyframe_rays(path, device) -> torch.Tensor:
