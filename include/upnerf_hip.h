@@ -2001,6 +2001,66 @@ typedef struct {
 } upnerf_env_composite_bwd_args;
 int upnerf_env_composite_bwd(const upnerf_env_composite_bwd_args* a, void* stream);
 
+/* ---- pruning a baked scene by what a set of rays sees (csrc/baked.hip, csrc/brick.hip).  Added under ABI 11: new
+ * symbols only.
+ *
+ * upnerf_baked_visibility: per point of a scene, the largest compositing weight that any ray of `rays` gives a sample in a cell
+ * touching the point, MAXED into `vis`, which the caller has zeroed.  One entry point for both layouts (`slots` NULL: a dense
+ * grid, else the pool of upnerf_baked_sparse_render) and every degree: a point is E bytes (16 | 32 | 64) with its fp32 sigma at
+ * byte `sigma_offset` (12, 24, 56 in the three layouts of this header), and nothing else of it is read.  One thread per ray row
+ * o | d | near | far, one wave per workgroup, one launch, nothing allocated, no host read-back.
+ *
+ * The definition.  The visited samples of a ray, their order, cells, f, blended sigma, delta, e, alpha, w_k = T_k alpha_k,
+ * T_{k+1} and the `stop` sample are the forward's, formed by the same code (the sigma channel of its blend); there is no
+ * background.  A visited sample with T_k > 0 records m_k = fmaxf(w_k, 2^-126), 2^-126 the smallest positive normal fp32; a
+ * sample with T_k == 0 records nothing (and the ray ends there: no later sample can record).  Then
+ *   vis[p] = max(vis[p], max over the rays and over their recorded samples in the (up to 8) cells that have p as a LIVE corner
+ *            -- a stored sigma that is not zero, upnerf_baked_render_bwd's rule -- of m_k).
+ * So vis[p] > 0 exactly when some ray reaches a cell of p with light left, and the value is the largest weight there.  The eight
+ * corners of a cell receive ONE value, no trilinear share: a cell that holds a significant sample keeps its whole integrand.
+ * The maxima of consecutive samples in one cell are taken in a register and go to memory once, with an atomic max on the bits
+ * of the value as an unsigned integer (every recorded value is a positive, finite float, so its bits order as it does).  A
+ * maximum is exact and commutative: THE SAME BITS EVERY RUN AND HOWEVER THE RAYS ARE CUT INTO LAUNCHES.
+ * A pool: `vis` is pool-shaped, [n_bricks][729], corner (x, y, z) of a cell at base + x + 9 y + 81 z as in
+ * upnerf_baked_sparse_render_bwd, and each copy of a shared point receives what its own brick's cells give it --
+ * upnerf_brick_face_max makes the copies whole.  A miss records nothing.
+ * Refused (UPNERF_EINVAL): what the forward of the layout refuses, a NULL vis, an E outside {16, 32, 64}, a sigma_offset that
+ * is negative, no multiple of 4 or > E - 4.  The fields keep the order of the other baked structs, scalars first. */
+typedef struct {
+  int32_t Cx, Cy, Cz, R;
+  float lo[3], hi[3];        /* hi > lo, finite */
+  float step;                /* > 0, finite */
+  float stop;                /* >= 0, < 1; 0 = never */
+  int32_t E;                 /* bytes of a point: 16, 32 or 64 */
+  int32_t sigma_offset;      /* the byte of the point's fp32 sigma: a multiple of 4, <= E - 4 */
+  const uint8_t* points;     /* rgbs, records, or a pool [n_bricks][9][9][9][E]; aligned to E */
+  const int32_t* slots;      /* NULL: a dense grid; else [Bz][By][Bx], every entry < n_bricks */
+  const uint32_t* words;     /* [upnerf_occ_words(Cx, Cy, Cz)] */
+  const float* rays;         /* [R][8], 16-byte aligned */
+  float* vis;                /* [(Cz+1)(Cy+1)(Cx+1)] or [n_bricks][9][9][9]; zeroed by the caller, maxed into */
+} upnerf_baked_visibility_args;
+int upnerf_baked_visibility(const upnerf_baked_visibility_args* a, void* stream);
+
+/* upnerf_brick_face_max: upnerf_brick_face_sum with fmaxf in place of +: every copy of a grid point becomes
+ * fmaxf(fmaxf(x_b1, x_b2), ...) over its copies in the occupied bricks -- the same struct, the same two launches, one writer
+ * per address, the same refusals, the same bits every run.  After it a pool-shaped visibility holds the point's value on every
+ * copy. */
+int upnerf_brick_face_max(const upnerf_brick_face_sum_args* a, void* stream);
+
+/* upnerf_baked_prune: in place on `points` [n][E] (a grid or a pool, any degree), a point with NOT (vis[p] >= min_weight) becomes
+ * an all-zero record, as upnerf_baked_pack leaves a dropped point; every other point keeps its bytes.  kept[p] (optional) =
+ * 1 / 0 accordingly.  One thread per point.  Refused (UPNERF_EINVAL): n <= 0, an E outside {16, 32, 64}, a NULL vis or points,
+ * points not 16-byte aligned, a min_weight that is NaN. */
+typedef struct {
+  int64_t n;
+  float min_weight;          /* not NaN */
+  int32_t E;                 /* bytes of a point: 16, 32 or 64 */
+  const float* vis;          /* [n] */
+  uint8_t* points;           /* [n][E], 16-byte aligned */
+  uint8_t* kept;             /* [n] or NULL */
+} upnerf_baked_prune_args;
+int upnerf_baked_prune(const upnerf_baked_prune_args* a, void* stream);
+
 #ifdef UPNERF_STAMPS
 /* Diagnostic build only (make -C upnerf_amd/csrc stamps -> libupnerf_hip_stamps.so, never the shipped library): per-phase
  * shader-clock sums accumulated by the f16x3 field kernels; out16[0..7] forward trunk phases, [8..15] backward stages. */

@@ -108,6 +108,8 @@ def main():
     ap.add_argument("--env", action="store_true", help="measure the environment map (upnerf_env_composite, its backward, the bake) instead; writes --env-out")
     ap.add_argument("--env-out", default=os.path.join(ROOT, "profiles", "baked_env.json"))
     ap.add_argument("--env-ratios", default=None, help="with --env: a JSON file of the tests' worst error / gate ratios to record beside the times")
+    ap.add_argument("--prune", action="store_true", help="measure the visibility march, the face max and prune() instead; writes --prune-out")
+    ap.add_argument("--prune-out", default=os.path.join(ROOT, "profiles", "baked_prune.json"))
     ap.add_argument("--parent-lib", default=None, help="with --sparse: the parent commit's libupnerf_hip.so, for the nine marchers' times beside this build's")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -134,6 +136,8 @@ def main():
     res = tuple(a.resolution)
     if a.env:
         return env_main(a, sysm, path, dev)
+    if a.prune:
+        return prune_main(a, path, dev)
     if a.pose:
         return pose_main(a, path, dev)
     if a.tv:
@@ -572,6 +576,88 @@ def tv_main(a, path, dev):
     print(json.dumps(out))
 
 
+def _two_shells(n, degree, dev):
+    """_shell_scene with a second shell of half the radius inside it: what lies behind the first shell a ray meets is the hidden one."""
+    from upnerf_amd.baked import BakedScene, sphere_directions
+    dirs = sphere_directions(12) if degree else None
+    sigma, colour = shell_grids(n, dev, dirs)
+    t = torch.linspace(-1, 1, n, device=dev)
+    r = (t[None, None, :] ** 2 + t[None, :, None] ** 2 + t[:, None, None] ** 2).sqrt()
+    sigma = torch.where((r - 0.3).abs() <= 2.0 * 2 / (n - 1), torch.full((), 40.0, device=dev), sigma)
+    if degree == 0:
+        return BakedScene.from_grids(sigma, colour, BOUNDS, 1.0)
+    return BakedScene.from_direction_grids(sigma, colour, dirs, BOUNDS, 1.0, sh_degree=2)
+
+
+def prune_main(a, path, dev):
+    """upnerf_baked_visibility beside the forward launch of the same scene, dense and pool, degree 0 and 2, on two analytic shells
+    at 128^3 points; the face max; and pool bytes, bricks and forward ms before and after prune().  Alternately in one process,
+    medians of --reps."""
+    import statistics as st
+    from upnerf_amd import baked_prune, novel_view
+    W, H = a.width, a.height
+    rays = novel_view.path_rays(*novel_view.path_poses(path.key_c2w.to(dev), path.key_near_far.to(dev), path.u.to(dev), path.mode),
+                                (W, H), path.K, 0, H * W)[0][:a.chunk].contiguous()
+    R, n, STEPS, rows = rays.shape[0], 128, 5, []
+    for degree in (0, 2):
+        dense = _two_shells(n, degree, dev)
+        sparse = dense.sparsify()
+        vis_d = torch.zeros(dense.resolution[::-1], device=dev)
+        vis_p = torch.zeros(sparse.n_bricks, 9, 9, 9, device=dev)
+        pruned = {w: sparse.prune(rays, a.step, min_weight=w) for w in (None, 1e-2)}
+        out = {k: torch.empty(R, 3 if k == "rgb" else 1, device=dev).squeeze(-1) for k in ("rgb", "depth", "opacity")}
+        legs = {"forward_dense": lambda: dense.render(rays, a.step, out=out),
+                "forward_pool": lambda: sparse.render(rays, a.step, out=out),
+                "visibility_dense": lambda: baked_prune.march_visibility(dense, rays, a.step, 0.0, vis_d),
+                "visibility_pool": lambda: baked_prune.march_visibility(sparse, rays, a.step, 0.0, vis_p),
+                "face_max": lambda: baked_prune.face_max(vis_p, sparse),
+                "forward_pool_pruned": lambda: pruned[None].render(rays, a.step, out=out),
+                "forward_pool_pruned_1e-2": lambda: pruned[1e-2].render(rays, a.step, out=out)}
+        for fn in legs.values():
+            fn()
+
+        def cold_ms(fn, buf):
+            # what a caller pays: visibility() and prune() start from a zeroed buffer, so every atomic of the launch is issued.  (In
+            # the legs above the buffer holds the maxima of the launch before and the load in front of the atomic skips them all.)
+            total = 0.0
+            for _ in range(STEPS):
+                buf.zero_()  # untimed
+                total += _event_ms(fn)
+            return total / STEPS
+
+        cold = {"visibility_dense_cold": lambda: cold_ms(legs["visibility_dense"], vis_d),
+                "visibility_pool_cold": lambda: cold_ms(legs["visibility_pool"], vis_p)}
+        ms = {k: [] for k in list(legs) + list(cold)}
+        for _ in range(a.reps):
+            for k, fn in legs.items():
+                ms[k].append(_event_ms(fn, STEPS))
+            for k, fn in cold.items():
+                ms[k].append(fn())
+        med = {k: st.median(v) for k, v in ms.items()}
+        same = all(torch.equal(sparse.render(rays, a.step)[k], pruned[None].render(rays, a.step)[k]) for k in ("rgb", "depth", "opacity"))
+        size = lambda s: {"pool_bytes": s.pool.numel() * s.pool.element_size(), "n_bricks": s.n_bricks, "f_b": s.brick_fraction, "nbytes": s.nbytes}
+        rows.append({"resolution": n, "degree": degree, "ms": med, "ms_all": {k: sorted(v) for k, v in ms.items()},
+                     "visibility_over_forward_dense": med["visibility_dense_cold"] / med["forward_dense"],
+                     "visibility_over_forward_pool": med["visibility_pool_cold"] / med["forward_pool"],
+                     "warm_visibility_over_forward_dense": med["visibility_dense"] / med["forward_dense"],
+                     "warm_visibility_over_forward_pool": med["visibility_pool"] / med["forward_pool"],
+                     "before": size(sparse), "after_default": size(pruned[None]), "after_1e-2": size(pruned[1e-2]),
+                     "points_seen_share": float((dense.visibility(rays, a.step) > 0).float().mean()),
+                     "pruned_renders_the_rays_to_the_same_bits": same})
+        del dense, sparse, pruned, vis_d, vis_p, legs
+        torch.cuda.empty_cache()
+    res = {"metric": "one upnerf_baked_visibility launch into a zeroed buffer (_cold: the zeroing untimed; the legs without the suffix max into the "
+                     "buffer of the launch before, so their atomics are all skipped) beside the forward launch of the same scene in the same process; upnerf_brick_face_max on the "
+                     "pool-shaped visibility; a sparse scene before and after prune() for the same rays (default weight, and 1e-2); two analytic shells",
+           "rays": R, "step": a.step, "reps": a.reps, "launches_per_timing": STEPS, "bounds": [list(b) for b in BOUNDS], "rows": rows,
+           "note": "analytic shells, not a trained scene: what share of a trained scene a prune removes, and which min_weight serves, is unchecked"}
+    os.makedirs(os.path.dirname(os.path.abspath(a.prune_out)), exist_ok=True)
+    with open(a.prune_out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def upsample_main(a, sysm, path, dev):
     """scene.upsample() 128^3 -> 255^3 and 256^3 -> 511^3 on the analytic shell, dense and pool to pool: time and peak device bytes;
     for degree 2 at 128^3 -> 255^3, BakedScene.build(..., sparse=True) at the target size on bench.py's seeded weights beside them."""
@@ -914,7 +1000,8 @@ def sparse_main(a, sysm, path, dev):
                     ms[k, w].append(leg())
         bk.lib = baked_tune.lib = new
         parent = {k: {"parent_ms_per_launch": st.median(ms[k, "parent"][1:]), "this_ms_per_launch": st.median(ms[k, "this"][1:]),
-                      "parent_over_this": st.median(ms[k, "parent"][1:]) / st.median(ms[k, "this"][1:])} for k in legs}
+                      "parent_over_this": st.median(ms[k, "parent"][1:]) / st.median(ms[k, "this"][1:]),
+                      "parent_ms_all": sorted(ms[k, "parent"][1:]), "this_ms_all": sorted(ms[k, "this"][1:])} for k in legs}
     out = {"metric": "sparse baked scenes: the marcher dense against sparse on an analytic shell, the degree-2 bake dense against sparse, the nine marchers against the parent commit's",
            "frames": F, "img_wh": [W, H], "chunk": a.chunk, "step": a.step, "reps": a.reps, "bounds": [list(b) for b in BOUNDS],
            "marcher": marcher, "bake": bake_out, "marchers_vs_parent": parent}

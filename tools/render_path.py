@@ -6,7 +6,8 @@ appearance moving from photograph to photograph (upnerf_amd/novel_view.py; DESIG
                                 [--occupancy NX NY NZ --level SIGMA [--dilate K] [--bounds X0 Y0 Z0 X1 Y1 Z1 | --margin M]]
                                 [--baked NX NY NZ --level SIGMA --step DT [--bake-image ID] [--save-baked F | --load-baked F]
                                  [--baked-sh {1,2} [--baked-dirs K]] [--baked-sparse] [--baked-tune ITERS [--baked-tune-lr LR] [--baked-tune-pool]
-                                  [--baked-tv LS LC] [--baked-upsample-at I [I ...]]] [--baked-env E [--baked-env-far T]]]
+                                  [--baked-tv LS LC] [--baked-upsample-at I [I ...]]
+                                  [--baked-prune-at I [I ...] [--baked-prune-weight W]]] [--baked-env E [--baked-env-far T]]]
 
 --occupancy skips empty space: the fine field's density is sampled on NX x NY x NZ grid points over the box (--bounds, or the
 box round the refined cameras and their far points grown by --margin), cells with a corner >= --level (grown by --dilate
@@ -31,6 +32,9 @@ place, with no buffer the size of the grid (upnerf_amd/baked_sparse_tune.py; DES
 --baked-tv LS LC adds a total variation penalty to --baked-tune (weights of sigma and of the colour, per occupied cell), and
 --baked-upsample-at I [I ...] doubles the grid's resolution before each listed iteration, dense to dense or pool to pool
 (upnerf_amd/baked_reg.py): the rendered and saved scene has the final resolution.
+--baked-prune-at I [I ...] drops, before each listed iteration (and before an upsampling of the same iteration), the grid points
+to which the keyframe cameras' rays give a compositing weight below --baked-prune-weight W (default: the points none of them sees
+at all), and with them the bricks of a pool that are left empty (upnerf_amd/baked_prune.py).
 --baked-env E also bakes an environment: a cube map of E cells per face side of what the field shows from the box centre outwards
 (to --baked-env-far, default the training images' largest far plane), composited behind the march instead of the flat backdrop
 (upnerf_amd/baked_env.py); it has no parallax.  The tuners keep it frozen and it is saved with the grid.
@@ -82,6 +86,8 @@ def parser():
     ap.add_argument("--baked-tune-pool", action="store_true", help="tune a --baked-sparse scene in place on its brick pool instead of through the dense layout (with --baked-sparse and --baked-tune)")
     ap.add_argument("--baked-tv", type=float, nargs=2, default=None, metavar=("LS", "LC"), help="total variation weights of sigma and of the colour in --baked-tune")
     ap.add_argument("--baked-upsample-at", type=int, nargs="+", default=None, metavar="I", help="double the grid's resolution before these iterations of --baked-tune")
+    ap.add_argument("--baked-prune-at", type=int, nargs="+", default=None, metavar="I", help="prune the grid by what the keyframe cameras see before these iterations of --baked-tune")
+    ap.add_argument("--baked-prune-weight", type=float, default=None, metavar="W", help="the compositing weight below which --baked-prune-at drops a point (default: only what no ray sees)")
     ap.add_argument("--baked-env", type=int, default=None, metavar="E", help="also bake an environment map of E cells per cube face side and show it behind the grid (with --baked)")
     ap.add_argument("--baked-env-far", type=float, default=None, metavar="T", help="far end of the environment's rays (default: the largest far plane of the training images)")
     ap.add_argument("--save-baked", default=None, help="write the baked grid to this .npz")
@@ -117,6 +123,12 @@ def check_args(a):
         raise SystemExit("--baked-tv and --baked-upsample-at belong to --baked-tune")
     if a.baked_upsample_at is not None and any(not 0 <= i < a.baked_tune for i in a.baked_upsample_at):
         raise SystemExit("--baked-upsample-at lists iterations of --baked-tune: 0 .. ITERS - 1")
+    if a.baked_prune_at is not None and a.baked_tune is None:
+        raise SystemExit("--baked-prune-at belongs to --baked-tune")
+    if a.baked_prune_at is not None and any(not 0 <= i < a.baked_tune for i in a.baked_prune_at):
+        raise SystemExit("--baked-prune-at lists iterations of --baked-tune: 0 .. ITERS - 1")
+    if a.baked_prune_weight is not None and a.baked_prune_at is None:
+        raise SystemExit("--baked-prune-weight is the weight of --baked-prune-at")
     if a.baked_tune is not None and a.baked_tune < 1:
         raise SystemExit("--baked-tune counts iterations: one at least")
     if a.baked is None and (a.baked_env is not None or a.baked_env_far is not None):
@@ -177,7 +189,8 @@ def main(argv=None):
                 tt = time.perf_counter()
                 tuned, curve = distill(system, scene if a.baked_tune_pool else scene.densify(), path, iters=a.baked_tune, batch=a.chunk or system.hparams["val.chunk_size"], baked_step=a.step,
                                        seed=0, lr=0.01 if a.baked_tune_lr is None else a.baked_tune_lr, img_id=a.images[0] if a.bake_image is None else a.bake_image,
-                                       tv=tuple(a.baked_tv or (0.0, 0.0)), upsample_at=tuple(a.baked_upsample_at or ()))
+                                       tv=tuple(a.baked_tv or (0.0, 0.0)), upsample_at=tuple(a.baked_upsample_at or ()),
+                                       prune_at=tuple(a.baked_prune_at or ()), prune_weight=a.baked_prune_weight)
                 scene = tuned.sparsify() if a.baked_sparse else tuned  # (a tuned pool is sparse already: sparsify() returns it)
                 tune_extra = {"tune_iters": a.baked_tune, "tune_loss_first": curve[0], "tune_loss_last": curve[-1], "tune_seconds": time.perf_counter() - tt}
             if a.save_baked is not None:

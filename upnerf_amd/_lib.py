@@ -500,6 +500,16 @@ class EnvCompositeBwdArgs(C.Structure):
                 ("g_rays", _fp)]
 
 
+class BakedVisibilityArgs(C.Structure):
+    _fields_ = [("Cx", C.c_int32), ("Cy", C.c_int32), ("Cz", C.c_int32), ("R", C.c_int32), ("lo", C.c_float * 3),
+                ("hi", C.c_float * 3), ("step", C.c_float), ("stop", C.c_float), ("E", C.c_int32), ("sigma_offset", C.c_int32),
+                ("points", _fp), ("slots", _fp), ("words", _fp), ("rays", _fp), ("vis", _fp)]
+
+
+class BakedPruneArgs(C.Structure):
+    _fields_ = [("n", C.c_int64), ("min_weight", C.c_float), ("E", C.c_int32), ("vis", _fp), ("points", _fp), ("kept", _fp)]
+
+
 class DensityGradArgs(C.Structure):
     _fields_ = [("M", C.c_int32), ("reserved_", C.c_int32), ("points", _fp), ("P", _fp), ("PT", _fp), ("wk_xyz", C.c_float * 10),
                 ("sigma", _fp), ("grad", _fp)]
@@ -643,6 +653,9 @@ _SIGNATURES = {
     "upnerf_env_seam": [C.POINTER(EnvSeamArgs), _p],
     "upnerf_env_composite": [C.POINTER(EnvCompositeArgs), _p],
     "upnerf_env_composite_bwd": [C.POINTER(EnvCompositeBwdArgs), _p],
+    "upnerf_baked_visibility": [C.POINTER(BakedVisibilityArgs), _p],
+    "upnerf_brick_face_max": [C.POINTER(BrickFaceSumArgs), _p],
+    "upnerf_baked_prune": [C.POINTER(BakedPruneArgs), _p],
 }
 _LONGLONG = ("upnerf_wgrad16_scratch", "upnerf_mtet_scratch", "upnerf_occ_words", "upnerf_occ_build_scratch",
              "upnerf_occ_compact_scratch", "upnerf_pca_fit_scratch", "upnerf_brick_table_scratch", "upnerf_baked_tv_blocks")

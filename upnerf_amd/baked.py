@@ -683,6 +683,20 @@ class BakedScene:
         from .baked_reg import upsample
         return upsample(self, level)
 
+    def visibility(self, rays: torch.Tensor, step: float, stop: float = 0.0, chunk: int = 16384) -> torch.Tensor:
+        """Per point, the largest compositing weight any of `rays` gives a sample in a cell touching it (at least 2^-126 where a
+        ray reaches such a cell with light left, else 0): fp32 [Nz, Ny, Nx], or [n_bricks, 9, 9, 9] of a sparse scene, the copies
+        of a shared point equal.  The same bits every run and for every `chunk`.  `baked_prune.visibility`; DESIGN.md 2.39."""
+        from .baked_prune import visibility
+        return visibility(self, rays, step, stop, chunk)
+
+    def prune(self, rays: torch.Tensor, step: float, min_weight: Optional[float] = None, stop: float = 0.0, chunk: int = 16384) -> "BakedScene":
+        """A new scene of the same bounds, degree, level, layout and environment without the points whose visibility from `rays`
+        is below `min_weight` (default 2^-126: only what no ray sees goes, and `rays` render to the same bits at this `step` and
+        `stop`); a sparse scene loses the bricks that are left empty.  This scene is not modified.  `baked_prune.prune`."""
+        from .baked_prune import prune
+        return prune(self, rays, step, min_weight, stop, chunk)
+
     # ---- files -------------------------------------------------------------------------------------------------------------
 
     def save(self, path: str) -> None:

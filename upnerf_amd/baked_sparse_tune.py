@@ -249,9 +249,11 @@ class PoolTuner(BakedTuner):
 
 
 def distill(system, scene: BakedScene, path_or_img_ids, iters: int, batch: int, baked_step: float, seed: int = 0, lr: float = 1e-2,
-            img_id: Optional[int] = None, chunk: Optional[int] = None, tv: Tuple[float, float] = (0.0, 0.0), upsample_at=()):
+            img_id: Optional[int] = None, chunk: Optional[int] = None, tv: Tuple[float, float] = (0.0, 0.0), upsample_at=(),
+            prune_at=(), prune_weight: Optional[float] = None):
     """baked_tune.distill for a sparse scene, tuned in place on its pool (PoolTuner): the same cameras, targets, batches and
     return value (the tuned SPARSE scene -- with the same bricks unless upsample_at refines it pool to pool -- and the loss curve);
-    tv and upsample_at as there."""
+    tv, upsample_at, prune_at and prune_weight as there (a pruned pool loses the bricks that are left empty)."""
     _sparse(scene, "distill")
-    return _distill(PoolTuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk, tv, upsample_at)
+    return _distill(PoolTuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk, tv, upsample_at,
+                    prune_at, prune_weight)

@@ -241,6 +241,12 @@ class BakedTuner:
         reset (t = 0, zero moments)."""
         return type(self)(self.scene().upsample(), self.lr, **self._settings())
 
+    @torch.no_grad()
+    def pruned(self, rays: torch.Tensor, step: float, min_weight: Optional[float] = None, stop: float = 0.0) -> "BakedTuner":
+        """A fresh tuner of the same kind and settings on self.scene().prune(rays, step, min_weight, stop) -- without the points
+        that `rays` give less than `min_weight` (default: that no ray sees) -- the Adam state reset."""
+        return type(self)(self.scene().prune(rays, step, min_weight, stop), self.lr, **self._settings())
+
     @property
     def points(self) -> torch.Tensor:
         """The grid the marcher reads now: the master rgbs, or the records packed from the masters."""
@@ -309,7 +315,8 @@ def keyframe_rays(path, device) -> torch.Tensor:
 
 
 def distill(system, scene: BakedScene, path_or_img_ids, iters: int, batch: int, baked_step: float, seed: int = 0, lr: float = 1e-2,
-            img_id: Optional[int] = None, chunk: Optional[int] = None, tv: Tuple[float, float] = (0.0, 0.0), upsample_at: Sequence[int] = ()):
+            img_id: Optional[int] = None, chunk: Optional[int] = None, tv: Tuple[float, float] = (0.0, 0.0), upsample_at: Sequence[int] = (),
+            prune_at: Sequence[int] = (), prune_weight: Optional[float] = None):
     """Fit a dense baked scene to the field's own renders.  Cameras: the keyframes of a `novel_view.CameraPath`, or the refined
     training cameras `img_ids` (two at least).  The targets are rendered ONCE from the field by the static renderer
     (static_scene.render_static, through render_path) for those cameras' rays, all under the appearance of training image
@@ -317,12 +324,17 @@ def distill(system, scene: BakedScene, path_or_img_ids, iters: int, batch: int, 
     `iters` steps of BakedTuner(scene, lr) at sample spacing `baked_step`.  Returns (the tuned scene, the loss curve as a list of
     floats -- one host read, at the end).  tv = (tv_sigma, tv_colour): the tuner's total variation weights.  upsample_at: before
     each listed iteration (0-based) the tuner is replaced by tuner.upsampled() -- the returned scene has the final resolution; the
-    sample spacing stays `baked_step`."""
+    sample spacing stays `baked_step`.  prune_at: before each listed iteration the tuner is replaced by tuner.pruned(all the cameras'
+    rays, baked_step, prune_weight) -- what those rays give less than prune_weight (None: what none of them sees) leaves the scene
+    (DESIGN.md 2.39); an iteration listed in both prunes first, then upsamples.  With prune_at empty nothing changes and nothing is
+    launched."""
     _dense(scene, "distill")
-    return _distill(BakedTuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk, tv, upsample_at)
+    return _distill(BakedTuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk, tv, upsample_at,
+                    prune_at, prune_weight)
 
 
-def _distill(make_tuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk, tv=(0.0, 0.0), upsample_at=()):
+def _distill(make_tuner, system, scene, path_or_img_ids, iters, batch, baked_step, seed, lr, img_id, chunk, tv=(0.0, 0.0), upsample_at=(),
+             prune_at=(), prune_weight=None):
     """distill on a scene its caller has accepted, with the tuner make_tuner(scene, lr)."""
     from .novel_view import CameraPath, render_path
     if img_id is None:
@@ -334,6 +346,11 @@ def _distill(make_tuner, system, scene, path_or_img_ids, iters, batch, baked_ste
     upsample_at = sorted(int(i) for i in upsample_at)
     if any(not 0 <= i < iters for i in upsample_at) or len(set(upsample_at)) != len(upsample_at):
         raise ValueError(f"upsample_at lists distinct iterations in [0, {iters})")
+    prune_at = sorted(int(i) for i in prune_at)
+    if any(not 0 <= i < iters for i in prune_at) or len(set(prune_at)) != len(prune_at):
+        raise ValueError(f"prune_at lists distinct iterations in [0, {iters})")
+    if prune_weight is not None and float(prune_weight) != float(prune_weight):
+        raise ValueError("prune_weight is not a number")
     src = path_or_img_ids if isinstance(path_or_img_ids, CameraPath) else \
         CameraPath.through_images(system, list(path_or_img_ids), n_frames=len(list(path_or_img_ids)))
     K = src.key_c2w.shape[0]
@@ -347,6 +364,8 @@ def _distill(make_tuner, system, scene, path_or_img_ids, iters, batch, baked_ste
     gen = torch.Generator(device="cpu").manual_seed(int(seed))
     curve = []
     for it in range(iters):
+        if it in prune_at:
+            tuner = tuner.pruned(rays, baked_step, prune_weight)
         if it in upsample_at:
             tuner = tuner.upsampled()
         idx = torch.randint(0, rays.shape[0], (min(batch, rays.shape[0]),), generator=gen).to(dev)

@@ -35,6 +35,12 @@
 //                        layouts: two marches again, the second one meets every sample's four gradients with the slopes of
 //                        the blend in its cell; all sums in the ray's registers, the row written once: the same bits every run.
 //   upnerf_baked_project the tuned points back into the marcher's domain (sigma >= 0 and finite; degree 0: colours in [0, 1]).
+//   upnerf_baked_visibility  what a set of rays sees of a scene, both layouts and every degree in one instantiation
+//                        per layout: one more march with the forward's walk, ray and blend, the corners read through a reader that
+//                        returns (0, 0, 0, sigma) from a point of E bytes -- w depends on sigma alone.  The largest w of the ray's
+//                        samples in a cell is kept in a register and, when the ray leaves the cell, maxed into the cell's live
+//                        corners with atomicMax on the bits of a positive float: exact and commutative, the same bits every run.
+//   upnerf_baked_prune   a point whose visibility is below a weight becomes the all-zero record upnerf_baked_pack leaves.
 // All stores are ordinary vector stores and vector float atomics from plain C++.
 #include "common.cuh"
 #include "grid.cuh"
@@ -138,6 +144,18 @@ struct BakedCorner<0> {
   const f32x4* pts;
   __host__ __device__ __forceinline__ BakedCorner(const void* points, const float*, float) : pts((const f32x4*)points) {}
   __host__ __device__ __forceinline__ f32x4 operator()(int64_t p) const { return pts[p]; }
+};
+
+// the sigma of a point of any degree, colours zero: BAKED_SIGMA is no degree, and baked_blend<BAKED_SIGMA> clamps nothing, so its
+// colour blends are dead code and its sigma, e, alpha, w and T are the forward's of the scene's own degree
+#define BAKED_SIGMA (-1)
+template <>
+struct BakedCorner<BAKED_SIGMA> {
+  const uint8_t* bytes;
+  int64_t E;
+  __host__ __device__ __forceinline__ BakedCorner(const void* points, int E_, int sigma_offset)
+      : bytes((const uint8_t*)points + sigma_offset), E(E_) {}
+  __host__ __device__ __forceinline__ f32x4 operator()(int64_t p) const { return f32x4{0.0f, 0.0f, 0.0f, *(const float*)(bytes + p * E)}; }
 };
 
 // a ray as both marches read it: the 32-byte row o | d | near | far (16-byte aligned), whether it can hit at all (eight finite
@@ -282,6 +300,8 @@ __host__ __device__ __forceinline__ BakedBlend baked_blend(const BakedCorner<DEG
 #pragma unroll
   for (int j = 0; j < 8; ++j) b.live |= (c[j][3] != 0.0f ? 1u : 0u) << j;
   b.open = 7u;
+  // (DEG > 0, not DEG != 0: BAKED_SIGMA is -1 and, like degree 0, clamps nothing -- upnerf_baked_visibility rests on that)
+  static_assert(DEG >= BAKED_SIGMA && DEG <= 2, "a degree, or the sigma-only reader");
   if (DEG > 0) {  // an expansion is not held to [0, 1] as the colour head's sigmoid is
     b.open = 0u;
 #pragma unroll
@@ -597,6 +617,79 @@ __global__ __launch_bounds__(BAKED_THREADS) void baked_ray_bwd_kernel(BakedRayAr
   dst[1] = f32x4{out.v[4], out.v[5], out.v[6], out.v[7]};
 }
 
+// ---- what a set of rays sees: upnerf_baked_visibility (include/upnerf_hip.h states the definition).  What a launch
+// reads and writes, scalars first (BakedArgs says why); both layouts, the degree only through E and the sigma's byte offset.
+struct BakedVisArgs {
+  int R;
+  float step, stop;
+  int E, sigma_offset;
+  const void* points;
+  const int32_t* slots;  // NULL: a dense layout
+  const uint32_t* words;
+  const float* rays;
+  float* vis;
+};
+
+// the march of one ray row for its visibility (host and device: the host build is what tests/host/baked_vis_host.hip runs).  A
+// sample met with T > 0 gives m = fmaxf(w, 2^-126); the largest m of the consecutive samples in one cell (`cell` is the visit's
+// `base`, as in the backward) goes to record(p, m) for each live corner p of the cell when the ray leaves it.  Once T is exactly
+// zero nothing later can record and the ray ends.
+template <bool SPARSE, class Record>
+__host__ __device__ __forceinline__ void baked_visibility_ray(const BakedVisArgs& A, const BakedGrid& G, const OccDims& dm, const float* row,
+                                                              bool use_bits, Record&& record) {
+  const BakedRay ray(row, A.step);
+  if (!ray.ok) return;  // a miss
+  const BakedCorner<BAKED_SIGMA> pts(A.points, A.E, A.sigma_offset);
+  float T = 1.0f, m = 0.0f;
+  int64_t cell = -1;
+  unsigned live = 0u;
+  auto flush = [&]() __attribute__((always_inline)) {
+    const int64_t sy = SPARSE ? UPNERF_BRICK_POINTS : G.sy, sz = SPARSE ? UPNERF_BRICK_POINTS * UPNERF_BRICK_POINTS : G.sz;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (live >> j & 1u) record(cell + (j & 1) + (j >> 1 & 1) * sy + (j >> 2) * sz, m);
+  };
+  auto see = [&](const BakedSample& s, int64_t base, int64_t sy, int64_t sz) __attribute__((always_inline)) {
+    if (!(T > 0.0f)) return true;
+    const BakedBlend b = baked_blend<BAKED_SIGMA>(pts, s, base, sy, sz, ray.delta, T);
+    if (base != cell) {
+      if (cell >= 0) flush();
+      cell = base;
+      live = b.live;
+      m = 0.0f;
+    }
+    m = fmaxf(m, fmaxf(b.w, 1.17549435e-38f));  // (2^-126: a sample met with light left is seen, however small its weight)
+    T = b.Tn;
+    return A.stop > 0.0f && T < A.stop;
+  };
+  baked_walk<SPARSE>(A.words, A.slots, A.step, G, dm, ray, use_bits, see);
+  if (cell >= 0) flush();
+}
+
+template <bool SPARSE>
+__global__ __launch_bounds__(BAKED_THREADS) void baked_visibility_kernel(BakedVisArgs a, BakedGrid G, OccDims dm) {
+  const int r = blockIdx.x * BAKED_THREADS + threadIdx.x;
+  if (r >= a.R) return;
+  // every recorded value is a positive, finite float: its bits order as it does.  (The load first is a monotone race: a stale
+  // value is a smaller one and only lets an atomic through that changes nothing.)
+  auto record = [&](int64_t p, float m) __attribute__((always_inline)) {
+    if (!(a.vis[p] >= m)) atomicMax((unsigned*)(a.vis + p), __builtin_bit_cast(unsigned, m));
+  };
+  baked_visibility_ray<SPARSE>(a, G, dm, a.rays + (int64_t)r * 8, true, record);
+}
+
+// upnerf_baked_prune: one thread per point of E bytes
+__global__ __launch_bounds__(NTHREADS) void baked_prune_kernel(upnerf_baked_prune_args a) {
+  const int64_t n = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
+  if (n >= a.n) return;
+  const bool keep = a.vis[n] >= a.min_weight;
+  if (!keep) {
+    u32x4* rec = (u32x4*)(a.points + n * a.E);
+    for (int q = 0; q < a.E / 16; ++q) rec[q] = u32x4{0u, 0u, 0u, 0u};
+  }
+  if (a.kept) a.kept[n] = keep ? 1 : 0;
+}
+
 // upnerf_baked_project: the point of a tuned scene back into the set the marcher is defined on
 __global__ __launch_bounds__(NTHREADS) void baked_project_kernel(upnerf_baked_project_args a) {
   const int64_t n = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
@@ -781,6 +874,34 @@ extern "C" int upnerf_baked_ray_bwd(const upnerf_baked_ray_bwd_args* a, void* st
     else
       hipLaunchKernelGGL((baked_ray_bwd_kernel<decltype(deg)::value, false>), baked_blocks(a->R), dim3(BAKED_THREADS), 0, (hipStream_t)stream, A, G, dm);
   });
+  return (int)hipGetLastError();
+}
+
+extern "C" int upnerf_baked_visibility(const upnerf_baked_visibility_args* a, void* stream) {
+  BakedGrid G;
+  OccDims dm;
+  if (!a || !a->vis || (a->E != 16 && a->E != 32 && a->E != 64)) return UPNERF_EINVAL;
+  if (a->sigma_offset < 0 || (a->sigma_offset & 3) || a->sigma_offset > a->E - 4) return UPNERF_EINVAL;
+  // the forward's refusals, on the forward's own struct (its background is not this entry point's: zero)
+  upnerf_baked_sparse_render_args f = {};
+  f.Cx = a->Cx, f.Cy = a->Cy, f.Cz = a->Cz, f.R = a->R;
+  for (int k = 0; k < 3; ++k) f.lo[k] = a->lo[k], f.hi[k] = a->hi[k];
+  f.step = a->step, f.stop = a->stop, f.words = a->words, f.rays = a->rays;
+  if (!baked_lattice(&f, a->points, (size_t)a->E, &G, &dm)) return UPNERF_EINVAL;
+  const BakedVisArgs A = {a->R, a->step, a->stop, a->E, a->sigma_offset, a->points, a->slots, a->words, a->rays, a->vis};
+  if (a->slots)
+    hipLaunchKernelGGL(baked_visibility_kernel<true>, baked_blocks(a->R), dim3(BAKED_THREADS), 0, (hipStream_t)stream, A, G, dm);
+  else
+    hipLaunchKernelGGL(baked_visibility_kernel<false>, baked_blocks(a->R), dim3(BAKED_THREADS), 0, (hipStream_t)stream, A, G, dm);
+  return (int)hipGetLastError();
+}
+
+extern "C" int upnerf_baked_prune(const upnerf_baked_prune_args* a, void* stream) {
+  if (!a || a->n <= 0 || (a->E != 16 && a->E != 32 && a->E != 64) || !a->vis || !a->points || !baked_aligned16(a->points)) return UPNERF_EINVAL;
+  if (a->min_weight != a->min_weight) return UPNERF_EINVAL;
+  const int64_t blocks = (a->n + NTHREADS - 1) / NTHREADS;
+  if (blocks > 0x7fffffff) return UPNERF_EUNSUP;
+  hipLaunchKernelGGL(baked_prune_kernel, dim3((unsigned)blocks), dim3(NTHREADS), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }
 

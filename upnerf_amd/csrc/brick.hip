@@ -9,6 +9,7 @@
 //   upnerf_brick_columns  the rays that make the field kernels evaluate the pool's lines (upnerf_grid_columns for a brick pool).
 //   upnerf_brick_face_sum in place on a pool-shaped fp32 array, every copy of a point on a face that bricks share becomes the sum over
 //                         the copies, in ascending brick index: one launch collects into the first copy, one spreads it.
+//   upnerf_brick_face_max the same kernel with fmaxf for +: what a pool-shaped visibility needs.
 // Everything is streaming and memory-bound; no LDS beyond the scan, no atomics.  All stores are ordinary vector stores from plain C++.
 #include "common.cuh"
 #include "grid.cuh"
@@ -190,10 +191,17 @@ __device__ __forceinline__ BrickHolders brick_holders(int b, int l, int B) {
   return h;
 }
 
-// COLLECT: the copy in the first occupied holder becomes the sum over the occupied holders, in ascending brick index; the other
-// copies are read and not written.  !COLLECT (the launch after it): the other copies become the first.  One thread per float of a
-// face point of a slot; a point with one copy, or beyond the grid, is left alone.
-template <bool COLLECT>
+struct BrickAdd {
+  __device__ __forceinline__ float operator()(float a, float b) const { return a + b; }
+};
+struct BrickMax {
+  __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); }
+};
+
+// COLLECT: the copy in the first occupied holder becomes the sum (Op: BrickAdd; the maximum with BrickMax) over the occupied
+// holders, in ascending brick index; the other copies are read and not written.  !COLLECT (the launch after it): the other copies
+// become the first.  One thread per float of a face point of a slot; a point with one copy, or beyond the grid, is left alone.
+template <bool COLLECT, class Op>
 __global__ __launch_bounds__(NTHREADS) void brick_face_sum_kernel(upnerf_brick_face_sum_args a, OccDims d, int64_t n_threads) {
   const int64_t id = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
   if (id >= n_threads) return;
@@ -226,7 +234,7 @@ __global__ __launch_bounds__(NTHREADS) void brick_face_sum_kernel(upnerf_brick_f
             return;
           }
         } else {
-          sum += a.data[at];
+          sum = Op()(sum, a.data[at]);
         }
         ++m;
       }
@@ -316,14 +324,23 @@ extern "C" int upnerf_brick_columns(const upnerf_brick_columns_args* a, void* st
   return (int)hipGetLastError();
 }
 
-extern "C" int upnerf_brick_face_sum(const upnerf_brick_face_sum_args* a, void* stream) {
+namespace {
+
+template <class Op>
+int brick_face_reduce(const upnerf_brick_face_sum_args* a, void* stream) {
   OccDims d;
   if (!a || !occ_dims(a->Cx, a->Cy, a->Cz, &d) || a->F < 1) return UPNERF_EINVAL;
   if (a->n_bricks < 1 || a->n_bricks > d.bricks || !a->slots || !a->bricks || !a->data || ((uintptr_t)a->data & 3) != 0) return UPNERF_EINVAL;
   const int64_t n = (int64_t)a->n_bricks * BRICK_FACE * a->F;
   if (ceil_div64(n, NTHREADS) > INT_MAX) return UPNERF_EUNSUP;
   const dim3 grid((unsigned)ceil_div64(n, NTHREADS)), block(NTHREADS);
-  hipLaunchKernelGGL(brick_face_sum_kernel<true>, grid, block, 0, (hipStream_t)stream, *a, d, n);
-  hipLaunchKernelGGL(brick_face_sum_kernel<false>, grid, block, 0, (hipStream_t)stream, *a, d, n);
+  hipLaunchKernelGGL((brick_face_sum_kernel<true, Op>), grid, block, 0, (hipStream_t)stream, *a, d, n);
+  hipLaunchKernelGGL((brick_face_sum_kernel<false, Op>), grid, block, 0, (hipStream_t)stream, *a, d, n);
   return (int)hipGetLastError();
 }
+
+}  // namespace
+
+extern "C" int upnerf_brick_face_sum(const upnerf_brick_face_sum_args* a, void* stream) { return brick_face_reduce<BrickAdd>(a, stream); }
+
+extern "C" int upnerf_brick_face_max(const upnerf_brick_face_sum_args* a, void* stream) { return brick_face_reduce<BrickMax>(a, stream); }
