@@ -48,7 +48,7 @@ from .occupancy import OccupancyGrid
 from .ops import TIMER
 from .static_scene import box, c_float3, field_of, refined_training_poses, require_cuda
 
-__all__ = ["BakedScene", "field_colour", "pool_colour", "sphere_directions", "sh_basis", "sh_weights", "save_bricks", "load_bricks", "TINY"]
+__all__ = ["BakedScene", "Layout", "field_colour", "pool_colour", "sphere_directions", "sh_basis", "sh_weights", "save_bricks", "load_bricks", "TINY"]
 
 TINY = float(np.float32(2.0 ** -149))  # the smallest positive fp32: the level at which the kept sigmas are packed into bits
 
@@ -196,6 +196,73 @@ def _aligned_copy(t: torch.Tensor, size: int) -> torch.Tensor:
     return t if t.data_ptr() % size == 0 else _aligned(n, size, t.device)[:n].view(t.dtype).view(t.shape).copy_(t)
 
 
+class Layout:
+    """What the marcher needs beside a point array, dense grid or brick pool, and everything that follows from it: the (frozen)
+    `occupancy`, the `bounds`, the `degree`, and of a pool its table `slots` [Bz, By, Bx] and `bricks` [n_bricks] (both None for a
+    dense grid).  Derived once: `resolution` (the grid's points per axis), `sparse`, `shape`, `point_bytes`, `sigma_at`, `nb` and
+    `param_shapes`.  Immutable; no device work, so CPU tensors do for its arithmetic."""
+
+    __slots__ = ("occupancy", "bounds", "degree", "slots", "bricks", "resolution", "sparse", "shape", "point_bytes", "sigma_at", "nb",
+                 "param_shapes", "_spare")
+
+    def __init__(self, occupancy, bounds, degree: int, slots: Optional[torch.Tensor] = None, bricks: Optional[torch.Tensor] = None):
+        if (slots is None) != (bricks is None):
+            raise ValueError("a pool's table is both slots and bricks; a dense grid has neither")
+        sparse, P, nb = slots is not None, _lib.BRICK_POINTS, (int(degree) + 1) ** 2
+        resolution = tuple(c + 1 for c in occupancy.dims)
+        shape = (bricks.numel(), P, P, P) if sparse else resolution[::-1]  # the points' leading shape: bricks, or (Nz, Ny, Nx)
+        E = POINT_BYTES.get(degree)
+        # the fp32 parameters: (rgbs,) at degree 0, else (coef, sigma)
+        param_shapes = (shape + (4,),) if degree == 0 else (shape + (3, nb), shape)
+        # with no brick at all the marcher is still given an address: one spare aligned point (never read)
+        spare = _aligned(E, E, slots.device) if sparse and E and shape[0] == 0 else None
+        values = (occupancy, bounds, int(degree), slots, bricks, resolution, sparse, shape, E, SIGMA_AT.get(degree), nb, param_shapes, spare)
+        for name, value in zip(self.__slots__, values):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Layout is immutable")
+
+    def zeros(self, device) -> tuple:
+        """Zeroed gradients of the parameter shapes."""
+        return tuple(torch.zeros(shape, device=device) for shape in self.param_shapes)
+
+    @staticmethod
+    def empty_pool(degree: int, device) -> torch.Tensor:
+        """The pool of a degree with no brick: [0, 9, 9, 9, 4] fp32, or [0, 9, 9, 9, 32 | 64] uint8."""
+        P = _lib.BRICK_POINTS
+        if degree == 0:
+            return torch.empty((0, P, P, P, 4), device=device, dtype=torch.float32)
+        return torch.empty((0, P, P, P, POINT_BYTES[degree]), device=device, dtype=torch.uint8)
+
+    def marched(self, points: torch.Tensor) -> torch.Tensor:
+        """The tensor whose address the marcher is given for `points`: `points`, or the spare point of a pool with no brick."""
+        return points if self._spare is None or points.numel() else self._spare
+
+    def pointers(self, points: torch.Tensor) -> tuple:
+        """(the points' address, the slots' or None): the pair the C structs take."""
+        return ptr(self.marched(points)), ptr(self.slots)
+
+
+DENSE_REFUSAL = ("a dense baked scene has no brick pool to tune: use baked_tune (scene.tune), or scene.sparsify() first")
+
+
+def a_scene(scene, what: str) -> "BakedScene":
+    if not isinstance(scene, BakedScene):
+        raise ValueError(f"{what} takes a baked.BakedScene")
+    return scene
+
+
+def pool_layout(of) -> Layout:
+    """The Layout of a brick pool: `of` itself, or that of a sparse BakedScene or of a baked_sparse_tune.PoolParams."""
+    if isinstance(of, BakedScene) and not of.sparse:
+        raise ValueError(DENSE_REFUSAL)
+    layout = of if isinstance(of, Layout) else getattr(of, "layout", None)
+    if not isinstance(layout, Layout) or not layout.sparse:
+        raise ValueError("the layout is a brick pool's baked.Layout, a sparse baked.BakedScene or a PoolParams")
+    return layout
+
+
 def brick_table(words: torch.Tensor, dims: Sequence[int]):
     """(slots int32 [Bz, By, Bx], bricks int32 [n_bricks], n_bricks) of the brick bits of an occupancy grid's words
     (upnerf_brick_table).  One host read: the count."""
@@ -251,6 +318,32 @@ def brick_words(pool_bytes: torch.Tensor, slots: torch.Tensor, n_bricks: int, re
                           pool=ptr(pool_bytes) if n_bricks else None, words=ptr(words))
     check(TIMER.run("brick_occ", lambda: lib.upnerf_brick_occ(C.byref(a), stream()), units=words.numel()), "upnerf_brick_occ")
     return words
+
+
+def brick_face(op: str, t: torch.Tensor, layout: Layout, what: str) -> torch.Tensor:
+    """upnerf_brick_face_<op> (sum | max) in place on the pool-shaped fp32 tensor `t` [n_bricks, 9, 9, 9, ...] (any trailing shape:
+    F floats per point): every copy of a grid point that bricks share becomes the sum (in ascending brick order) or the maximum
+    over its copies.  With no brick nothing is shared and nothing is launched.  Returns `t`."""
+    require_cuda(what, t)
+    n, P = layout.shape[:2]
+    if t.dtype != torch.float32 or t.dim() < 4 or tuple(t.shape[:4]) != layout.shape or not t.is_contiguous():
+        raise ValueError(f"a pool-shaped tensor is contiguous fp32 [{n}, {P}, {P}, {P}, ...]")
+    if n == 0:
+        return t
+    Cx, Cy, Cz = layout.occupancy.dims
+    F = t.numel() // (n * P ** 3)
+    a = _lib.BrickFaceSumArgs(Cx=Cx, Cy=Cy, Cz=Cz, n_bricks=n, F=F, slots=ptr(layout.slots), bricks=ptr(layout.bricks), data=ptr(t))
+    fn = getattr(lib, "upnerf_brick_face_" + op)
+    check(TIMER.run("brick_face_" + op, lambda: fn(C.byref(a), stream()), units=n * 386 * F), "upnerf_brick_face_" + op)
+    return t
+
+
+def face_sum(t: torch.Tensor, scene) -> torch.Tensor:
+    """upnerf_brick_face_sum in place on the pool-shaped fp32 tensor `t` of `scene` (a pool's Layout, a sparse BakedScene or a
+    PoolParams): every copy of a shared grid point becomes the sum over its copies, in ascending brick order.  Returns `t`."""
+    return brick_face("sum", t, pool_layout(scene), "baked_sparse_tune.face_sum")
+
+
 _Y = (0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396)
 
 
@@ -336,6 +429,25 @@ def _render_args(rays, step, background, stop):
     return step, background, stop
 
 
+def pack_rgbs(sigma: torch.Tensor, rgb: Optional[torch.Tensor], level: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The points [shape of sigma, 4] fp32 of contiguous fp32 sigmas and colours [shape of sigma, 3] (None: black), pruned at
+    `level` (upnerf_baked_pack), written to `out` where given: a pool wants its own aligned store."""
+    if out is None:
+        out = torch.empty(tuple(sigma.shape) + (4,), device=sigma.device, dtype=torch.float32)
+    a = _lib.BakedPackArgs(n=sigma.numel(), level=level, sigma=ptr(sigma), rgb=ptr(rgb), rgbs=ptr(out), kept=None)
+    check(TIMER.run("baked_pack", lambda: lib.upnerf_baked_pack(C.byref(a), stream()), units=sigma.numel()), "upnerf_baked_pack")
+    return out
+
+
+def _upstream(R: int, g_rgb, g_depth, g_opacity) -> None:
+    """The upstream gradients of R rays, as every backward wrapper takes them."""
+    if g_rgb.dtype != torch.float32 or tuple(g_rgb.shape) != (R, 3):
+        raise ValueError("g_rgb is a fp32 tensor [R, 3]")
+    for g in (g_depth, g_opacity):
+        if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != (R,)):
+            raise ValueError("g_depth and g_opacity are fp32 tensors [R] or None")
+
+
 def _common(occupancy, bounds, rays, step, background, stop):
     Cx, Cy, Cz = occupancy.dims
     lo, hi = bounds
@@ -348,16 +460,17 @@ def _rays16(rays: torch.Tensor) -> torch.Tensor:
     return rays.clone() if rays.data_ptr() % 16 else rays
 
 
-def march(points: torch.Tensor, degree: int, slots: Optional[torch.Tensor], occupancy, bounds, rays, step, background, stop, rgb, depth, opacity) -> None:
+def march(points: torch.Tensor, layout: Layout, rays, step, background, stop, rgb, depth, opacity) -> None:
     """One launch of the marcher on checked arguments (_render_args, _rays16) into rgb [>= R, 3], depth and opacity [>= R]: through
-    the pool `points` where `slots` is given, else on the records `points` at degree 1 | 2 and on rgbs at degree 0."""
-    common = dict(_common(occupancy, bounds, rays, step, background, stop), rgb=ptr(rgb), depth=ptr(depth), opacity=ptr(opacity))
-    if slots is not None:
-        name, a = "baked_sparse_render", _lib.BakedSparseRenderArgs(degree=degree, pool=ptr(points), slots=ptr(slots), **common)
-    elif degree:
-        name, a = "baked_sh_render", _lib.BakedShRenderArgs(degree=degree, records=ptr(points), **common)
+    the pool `points` of a sparse layout, else on the records `points` at degree 1 | 2 and on rgbs at degree 0."""
+    common = dict(_common(layout.occupancy, layout.bounds, rays, step, background, stop), rgb=ptr(rgb), depth=ptr(depth), opacity=ptr(opacity))
+    points, slots = layout.pointers(points)
+    if layout.sparse:
+        name, a = "baked_sparse_render", _lib.BakedSparseRenderArgs(degree=layout.degree, pool=points, slots=slots, **common)
+    elif layout.degree:
+        name, a = "baked_sh_render", _lib.BakedShRenderArgs(degree=layout.degree, records=points, **common)
     else:
-        name, a = "baked_render", _lib.BakedRenderArgs(rgbs=ptr(points), **common)
+        name, a = "baked_render", _lib.BakedRenderArgs(rgbs=points, **common)
     fn = getattr(lib, "upnerf_" + name)
     check(TIMER.run(name, lambda: fn(C.byref(a), stream()), units=rays.shape[0]), "upnerf_" + name)
 
@@ -370,6 +483,7 @@ class BakedScene:
     sh_degree = 0
     records = None
     pool = slots = bricks = None  # a sparse scene's (sparsify, from_bricks, build(sparse=True)): see _sparse
+    layout = None  # the scene's Layout: what the marcher, the tuners and the regularisers take beside a point array
     env = None  # a baked_env.Environment behind the march (with_environment, build(env_size=...)), or None: the flat `background`
 
     def with_environment(self, env) -> "BakedScene":
@@ -382,14 +496,38 @@ class BakedScene:
         other.env = env
         return other
 
+    def _set(self, points: torch.Tensor, bounds, level: float, degree: int, slots=None, bricks=None, resolution=None) -> "BakedScene":
+        """What every constructor ends in, on checked arguments: `points` are rgbs (degree 0) or records of a dense scene, or with
+        the table `slots` and `bricks` the pool of a grid of `resolution` points.  The bits are the kept sigmas': of a dense scene
+        from its sigmas (upnerf_occ_build), of a sparse one from the pool alone (upnerf_brick_occ)."""
+        sparse = slots is not None
+        self.sh_degree = int(degree)
+        self.rgbs = points if not sparse and degree == 0 else None
+        self.records = points if not sparse and degree else None
+        self.pool, self.slots, self.bricks = (points, slots, bricks) if sparse else (None, None, None)
+        self.bounds = box(bounds, strict=True)
+        self.level = float(level)
+        E, at = POINT_BYTES[self.sh_degree], SIGMA_AT[self.sh_degree]
+        if sparse:
+            Nx, Ny, Nz = (int(n) for n in resolution)
+            words = brick_words(points, slots, bricks.numel(), (Nx, Ny, Nz), E, at)
+            occupancy = OccupancyGrid(words, self.bounds, (Nx - 1, Ny - 1, Nz - 1))
+        else:
+            sigma = points[..., 3] if degree == 0 else points[..., at:at + 4].contiguous().view(torch.float32).squeeze(-1)
+            occupancy = OccupancyGrid.from_density(sigma.contiguous(), self.bounds, level=TINY, dilate=0)
+        self.occupancy = occupancy
+        self.layout = Layout(occupancy, self.bounds, self.sh_degree, slots, bricks)
+        return self
+
+    @classmethod
+    def _new(cls, *args, **kwargs) -> "BakedScene":
+        return cls.__new__(cls)._set(*args, **kwargs)
+
     def __init__(self, rgbs: torch.Tensor, bounds, level: float):
         require_cuda("BakedScene", rgbs)
         if rgbs.dtype != torch.float32 or rgbs.dim() != 4 or rgbs.shape[3] != 4 or not rgbs.is_contiguous():
             raise ValueError("rgbs is a contiguous fp32 tensor [Nz, Ny, Nx, 4]")
-        self.rgbs = rgbs
-        self.bounds = box(bounds, strict=True)
-        self.level = float(level)
-        self.occupancy = OccupancyGrid.from_density(rgbs[..., 3].contiguous(), self.bounds, level=TINY, dilate=0)
+        self._set(rgbs, bounds, level, 0)
 
     @classmethod
     def from_records(cls, records: torch.Tensor, bounds, level: float, sh_degree: int) -> "BakedScene":
@@ -400,14 +538,15 @@ class BakedScene:
         size = RECORD_BYTES[degree]
         if records.dtype != torch.uint8 or records.dim() != 4 or records.shape[3] != size or min(records.shape[:3]) < 2:
             raise ValueError(f"records is a uint8 tensor [Nz, Ny, Nx, {size}] with two points per axis at least")
-        records = _aligned_copy(records.contiguous(), size)  # (a record is aligned to its own size)
-        self = cls.__new__(cls)
-        self.rgbs, self.records, self.sh_degree = None, records, degree
-        self.bounds = box(bounds, strict=True)
-        self.level = float(level)
-        sigma = records[..., SIGMA_BYTE[degree]:SIGMA_BYTE[degree] + 4].contiguous().view(torch.float32).squeeze(-1)
-        self.occupancy = OccupancyGrid.from_density(sigma.contiguous(), self.bounds, level=TINY, dilate=0)
-        return self
+        return cls._new(_aligned_copy(records.contiguous(), size), bounds, level, degree)  # (a record is aligned to its own size)
+
+    @classmethod
+    def from_points(cls, points: torch.Tensor, bounds, level: float, degree: int) -> "BakedScene":
+        """The dense scene of a point array [Nz, Ny, Nx, ...] of `degree`, given as bytes or as fp32: rgbs at degree 0 (the scene
+        of BakedScene(rgbs, ...)), else records (from_records), at an address aligned to a point as from_records aligns."""
+        if degree:
+            return cls.from_records(points.view(torch.uint8), bounds, level, degree)
+        return cls(_aligned_copy(points.view(torch.float32), POINT_BYTES[0]), bounds, level)
 
     # ---- sparse scenes: a pool of the occupied bricks (include/upnerf_hip.h states the layout; DESIGN.md 2.33) -------------------
 
@@ -416,19 +555,7 @@ class BakedScene:
                 degree: int) -> "BakedScene":
         """The sparse scene of a pool [n_bricks, 9, 9, 9, 4] fp32 (degree 0) or [n_bricks, 9, 9, 9, 32 | 64] uint8 aligned to its
         point size, and its table.  Every sparse scene gets its bits here, from the pool alone (upnerf_brick_occ)."""
-        self = cls.__new__(cls)
-        self.rgbs, self.records, self.sh_degree = None, None, int(degree)
-        self.pool, self.slots, self.bricks = pool, slots, bricks
-        self._resolution = tuple(int(n) for n in resolution)
-        self.bounds = box(bounds, strict=True)
-        self.level = float(level)
-        E = POINT_BYTES[self.sh_degree]
-        # the address the marcher is given: the pool's, or with no brick at all one spare aligned point (never read)
-        self._pool_bytes = pool.view(torch.uint8).view(-1) if bricks.numel() else _aligned(E, E, slots.device)
-        Nx, Ny, Nz = self._resolution
-        words = brick_words(self._pool_bytes, slots, bricks.numel(), self._resolution, E, SIGMA_AT[self.sh_degree])
-        self.occupancy = OccupancyGrid(words, self.bounds, (Nx - 1, Ny - 1, Nz - 1))
-        return self
+        return cls._new(pool, slots=slots, bricks=bricks, resolution=resolution, bounds=bounds, level=level, degree=degree)
 
     @torch.no_grad()
     def sparsify(self) -> "BakedScene":
@@ -446,10 +573,8 @@ class BakedScene:
         """The dense scene of a sparse one (upnerf_brick_scatter into a zeroed grid)."""
         if not self.sparse:
             return self
-        grid = brick_scatter(self.pool, self.bricks, self._resolution)
-        if self.sh_degree:
-            return self.from_records(grid, self.bounds, self.level, self.sh_degree).with_environment(self.env)
-        return type(self)(grid, self.bounds, self.level).with_environment(self.env)
+        grid = brick_scatter(self.pool, self.bricks, self.resolution)
+        return self.from_points(grid, self.bounds, self.level, self.sh_degree).with_environment(self.env)
 
     @classmethod
     def from_bricks(cls, pool: torch.Tensor, bricks: torch.Tensor, resolution: Sequence[int], bounds, level: float,
@@ -501,10 +626,8 @@ class BakedScene:
         level = _level(level)
         sigma = sigma.detach().contiguous()
         rgb = rgb.detach().contiguous() if rgb is not None else None
-        rgbs = torch.empty(tuple(sigma.shape) + (4,), device=sigma.device, dtype=torch.float32)
-        a = _lib.BakedPackArgs(n=sigma.numel(), level=level, sigma=ptr(sigma), rgb=ptr(rgb), rgbs=ptr(rgbs), kept=None)
-        check(TIMER.run("baked_pack", lambda: lib.upnerf_baked_pack(C.byref(a), stream()), units=sigma.numel()), "upnerf_baked_pack")
-        return cls(rgbs, bounds, level).sparsify() if sparse else cls(rgbs, bounds, level)
+        scene = cls(pack_rgbs(sigma, rgb, level), bounds, level)
+        return scene.sparsify() if sparse else scene
 
     @classmethod
     @torch.no_grad()
@@ -626,12 +749,10 @@ class BakedScene:
         P, dev = _lib.BRICK_POINTS, pool_sigma.device
         E = POINT_BYTES[degree]
         if n == 0:
-            pool = torch.empty((0, P, P, P, 4) if degree == 0 else (0, P, P, P, E), device=dev, dtype=torch.float32 if degree == 0 else torch.uint8)
+            pool = Layout.empty_pool(degree, dev)
         elif degree == 0:
             rgb = pool_colour(system, bounds, res, bricks, view_dir, img_id=img_id, rows=rows, field=field, chunk=chunk)
-            pool = _aligned(n * P ** 3 * E, E, dev)[:n * P ** 3 * E].view(n, P, P, P, E).view(torch.float32)
-            a = _lib.BakedPackArgs(n=pool_sigma.numel(), level=level, sigma=ptr(pool_sigma), rgb=ptr(rgb), rgbs=ptr(pool), kept=None)
-            check(TIMER.run("baked_pack", lambda: lib.upnerf_baked_pack(C.byref(a), stream()), units=pool_sigma.numel()), "upnerf_baked_pack")
+            pool = pack_rgbs(pool_sigma, rgb, level, out=_aligned(n * P ** 3 * E, E, dev)[:n * P ** 3 * E].view(n, P, P, P, E).view(torch.float32))
         else:
             colour = lambda k: pool_colour(system, bounds, res, bricks, dirs[k], img_id=img_id, rows=rows, field=field, chunk=chunk)
             pool = cls._project_records(pool_sigma, colour, dirs, level, degree)
@@ -658,8 +779,7 @@ class BakedScene:
             t = out[k]
             if t.dtype != torch.float32 or t.shape[0] < R or tuple(t.shape[1:]) != shape or t.device != dev:
                 raise ValueError("the outputs are fp32 [>= R, 3], [>= R] and [>= R] on the rays' device")
-        march(self._pool_bytes if self.sparse else self.grid, self.sh_degree, self.slots, self.occupancy, self.bounds, rays, step,
-              background if self.env is None else 0.0, stop, out["rgb"], out["depth"], out["opacity"])
+        march(self.grid, self.layout, rays, step, background if self.env is None else 0.0, stop, out["rgb"], out["depth"], out["opacity"])
         if self.env is not None:
             self.env.composite_(rays, out["rgb"], out["opacity"])
         return {k: out[k][:R] for k in ("rgb", "depth", "opacity")}
@@ -704,7 +824,7 @@ class BakedScene:
         rebuilt on load.  A sparse scene: pool, bricks, resolution, degree, bounds, level (save_bricks)."""
         env = self.env.env.cpu().numpy() if self.env is not None else None  # (a scene without one writes the file it always wrote)
         if self.sparse:
-            save_bricks(path, self.pool.detach().cpu().numpy(), self.bricks.cpu().numpy(), self._resolution, self.bounds, self.level,
+            save_bricks(path, self.pool.detach().cpu().numpy(), self.bricks.cpu().numpy(), self.resolution, self.bounds, self.level,
                         sh_degree=self.sh_degree, env=env)
         elif self.sh_degree:
             save_arrays(path, self.records.detach().cpu().numpy(), self.bounds, self.level, sh_degree=self.sh_degree, env=env)
@@ -769,11 +889,13 @@ class BakedScene:
         return self.occupancy.words.device
 
     @property
+    def points(self) -> torch.Tensor:
+        """The tensor whose address the marcher is given: `grid`, or of a sparse scene with no brick its layout's spare point."""
+        return self.layout.marched(self.grid)
+
+    @property
     def resolution(self):
-        if self.sparse:
-            return self._resolution
-        Nz, Ny, Nx, _ = self.grid.shape
-        return Nx, Ny, Nz
+        return self.layout.resolution
 
     @property
     def nbytes(self) -> int:

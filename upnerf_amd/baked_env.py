@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream
+from .baked import _appearance
 from .ops import TIMER
 from .static_scene import box, c_float3, require_cuda
 
@@ -134,7 +135,6 @@ class Environment:
         the training images) -- under the appearance of training image `img_id` (or `rows`, a row of the caller's own: the
         arguments of BakedScene.build), val.chunk_size rays at a time, then upnerf_env_seam.  `field` names the network whose
         appearance table the row is checked against and whose colour is taken."""
-        from .baked import _appearance
         from .static_scene import field_of, near_far, render_static, static_keys
         model, dev = field_of(system, field, "Environment.build")
         E = _size(E)

@@ -21,17 +21,11 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream
-from .baked import BakedScene, _common, _rays16, _render_args
+from .baked import BakedScene, _common, _rays16, _render_args, _upstream, a_scene
 from .ops import TIMER
 from .static_scene import require_cuda
 
 __all__ = ["ray_backward", "render", "BakedLocaliser", "localise", "pixel_directions"]
-
-
-def _scene(scene, what: str) -> BakedScene:
-    if not isinstance(scene, BakedScene):
-        raise ValueError(f"{what} takes a baked.BakedScene")
-    return scene
 
 
 def ray_backward(scene: BakedScene, rays: torch.Tensor, step: float, background: float, stop: float, g_rgb: torch.Tensor,
@@ -39,16 +33,12 @@ def ray_backward(scene: BakedScene, rays: torch.Tensor, step: float, background:
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """upnerf_baked_ray_bwd, called directly: the gradient [R, 8] of a loss with the upstream gradients g_rgb [R, 3], g_depth
     [R] | None and g_opacity [R] | None with respect to the rows of `rays` [R, 8], WRITTEN into `out` (allocated when None)."""
-    _scene(scene, "baked_pose.ray_backward")
+    a_scene(scene, "baked_pose.ray_backward")
     require_cuda("baked_pose.ray_backward", rays, g_rgb)
     step, background, stop = _render_args(rays, step, background, stop)
     rays = _rays16(rays)
     R, dev = rays.shape[0], rays.device
-    if g_rgb.dtype != torch.float32 or tuple(g_rgb.shape) != (R, 3):
-        raise ValueError("g_rgb is a fp32 tensor [R, 3]")
-    for g in (g_depth, g_opacity):
-        if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != (R,)):
-            raise ValueError("g_depth and g_opacity are fp32 tensors [R] or None")
+    _upstream(R, g_rgb, g_depth, g_opacity)
     if out is None:
         out = torch.empty(R, 8, device=dev)
     if out.dtype != torch.float32 or tuple(out.shape) != (R, 8) or not out.is_contiguous() or out.device != dev:
@@ -56,8 +46,8 @@ def ray_backward(scene: BakedScene, rays: torch.Tensor, step: float, background:
     g_rgb = g_rgb.contiguous()  # (kept alive until the launch is enqueued)
     g_depth = g_depth.contiguous() if g_depth is not None else None
     g_opacity = g_opacity.contiguous() if g_opacity is not None else None
-    a = _lib.BakedRayBwdArgs(degree=scene.sh_degree, points=ptr(scene._pool_bytes if scene.sparse else scene.grid),
-                             slots=ptr(scene.slots) if scene.sparse else None, g_rgb=ptr(g_rgb), g_depth=ptr(g_depth),
+    points, slots = scene.layout.pointers(scene.points)
+    a = _lib.BakedRayBwdArgs(degree=scene.sh_degree, points=points, slots=slots, g_rgb=ptr(g_rgb), g_depth=ptr(g_depth),
                              g_opacity=ptr(g_opacity), g_rays=ptr(out), **_common(scene.occupancy, scene.bounds, rays, step, background, stop))
     check(TIMER.run("baked_ray_bwd", lambda: lib.upnerf_baked_ray_bwd(C.byref(a), stream()), units=R), "upnerf_baked_ray_bwd")
     return out
@@ -86,7 +76,7 @@ def render(scene: BakedScene, rays: torch.Tensor, step: float, background: float
     forward the marcher of the scene's layout and degree (BakedScene.render, the same bits), backward upnerf_baked_ray_bwd.
     With scene.env set: the march at background 0 (`background` is not looked at), then the environment's composite through its
     own autograd function (upnerf_env_composite / _bwd) -- the rays receive the gradient of both, the sky's included."""
-    _scene(scene, "baked_pose.render")
+    a_scene(scene, "baked_pose.render")
     require_cuda("baked_pose.render", rays)
     step, background, stop = _render_args(rays, step, background, stop)
     if scene.env is None:
@@ -112,7 +102,7 @@ class BakedLocaliser:
 
     def __init__(self, scene: BakedScene, targets: torch.Tensor, K, c2w_init: torch.Tensor, near_far, lr: float = 1e-2,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, background: float = 0.0, stop: float = 0.0):
-        _scene(scene, "BakedLocaliser")
+        a_scene(scene, "BakedLocaliser")
         require_cuda("BakedLocaliser", targets, c2w_init)
         if targets.dtype != torch.float32 or targets.dim() != 4 or targets.shape[3] != 3 or targets.shape[0] < 1:
             raise ValueError("targets is a fp32 tensor [N, H, W, 3] with N >= 1")

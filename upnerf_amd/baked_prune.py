@@ -21,18 +21,13 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream
-from .baked import POINT_BYTES, SIGMA_AT, BakedScene, _aligned, _aligned_copy, _common, _rays16, _render_args, brick_table, brick_words
+from .baked import BakedScene, _aligned, _aligned_copy, _common, _rays16, _render_args, a_scene, brick_face, brick_table, brick_words
 from .ops import TIMER
 from .static_scene import require_cuda
 
 __all__ = ["visibility", "march_visibility", "prune", "prune_points", "face_max", "TINY_NORMAL"]
 
 TINY_NORMAL = float(np.float32(2.0 ** -126))  # the smallest positive normal fp32: what a sample met with light left records at least
-
-
-def _scene(scene, what: str) -> None:
-    if not isinstance(scene, BakedScene):
-        raise ValueError(f"{what} takes a baked.BakedScene")
 
 
 def _weight(min_weight) -> float:
@@ -45,31 +40,19 @@ def _weight(min_weight) -> float:
 def face_max(t: torch.Tensor, scene: BakedScene) -> torch.Tensor:
     """upnerf_brick_face_max in place on the pool-shaped fp32 tensor `t` [n_bricks, 9, 9, 9, ...] of the sparse `scene`: every copy
     of a grid point that bricks share becomes the maximum over its copies.  Returns `t`."""
-    _scene(scene, "face_max")
-    if not scene.sparse:
+    if not a_scene(scene, "face_max").sparse:
         raise ValueError("face_max is for a sparse scene's pool-shaped tensors")
-    require_cuda("baked_prune.face_max", t)
-    P, n = _lib.BRICK_POINTS, scene.n_bricks
-    if t.dtype != torch.float32 or t.dim() < 4 or tuple(t.shape[:4]) != (n, P, P, P) or not t.is_contiguous():
-        raise ValueError(f"a pool-shaped tensor is contiguous fp32 [{n}, {P}, {P}, {P}, ...]")
-    if n == 0:
-        return t
-    Cx, Cy, Cz = scene.occupancy.dims
-    F = t.numel() // (n * P ** 3)
-    a = _lib.BrickFaceSumArgs(Cx=Cx, Cy=Cy, Cz=Cz, n_bricks=n, F=F, slots=ptr(scene.slots), bricks=ptr(scene.bricks), data=ptr(t))
-    check(TIMER.run("brick_face_max", lambda: lib.upnerf_brick_face_max(C.byref(a), stream()), units=n * 386 * F), "upnerf_brick_face_max")
-    return t
+    return brick_face("max", t, scene.layout, "baked_prune.face_max")
 
 
 def march_visibility(scene: BakedScene, rays: torch.Tensor, step: float, stop: float, vis: torch.Tensor) -> None:
     """One launch of upnerf_baked_visibility on checked arguments (_render_args, _rays16), maxed into `vis` (the per-copy values of
     a sparse scene: no face max)."""
-    degree = scene.sh_degree
-    points = scene._pool_bytes if scene.sparse else scene.grid
-    common = _common(scene.occupancy, scene.bounds, rays, step, 0.0, stop)
+    layout = scene.layout
+    points, slots = layout.pointers(scene.points)
+    common = _common(layout.occupancy, layout.bounds, rays, step, 0.0, stop)
     del common["background"]
-    a = _lib.BakedVisibilityArgs(E=POINT_BYTES[degree], sigma_offset=SIGMA_AT[degree], points=ptr(points),
-                                 slots=ptr(scene.slots) if scene.sparse else None, vis=ptr(vis), **common)
+    a = _lib.BakedVisibilityArgs(E=layout.point_bytes, sigma_offset=layout.sigma_at, points=points, slots=slots, vis=ptr(vis), **common)
     check(TIMER.run("baked_visibility", lambda: lib.upnerf_baked_visibility(C.byref(a), stream()), units=rays.shape[0]), "upnerf_baked_visibility")
 
 
@@ -78,16 +61,14 @@ def visibility(scene: BakedScene, rays: torch.Tensor, step: float, stop: float =
     """The fp32 device tensor [Nz, Ny, Nx] (dense) or [n_bricks, 9, 9, 9] (sparse; after upnerf_brick_face_max, so the copies of
     a shared point are equal) of `rays` [R, 8] marched at `step` and `stop` as render marches them, `chunk` rays a launch.  The
     values do not depend on `chunk`."""
-    _scene(scene, "visibility")
+    a_scene(scene, "visibility")
     require_cuda("baked_prune.visibility", rays)
     step, _, stop = _render_args(rays, step, 0.0, stop)
     chunk = int(chunk)
     if chunk < 1:
         raise ValueError(f"chunk must be positive, got {chunk}")
     rays = _rays16(rays)
-    P = _lib.BRICK_POINTS
-    Nx, Ny, Nz = scene.resolution
-    vis = torch.zeros((scene.n_bricks, P, P, P) if scene.sparse else (Nz, Ny, Nx), device=rays.device, dtype=torch.float32)
+    vis = torch.zeros(scene.layout.shape, device=rays.device, dtype=torch.float32)
     if scene.sparse and scene.n_bricks == 0:
         return vis
     for r0 in range(0, rays.shape[0], chunk):
@@ -117,25 +98,22 @@ def prune(scene: BakedScene, rays: torch.Tensor, step: float, min_weight: Option
     words rebuilt from it (upnerf_brick_occ) and the table from the words (upnerf_brick_table; one host read, the count), the
     surviving bricks selected through the old slots -- nothing the size of the grid is allocated.  env, level, bounds and
     sh_degree carry over.  At the default weight `rays` render at `step` and `stop` to the bits they rendered to before."""
-    _scene(scene, "prune")
+    a_scene(scene, "prune")
     w = _weight(min_weight)
-    degree = scene.sh_degree
-    E = POINT_BYTES[degree]
+    degree, E = scene.sh_degree, scene.layout.point_bytes
     vis = visibility(scene, rays, step, stop, chunk)
     if not scene.sparse:
         grid = scene.grid.contiguous().view(torch.uint8)
         points = _aligned(grid.numel(), max(E, 16), grid.device)[:grid.numel()].view(grid.shape).copy_(grid)
         prune_points(points, vis, E, w)
-        if degree:
-            return BakedScene.from_records(points, scene.bounds, scene.level, degree).with_environment(scene.env)
-        return BakedScene(points.view(torch.float32), scene.bounds, scene.level).with_environment(scene.env)
-    n, P, dev = scene.n_bricks, _lib.BRICK_POINTS, scene.device
+        return BakedScene.from_points(points, scene.bounds, scene.level, degree).with_environment(scene.env)
+    n, dev = scene.n_bricks, scene.device
     if n == 0:
         return scene.with_environment(scene.env)  # (nothing to drop: the same tensors)
     pool = scene.pool.contiguous().view(torch.uint8)
     points = _aligned(pool.numel(), E, dev)[:pool.numel()].view(pool.shape).copy_(pool)
     prune_points(points, vis, E, w)
-    words = brick_words(points.view(-1), scene.slots, n, scene.resolution, E, SIGMA_AT[degree])
+    words = brick_words(points.view(-1), scene.slots, n, scene.resolution, E, scene.layout.sigma_at)
     slots, bricks, m = brick_table(words, scene.occupancy.dims)
     old = scene.slots.view(-1).index_select(0, bricks.long()).long()  # where each surviving brick lay in the old pool
     kept = _aligned_copy(points.index_select(0, old), E) if m else points[:0]

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream
-from .baked import POINT_BYTES, BakedScene, _aligned, _aligned_copy, _level, brick_table
+from .baked import POINT_BYTES, BakedScene, Layout, _aligned, _aligned_copy, _level, a_scene, brick_table, face_sum as _sum_faces, pool_layout
 from .ops import TIMER
 from .static_scene import require_cuda
 
@@ -46,7 +46,7 @@ def _sigma_stride(sigma: torch.Tensor, shape) -> int:
 def tv_backward(data: torch.Tensor, sigma: torch.Tensor, occupancy, weights: Sequence[float], eps: float, layout=None,
                 out: Optional[torch.Tensor] = None, face_sum: bool = True) -> tuple:
     """upnerf_baked_tv.  data: contiguous fp32 [Nz, Ny, Nx, ...] (F floats per point, any trailing shape, none: F = 1) of a dense
-    grid, or with `layout` (a sparse BakedScene or a PoolParams) [n_bricks, 9, 9, 9, ...] of its pool; sigma: the points' sigmas
+    grid, or with `layout` (a pool's baked.Layout, a sparse BakedScene or a PoolParams) [n_bricks, 9, 9, 9, ...] of its pool; sigma: the points' sigmas
     (liveness), `data`'s leading shape, possibly a view such as rgbs[..., 3]; weights: F finite floats; eps > 0.  The gradient is
     ADDED into `out` (data's shape; zeroed here when None).  On a pool the face sum runs over `out` afterwards unless
     face_sum = False, which leaves each copy with what the cells of its own brick give it.  Returns (value, out): the value a 0-dim
@@ -54,11 +54,10 @@ def tv_backward(data: torch.Tensor, sigma: torch.Tensor, occupancy, weights: Seq
     require_cuda("baked_reg.tv", data, sigma)
     Cx, Cy, Cz = occupancy.dims
     if layout is not None:
-        from .baked_sparse_tune import _sum_faces, _table
-        slots, bricks, dims = _table(layout)
-        if tuple(dims) != (Cx, Cy, Cz):
+        layout = pool_layout(layout)
+        if layout.occupancy.dims != (Cx, Cy, Cz):
             raise ValueError("the layout and the occupancy are of different grids")
-        n_bricks, shape = bricks.numel(), (bricks.numel(), 9, 9, 9)
+        slots, bricks, n_bricks, shape = layout.slots, layout.bricks, layout.shape[0], layout.shape
     else:
         slots = bricks = None
         n_bricks, shape = 0, (Cz + 1, Cy + 1, Cx + 1)
@@ -91,10 +90,11 @@ def tv(data: torch.Tensor, sigma: torch.Tensor, occupancy, weights: Sequence[flo
     return tv_backward(data, sigma, occupancy, weights, eps, layout=layout, face_sum=face_sum)
 
 
-def tuner_tv(tuner, layout=None) -> torch.Tensor:
+def tuner_tv(tuner) -> torch.Tensor:
     """The TV gradient of a tuner's masters added into its gradient, weights per occupied cell (the host folds 1 / tuner.tv_cells, the number of
     occupied cells counted when the tuner was made, into w); on a pool the per-copy gradient, the caller sums the faces.  Returns the value."""
     ls, lc = tuner.tv_sigma / tuner.tv_cells, tuner.tv_colour / tuner.tv_cells
+    layout = tuner.layout if tuner.layout.sparse else None
     if tuner.degree == 0:
         rgbs = tuner.masters[0]
         value, _ = tv_backward(rgbs, rgbs[..., 3], tuner.occupancy, (lc, lc, lc, ls), tuner.tv_eps, layout=layout, out=tuner.grads[0],
@@ -123,9 +123,7 @@ def upsample(scene: BakedScene, level: Optional[float] = None) -> BakedScene:
     (default: the scene's).  Dense: upnerf_baked_upsample, the bits rebuilt from the child's sigmas.  Sparse, pool to pool with
     nothing the size of either grid but the bits: upnerf_brick_upsample_mark, upnerf_brick_table (the one host read: the child's
     brick count), upnerf_brick_upsample_fill, upnerf_brick_occ."""
-    if not isinstance(scene, BakedScene):
-        raise ValueError("upsample takes a baked.BakedScene")
-    return _upsample(scene, level).with_environment(scene.env)  # (the environment is no function of the grid: carried along)
+    return _upsample(a_scene(scene, "upsample"), level).with_environment(scene.env)  # (the environment is no function of the grid: carried along)
 
 
 def _upsample(scene: BakedScene, level: Optional[float]) -> BakedScene:
@@ -142,25 +140,23 @@ def _upsample(scene: BakedScene, level: Optional[float]) -> BakedScene:
         out = _store(Mz * My * Mx, degree, dev).view(Mz, My, Mx, E)
         a = _lib.BakedUpsampleArgs(Cx=Cx, Cy=Cy, Cz=Cz, degree=degree, level=level, points=ptr(points), out=ptr(out))
         check(TIMER.run("baked_upsample", lambda: lib.upnerf_baked_upsample(C.byref(a), stream()), units=Mz * My * Mx), "upnerf_baked_upsample")
-        if degree:
-            return BakedScene.from_records(out, scene.bounds, level, degree)
-        return BakedScene(out.view(torch.float32), scene.bounds, level)
+        return BakedScene.from_points(out, scene.bounds, level, degree)
     res = (Mx, My, Mz)
     P = _lib.BRICK_POINTS
     B = tuple((2 * c + 7) // 8 for c in (Cx, Cy, Cz))
-    empty_pool = lambda: torch.empty((0, P, P, P, 4) if degree == 0 else (0, P, P, P, E), device=dev, dtype=torch.float32 if degree == 0 else torch.uint8)
     if scene.n_bricks == 0:
         slots = torch.full((B[2], B[1], B[0]), -1, device=dev, dtype=torch.int32)
-        return BakedScene._sparse(empty_pool(), slots, torch.empty(0, device=dev, dtype=torch.int32), res, scene.bounds, level, degree)
+        return BakedScene._sparse(Layout.empty_pool(degree, dev), slots, torch.empty(0, device=dev, dtype=torch.int32), res, scene.bounds, level, degree)
     words = torch.empty(int(lib.upnerf_occ_words(2 * Cx, 2 * Cy, 2 * Cz)), device=dev, dtype=torch.int32)  # (its brick words are written)
-    common = dict(Cx=Cx, Cy=Cy, Cz=Cz, degree=degree, level=level, n_bricks=scene.n_bricks, slots=ptr(scene.slots), pool=ptr(scene._pool_bytes))
+    pool, slots = scene.layout.pointers(scene.points)
+    common = dict(Cx=Cx, Cy=Cy, Cz=Cz, degree=degree, level=level, n_bricks=scene.n_bricks, slots=slots, pool=pool)
     a = _lib.BrickUpsampleArgs(words=ptr(words), **common)
     check(TIMER.run("brick_upsample_mark", lambda: lib.upnerf_brick_upsample_mark(C.byref(a), stream()), units=B[0] * B[1] * B[2]),
           "upnerf_brick_upsample_mark")
     slots, bricks, n = brick_table(words, (2 * Cx, 2 * Cy, 2 * Cz))
     del words
     if n == 0:
-        return BakedScene._sparse(empty_pool(), slots, bricks, res, scene.bounds, level, degree)
+        return BakedScene._sparse(Layout.empty_pool(degree, dev), slots, bricks, res, scene.bounds, level, degree)
     out = _store(n * P ** 3, degree, dev).view(n, P, P, P, E)
     f = _lib.BrickUpsampleArgs(n_child=n, child_bricks=ptr(bricks), out=ptr(out), **common)
     check(TIMER.run("brick_upsample_fill", lambda: lib.upnerf_brick_upsample_fill(C.byref(f), stream()), units=n * P ** 3),

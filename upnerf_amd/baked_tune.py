@@ -26,7 +26,9 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream
-from .baked import SIGMA_BYTE, BakedScene, _common, _rays16, _render_args, march, pack_records
+from .baked import SIGMA_BYTE, BakedScene, Layout, _common, _rays16, _render_args, _upstream, a_scene, face_sum, march, pack_records, pack_rgbs
+from .baked_env import composite_backward
+from .baked_reg import tuner_tv
 from .ops import TIMER
 from .static_scene import require_cuda
 
@@ -37,9 +39,7 @@ SPARSE_REFUSAL = ("a sparse baked scene cannot be tuned: its pool stores the fac
 
 
 def _dense(scene, what: str) -> None:
-    if not isinstance(scene, BakedScene):
-        raise ValueError(f"{what} takes a baked.BakedScene")
-    if scene.sparse:
+    if a_scene(scene, what).sparse:
         raise ValueError(SPARSE_REFUSAL)
 
 
@@ -52,34 +52,32 @@ def unpack_records(records: torch.Tensor, degree: int) -> Tuple[torch.Tensor, to
     return coef.contiguous(), records[..., at:at + 4].contiguous().view(torch.float32).squeeze(-1).contiguous()
 
 
-class SceneParams:
-    """The fp32 parameters of a dense scene with what the marcher needs beside them: `rgbs` [Nz, Ny, Nx, 4] at degree 0, else
-    `coef` [Nz, Ny, Nx, 3, nb] and `sigma` [Nz, Ny, Nx]; the (frozen) occupancy, the bounds, the degree.  The tensors are leaves a
-    caller may set requires_grad on; `tensors` lists them."""
+class Params:
+    """The fp32 parameters of a scene over its points, grid or pool, with their `layout`: `rgbs` [.., 4] at degree 0, else `coef`
+    [.., 3, nb] and `sigma` [..], where [..] is layout.shape.  The tensors are leaves a caller may set requires_grad on; `tensors`
+    lists them.  SceneParams (dense, below) and baked_sparse_tune.PoolParams are its two constructors."""
 
-    def __init__(self, occupancy, bounds, degree: int, rgbs=None, coef=None, sigma=None, env=None):
-        self.occupancy, self.bounds, self.degree = occupancy, bounds, int(degree)
+    noun = "scene"  # what the refusal calls the points
+
+    def __init__(self, layout: Layout, rgbs=None, coef=None, sigma=None, env=None):
+        self.layout, self.occupancy, self.bounds, self.degree = layout, layout.occupancy, layout.bounds, layout.degree
+        self.slots, self.bricks = layout.slots, layout.bricks
         self.rgbs, self.coef, self.sigma, self.env = rgbs, coef, sigma, env
-        nb = (self.degree + 1) ** 2
-        Cx, Cy, Cz = occupancy.dims
-        shape = (Cz + 1, Cy + 1, Cx + 1)
-        if self.degree == 0:
-            ok = rgbs is not None and rgbs.dtype == torch.float32 and tuple(rgbs.shape) == shape + (4,)
-        else:
-            ok = self.degree in (1, 2) and coef is not None and sigma is not None and coef.dtype == sigma.dtype == torch.float32 and \
-                tuple(coef.shape) == shape + (3, nb) and tuple(sigma.shape) == shape
+        ok = self.degree in (0, 1, 2) and all(t is not None and t.dtype == torch.float32 and tuple(t.shape) == shape
+                                              for t, shape in zip(self.tensors, layout.param_shapes))
         if not ok:
-            raise ValueError(f"a degree-{degree} scene of {shape} points has fp32 rgbs [.., 4] (degree 0) or coef [.., 3, nb] and sigma [..]")
-        require_cuda("SceneParams", *self.tensors)
+            raise ValueError(f"a degree-{self.degree} {self.noun} of {layout.shape} points has fp32 rgbs [.., 4] (degree 0) or "
+                             f"coef [.., 3, nb] and sigma [..]")
+        require_cuda(type(self).__name__, *((layout.slots, layout.bricks) if layout.sparse else ()), *self.tensors)
 
     @classmethod
-    def of(cls, scene: BakedScene, requires_grad: bool = True) -> "SceneParams":
-        _dense(scene, "SceneParams.of")
+    def _of(cls, scene: BakedScene, requires_grad: bool, *head) -> "Params":
+        """The parameters of an accepted scene, a copy of its rgbs or its records unpacked: cls(*head, the tensors, the scene's env)."""
         if scene.sh_degree == 0:
-            p = cls(scene.occupancy, scene.bounds, 0, rgbs=scene.rgbs.detach().clone(), env=scene.env)
+            p = cls(*head, rgbs=scene.grid.detach().clone(), env=scene.env)
         else:
-            coef, sigma = unpack_records(scene.records, scene.sh_degree)
-            p = cls(scene.occupancy, scene.bounds, scene.sh_degree, coef=coef, sigma=sigma, env=scene.env)
+            coef, sigma = unpack_records(scene.grid, scene.sh_degree)
+            p = cls(*head, coef=coef, sigma=sigma, env=scene.env)
         for t in p.tensors:
             t.requires_grad_(requires_grad)
         return p
@@ -89,11 +87,60 @@ class SceneParams:
         return (self.rgbs,) if self.degree == 0 else (self.coef, self.sigma)
 
 
-def _forward(points: torch.Tensor, degree: int, occupancy, bounds, rays, step, background, stop):
+class SceneParams(Params):
+    """The fp32 parameters of a dense scene with what the marcher needs beside them: `rgbs` [Nz, Ny, Nx, 4] at degree 0, else
+    `coef` [Nz, Ny, Nx, 3, nb] and `sigma` [Nz, Ny, Nx]; the (frozen) occupancy, the bounds, the degree."""
+
+    def __init__(self, occupancy, bounds, degree: int, rgbs=None, coef=None, sigma=None, env=None):
+        super().__init__(Layout(occupancy, bounds, degree), rgbs, coef, sigma, env)
+
+    @classmethod
+    def of(cls, scene: BakedScene, requires_grad: bool = True) -> "SceneParams":
+        _dense(scene, "SceneParams.of")
+        return cls._of(scene, requires_grad, scene.occupancy, scene.bounds, scene.sh_degree)
+
+
+def _forward(points: torch.Tensor, layout: Layout, rays, step, background, stop):
     R, dev = rays.shape[0], rays.device
     rgb, depth, opacity = torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)
-    march(points, degree, None, occupancy, bounds, rays, step, background, stop, rgb, depth, opacity)
+    march(points, layout, rays, step, background, stop, rgb, depth, opacity)
     return rgb, depth, opacity
+
+
+def _backward(what: str, points: torch.Tensor, layout: Layout, rays, step, background, stop, g_rgb, g_depth, g_opacity, out, sum_faces):
+    """The marcher's backward pass on the points of `layout`, grid or pool: upnerf_baked_render_bwd or
+    upnerf_baked_sparse_render_bwd, then on a pool with `sum_faces` the face sum over every gradient array.  The gradient is
+    ADDED into `out` (zeroed here when None) and returned as `out` was given: one tensor at degree 0, else the pair."""
+    require_cuda(what, points, rays, g_rgb)
+    step, background, stop = _render_args(rays, step, background, stop)
+    rays = _rays16(rays)
+    R, degree = rays.shape[0], layout.degree
+    _upstream(R, g_rgb, g_depth, g_opacity)
+    if points.numel() * points.element_size() != math.prod(layout.shape) * layout.point_bytes:
+        raise ValueError(f"points is the pool of {layout.shape[0]} bricks at degree {degree}" if layout.sparse else
+                         f"points is the grid of {layout.shape} points at degree {degree}")
+    if out is None:
+        zeros = layout.zeros(rays.device)
+        out = zeros if degree else zeros[0]
+    outs = (out,) if degree == 0 else tuple(out)
+    want = layout.param_shapes
+    if len(outs) != len(want) or any(t.dtype != torch.float32 or tuple(t.shape) != w for t, w in zip(outs, want)):
+        raise ValueError(f"out is fp32 {want}")
+    grads = dict(grad=ptr(out)) if degree == 0 else dict(grad_coef=ptr(out[0]), grad_sigma=ptr(out[1]))
+    address, slots = layout.pointers(points)
+    upstream = dict(g_rgb=ptr(g_rgb.contiguous()), g_depth=ptr(g_depth.contiguous()) if g_depth is not None else None,
+                    g_opacity=ptr(g_opacity.contiguous()) if g_opacity is not None else None)
+    common = _common(layout.occupancy, layout.bounds, rays, step, background, stop)
+    if layout.sparse:
+        name, a = "baked_sparse_render_bwd", _lib.BakedSparseRenderBwdArgs(degree=degree, pool=address, slots=slots, **upstream, **grads, **common)
+    else:
+        name, a = "baked_render_bwd", _lib.BakedRenderBwdArgs(degree=degree, points=address, slots=None, **upstream, **grads, **common)
+    fn = getattr(lib, "upnerf_" + name)
+    check(TIMER.run(name, lambda: fn(C.byref(a), stream()), units=R), "upnerf_" + name)
+    if layout.sparse and sum_faces:
+        for t in outs:
+            face_sum(t, layout)
+    return out
 
 
 def backward(points: torch.Tensor, degree: int, occupancy, bounds, rays: torch.Tensor, step: float, background: float, stop: float,
@@ -101,26 +148,8 @@ def backward(points: torch.Tensor, degree: int, occupancy, bounds, rays: torch.T
     """upnerf_baked_render_bwd, called directly.  points: the grid the forward marched (`rgbs` [Nz, Ny, Nx, 4] fp32 at degree 0,
     the uint8 records at degree 1 | 2).  Returns the gradient ADDED into `out` (zeroed here when None): one fp32 tensor
     [Nz, Ny, Nx, 4] at degree 0, else the pair ([Nz, Ny, Nx, 3, nb], [Nz, Ny, Nx])."""
-    require_cuda("baked_tune.backward", points, rays, g_rgb)
-    step, background, stop = _render_args(rays, step, background, stop)
-    rays = _rays16(rays)
-    R, dev = rays.shape[0], rays.device
-    if g_rgb.dtype != torch.float32 or tuple(g_rgb.shape) != (R, 3):
-        raise ValueError("g_rgb is a fp32 tensor [R, 3]")
-    for g in (g_depth, g_opacity):
-        if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != (R,)):
-            raise ValueError("g_depth and g_opacity are fp32 tensors [R] or None")
-    Cx, Cy, Cz = occupancy.dims
-    shape, nb = (Cz + 1, Cy + 1, Cx + 1), (degree + 1) ** 2
-    if out is None:
-        out = torch.zeros(shape + (4,), device=dev) if degree == 0 else (torch.zeros(shape + (3, nb), device=dev), torch.zeros(shape, device=dev))
-    grads = dict(grad=ptr(out)) if degree == 0 else dict(grad_coef=ptr(out[0]), grad_sigma=ptr(out[1]))
-    a = _lib.BakedRenderBwdArgs(degree=degree, points=ptr(points), slots=None, g_rgb=ptr(g_rgb.contiguous()),
-                                g_depth=ptr(g_depth.contiguous()) if g_depth is not None else None,
-                                g_opacity=ptr(g_opacity.contiguous()) if g_opacity is not None else None, **grads,
-                                **_common(occupancy, bounds, rays, step, background, stop))
-    check(TIMER.run("baked_render_bwd", lambda: lib.upnerf_baked_render_bwd(C.byref(a), stream()), units=R), "upnerf_baked_render_bwd")
-    return out
+    return _backward("baked_tune.backward", points, Layout(occupancy, bounds, degree), rays, step, background, stop, g_rgb, g_depth,
+                     g_opacity, out, False)
 
 
 def project(degree: int, rgbs: Optional[torch.Tensor] = None, sigma: Optional[torch.Tensor] = None) -> None:
@@ -132,7 +161,7 @@ def project(degree: int, rgbs: Optional[torch.Tensor] = None, sigma: Optional[to
 
 
 class _Render(torch.autograd.Function):
-    """The marcher with its backward: (rgb, depth, opacity) of the parameter tensors of a SceneParams."""
+    """The marcher with its backward (on a pool: and the face sum): (rgb, depth, opacity) of the parameter tensors of a Params."""
 
     @staticmethod
     def forward(ctx, params, rays, step, background, stop, *tensors):
@@ -142,16 +171,26 @@ class _Render(torch.autograd.Function):
             points = pack_records(tensors[0].detach().contiguous(), tensors[1].detach().contiguous(), params.degree, 0.0)
         ctx.points, ctx.params, ctx.rays, ctx.args = points, params, rays, (step, background, stop)
         ctx.set_materialize_grads(False)
-        return _forward(points, params.degree, params.occupancy, params.bounds, rays, step, background, stop)
+        return _forward(points, params.layout, rays, step, background, stop)
 
     @staticmethod
     def backward(ctx, g_rgb, g_depth, g_opacity):
         p, R = ctx.params, ctx.rays.shape[0]
         if g_rgb is None:
             g_rgb = torch.zeros(R, 3, device=ctx.rays.device)
-        out = backward(ctx.points, p.degree, p.occupancy, p.bounds, ctx.rays, *ctx.args, g_rgb.contiguous(),
-                       g_depth, g_opacity)
+        out = _backward("baked_tune.render", ctx.points, p.layout, ctx.rays, *ctx.args, g_rgb.contiguous(), g_depth, g_opacity, None, True)
         return (None,) * 5 + ((out,) if p.degree == 0 else tuple(out))
+
+
+def _render(what: str, params: Params, rays: torch.Tensor, step: float, background: float, stop: float) -> dict:
+    """render and baked_sparse_tune.render on parameters their caller has accepted."""
+    require_cuda(what, rays)
+    step, background, stop = _render_args(rays, step, background, stop)
+    rays = _rays16(rays)
+    rgb, depth, opacity = _Render.apply(params, rays, step, background if params.env is None else 0.0, stop, *params.tensors)
+    if params.env is not None:
+        rgb = params.env.composite(rays, rgb, opacity)
+    return {"rgb": rgb, "depth": depth, "opacity": opacity}
 
 
 def render(scene_params: SceneParams, rays: torch.Tensor, step: float, background: float = 0.0, stop: float = 0.0) -> dict:
@@ -162,20 +201,14 @@ def render(scene_params: SceneParams, rays: torch.Tensor, step: float, backgroun
     its own autograd function -- the points receive g_opacity - g_rgb . env(d) through the opacity."""
     if not isinstance(scene_params, SceneParams):
         raise ValueError("scene_params is a baked_tune.SceneParams (SceneParams.of(scene))")
-    require_cuda("baked_tune.render", rays)
-    step, background, stop = _render_args(rays, step, background, stop)
-    rays = _rays16(rays)
-    rgb, depth, opacity = _Render.apply(scene_params, rays, step, background if scene_params.env is None else 0.0, stop, *scene_params.tensors)
-    if scene_params.env is not None:
-        rgb = scene_params.env.composite(rays, rgb, opacity)
-    return {"rgb": rgb, "depth": depth, "opacity": opacity}
+    return _render("baked_tune.render", scene_params, rays, step, background, stop)
 
 
 class BakedTuner:
     """Adam on the points of a dense scene against target pixels.  Holds the fp32 masters (one flat buffer: rgbs, or the
     coefficients followed by the sigmas), their gradient and the Adam moments; the occupancy is the scene's and is frozen.
-    (The layout -- which scenes are taken, the shape of the point array, the forward and the gradient launches -- is in the four
-    methods after __init__; baked_sparse_tune.PoolTuner states them for a brick pool and shares the rest.)"""
+    Everything that depends on the layout -- the shape of the point array, the forward and the gradient launches -- comes from
+    self.layout, the scene's; baked_sparse_tune.PoolTuner is this tuner on a brick pool."""
 
     def __init__(self, scene: BakedScene, lr: float, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  tv_sigma: float = 0.0, tv_colour: float = 0.0, tv_eps: float = 1e-8):
@@ -187,13 +220,14 @@ class BakedTuner:
         if not (np.isfinite(self.tv_sigma) and np.isfinite(self.tv_colour) and self.tv_eps > 0 and np.isfinite(self.tv_eps)):
             raise ValueError("tv_sigma and tv_colour are finite weights, tv_eps is positive and finite")
         self.lr, self.betas, self.eps, self.t = lr, (float(betas[0]), float(betas[1])), eps, 0
+        self.layout = scene.layout
         self.degree, self.bounds, self.level, self.occupancy = scene.sh_degree, scene.bounds, scene.level, scene.occupancy
         self.env = scene.env  # frozen: composited behind the march in step(), carried to scene()
         # the total variation penalty (baked_reg): off at the defaults, and then nothing is launched for it
         self.last_tv = None
         self.tv_cells = max(1, self.occupancy.n_occupied()) if self.tv_on else None
         dev = scene.device
-        shape, grid = self._points(scene)
+        shape, grid = self.layout.shape, scene.grid
         nb, n = (self.degree + 1) ** 2, math.prod(shape)
         per = 4 if self.degree == 0 else 3 * nb + 1
         self.p = torch.empty(n * per, device=dev)
@@ -211,22 +245,17 @@ class BakedTuner:
     def _accept(self, scene) -> None:
         _dense(scene, "BakedTuner")
 
-    def _points(self, scene):
-        """(the shape of the scene's point array, the array: rgbs or records)."""
-        Nx, Ny, Nz = scene.resolution
-        return (Nz, Ny, Nx), scene.grid
-
-    def _march(self, rays, step, background, stop):
-        return _forward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop)
-
     def _gradient(self, rays, step, background, stop, g_rgb, g_opacity=None) -> None:
         """The gradient of the points, added into self.grads (zeroed by the caller); with the penalty on, its gradient after the
-        marcher's (upnerf_baked_tv), the value left in self.last_tv."""
-        backward(self.points, self.degree, self.occupancy, self.bounds, rays, step, background, stop, g_rgb, g_opacity=g_opacity,
-                 out=self.grads[0] if self.degree == 0 else self.grads)
+        marcher's (upnerf_baked_tv), the value left in self.last_tv.  On a pool the face sum comes last, ONE over the per-copy
+        gradients of both."""
+        out = self.grads[0] if self.degree == 0 else self.grads
+        _backward("BakedTuner.step", self.points, self.layout, rays, step, background, stop, g_rgb, None, g_opacity, out, not self.tv_on)
         if self.tv_on:
-            from .baked_reg import tuner_tv
             self.last_tv = tuner_tv(self)
+            if self.layout.sparse:
+                for t in self.grads:
+                    face_sum(t, self.layout)
 
     @property
     def tv_on(self) -> bool:
@@ -274,7 +303,7 @@ class BakedTuner:
         check(lib.upnerf_zero(ptr(self.g), self.g.numel(), st), "upnerf_zero")
         if self.env is not None:
             background = 0.0
-        rgb, _, opacity = self._march(rays, step, background, stop)
+        rgb, _, opacity = _forward(self.points, self.layout, rays, step, background, stop)
         if self.env is not None:
             self.env.composite_(rays, rgb, opacity)
         diff = rgb - target_rgb
@@ -282,7 +311,6 @@ class BakedTuner:
         g_rgb = diff * (2.0 / (3 * R))
         g_opacity = None
         if self.env is not None:
-            from .baked_env import composite_backward
             g_opacity = composite_backward(self.env.env, rays, opacity, g_rgb)[0]
         self._gradient(rays, step, background, stop, g_rgb, g_opacity)
         self.t += 1
@@ -297,13 +325,17 @@ class BakedTuner:
             pack_records(*self.masters, self.degree, 0.0, out=self.records)
         return loss
 
+    def _pruned_points(self) -> torch.Tensor:
+        """The masters pruned again at the scene's level: fresh rgbs (upnerf_baked_pack) or records (upnerf_baked_sh_pack)."""
+        if self.degree:
+            return pack_records(*self.masters, self.degree, self.level)
+        rgbs = self.masters[0]
+        return pack_rgbs(rgbs[..., 3].contiguous(), rgbs[..., :3].contiguous(), self.level)
+
     @torch.no_grad()
     def scene(self) -> BakedScene:
-        """The tuned scene: the masters pruned again at the scene's level, the bits rebuilt (from_grids / from_records)."""
-        if self.degree == 0:
-            rgbs = self.masters[0]
-            return BakedScene.from_grids(rgbs[..., 3].contiguous(), rgbs[..., :3].contiguous(), self.bounds, self.level).with_environment(self.env)
-        return BakedScene.from_records(pack_records(*self.masters, self.degree, self.level), self.bounds, self.level, self.degree).with_environment(self.env)
+        """The tuned scene: the masters pruned again at the scene's level, the bits rebuilt."""
+        return BakedScene.from_points(self._pruned_points(), self.bounds, self.level, self.degree).with_environment(self.env)
 
 
 def keyframe_rays(path, device) -> torch.Tensor:
