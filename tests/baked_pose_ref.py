@@ -1,8 +1,8 @@
 """fp64 numpy restatement of the baked marcher's gradient with respect to its rays (include/upnerf_hip.h: upnerf_baked_ray_bwd;
 upnerf_amd/baked_pose.py): brute force over every lattice sample, the occupancy bits never consulted.  It builds
-on tests/baked_ref.py, tests/baked_sh_ref.py and tests/baked_tune_ref.py, whose definitions, grids, rays and gate recurrences
-(dg, dv, dalpha, dT, dw, dq, the suffix and `inner`) it uses and does not derive again.  Shared by tests/test_baked_pose_cpu.py
-and tests/test_hip_baked_pose.py.
+on tests/baked_ref.py, tests/baked_sh_ref.py and tests/baked_tune_ref.py, whose definitions, grids, rays and gates (dg, dv,
+dalpha, dT, dw, dq, the suffix, `inner` and a, all through baked_tune_ref.march) it calls and does not state again.
+Shared by tests/test_baked_pose_cpu.py and tests/test_hip_baked_pose.py.
 
     ray_grad(points, degree, bounds, rays, step, background, stop, g_rgb, g_depth, g_opacity, gates=True, omit=()) -> dict
         points as baked_tune_ref.grad takes them; "grad", "gate" [R, 8] (o | d | near | far), "stop_margin"
@@ -67,19 +67,6 @@ def slopes(grid, g, C):
     return np.stack([sx, sy, sz], 1)
 
 
-def _moved(fn, g, dg, C):
-    """sum over the axes of the largest |fn(g +- dg e_a) - fn(g)|."""
-    base, total = fn(g), 0.0
-    for a in range(3):
-        e = np.zeros(3)
-        e[a] = 1.0
-        worst = 0.0
-        for s in (-1.0, 1.0):
-            worst = np.maximum(worst, np.abs(fn(np.clip(g + s * dg[:, a:a + 1] * e, 0.0, C)) - base))
-        total = total + worst
-    return total
-
-
 def dbasis(unit, degree):
     """(dY/du [nb, 3], the magnitudes of its terms [nb, 3]) of sh.basis at a unit vector, the basis taken as the polynomial it
     is written as."""
@@ -90,78 +77,26 @@ def dbasis(unit, degree):
     return D[:sh.NB[degree]], np.abs(D[:sh.NB[degree]])
 
 
-def _ray(grid, dcol, coef, clamp, lo, hi, C, row, step, background, stop, gr, gd, go, gates, omit, Y=None, degree=0):
+def _ray(grid, dcol, coef, clamp, lo, hi, C, row, step, background, stop, gr, gd, go, gates, omit, degree=0):
     """(grad [8], gate [8], stop margin) of one ray, or None for a row of zeros."""
-    o, d, near, far = row[:3], row[3:6], row[6], row[7]
-    if not np.isfinite(row).all() or not far > near or (not gr.any() and gd == 0 and go == 0) or not (d * d).sum() > 0:
+    d = row[3:6]
+    m = tr.march(grid, dcol, clamp, lo, hi, C, row, step, background, stop, gr, gd, go, gates, apart=True, omit_open="open" in omit)
+    if m is None or not (d * d).sum() > 0:
         return None
-    K = br.n_samples(near, far, step)
-    t = near + (np.arange(K, dtype=np.float64) + 0.5) * step
-    inv = C / (hi - lo)
-    p = o + t[:, None] * d
-    g = (p - lo) * inv
-    v, inside, cmax = br.trilinear(grid, g, C)
-    dg = U * (inv * (np.abs(t[:, None] * d) + np.abs(p) + np.abs(p - lo)) + 2 * np.abs(g))
-    dv = np.zeros_like(v)
-    if gates:  # (baked_ref's dv, with baked_sh_ref's dcol)
-        dv = 9 * U * cmax + (br.trilinear(dcol, g, C)[2] if dcol is not None else 0.0) + _moved(lambda x: br.trilinear(grid, x, C)[0], g, dg, C)
-    raw = v[:, :3].copy()
-    if clamp:
-        v[:, :3] = np.clip(raw, 0.0, 1.0)
-    length = np.sqrt((d * d).sum())
-    delta = step * length
-    x = delta * v[:, 3]
-    alpha = -np.expm1(-x)
-    dalpha = np.exp(-x) * (6 * U * np.abs(x) + delta * dv[:, 3] + 2 * U) + U * np.abs(alpha)
-    ks, w, dw, Tn, dTn = [], [], [], [], []
-    T, dT, margin = 1.0, 0.0, np.inf
-    for k in np.nonzero(inside)[0]:  # (baked_ref's recurrence)
-        a_k = alpha[k]
-        ks.append(k), w.append(T * a_k), dw.append(dT * a_k + T * dalpha[k] + U * T * a_k)
-        T2 = T * (1.0 - a_k)
-        dT = dT * (1.0 - a_k) + T * (dalpha[k] + U * (1.0 - a_k)) + U * T2
-        T = T2
-        Tn.append(T), dTn.append(dT)
-        if stop > 0:
-            margin = min(margin, abs(T - stop) - dT)
-            if T < stop:
-                break
     grad, gate = np.zeros(8), np.zeros(8)
-    ks = np.asarray(ks, np.int64)
-    w, dw, Tn, dTn = (np.asarray(z, np.float64) for z in (w, dw, Tn, dTn))
-    n = ks.size
+    n, w, dw, tk, gk, dgk, dvk, inv, margin = m.n, m.w, m.dw, m.t, m.g, m.dg, m.dv, m.inv, m.margin
     O, dO = w.sum(), dw.sum() + n * U * w.sum()
     grad[7] = gd * (1.0 - O)
     gate[7] = abs(gd) * (dO + 2 * U * (1.0 + O))
     if n == 0:
         return grad, gate, margin
-    c, tk, dvk, rawk, gk, dgk = v[ks, :3], t[ks], dv[ks], raw[ks], g[ks], dg[ks]
-    # (baked_tune_ref's q, suffix, inner and dX)
-    q = (c - background) @ gr + gd * (tk - far) + go
-    mq = np.abs(c - background) @ np.abs(gr) + abs(gd) * np.abs(tk - far) + abs(go)
-    dq = dvk[:, :3] @ np.abs(gr) + abs(gd) * U * np.abs(tk) + 5 * U * mq
-    wq = w * q
-    dwq = dw * np.abs(q) + w * dq + U * np.abs(wq)
-    after = lambda z: np.concatenate([np.cumsum(z[::-1])[::-1][1:], [0.0]])
-    S, dS = after(wq), after(dwq) + (n + 2) * U * np.abs(wq).sum()
-    inner = Tn * q - S
-    dinner = dTn * np.abs(q) + Tn * dq + dS + U * np.abs(inner)
-    a, da = np.zeros((n, 4)), np.zeros((n, 4))
-    a[:, 3] = delta * inner
-    da[:, 3] = delta * dinner + 6 * U * np.abs(a[:, 3])
-    is_open = (rawk >= 0) & (rawk <= 1) if clamp and "open" not in omit else np.ones_like(rawk, bool)
-    full = w[:, None] * gr
-    a[:, :3] = np.where(is_open, full, 0.0)
-    da[:, :3] = dw[:, None] * np.abs(gr) + U * np.abs(full)
-    if clamp:
-        edge = (np.abs(rawk) <= dvk[:, :3]) | (np.abs(rawk - 1) <= dvk[:, :3])
-        da[:, :3] += np.where(edge, np.abs(full), 0.0)
+    a, da, inner, dinner, length = m.a, m.da, m.inner, m.dinner, np.sqrt((d * d).sum())
     # the slopes and S_k
     s = slopes(grid, gk, C)  # [n, 3, 4]
     ds = np.zeros_like(s)
     if gates:
         ck = br.trilinear(grid, gk, C)[2]
-        ds = 5 * U * 2 * ck[:, None, :] + _moved(lambda x: slopes(grid, x, C), gk, dgk, C)
+        ds = 5 * U * 2 * ck[:, None, :] + br.moved(lambda x: slopes(grid, x, C), gk, dgk, C)
         if dcol is not None:
             ds = ds + 2 * br.trilinear(dcol, gk, C)[2][:, None, :]
     Sk = (a[:, None, :] * s).sum(2)  # [n, 3]
@@ -176,7 +111,7 @@ def _ray(grid, dcol, coef, clamp, lo, hi, C, row, step, background, stop, gr, gd
     part = [inv * St]
     err = inv * dSt + 2 * U * inv * (tabs * Mk).sum(0)
     if "delta" not in omit:
-        sig = v[ks, 3]
+        sig = m.v[:, 3]
         E = (sig * inner).sum()
         dE = (dvk[:, 3] * np.abs(inner) + np.abs(sig) * dinner).sum() + (n + 1) * U * np.abs(sig * inner).sum()
         part.append(E * step * unit)
@@ -187,7 +122,7 @@ def _ray(grid, dcol, coef, clamp, lo, hi, C, row, step, background, stop, gr, gd
         blend = lambda x: br.trilinear(flat, x, C)[0]
         m = blend(gk).reshape(n, 3, nb)
         mabs = br.trilinear(np.abs(flat), gk, C)[0].reshape(n, 3, nb)
-        dm = _moved(blend, gk, dgk, C).reshape(n, 3, nb) if gates else np.zeros_like(m)
+        dm = br.moved(blend, gk, dgk, C).reshape(n, 3, nb) if gates else np.zeros_like(m)
         Z = (a[:, :3, None] * m).sum((0, 1))
         dZ = (da[:, :3, None] * np.abs(m) + np.abs(a[:, :3, None]) * dm).sum((0, 1)) + (6 + 24 * n) * U * (np.abs(a[:, :3, None]) * mabs).sum((0, 1))
         D, Dabs = dbasis(unit, degree)
@@ -208,34 +143,20 @@ def _ray(grid, dcol, coef, clamp, lo, hi, C, row, step, background, stop, gr, gd
 
 def ray_grad(points, degree, bounds, rays, step, background=0.0, stop=0.0, g_rgb=None, g_depth=None, g_opacity=None, gates=True, omit=()):
     assert all(x in OMISSIONS for x in omit)
-    lo, hi = br.bounds64(bounds)
-    rays = np.asarray(rays, np.float32).astype(np.float64)
-    step, background, stop = (float(np.float32(z)) for z in (step, background, stop))
+    coef, sigma, grid = tr.points64(points, degree)
+    lo, hi, C, rays, step, background, stop = br.args64(bounds, rays, sigma.shape, step, background, stop)
     R = rays.shape[0]
-    g_rgb = np.asarray(g_rgb, np.float64)
-    g_depth = np.zeros(R) if g_depth is None else np.asarray(g_depth, np.float64)
-    g_opacity = np.zeros(R) if g_opacity is None else np.asarray(g_opacity, np.float64)
-    if degree == 0:
-        grid = np.asarray(points, np.float64)
-        sigma, coef = grid[..., 3], None
-    else:
-        coef, sigma = (np.asarray(z, np.float64) for z in points)
-        nb = sh.NB[degree]
-    C = np.array(sigma.shape[::-1], np.float64) - 1
+    g_rgb, g_depth, g_opacity = tr.upstream64(R, g_rgb, g_depth, g_opacity)
     out = {"grad": np.zeros((R, 8)), "gate": np.zeros((R, 8)), "stop_margin": np.inf}
     for r in range(R):
-        dcol, Y = None, None
+        dcol = None
         if degree:
             d = rays[r, 3:6]
             if not np.isfinite(rays[r]).all() or not (d * d).sum() > 0:
                 continue
-            unit = d / np.sqrt((d * d).sum())
-            Y, m = sh.basis(unit, degree)[0], sh.basis_magnitude(unit, degree)
-            grid = np.concatenate([coef @ Y, sigma[..., None]], -1)
-            if gates:
-                dcol = np.concatenate([U * (np.abs(coef) * ((nb + sh.N_BASIS[:nb]) * m)).sum(-1), np.zeros(sigma.shape + (1,))], -1)
+            grid, dcol = sh.ray_grid(coef, sigma, d, degree, gates)[:2]
         res = _ray(grid, dcol, coef, degree > 0, lo, hi, C, rays[r], step, background, stop, g_rgb[r], g_depth[r], g_opacity[r], gates,
-                   omit, Y, degree)
+                   omit, degree)
         if res is not None:
             out["grad"][r], out["gate"][r] = res[0], res[1]
             out["stop_margin"] = min(out["stop_margin"], res[2])

@@ -1,6 +1,6 @@
 """fp64 restatement of a baked scene's visibility (include/upnerf_hip.h: upnerf_baked_visibility), built on
-tests/baked_ref.py's per-sample numbers (w, dw, dT, dg: its gates, restated here sample by sample because render_ray keeps them
-to itself), and of upnerf_baked_prune.  Shared by tests/test_baked_prune_cpu.py and tests/test_hip_baked_prune.py.
+tests/baked_ref.py's per-sample numbers (w, dw, dT, dg and their gates, taken sample by sample from its lattice, blended, alphas
+and transmit), and of upnerf_baked_prune.  Shared by tests/test_baked_prune_cpu.py and tests/test_hip_baked_prune.py.
 
     visibility(sigma [Nz, Ny, Nx] fp32, bounds, rays, step, stop) -> (lo, hi), fp64 [Nz, Ny, Nx]
 
@@ -42,42 +42,20 @@ def _cell(x, C):
 
 def visibility_ray(grid, live, lo_b, hi_b, C, row, step, stop, lo, hi):
     """One ray into lo and hi (in place).  grid: sigma fp64 [Nz, Ny, Nx, 1]; live: bool [Nz, Ny, Nx]."""
-    o, d, near, far = row[:3], row[3:6], row[6], row[7]
-    if not np.isfinite(row).all() or not far > near:
+    lat = br.lattice(lo_b, hi_b, C, row, step)
+    if lat is None:
         return
-    K = br.n_samples(near, far, step)
-    t = near + (np.arange(K, dtype=np.float64) + 0.5) * step
-    inv = C / (hi_b - lo_b)
-    p = o + t[:, None] * d
-    g = (p - lo_b) * inv
-    dg = U * (inv * (np.abs(t[:, None] * d) + np.abs(p) + np.abs(p - lo_b)) + 2 * np.abs(g))
+    _, g, dg, _ = lat
     maybe = ((g + dg >= 0) & (g - dg <= C)).all(1)
-    surely = ((g - dg >= 0) & (g + dg <= C)).all(1)
-    ks = np.nonzero(maybe)[0]
-    if not len(ks):
+    if not maybe.any():
         return
-    g, dg, surely = g[ks], dg[ks], surely[ks]
-    v, _, cmax = br.trilinear(grid, g, C)
-    dv = 9 * U * cmax
-    for a in range(3):
-        e = np.zeros(3)
-        e[a] = 1.0
-        worst = np.zeros_like(v)
-        for s in (-1.0, 1.0):
-            moved = np.clip(g + s * dg[:, a:a + 1] * e, 0.0, C)
-            worst = np.maximum(worst, np.abs(br.trilinear(grid, moved, C)[0] - v))
-        dv = dv + worst
-    delta = step * np.sqrt((d * d).sum())
-    x = delta * v[:, 0]
-    dx = 6 * U * np.abs(x) + delta * dv[:, 0]
-    ex = np.exp(-x)
-    alpha = -np.expm1(-x)
-    dalpha = ex * (dx + 2 * U) + U * np.abs(alpha)
+    surely = ((g - dg >= 0) & (g + dg <= C)).all(1)[maybe]
+    g, dg = g[maybe], dg[maybe]
+    v, _, dv = br.blended(grid, g, dg, C)
+    _, x, dx, alpha, dalpha = br.alphas(v[:, 0], dv[:, 0], row[3:6], step)
     c_lo, c_hi = _cell(g - dg, C), _cell(g + dg, C)
-    T, dT, after = 1.0, 0.0, False
-    for n in range(len(ks)):
-        w = T * alpha[n]
-        dw = dT * alpha[n] + T * dalpha[n] + U * w
+    after = False
+    for n, T, dT, w, dw, Tn, dTn in br.transmit(alpha, dalpha, range(len(g))):
         certain = bool(surely[n] and (c_lo[n] == c_hi[n]).all() and T - dT > 0 and not after)
         top, low = max(w + dw, TINY_NORMAL), max(w - dw, TINY_NORMAL)
         for cx, cy, cz in itertools.product(*(range(c_lo[n, a], c_hi[n, a] + 1) for a in range(3))):
@@ -88,26 +66,18 @@ def visibility_ray(grid, live, lo_b, hi_b, C, row, step, stop, lo, hi):
                 lo[sl] = np.where(m, np.maximum(lo[sl], low), lo[sl])
         if surely[n] and np.exp(-(x[n] - dx[n])) * (1 + 2 * U) < OPAQUE:
             return  # fp32's alpha is 1: its T is exactly zero from here on
-        Tn = T * (1.0 - alpha[n])
-        dT = dT * (1.0 - alpha[n]) + T * (dalpha[n] + U * (1.0 - alpha[n])) + U * Tn
-        T = Tn
         if stop > 0:
-            if T + dT < stop:
+            if Tn + dTn < stop:
                 return
-            if T - dT < stop:
+            if Tn - dTn < stop:
                 after = True
 
 
 def visibility(sigma, bounds, rays, step, stop=0.0):
     """(lo, hi) fp64 [Nz, Ny, Nx] of the fp32 sigmas `sigma` [Nz, Ny, Nx] and rays [R, 8] fp32."""
-    lo_b, hi_b = br.bounds64(bounds)
     s32 = np.asarray(sigma, np.float32)
-    grid = s32.astype(np.float64)[..., None]
-    live = s32 != 0
-    C = np.array(s32.shape[::-1], np.float64) - 1
-    rays = np.asarray(rays, np.float32).astype(np.float64)
-    step, stop = float(np.float32(step)), float(np.float32(stop))
-    lo, hi = np.zeros(s32.shape), np.zeros(s32.shape)
+    lo_b, hi_b, C, rays, step, _, stop = br.args64(bounds, rays, s32.shape, step, 0.0, stop)
+    grid, live, lo, hi = s32.astype(np.float64)[..., None], s32 != 0, np.zeros(s32.shape), np.zeros(s32.shape)
     for row in rays:
         visibility_ray(grid, live, lo_b, hi_b, C, row, step, stop, lo, hi)
     return lo, hi

@@ -4,6 +4,11 @@ tests/test_hip_baked.py (the kernel), which also take their grids and rays from 
 
     render(rgbs, bounds, rays, step, background, stop) -> {"rgb" [R, 3], "depth" [R], "opacity" [R], "n" [R], "gate_*"}
 
+A ray's samples are stated here once, for every march of a baked scene (baked_sh_ref, baked_tune_ref, baked_pose_ref,
+baked_prune_ref and baked_upsample_ref call these and keep only what is their own): args64 (the arguments as fp32 numbers),
+lattice (t, g and the gate `g`), moved and blended (v and the gate `v`), alphas (the gate `alpha`), transmit (the gates `T` and `w`,
+sample by sample) and visited (the same as arrays up to `stop`).  A new march extends these; it does not copy them.
+
 The definition.  Inputs are fp32 numbers, all arithmetic fp64 except K, which IS a fp32 number: K = ceilf((far - near) / step).
 t_k = near + (k + 0.5) step; p = o + t_k d; g = (p - lo) C / (hi - lo) per axis; a sample with g < 0 or g > C on an axis
 contributes nothing; i = min(floor(g), C - 1), f = g - i; v = trilinear blend of the eight corners (r, g, b, sigma);
@@ -87,41 +92,107 @@ def trilinear(grid, g, C):
     return np.where(inside[:, None], v, 0.0), inside, np.where(inside[:, None], cmax, 0.0)
 
 
-def render_ray(grid, lo, hi, C, row, step, background, stop):
-    """One ray; returns (rgb [3], depth, opacity, n contributing samples, gates (rgb [3], depth, opacity), n inside)."""
+def args64(bounds, rays, shape, step, background=0.0, stop=0.0):
+    """(lo, hi, C, rays, step, background, stop) as a march takes them: the fp32 numbers of the arguments in fp64, and the cells
+    per axis C (x, y, z) of points [Nz, Ny, Nx, ...] of `shape`."""
+    lo, hi = bounds64(bounds)
+    C = np.array(shape[2::-1], np.float64) - 1
+    return (lo, hi, C, np.asarray(rays, np.float32).astype(np.float64)) + tuple(float(np.float32(x)) for x in (step, background, stop))
+
+
+def lattice(lo, hi, C, row, step):
+    """(t [K], g [K, 3], dg [K, 3], inv [3]) of a ray's samples, or None for a miss (a number that is not finite, far <= near)."""
     o, d, near, far = row[:3], row[3:6], row[6], row[7]
-    miss = (np.full(3, background), far, 0.0, 0, (np.zeros(3), 0.0, 0.0), 0)
     if not np.isfinite(row).all() or not far > near:
-        return miss
-    K = n_samples(near, far, step)
-    t = near + (np.arange(K, dtype=np.float64) + 0.5) * step
+        return None
+    t = near + (np.arange(n_samples(near, far, step), dtype=np.float64) + 0.5) * step
     inv = C / (hi - lo)
     p = o + t[:, None] * d
     g = (p - lo) * inv
-    v, inside, cmax = trilinear(grid, g, C)
-    dg = U * (inv * (np.abs(t[:, None] * d) + np.abs(p) + np.abs(p - lo)) + 2 * np.abs(g))
-    dv = 9 * U * cmax
+    return t, g, U * (inv * (np.abs(t[:, None] * d) + np.abs(p) + np.abs(p - lo)) + 2 * np.abs(g)), inv
+
+
+def moved(fn, g, dg, C, onto=0.0):
+    """`onto` plus, axis after axis, the largest |fn(g +- dg e_a) - fn(g)|.  (A sample just outside the box is judged at its face:
+    v = 0 there.)  Additions are not associative: a caller that adds the three axes' sum to its other terms passes nothing."""
+    base, total = fn(g), onto
     for a in range(3):
         e = np.zeros(3)
         e[a] = 1.0
-        worst = np.zeros_like(v)
+        worst = 0.0
         for s in (-1.0, 1.0):
-            moved = np.clip(g + s * dg[:, a:a + 1] * e, 0.0, C)  # (a sample just outside the box is judged at its face: v = 0 there)
-            worst = np.maximum(worst, np.abs(trilinear(grid, moved, C)[0] - v))
-        dv = dv + worst
+            worst = np.maximum(worst, np.abs(fn(np.clip(g + s * dg[:, a:a + 1] * e, 0.0, C)) - base))
+        total = total + worst
+    return total
+
+
+def blended(grid, g, dg, C, dcol=None, gates=True, apart=False):
+    """(v [K, ch], inside [K], dv [K, ch]) of the samples: the gate `v` of the docstring, with the largest dcol among a sample's
+    eight corners (baked_sh_ref) where the corners carry an error of their own; zeros with gates=False.  apart: the moves of the
+    three axes are summed on their own and added last (baked_pose_ref's order of the same terms)."""
+    v, inside, cmax = trilinear(grid, g, C)
+    if not gates:
+        return v, inside, np.zeros_like(v)
+    own = 9 * U * cmax + (trilinear(dcol, g, C)[2] if dcol is not None else 0.0)
+    move = moved(lambda x: trilinear(grid, x, C)[0], g, dg, C, 0.0 if apart else own)
+    return v, inside, own + move if apart else move
+
+
+def alphas(sigma, dsigma, d, step):
+    """(delta, x, dx, alpha, dalpha) of blended densities sigma [K] with gates dsigma: the gate `alpha`, dx the part of it on x."""
     delta = step * np.sqrt((d * d).sum())
-    x = delta * v[:, 3]
-    ex = np.exp(-x)
+    x = delta * sigma
+    dx = 6 * U * np.abs(x) + delta * dsigma
     alpha = -np.expm1(-x)
-    dalpha = ex * (6 * U * np.abs(x) + delta * dv[:, 3] + 2 * U) + U * np.abs(alpha)
+    return delta, x, dx, alpha, np.exp(-x) * (dx + 2 * U) + U * np.abs(alpha)
+
+
+def transmit(alpha, dalpha, ks):
+    """The gates `T` and `w` along the samples ks: yields (k, T, dT, w, dw, T', dT') -- the transmittance before sample k and
+    after it.  Where the ray ends is the consumer's decision: it breaks."""
+    T, dT = 1.0, 0.0
+    for k in ks:
+        a = alpha[k]
+        w = T * a
+        Tn = T * (1.0 - a)
+        dTn = dT * (1.0 - a) + T * (dalpha[k] + U * (1.0 - a)) + U * Tn
+        yield k, T, dT, w, dT * a + T * dalpha[k] + U * w, Tn, dTn
+        T, dT = Tn, dTn
+
+
+def visited(alpha, dalpha, inside, stop):
+    """(ks, w, dw, T', dT', stop margin) of the visited samples as arrays: those inside the box up to the one that brings T below
+    `stop`; the margin is the least |T' - stop| - dT' (only a positive one lets fp32 and fp64 end the ray alike)."""
+    rows, margin = [], np.inf
+    for k, _, _, w, dw, Tn, dTn in transmit(alpha, dalpha, np.nonzero(inside)[0]):
+        rows.append((k, w, dw, Tn, dTn))
+        if stop > 0:
+            margin = min(margin, abs(Tn - stop) - dTn)
+            if Tn < stop:
+                break
+    ks, w, dw, Tn, dTn = (np.asarray(z, np.float64) for z in zip(*rows)) if rows else (np.zeros(0),) * 5
+    return ks.astype(np.int64), w, dw, Tn, dTn, margin
+
+
+def render_ray(grid, lo, hi, C, row, step, background, stop, dcol=None, clamp=False):
+    """One ray; returns (rgb [3], depth, opacity, n contributing samples, gates (rgb [3], depth, opacity), n inside).  dcol: the
+    corners' own errors (baked_sh_ref).  clamp: the blended colours are held to [0, 1], and a seventh value counts the colour
+    values (below 0, above 1, neither) of the contributing samples."""
+    far, counts = row[7], np.zeros(3, np.int64)
+    lat = lattice(lo, hi, C, row, step)
+    if lat is None:
+        return (np.full(3, background), far, 0.0, 0, (np.zeros(3), 0.0, 0.0), 0) + ((counts,) if clamp else ())
+    t, g, dg, _ = lat
+    v, inside, dv = blended(grid, g, dg, C, dcol)
+    raw = v[:, :3].copy()
+    if clamp:
+        v[:, :3] = np.clip(raw, 0.0, 1.0)
+    alpha, dalpha = alphas(v[:, 3], dv[:, 3], row[3:6], step)[3:]
     rgb, depth, op = np.zeros(3), 0.0, 0.0
     g_rgb, g_depth, g_op = np.zeros(3), 0.0, 0.0
     s_rgb, s_depth = np.zeros(3), 0.0
-    T, dT, n = 1.0, 0.0, 0
-    for k in np.nonzero(inside)[0]:
-        a_k = alpha[k]
-        w = T * a_k
-        dw = dT * a_k + T * dalpha[k] + U * w
+    n = 0
+    for k, _, _, w, dw, Tn, _ in transmit(alpha, dalpha, np.nonzero(inside)[0]):
         rgb += w * v[k, :3]
         depth += w * t[k]
         op += w
@@ -132,34 +203,38 @@ def render_ray(grid, lo, hi, C, row, step, background, stop):
         s_depth += w * abs(t[k])
         if w != 0.0:
             n += 1
-        Tn = T * (1.0 - a_k)
-        dT = dT * (1.0 - a_k) + T * (dalpha[k] + U * (1.0 - a_k)) + U * Tn
-        T = Tn
-        if stop > 0 and T < stop:
+            counts += [int((raw[k] < 0).sum()), int((raw[k] > 1).sum()), int(((raw[k] >= 0) & (raw[k] <= 1)).sum())]
+        if stop > 0 and Tn < stop:
             break
     g_op += n * U * op
     g_rgb += (n + 2) * U * (s_rgb + abs(background)) + g_op * abs(background)
     g_depth += (n + 2) * U * (s_depth + abs(far)) + g_op * abs(far)
     rgb = rgb + (1.0 - op) * background
     depth = depth + (1.0 - op) * far
-    return rgb, depth, op, n, (g_rgb, g_depth, g_op), int(inside.sum())
+    return (rgb, depth, op, n, (g_rgb, g_depth, g_op), int(inside.sum())) + ((counts,) if clamp else ())
+
+
+def render_rows(rays, one, clamp=False):
+    """The dict of `render` from one(row) -> render_ray's tuple, ray by ray."""
+    R = rays.shape[0]
+    out = {"rgb": np.zeros((R, 3)), "depth": np.zeros(R), "opacity": np.zeros(R), "n": np.zeros(R, np.int64),
+           "gate_rgb": np.zeros((R, 3)), "gate_depth": np.zeros(R), "gate_opacity": np.zeros(R), "inside": np.zeros(R, np.int64)}
+    if clamp:
+        out["clamp"] = np.zeros((R, 3), np.int64)
+    for r in range(R):
+        res = one(rays[r])
+        out["rgb"][r], out["depth"][r], out["opacity"][r], out["n"][r], out["inside"][r] = res[:4] + res[5:6]
+        out["gate_rgb"][r], out["gate_depth"][r], out["gate_opacity"][r] = res[4]
+        if clamp:
+            out["clamp"][r] = res[6]
+    return out
 
 
 def render(rgbs, bounds, rays, step, background=0.0, stop=0.0):
     """The restatement over rays [R, 8] fp32 and rgbs [Nz, Ny, Nx, 4] fp32."""
-    lo, hi = bounds64(bounds)
     grid = np.asarray(rgbs, np.float32).astype(np.float64)
-    C = np.array(grid.shape[2::-1], np.float64) - 1
-    rays = np.asarray(rays, np.float32).astype(np.float64)
-    step, background, stop = (float(np.float32(x)) for x in (step, background, stop))
-    R = rays.shape[0]
-    out = {"rgb": np.zeros((R, 3)), "depth": np.zeros(R), "opacity": np.zeros(R), "n": np.zeros(R, np.int64),
-           "gate_rgb": np.zeros((R, 3)), "gate_depth": np.zeros(R), "gate_opacity": np.zeros(R), "inside": np.zeros(R, np.int64)}
-    for r in range(R):
-        c, dep, op, n, gates, ins = render_ray(grid, lo, hi, C, rays[r], step, background, stop)
-        out["rgb"][r], out["depth"][r], out["opacity"][r], out["n"][r], out["inside"][r] = c, dep, op, n, ins
-        out["gate_rgb"][r], out["gate_depth"][r], out["gate_opacity"][r] = gates
-    return out
+    lo, hi, C, rays, step, background, stop = args64(bounds, rays, grid.shape, step, background, stop)
+    return render_rows(rays, lambda row: render_ray(grid, lo, hi, C, row, step, background, stop))
 
 
 # ---- the test scenes ----------------------------------------------------------------------------------------------------------------

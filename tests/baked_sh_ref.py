@@ -1,6 +1,7 @@
 """fp64 numpy restatement of a baked scene with spherical-harmonic colour (include/upnerf_hip.h: upnerf_baked_sh_render,
-upnerf_sh_accumulate, upnerf_baked_sh_pack; upnerf_amd/baked.py).  Grids, rays, `trilinear`, `n_samples` and the
-gate recurrence are those of tests/baked_ref.py, whose definition and derivation this docstring extends and does not repeat.
+upnerf_sh_accumulate, upnerf_baked_sh_pack; upnerf_amd/baked.py).  Grids, rays and the whole march are those of
+tests/baked_ref.py (render_ray with dcol and the clamp), whose definition and derivation this docstring extends and does not
+repeat; ray_grid is what a direction adds.
 Shared by tests/test_baked_sh_cpu.py and tests/test_hip_baked_sh.py.
 
     basis(dirs, degree) -> [K, nb]                project(rgb_dirs, dirs, degree) -> (coefficients, condition sums)
@@ -104,91 +105,27 @@ def unpack(records, degree):
     return k, s.reshape(rec.shape[:-1])
 
 
-def render_ray(k, sigma, lo, hi, C, row, step, background, stop, degree, view_sign=1.0):
-    """One ray; baked_ref.render_ray's tuple, and the counts (below 0, above 1, neither) of the blended colour values of its
-    contributing samples.  view_sign = -1: the colours of the opposite direction on the same samples."""
-    o, d, near, far = row[:3], row[3:6], row[6], row[7]
-    none = np.zeros(3, np.int64)
-    if not np.isfinite(row).all() or not far > near:
-        return np.full(3, background), far, 0.0, 0, (np.zeros(3), 0.0, 0.0), 0, none
+def ray_grid(k, sigma, d, degree, gates=True, view_sign=1.0):
+    """(grid [Nz, Ny, Nx, 4], dcol [Nz, Ny, Nx, 4] or None, Y [nb], m [nb]) of a ray with direction d: the corners' four channels
+    (sum_j Y_j k[c][j], sigma) and the colours' own errors (docstring: corner).  view_sign = -1: the colours of the opposite
+    direction."""
     nb = NB[degree]
     unit = view_sign * d / np.sqrt((d * d).sum())
-    Y = basis(unit, degree)[0]
-    m = basis_magnitude(unit, degree)
-    grid = np.concatenate([k @ Y, sigma[..., None]], -1)
-    dcol = np.concatenate([U * (np.abs(k) * ((nb + N_BASIS[:nb]) * m)).sum(-1), np.zeros(sigma.shape + (1,))], -1)
-    K = br.n_samples(near, far, step)
-    t = near + (np.arange(K, dtype=np.float64) + 0.5) * step
-    inv = C / (hi - lo)
-    p = o + t[:, None] * d
-    g = (p - lo) * inv
-    v, inside, cmax = br.trilinear(grid, g, C)
-    dg = U * (inv * (np.abs(t[:, None] * d) + np.abs(p) + np.abs(p - lo)) + 2 * np.abs(g))
-    dv = 9 * U * cmax + br.trilinear(dcol, g, C)[2]
-    for a in range(3):
-        e = np.zeros(3)
-        e[a] = 1.0
-        worst = np.zeros_like(v)
-        for s in (-1.0, 1.0):
-            moved = np.clip(g + s * dg[:, a:a + 1] * e, 0.0, C)
-            worst = np.maximum(worst, np.abs(br.trilinear(grid, moved, C)[0] - v))
-        dv = dv + worst
-    raw = v[:, :3].copy()
-    v[:, :3] = np.clip(raw, 0.0, 1.0)
-    delta = step * np.sqrt((d * d).sum())
-    x = delta * v[:, 3]
-    ex = np.exp(-x)
-    alpha = -np.expm1(-x)
-    dalpha = ex * (6 * U * np.abs(x) + delta * dv[:, 3] + 2 * U) + U * np.abs(alpha)
-    rgb, depth, op = np.zeros(3), 0.0, 0.0
-    g_rgb, g_depth, g_op = np.zeros(3), 0.0, 0.0
-    s_rgb, s_depth = np.zeros(3), 0.0
-    T, dT, n = 1.0, 0.0, 0
-    clamp = none.copy()
-    for i in np.nonzero(inside)[0]:  # (baked_ref's recurrence, with the clamped colours)
-        a_k = alpha[i]
-        w = T * a_k
-        dw = dT * a_k + T * dalpha[i] + U * w
-        rgb += w * v[i, :3]
-        depth += w * t[i]
-        op += w
-        g_rgb += dw * np.abs(v[i, :3]) + w * dv[i, :3]
-        g_depth += dw * abs(t[i]) + w * U * abs(t[i])
-        g_op += dw
-        s_rgb += w * np.abs(v[i, :3])
-        s_depth += w * abs(t[i])
-        if w != 0.0:
-            n += 1
-            clamp += [int((raw[i] < 0).sum()), int((raw[i] > 1).sum()), int(((raw[i] >= 0) & (raw[i] <= 1)).sum())]
-        Tn = T * (1.0 - a_k)
-        dT = dT * (1.0 - a_k) + T * (dalpha[i] + U * (1.0 - a_k)) + U * Tn
-        T = Tn
-        if stop > 0 and T < stop:
-            break
-    g_op += n * U * op
-    g_rgb += (n + 2) * U * (s_rgb + abs(background)) + g_op * abs(background)
-    g_depth += (n + 2) * U * (s_depth + abs(far)) + g_op * abs(far)
-    rgb = rgb + (1.0 - op) * background
-    depth = depth + (1.0 - op) * far
-    return rgb, depth, op, n, (g_rgb, g_depth, g_op), int(inside.sum()), clamp
+    Y, m = basis(unit, degree)[0], basis_magnitude(unit, degree)
+    dcol = np.concatenate([U * (np.abs(k) * ((nb + N_BASIS[:nb]) * m)).sum(-1), np.zeros(sigma.shape + (1,))], -1) if gates else None
+    return np.concatenate([k @ Y, sigma[..., None]], -1), dcol, Y, m
 
 
 def render(records, degree, bounds, rays, step, background=0.0, stop=0.0, view_sign=1.0):
-    """The restatement over rays [R, 8] fp32 and records uint8 [Nz, Ny, Nx, 32 | 64]."""
-    lo, hi = br.bounds64(bounds)
+    """The restatement over rays [R, 8] fp32 and records uint8 [Nz, Ny, Nx, 32 | 64]: baked_ref.render_ray on the ray's own grid,
+    clamped, and "clamp": the counts (below 0, above 1, neither) of the blended colour values of its contributing samples."""
     k, sigma = unpack(records, degree)
-    C = np.array(sigma.shape[::-1], np.float64) - 1
-    rays = np.asarray(rays, np.float32).astype(np.float64)
-    step, background, stop = (float(np.float32(x)) for x in (step, background, stop))
-    R = rays.shape[0]
-    out = {"rgb": np.zeros((R, 3)), "depth": np.zeros(R), "opacity": np.zeros(R), "n": np.zeros(R, np.int64),
-           "gate_rgb": np.zeros((R, 3)), "gate_depth": np.zeros(R), "gate_opacity": np.zeros(R), "inside": np.zeros(R, np.int64),
-           "clamp": np.zeros((R, 3), np.int64)}
-    for r in range(R):
-        c, dep, op, n, gates, ins, clamp = render_ray(k, sigma, lo, hi, C, rays[r], step, background, stop, degree, view_sign)
-        out["rgb"][r], out["depth"][r], out["opacity"][r], out["n"][r], out["inside"][r], out["clamp"][r] = c, dep, op, n, ins, clamp
-        out["gate_rgb"][r], out["gate_depth"][r], out["gate_opacity"][r] = gates
-    return out
+    lo, hi, C, rays, step, background, stop = br.args64(bounds, rays, sigma.shape, step, background, stop)
+
+    def one(row):
+        grid, dcol = ray_grid(k, sigma, row[3:6], degree, True, view_sign)[:2]
+        return br.render_ray(grid, lo, hi, C, row, step, background, stop, dcol, clamp=True)
+    return br.render_rows(rays, one, clamp=True)
 
 
 # ---- the test scenes ----------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """fp64 numpy restatement of the baked marcher's gradient (include/upnerf_hip.h: upnerf_baked_render_bwd, upnerf_baked_project;
 upnerf_amd/baked_tune.py): brute force over every lattice sample, the occupancy bits never consulted.  It extends
-tests/baked_ref.py and tests/baked_sh_ref.py, whose definitions, grids, rays and gate recurrence it uses and does not repeat.
+tests/baked_ref.py and tests/baked_sh_ref.py, whose definitions, grids, rays and sample statements it calls and does not repeat;
+`march` adds what the upstream gradients make of a ray's visited samples, for this file's scatter and for baked_pose_ref.
 Shared by tests/test_baked_tune_cpu.py and tests/test_hip_baked_tune.py.
 
     grad(points, degree, bounds, rays, step, background, stop, g_rgb, g_depth, g_opacity, gates=True) -> dict
@@ -37,6 +38,8 @@ The gates (u = 2^-24), first order, every constant a count of roundings; baked_r
   element  a contribution wt X is off by dwt |X| + wt dX + 5 u |wt X|; the sum of an element's n contributions, in registers and in
            memory in whatever order they arrive, by n u sum |contribution|.
   Y_j      (degree > 0) baked_sh_ref's dY_j = N_j u m_j, and the product one rounding: |share| (N_j m_j + |Y_j|) u."""
+from types import SimpleNamespace
+
 import numpy as np
 
 import baked_ref as br
@@ -49,77 +52,56 @@ def _hat(x):
     return np.maximum(0.0, 1.0 - np.abs(x))
 
 
-def _ray(grid, dcol, clamp, lo, hi, C, row, step, background, stop, gr, gd, go, gates):
-    """The contributions of one ray: (point index [m, 3] as (z, y, x), value [m, 4], error [m, 4], stop margin) or None."""
-    o, d, near, far = row[:3], row[3:6], row[6], row[7]
-    if not np.isfinite(row).all() or not far > near or (not gr.any() and gd == 0 and go == 0):
+def march(grid, dcol, clamp, lo, hi, C, row, step, background, stop, gr, gd, go, gates, apart=False, omit_open=False):
+    """The visited samples of one ray and what the upstream gradients make of them, or None for a miss or a ray whose upstream
+    gradients are all zero.  Per visited sample: t, g, dg, v (clamped), dv, w, dw; n of them, delta, inv and the stop margin; and
+    with n > 0 the docstring's q, suffix and sigma gates as inner, dinner, and a, da [n, 4]: a[c] = w g_rgb[c] on the open
+    channels (else 0) with the gate `colour`, a[sigma] = delta inner with the gate `sigma`.  apart: baked_ref.blended's;
+    omit_open: the mask is left out (baked_pose_ref plants it)."""
+    lat = br.lattice(lo, hi, C, row, step)
+    if lat is None or (not gr.any() and gd == 0 and go == 0):
         return None
-    K = br.n_samples(near, far, step)
-    t = near + (np.arange(K, dtype=np.float64) + 0.5) * step
-    inv = C / (hi - lo)
-    p = o + t[:, None] * d
-    g = (p - lo) * inv
-    v, inside, cmax = br.trilinear(grid, g, C)
-    dg = U * (inv * (np.abs(t[:, None] * d) + np.abs(p) + np.abs(p - lo)) + 2 * np.abs(g))
-    dv = np.zeros_like(v)
-    if gates:
-        dv = 9 * U * cmax + (br.trilinear(dcol, g, C)[2] if dcol is not None else 0.0)
-        for a in range(3):
-            e = np.zeros(3)
-            e[a] = 1.0
-            worst = np.zeros_like(v)
-            for s in (-1.0, 1.0):
-                moved = np.clip(g + s * dg[:, a:a + 1] * e, 0.0, C)
-                worst = np.maximum(worst, np.abs(br.trilinear(grid, moved, C)[0] - v))
-            dv = dv + worst
+    t, g, dg, inv = lat
+    v, inside, dv = br.blended(grid, g, dg, C, dcol, gates, apart)
     raw = v[:, :3].copy()
     if clamp:
         v[:, :3] = np.clip(raw, 0.0, 1.0)
-    delta = step * np.sqrt((d * d).sum())
-    x = delta * v[:, 3]
-    ex = np.exp(-x)
-    alpha = -np.expm1(-x)
-    dalpha = ex * (6 * U * np.abs(x) + delta * dv[:, 3] + 2 * U) + U * np.abs(alpha)
-    ks, w, dw, Tn, dTn = [], [], [], [], []
-    T, dT, margin = 1.0, 0.0, np.inf
-    for k in np.nonzero(inside)[0]:  # (baked_ref's recurrence)
-        a_k = alpha[k]
-        ks.append(k), w.append(T * a_k), dw.append(dT * a_k + T * dalpha[k] + U * T * a_k)
-        T2 = T * (1.0 - a_k)
-        dT = dT * (1.0 - a_k) + T * (dalpha[k] + U * (1.0 - a_k)) + U * T2
-        T = T2
-        Tn.append(T), dTn.append(dT)
-        if stop > 0:
-            margin = min(margin, abs(T - stop) - dT)
-            if T < stop:
-                break
-    if not ks:
-        return None
-    ks = np.asarray(ks)
-    w, dw, Tn, dTn = (np.asarray(z) for z in (w, dw, Tn, dTn))
+    delta, _, _, alpha, dalpha = br.alphas(v[:, 3], dv[:, 3], row[3:6], step)
+    ks, w, dw, Tn, dTn, margin = br.visited(alpha, dalpha, inside, stop)
     n = ks.size
-    c, tk, dvk, rawk = v[ks, :3], t[ks], dv[ks], raw[ks]
-    q = (c - background) @ gr + gd * (tk - far) + go
-    mq = np.abs(c - background) @ np.abs(gr) + abs(gd) * np.abs(tk - far) + abs(go)
-    dq = dvk[:, :3] @ np.abs(gr) + abs(gd) * U * np.abs(tk) + 5 * U * mq
+    m = SimpleNamespace(t=t[ks], g=g[ks], dg=dg[ks], v=v[ks], dv=dv[ks], w=w, dw=dw, n=n, delta=delta, inv=inv, margin=margin)
+    if n == 0:
+        return m
+    c, rawk, far = m.v[:, :3], raw[ks], row[7]
+    q = (c - background) @ gr + gd * (m.t - far) + go
+    mq = np.abs(c - background) @ np.abs(gr) + abs(gd) * np.abs(m.t - far) + abs(go)
+    dq = m.dv[:, :3] @ np.abs(gr) + abs(gd) * U * np.abs(m.t) + 5 * U * mq
     wq = w * q
     dwq = dw * np.abs(q) + w * dq + U * np.abs(wq)
     after = lambda z: np.concatenate([np.cumsum(z[::-1])[::-1][1:], [0.0]])  # sum over the later samples
     S, dS = after(wq), after(dwq) + (n + 2) * U * np.abs(wq).sum()
-    inner = Tn * q - S
-    dinner = dTn * np.abs(q) + Tn * dq + dS + U * np.abs(inner)
-    X, dX = np.zeros((n, 4)), np.zeros((n, 4))
-    X[:, 3] = delta * inner
-    dX[:, 3] = delta * dinner + 6 * U * np.abs(X[:, 3])
-    is_open = (rawk >= 0) & (rawk <= 1) if clamp else np.ones_like(rawk, bool)
+    m.inner = Tn * q - S
+    m.dinner = dTn * np.abs(q) + Tn * dq + dS + U * np.abs(m.inner)
+    m.a, m.da = np.zeros((n, 4)), np.zeros((n, 4))
+    m.a[:, 3] = delta * m.inner
+    m.da[:, 3] = delta * m.dinner + 6 * U * np.abs(m.a[:, 3])
+    is_open = (rawk >= 0) & (rawk <= 1) if clamp and not omit_open else np.ones_like(rawk, bool)
     full = w[:, None] * gr
-    X[:, :3] = np.where(is_open, full, 0.0)
-    dX[:, :3] = dw[:, None] * np.abs(gr) + U * np.abs(full)
+    m.a[:, :3] = np.where(is_open, full, 0.0)
+    m.da[:, :3] = dw[:, None] * np.abs(gr) + U * np.abs(full)
     if clamp:
-        edge = (np.abs(rawk) <= dvk[:, :3]) | (np.abs(rawk - 1) <= dvk[:, :3])
-        dX[:, :3] += np.where(edge, np.abs(full), 0.0)
+        edge = (np.abs(rawk) <= m.dv[:, :3]) | (np.abs(rawk - 1) <= m.dv[:, :3])
+        m.da[:, :3] += np.where(edge, np.abs(full), 0.0)
+    return m
+
+
+def _ray(grid, dcol, clamp, lo, hi, C, row, step, background, stop, gr, gd, go, gates):
+    """The contributions of one ray: (point index [m, 3] as (z, y, x), value [m, 4], error [m, 4], stop margin) or None."""
+    m = march(grid, dcol, clamp, lo, hi, C, row, step, background, stop, gr, gd, go, gates)
+    if m is None or m.n == 0:
+        return None
+    n, gk, dgk, X, dX, margin = m.n, m.g, m.dg, m.a, m.da, m.margin
     # the weights of the 4 x 4 x 4 points round each sample's cell, and what a moved sample changes of them
-    gk, dgk = g[ks], dg[ks]
     i = np.minimum(np.floor(gk), C - 1)
     cand = i[:, :, None] + np.arange(-1, 3)  # [n, axis, 4]
     valid = (cand >= 0) & (cand <= C[None, :, None])
@@ -145,23 +127,24 @@ def _ray(grid, dcol, clamp, lo, hi, C, row, step, background, stop, gr, gd, go, 
     return np.stack([cz, cy, cx], 1), val, err, margin
 
 
-def grad(points, degree, bounds, rays, step, background=0.0, stop=0.0, g_rgb=None, g_depth=None, g_opacity=None, gates=True):
-    lo, hi = br.bounds64(bounds)
-    rays = np.asarray(rays, np.float32).astype(np.float64)
-    step, background, stop = (float(np.float32(z)) for z in (step, background, stop))
-    R = rays.shape[0]
-    g_rgb = np.asarray(g_rgb, np.float64)
-    g_depth = np.zeros(R) if g_depth is None else np.asarray(g_depth, np.float64)
-    g_opacity = np.zeros(R) if g_opacity is None else np.asarray(g_opacity, np.float64)
+def points64(points, degree):
+    """(k or None, sigma, rgbs or None) in fp64 of points as `grad` takes them, not rounded to fp32."""
     if degree == 0:
         grid = np.asarray(points, np.float64)
-        sigma = grid[..., 3]
-        nb = 0
-    else:
-        k, sigma = (np.asarray(z, np.float64) for z in points)
-        nb = sh.NB[degree]
-    shape = sigma.shape
-    C = np.array(shape[::-1], np.float64) - 1
+        return None, grid[..., 3], grid
+    k, sigma = (np.asarray(z, np.float64) for z in points)
+    return k, sigma, None
+
+
+def upstream64(R, g_rgb, g_depth, g_opacity):
+    return np.asarray(g_rgb, np.float64), *(np.zeros(R) if z is None else np.asarray(z, np.float64) for z in (g_depth, g_opacity))
+
+
+def grad(points, degree, bounds, rays, step, background=0.0, stop=0.0, g_rgb=None, g_depth=None, g_opacity=None, gates=True):
+    k, sigma, grid = points64(points, degree)
+    lo, hi, C, rays, step, background, stop = br.args64(bounds, rays, sigma.shape, step, background, stop)
+    R, shape, nb = rays.shape[0], sigma.shape, sh.NB.get(degree, 0)
+    g_rgb, g_depth, g_opacity = upstream64(R, g_rgb, g_depth, g_opacity)
     live = sigma != 0
     out4, gate4, abs4 = (np.zeros(shape + (4,)) for _ in range(3))
     count = np.zeros(shape)
@@ -174,11 +157,7 @@ def grad(points, degree, bounds, rays, step, background=0.0, stop=0.0, g_rgb=Non
             d = rays[r, 3:6]
             if not np.isfinite(rays[r]).all() or not (d * d).sum() > 0:
                 continue
-            unit = d / np.sqrt((d * d).sum())
-            Y, m = sh.basis(unit, degree)[0], sh.basis_magnitude(unit, degree)
-            grid = np.concatenate([k @ Y, sigma[..., None]], -1)
-            if gates:
-                dcol = np.concatenate([U * (np.abs(k) * ((nb + sh.N_BASIS[:nb]) * m)).sum(-1), np.zeros(shape + (1,))], -1)
+            grid, dcol, Y, m = sh.ray_grid(k, sigma, d, degree, gates)
         res = _ray(grid, dcol, degree > 0, lo, hi, C, rays[r], step, background, stop, g_rgb[r], g_depth[r], g_opacity[r], gates)
         if res is None:
             continue
@@ -204,23 +183,17 @@ def grad(points, degree, bounds, rays, step, background=0.0, stop=0.0, g_rgb=Non
 
 
 def render64(points, degree, bounds, rays, step, background=0.0, stop=0.0):
-    """(rgb [R, 3], depth [R], opacity [R]) of fp64 parameters: baked_ref's / baked_sh_ref's render_ray on numbers that are NOT
-    rounded to fp32 first (a central difference needs the parameters as they are given)."""
-    lo, hi = br.bounds64(bounds)
-    rays = np.asarray(rays, np.float32).astype(np.float64)
-    step, background, stop = (float(np.float32(z)) for z in (step, background, stop))
+    """(rgb [R, 3], depth [R], opacity [R]) of fp64 parameters: baked_ref.render_ray on numbers that are NOT rounded to fp32
+    first (a central difference needs the parameters as they are given)."""
+    k, sigma, grid = points64(points, degree)
+    lo, hi, C, rays, step, background, stop = br.args64(bounds, rays, sigma.shape, step, background, stop)
     R = rays.shape[0]
     rgb, depth, op = np.zeros((R, 3)), np.zeros(R), np.zeros(R)
-    if degree == 0:
-        grid = np.asarray(points, np.float64)
-        C = np.array(grid.shape[2::-1], np.float64) - 1
-        for r in range(R):
-            rgb[r], depth[r], op[r] = br.render_ray(grid, lo, hi, C, rays[r], step, background, stop)[:3]
-    else:
-        k, sigma = (np.asarray(z, np.float64) for z in points)
-        C = np.array(sigma.shape[::-1], np.float64) - 1
-        for r in range(R):
-            rgb[r], depth[r], op[r] = sh.render_ray(k, sigma, lo, hi, C, rays[r], step, background, stop, degree)[:3]
+    for r in range(R):
+        dcol = None
+        if degree:
+            grid, dcol = sh.ray_grid(k, sigma, rays[r, 3:6], degree)[:2]
+        rgb[r], depth[r], op[r] = br.render_ray(grid, lo, hi, C, rays[r], step, background, stop, dcol, clamp=degree > 0)[:3]
     return rgb, depth, op
 
 

@@ -80,34 +80,25 @@ def deltas(parent, degree):
 
 
 def render_gate(child, parent, degree, bounds, rays, step, background=0.0):
-    lo, hi = br.bounds64(bounds)
-    rays = np.asarray(rays, np.float32).astype(np.float64)
-    step, background = float(np.float32(step)), float(np.float32(background))
     d_all = deltas(parent, degree)
+    lo, hi, C, rays, step, background, _ = br.args64(bounds, rays, d_all.shape, step, background)
     if degree == 0:
         grid = numbers(child, 0)
         dgrid = d_all
     else:
         k, sigma = numbers(child, degree)
-        nb = sh.NB[degree]
-        dk = d_all[..., :-1].reshape(sigma.shape + (3, nb))
-    C = np.array(d_all.shape[2::-1], np.float64) - 1
+        dk = d_all[..., :-1].reshape(sigma.shape + (3, sh.NB[degree]))
     R = rays.shape[0]
     g_rgb, g_depth, g_op = np.zeros((R, 3)), np.zeros(R), np.zeros(R)
     for r in range(R):
-        row = rays[r]
-        o, d, near, far = row[:3], row[3:6], row[6], row[7]
-        if not np.isfinite(row).all() or not far > near:
+        d, far = rays[r, 3:6], rays[r, 7]
+        lat = br.lattice(lo, hi, C, rays[r], step)
+        if lat is None or (degree and not (d * d).sum() > 0):
             continue
         if degree:
-            if not (d * d).sum() > 0:
-                continue
-            Y = sh.basis(d / np.sqrt((d * d).sum()), degree)[0]
-            grid = np.concatenate([k @ Y, sigma[..., None]], -1)
+            grid, _, Y, _ = sh.ray_grid(k, sigma, d, degree, gates=False)
             dgrid = np.concatenate([dk @ np.abs(Y), d_all[..., -1:]], -1)
-        K = br.n_samples(near, far, step)
-        t = near + (np.arange(K, dtype=np.float64) + 0.5) * step
-        g = (o + t[:, None] * d - lo) * (C / (hi - lo))
+        t, g = lat[:2]
         v, inside, _ = br.trilinear(grid, g, C)
         dv = br.trilinear(dgrid, g, C)[0]
         if degree:
@@ -116,7 +107,7 @@ def render_gate(child, parent, degree, bounds, rays, step, background=0.0):
         alpha = -np.expm1(-dl * v[:, 3])
         dalpha = np.exp(-dl * v[:, 3]) * dl * dv[:, 3]
         T, dT = 1.0, 0.0
-        for i in np.nonzero(inside)[0]:
+        for i in np.nonzero(inside)[0]:  # (no rounding terms: the shared recurrence does not state this one)
             a = alpha[i]
             w, dw = T * a, dT * a + T * dalpha[i]
             g_rgb[r] += dw * np.abs(v[i, :3]) + w * dv[i, :3]

@@ -14,7 +14,9 @@ import numpy as np
 import pytest
 import torch
 
+import baked_cases as cases
 import baked_ref as br
+from baked_cases import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +28,6 @@ GRIDS = {"blob": br.blob_grid, "corners": br.corner_grid}
 _CACHE = {}
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def steps(rgbs):
     cell = br.cell_size(rgbs)
     return {"coarse": float(np.float32(3 * cell)), "fine": float(np.float32(cell / 30))}
@@ -37,12 +35,8 @@ def steps(rgbs):
 
 def scene_of(name):
     """(BakedScene, rgbs) of a test grid, built once (from_grids prunes again what the reference pruned: the same grid)."""
-    if name not in _CACHE:
-        from upnerf_amd.baked import BakedScene
-        rgbs, level = GRIDS[name]()
-        scene = BakedScene.from_grids(dev(rgbs[..., 3]), dev(rgbs[..., :3]), br.BOUNDS, level)
-        _CACHE[name] = (scene, rgbs)
-    return _CACHE[name]
+    rgbs, level = GRIDS[name]()
+    return cases.scene_of((__name__, name), lambda: cases.build(rgbs, level)), rgbs
 
 
 def reference(name, step, background):
@@ -167,8 +161,7 @@ IMG = 4
 
 @pytest.fixture(scope="module")
 def system():
-    from test_hip_tsdf import make_system  # the synthetic system of the scene-tool tests: trained-like fields, posed cameras
-    return make_system()
+    return cases.make_system()
 
 
 def oracle_rgb(system, view_dir, img_id):

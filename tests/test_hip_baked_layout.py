@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 import torch
 
+import baked_cases as cases
 import baked_ref as br
+from baked_cases import dev
 from test_hip_baked_sparse import CELLS, pattern
 
 pytestmark = pytest.mark.gpu
@@ -19,10 +21,6 @@ pytestmark = pytest.mark.gpu
 CELL = CELLS[1]
 STEP = 0.05
 _CACHE = {}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def rays():
@@ -38,25 +36,20 @@ def environment():
 
 def scene_of(degree, sparse=False):
     """The test scene at a degree, dense or its sparsify(); built once and never changed."""
-    key = ("scene", degree, sparse)
-    if key not in _CACHE:
+    def make():
         from upnerf_amd.baked import BakedScene, sphere_directions
-        if sparse:
-            _CACHE[key] = scene_of(degree).sparsify()
-        else:
-            Cx, Cy, Cz = CELL
-            rng = np.random.RandomState(7)
-            sigma = np.zeros((Cz + 1, Cy + 1, Cx + 1), np.float32)
-            sigma[:Cz, :Cy, :Cx] = np.where(pattern(CELL, "seeded"), rng.uniform(2, 30, (Cz, Cy, Cx)), 0)
-            sigma[:, 15:] = 0
-            if degree == 0:
-                rgb = rng.uniform(0, 1, sigma.shape + (3,)).astype(np.float32)
-                _CACHE[key] = BakedScene.from_grids(dev(sigma), dev(rgb), br.BOUNDS, 0.0)
-            else:
-                dirs = sphere_directions(12)
-                rgb = rng.uniform(0, 1, (12,) + sigma.shape + (3,)).astype(np.float32)
-                _CACHE[key] = BakedScene.from_direction_grids(dev(sigma), dev(rgb), dirs, br.BOUNDS, 0.0, sh_degree=degree)
-    return _CACHE[key]
+        Cx, Cy, Cz = CELL
+        rng = np.random.RandomState(7)
+        sigma = np.zeros((Cz + 1, Cy + 1, Cx + 1), np.float32)
+        sigma[:Cz, :Cy, :Cx] = np.where(pattern(CELL, "seeded"), rng.uniform(2, 30, (Cz, Cy, Cx)), 0)
+        sigma[:, 15:] = 0
+        if degree == 0:
+            rgb = rng.uniform(0, 1, sigma.shape + (3,)).astype(np.float32)
+            return BakedScene.from_grids(dev(sigma), dev(rgb), br.BOUNDS, 0.0)
+        dirs = sphere_directions(12)
+        rgb = rng.uniform(0, 1, (12,) + sigma.shape + (3,)).astype(np.float32)
+        return BakedScene.from_direction_grids(dev(sigma), dev(rgb), dirs, br.BOUNDS, 0.0, sh_degree=degree)
+    return cases.scene_of((__name__, degree), make, sparse)
 
 
 # ---- 1. the launches -----------------------------------------------------------------------------------------------------------------

@@ -11,10 +11,12 @@ import numpy as np
 import pytest
 import torch
 
+import baked_cases as cases
 import baked_pose_ref as pr
 import baked_ref as br
 import baked_sh_ref as sh
 import baked_tune_ref as tr
+from baked_cases import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -22,31 +24,15 @@ _CACHE = {}
 SETTINGS = {"bg0-all": (0.0, 0.0, True), "bg1-stop-rgb": (1.0, 1e-3, False)}  # (those of tests/test_hip_baked_tune.py)
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def rays_all(name):
-    return np.concatenate([br.make_rays(), tr.extra_rays(sh.GRIDS[name]()[0])])
+    return cases.rays_all(sh.GRIDS[name]()[0])
 
 
 def scene_of(name, degree, sparse=False):
     """(BakedScene, the numbers the reference differentiates: rgbs, or (k, sigma) of the stored records)."""
-    key = ("scene", name, degree)
-    if key not in _CACHE:
-        from upnerf_amd.baked import BakedScene
-        if degree == 0:
-            rgbs, level = sh.GRIDS[name]()
-            _CACHE[key] = (BakedScene.from_grids(dev(rgbs[..., 3]), dev(rgbs[..., :3]), br.BOUNDS, level), rgbs)
-        else:
-            records, level = sh.sh_grid(name, degree)
-            _CACHE[key] = (BakedScene.from_records(dev(records), br.BOUNDS, level, degree), sh.unpack(records, degree))
-    scene, numbers = _CACHE[key]
-    if sparse:
-        if key + ("sparse",) not in _CACHE:
-            _CACHE[key + ("sparse",)] = scene.sparsify()
-        scene = _CACHE[key + ("sparse",)]
-    return scene, numbers
+    points, level = sh.GRIDS[name]() if degree == 0 else sh.sh_grid(name, degree)
+    scene = cases.scene_of((__name__, name, degree), lambda: cases.build(points, level, degree), sparse)
+    return scene, points if degree == 0 else sh.unpack(points, degree)
 
 
 def reference(name, degree, setting):

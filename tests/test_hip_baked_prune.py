@@ -15,12 +15,14 @@ import numpy as np
 import pytest
 import torch
 
+import baked_cases as cases
 import baked_prune_ref as pr
 import baked_ref as br
 import baked_sh_ref as sh
 import baked_sparse_ref as sr
 import baked_sparse_tune_ref as ft
 import baked_tune_ref as tr
+from baked_cases import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -28,10 +30,6 @@ _CACHE = {}
 F32 = np.float32
 GRIDS = {"blob": br.blob_grid, "corners": br.corner_grid, "ragged": pr.ragged_grid, "wall": pr.wall_grid}
 STOPS = (0.0, 1e-3)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def grid_of(name):
@@ -52,18 +50,9 @@ def steps_of(name):
 
 
 def scene_of(name, degree=0, sparse=False):
-    key = ("scene", name, degree, sparse)
-    if key not in _CACHE:
-        from upnerf_amd.baked import BakedScene
-        rgbs, level = grid_of(name)
-        if sparse:
-            _CACHE[key] = scene_of(name, degree).sparsify()
-        elif degree == 0:
-            _CACHE[key] = BakedScene.from_grids(dev(rgbs[..., 3]), dev(rgbs[..., :3]), br.BOUNDS, level)
-        else:
-            records = sh.pack(sh.coefficients(rgbs[..., 3].shape, degree, 31 + degree), rgbs[..., 3], level, degree)[0]
-            _CACHE[key] = BakedScene.from_records(dev(records), br.BOUNDS, level, degree)
-    return _CACHE[key]
+    rgbs, level = grid_of(name)
+    records = lambda: sh.pack(sh.coefficients(rgbs[..., 3].shape, degree, 31 + degree), rgbs[..., 3], level, degree)[0]
+    return cases.scene_of((__name__, name, degree), lambda: cases.build(rgbs if degree == 0 else records(), level, degree), sparse)
 
 
 def reference(name, step_name, stop):
@@ -316,8 +305,7 @@ def test_tuner_pruned_keeps_kind_and_settings_resets_adam_and_still_learns(spars
 
 @pytest.fixture(scope="module")
 def system():
-    from test_hip_tsdf import make_system  # the synthetic system of the existing distill tests
-    return make_system()
+    return cases.make_system()
 
 
 @pytest.mark.parametrize("sparse", [False, True])

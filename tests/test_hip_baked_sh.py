@@ -12,8 +12,10 @@ import numpy as np
 import pytest
 import torch
 
+import baked_cases as cases
 import baked_ref as br
 import baked_sh_ref as sh
+from baked_cases import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -21,18 +23,10 @@ _CACHE = {}
 U = sh.U
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def scene_of(name, degree):
     """(BakedScene, records) of a test grid, built once."""
-    key = ("scene", name, degree)
-    if key not in _CACHE:
-        from upnerf_amd.baked import BakedScene
-        records, level = sh.sh_grid(name, degree)
-        _CACHE[key] = (BakedScene.from_records(dev(records), br.BOUNDS, level, degree), records)
-    return _CACHE[key]
+    records, level = sh.sh_grid(name, degree)
+    return cases.scene_of((__name__, name, degree), lambda: cases.build(records, level, degree)), records
 
 
 def reference(name, degree, step, background):
@@ -227,8 +221,7 @@ IMG = 4
 
 @pytest.fixture(scope="module")
 def system():
-    from test_hip_tsdf import make_system
-    return make_system()
+    return cases.make_system()
 
 
 def test_build_is_from_direction_grids_on_the_fields_own_grids(system):

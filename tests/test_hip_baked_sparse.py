@@ -13,18 +13,15 @@ import numpy as np
 import pytest
 import torch
 
+import baked_cases as cases
 import baked_ref as br
 import baked_sh_ref as sh
 import baked_sparse_ref as sr
+from baked_cases import dev
 
 pytestmark = pytest.mark.gpu
 
 CELLS = [(8, 8, 8), (9, 17, 5), (20, 12, 33)]  # one brick; 2 x 3 x 1 bricks, ragged on every axis; 3 x 2 x 5 bricks
-_CACHE = {}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def host_words(words):
@@ -95,16 +92,7 @@ def test_table_gather_scatter_and_bits_are_the_restatements_byte_for_byte(cells,
 
 def dense_scene(name, degree):
     """A test grid of baked_ref as a dense scene of the degree (the SH records are baked_sh_ref's), built once."""
-    key = (name, degree)
-    if key not in _CACHE:
-        from upnerf_amd.baked import BakedScene
-        if degree == 0:
-            rgbs, level = sh.GRIDS[name]()
-            _CACHE[key] = BakedScene.from_grids(dev(rgbs[..., 3]), dev(rgbs[..., :3]), br.BOUNDS, level)
-        else:
-            records, level = sh.sh_grid(name, degree)
-            _CACHE[key] = BakedScene.from_records(dev(records), br.BOUNDS, level, degree)
-    return _CACHE[key]
+    return cases.scene_of((__name__, name, degree), lambda: cases.build(*(sh.GRIDS[name]() if degree == 0 else sh.sh_grid(name, degree)), degree))
 
 
 @pytest.mark.parametrize("name", ["blob", "corners"])
@@ -189,8 +177,7 @@ IMG = 4
 
 @pytest.fixture(scope="module")
 def system():
-    from test_hip_tsdf import make_system
-    return make_system()
+    return cases.make_system()
 
 
 def test_the_sparse_bake_is_the_dense_bake_sparsified_bit_for_bit(system):

@@ -15,13 +15,15 @@ import numpy as np
 import pytest
 import torch
 
+import baked_cases as cases
 import baked_ref as br
 import baked_sh_ref as sh
 import baked_sparse_ref as sr
 import baked_sparse_tune_ref as ft
 import baked_tune_ref as tr
 from test_hip_baked_sparse import CELLS, pattern
-from test_hip_baked_tune import SETTINGS, dev, within
+from baked_cases import dev
+from test_hip_baked_tune import SETTINGS, within
 
 pytestmark = pytest.mark.gpu
 
@@ -48,18 +50,12 @@ def numbers(name, degree):
 
 def scene_of(name, degree):
     """The sparse scene of a grid (the dense scene's sparsify())."""
-    key = ("scene", name, degree)
-    if key not in _CACHE:
-        from upnerf_amd.baked import BakedScene
-        pts, records, level = numbers(name, degree)
-        dense = BakedScene.from_grids(dev(pts[..., 3]), dev(pts[..., :3]), br.BOUNDS, level) if degree == 0 else \
-            BakedScene.from_records(dev(records), br.BOUNDS, level, degree)
-        _CACHE[key] = dense.sparsify()
-    return _CACHE[key]
+    pts, records, level = numbers(name, degree)
+    return cases.scene_of((__name__, name, degree), lambda: cases.build(pts if degree == 0 else records, level, degree), sparse=True)
 
 
 def rays_of(name):
-    return np.concatenate([br.make_rays(), tr.extra_rays(GRIDS[name]()[0])])  # the 132 rays of tests/test_hip_baked_tune.py
+    return cases.rays_all(GRIDS[name]()[0])
 
 
 def to_pool(ref, degree, bricks):
@@ -342,8 +338,7 @@ def test_the_pool_tuner_brings_a_perturbed_scene_back_and_keeps_the_copies_ident
 
 @pytest.fixture(scope="module")
 def system():
-    from test_hip_tsdf import make_system
-    return make_system()
+    return cases.make_system()
 
 
 def test_distill_on_a_sparse_bake_lowers_the_loss_and_keeps_the_bricks(system):

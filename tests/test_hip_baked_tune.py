@@ -13,9 +13,11 @@ import numpy as np
 import pytest
 import torch
 
+import baked_cases as cases
 import baked_ref as br
 import baked_sh_ref as sh
 import baked_tune_ref as tr
+from baked_cases import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -24,26 +26,15 @@ _CACHE = {}
 SETTINGS = {"bg0-all": (0.0, 0.0, True), "bg1-stop-rgb": (1.0, 1e-3, False)}
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def rays_all(name):
-    return np.concatenate([br.make_rays(), tr.extra_rays(sh.GRIDS[name]()[0])])
+    return cases.rays_all(sh.GRIDS[name]()[0])
 
 
 def scene_of(name, degree):
     """(BakedScene, the numbers the reference differentiates: rgbs, or (k, sigma) of the stored records)."""
-    key = ("scene", name, degree)
-    if key not in _CACHE:
-        from upnerf_amd.baked import BakedScene
-        if degree == 0:
-            rgbs, level = sh.GRIDS[name]()
-            _CACHE[key] = (BakedScene.from_grids(dev(rgbs[..., 3]), dev(rgbs[..., :3]), br.BOUNDS, level), rgbs)
-        else:
-            records, level = sh.sh_grid(name, degree)
-            _CACHE[key] = (BakedScene.from_records(dev(records), br.BOUNDS, level, degree), sh.unpack(records, degree))
-    return _CACHE[key]
+    points, level = sh.GRIDS[name]() if degree == 0 else sh.sh_grid(name, degree)
+    scene = cases.scene_of((__name__, name, degree), lambda: cases.build(points, level, degree))
+    return scene, points if degree == 0 else sh.unpack(points, degree)
 
 
 def reference(name, step, degree, setting):
@@ -233,8 +224,7 @@ def test_the_tuner_brings_a_perturbed_scene_back_towards_its_targets(degree):
 
 @pytest.fixture(scope="module")
 def system():
-    from test_hip_tsdf import make_system  # the synthetic system of the scene-tool tests: trained-like fields, posed cameras
-    return make_system()
+    return cases.make_system()
 
 
 def test_distill_lowers_the_loss_against_the_fields_own_renders(system):

@@ -11,19 +11,17 @@ import numpy as np
 import pytest
 import torch
 
+import baked_cases as cases
 import baked_ref as br
 import baked_sparse_ref as sr
 import baked_tv_ref as tvr
+from baked_cases import dev
 
 pytestmark = pytest.mark.gpu
 
 _CACHE = {}
 FS = [1, 4, 12, 27]
 EPS = [1e-8, 1.0]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def grid(name):
@@ -191,11 +189,8 @@ def missing_rays(R=16):
 
 
 def scene_of(degree, sparse):
-    from upnerf_amd.baked import BakedScene
     import baked_upsample_ref as ur
-    points, level = ur.parents("big", degree)
-    dense = BakedScene.from_grids(dev(points[..., 3]), dev(points[..., :3]), br.BOUNDS, level) if degree == 0 else \
-        BakedScene.from_records(dev(points), br.BOUNDS, level, degree)
+    dense = cases.build(*ur.parents("big", degree), degree)  # (built anew at every call)
     return dense.sparsify() if sparse else dense
 
 

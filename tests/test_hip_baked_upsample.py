@@ -17,31 +17,22 @@ import numpy as np
 import pytest
 import torch
 
+import baked_cases as cases
 import baked_ref as br
 import baked_sh_ref as sh
 import baked_sparse_ref as sr
 import baked_tune_ref as tr
 import baked_tv_ref as tvr
 import baked_upsample_ref as ur
+from baked_cases import dev
 
 pytestmark = pytest.mark.gpu
 
-_CACHE = {}
 TINY = float(ur.TINY)
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def scene_of(name, degree):
-    key = ("scene", name, degree)
-    if key not in _CACHE:
-        from upnerf_amd.baked import BakedScene
-        points, level = ur.parents(name, degree)
-        _CACHE[key] = BakedScene.from_grids(dev(points[..., 3]), dev(points[..., :3]), br.BOUNDS, level) if degree == 0 else \
-            BakedScene.from_records(dev(points), br.BOUNDS, level, degree)
-    return _CACHE[key]
+    return cases.scene_of((__name__, name, degree), lambda: cases.build(*ur.parents(name, degree), degree))
 
 
 def host(t):
@@ -138,8 +129,7 @@ def test_tuner_upsampled_doubles_the_cells_and_resets_adam(sparse):
 
 @pytest.fixture(scope="module")
 def system():
-    from test_hip_tsdf import make_system  # the synthetic system of the existing distill tests
-    return make_system()
+    return cases.make_system()
 
 
 @pytest.mark.parametrize("sparse", [False, True])
