@@ -16,6 +16,7 @@ import field_cases
 import kernel_space as ks
 from field_cases import TOL_ACT, TOL_GRAD, check_field_pass
 from golden_util import GOLDEN, Case, orc, rel_err
+from prologue_ref import philox_uniform
 
 pytestmark = pytest.mark.gpu
 
@@ -1567,24 +1568,9 @@ def test_flat_adam_follows_torch_adam_including_skipped_parameters():
     assert rel_err(sd["state"][4]["exp_avg"].cpu(), o_ref.state_dict()["state"][4]["exp_avg"]) < 2e-6
 
 
-def _philox4x32_10(c, k):
-    """numpy restatement of Philox4x32-10 (Salmon et al., SC'11): c [N,4] uint32 counters, k (k0, k1)."""
-    import numpy as np
-    c = c.astype(np.uint64).copy()
-    k0, k1 = np.uint64(k[0]), np.uint64(k[1])
-    M0, M1, MASK = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = M0 * c[:, 0], M1 * c[:, 2]
-        n0 = ((p1 >> np.uint64(32)) ^ c[:, 1] ^ k0) & MASK
-        n2 = ((p0 >> np.uint64(32)) ^ c[:, 3] ^ k1) & MASK
-        c = np.stack([n0, p1 & MASK, n2, p0 & MASK], 1)
-        k0 = (k0 + np.uint64(0x9E3779B9)) & MASK
-        k1 = (k1 + np.uint64(0xBB67AE85)) & MASK
-    return c.astype(np.uint32)
-
-
 def test_keyed_uniform_draws_follow_the_philox_spec_and_the_global_row(hip):
-    """upnerf_uniform_keyed: values = Philox4x32-10(counter (row0 + r, c / 4, step, draw), key seed) >> 8 scaled by 2^-24;
+    """upnerf_uniform_keyed: values = Philox4x32-10(counter (row0 + r, c / 4, step, draw), key seed) >> 8 scaled by 2^-24
+    (the numpy restatement: tests/prologue_ref.py, held to the published known answers by tests/test_prologue_ref_cpu.py);
     a batch drawn in two halves with their global row offsets equals the batch drawn at once (rank-count invariance,
     SURVEY.md 8e); the step can come from device memory (graph replay)."""
     import numpy as np
@@ -1592,11 +1578,8 @@ def test_keyed_uniform_draws_follow_the_philox_spec_and_the_global_row(hip):
     R, n, seed, step, draw = 37, 90, 0x1234567890ABCDEF, 4711, 2
     out = torch.empty(R, n, device="cuda")
     check(lib.upnerf_uniform_keyed(R, n, seed, step, None, 100, 1, draw, ptr(out), stream()), "uniform")
-    q4 = (n + 3) // 4
-    rr, qq = np.meshgrid(np.arange(R), np.arange(q4), indexing="ij")
-    ctr = np.stack([100 + rr.ravel(), qq.ravel(), np.full(R * q4, step), np.full(R * q4, draw)], 1).astype(np.uint32)
-    ref = _philox4x32_10(ctr, (seed & 0xFFFFFFFF, seed >> 32)).reshape(R, q4 * 4)[:, :n]
-    ref = (ref >> 8).astype(np.float32) * np.float32(2.0 ** -24)
+    ref = philox_uniform(seed, step, 100 + np.arange(R), n, draw)
+    assert ref.dtype == np.float32 and ref.shape == (R, n)
     assert np.array_equal(cpu(out).numpy(), ref)
     assert 0.0 <= float(out.min()) and float(out.max()) < 1.0 and abs(float(out.mean()) - 0.5) < 0.03
     a, b = torch.empty(20, n, device="cuda"), torch.empty(17, n, device="cuda")

@@ -848,7 +848,8 @@ extern "C" int upnerf_gather_rays(const upnerf_gather_rays_args* a, void* stream
   if (!a || a->R <= 0 || !a->idx || !a->all_ray_infos || !a->all_directions || !a->all_rgbs || !a->poses || !a->ray_infos ||
       !a->directions || !a->img_idx || !a->c2w || !a->rgbs)
     return UPNERF_EINVAL;
-  if (a->feats && (!a->feat_maps || !a->all_pxl_coords || a->h < 2 || a->C <= 0)) return UPNERF_EINVAL;
+  // h == 1: a one-pixel map; both weights of each axis vanish there (the last row / column rule), the feature is the zero vector
+  if (a->feats && (!a->feat_maps || !a->all_pxl_coords || a->h < 1 || a->C <= 0)) return UPNERF_EINVAL;
   if (a->inv_depths && !a->all_inv_depths) return UPNERF_EINVAL;
   hipLaunchKernelGGL(gather_rays_kernel, dim3((a->R + 3) / 4), dim3(NTHREADS), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();

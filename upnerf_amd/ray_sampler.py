@@ -77,8 +77,17 @@ class GpuRaySampler:
         return self.N
 
     def sample(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """Batch for the ray indices `idx` (int64, on the device): the reference's collated `__getitem__` results."""
+        """Batch for the ray indices `idx` (int64, on the device): the reference's collated `__getitem__` results.  An index
+        outside the split is refused here, before anything is launched (the kernel reads the flat buffers unchecked); the
+        check reads the indices' range back, which `batches` -- whose indices are a permutation of the split -- does not pay."""
         idx = idx.to(self.device, torch.int64).contiguous()
+        if idx.numel():
+            lo, hi = (int(v) for v in torch.aminmax(idx))
+            if lo < 0 or hi >= self.N:
+                raise IndexError(f"ray index out of range: [{lo}, {hi}] for a split of {self.N} rays")
+        return self._gather(idx)
+
+    def _gather(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
         R = idx.numel()
         dev = self.device
         e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
@@ -122,4 +131,4 @@ class GpuRaySampler:
             sl = perm[lo: lo + batch_size]
             if drop_last and sl.numel() < batch_size:
                 return
-            yield self.sample(sl)
+            yield self._gather(sl)  # a slice of a permutation of range(N): inside the split, contiguous, on the device
